@@ -1,11 +1,23 @@
 #!/usr/bin/env python3
 """Benchmark of the retrieval-evaluation hot path (BASELINE.json metric: queries/sec).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c5|c1|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c5|c1|c4] [--full] [--dump-outputs DIR]
 
 One step = one full pass of the path over the query batch with codes and labels already resident in HBM:
 sampled histogram -> threshold guess -> select -> verify + order + label match -> AP (all HIP) -> per-query AP to
 the host -> mean.  `value` = Q / step time: queries per second, whole job.
+
+A plain run sets up, runs the untimed steps, times exactly K steps and prints the line (`value`, `ms_per_step`, the
+per-step spread, `map`).  Everything else the benchmark measures or checks is behind --full: parity against the
+reference's golden, engine counters, per-kernel HIP-event timing and the roofline (`--kernel-timing` defaults to
+pair-passes there, to none in a plain run), the one-call-at-a-time and pipeline legs, the sharded run's exchange timing
+and query-split leg, and on one GPU the side legs (h2d_inclusive, drop_in_literal, class_sorted_database, real_valued,
+large_r, configs, scaling_reference_c4_one_gpu, cpu_baseline; each can still be left out with its --no-* switch).
+
+  --dump-outputs DIR   after the timed steps, rank 0 writes what the last timed step returned to its caller:
+                       DIR/ap.npy (float64 [Q], per-query AP, nan where a query has no hit), DIR/hits.npy (float64 [Q],
+                       relevant items in each top R) and DIR/map.npy (float64 [1], the mean over queries with hits).
+                       The inputs are seeded, so two builds run with the same arguments can be compared file for file.
 
   --gpus 1 (default)   C2 = BASELINE.json configs[1]: Q=10k, N=1M, b=64, R=5000 on one MI355X -- the configuration
                        the metric is quoted on.
@@ -769,10 +781,22 @@ def main():
     ap.add_argument("--timing-every", type=int, default=4,
                     help="pair-passes timing brackets the select pass on every n-th step of the timed region (its events cost a "
                          "step ~0.025 ms: tools/gpu_event_cost.sh); the average is over those launches")
-    ap.add_argument("--kernel-timing", default="pair-passes", choices=["pair-passes", "all", "none"],
-                    help="HIP events around the select pass over the pairs only (the roofline kernel; default), around every "
-                         "kernel (events keep kernels from being dispatched back to back), or none")
+    ap.add_argument("--kernel-timing", default=None, choices=["pair-passes", "all", "none"],
+                    help="HIP events around the select pass over the pairs only (the roofline kernel; the default with --full), "
+                         "around every kernel (events keep kernels from being dispatched back to back), or none (the default "
+                         "of a plain run)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: parity, counters, kernel timing and roofline, the pipeline legs and the side "
+                         "legs (see the module docstring); a plain run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (ap.npy, hits.npy, map.npy; float64) to DIR")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.kernel_timing is None:
+        args.kernel_timing = "pair-passes" if args.full else "none"
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args, sys.argv[1:]))           # no launcher: be one
@@ -833,14 +857,14 @@ def main():
 
         def step():
             a, r = sharded.evaluate_shard(eng, comm, R, always_gather=force)
-            return sharded.mean_ap(a, r), a
+            return sharded.mean_ap(a, r), a, r
 
         def fence():
             comm.barrier()                              # hipStreamSynchronize + a tiny all-reduce on every rank
     else:
         def step():
             a, r = ctx.map(R)
-            return metric.mean_over_hits(a, r), a
+            return metric.mean_over_hits(a, r), a, r
 
         def fence():
             ctx.synchronize()                           # hipStreamSynchronize (every one-shot call also ends synchronised)
@@ -856,7 +880,7 @@ def main():
     ctx.timing_enable(level)
     untimed = args.warmup if dry_dir else max(args.warmup, SETTLE_STEPS)      # (a dry run through files measures nothing)
     for _ in range(untimed):
-        m, a = step()
+        m, a, r = step()
     ctx.set_option("timing_every", every)
     ctx.timing_enable(level)                            # restarts the every-n-th count
     ctx.timing_reset()
@@ -879,16 +903,21 @@ def main():
     else:
         for _ in range(args.steps):
             t1 = time.perf_counter()
-            m, a = step()                               # (ends synchronised: the AP vector is on the host)
+            m, a, r = step()                            # (ends synchronised: the AP vector is on the host)
             each.append(time.perf_counter() - t1)
     fence()
     dt = time.perf_counter() - t0
     if sharded_leg:
         dt = comm.allreduce_max(dt)                     # the slowest rank's clock
-    timing = ctx.timing_read()
+    timing = ctx.timing_read() if level else {}
     ctx.timing_enable(False)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller (the legs of --full below run steps of their own afterwards)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, arr in (("ap", a), ("hits", r), ("map", [m])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(arr, dtype=np.float64))
     pipe = None
-    if pipelined:
+    if pipelined and args.full:
         # the same steps one at a time (hg_map: enqueue, wait, copy out, return), for the latency of a single call
         ns = max(1, min(args.steps, 20))
         fence()
@@ -967,7 +996,7 @@ def main():
         except Exception as e:      # noqa: BLE001
             pipe["two_contexts_alternating"] = {"error": "%s: %s" % (type(e).__name__, e)}
     exchange = None
-    if sharded_leg:
+    if sharded_leg and args.full:
         # what crosses the wire per step and rank (the owner-routed form: three all-to-alls and one small all-gather), and how long the
         # exchanges take on the stream (HIP events around every kernel and collective: a short pass of its own, after the timed region)
         NBp, HC, width, RWw = b + 1, min((b + 1) // 2 + 2, b + 1), -(-Q // world), -(-R // 64)
@@ -997,7 +1026,7 @@ def main():
         except Exception as e:      # noqa: BLE001 -- a side measurement must never cost the main line
             exchange["timing_error"] = "%s: %s" % (type(e).__name__, e)
     qsplit = None
-    if sharded_leg and not args.no_query_split:
+    if sharded_leg and args.full and not args.no_query_split:
         try:
             qsplit = query_split_leg(args, spec, rank, world, local_rank, dry_dir, comm, qw, ql)
         except Exception as e:      # noqa: BLE001 -- a side measurement must never cost the main line
@@ -1008,12 +1037,6 @@ def main():
             if not dry_dir:
                 ctx.comm_destroy()
         return
-
-    # parity flag: the first queries are a golden case of the unmodified reference
-    from tests import cases
-    g = cases.load_golden(spec["golden"])
-    k = g["ap"].shape[0]
-    parity = bool(np.array_equal(a[:k], g["ap"], equal_nan=True))
 
     per_step = dt / args.steps
     out = {
@@ -1026,13 +1049,19 @@ def main():
                    "parallelism": ("database sharded over %d GPU%s (%d rows on rank 0); native RCCL all-gather of shard "
                                    "histograms / record counts and match bitmaps" % (world, "s" if world > 1 else "", rows))
                    if sharded_leg else "1 GPU"},
-        "map": float(m), "parity_vs_reference_golden": parity,
-        "optimistic_runs": ctx.get_stat("optimistic_runs"), "optimistic_fallbacks": ctx.get_stat("optimistic_fallbacks"),
-        "pairs_per_sec": Q * N / per_step,
+        "map": float(m), "pairs_per_sec": Q * N / per_step,
     }
-    kept = ctx.get_stat("records_kept")              # the last step's slice counts, downloaded now (outside the timed region)
-    if kept >= 0:
-        out["records_kept_over_R"] = round(kept / float(Q * R), 4)      # what the guess's safety margin costs the select's drain (1.0 = no surplus)
+    if args.full:
+        # parity flag: the first queries are a golden case of the unmodified reference
+        from tests import cases
+        g = cases.load_golden(spec["golden"])
+        k = g["ap"].shape[0]
+        out["parity_vs_reference_golden"] = bool(np.array_equal(a[:k], g["ap"], equal_nan=True))
+        out["optimistic_runs"] = ctx.get_stat("optimistic_runs")
+        out["optimistic_fallbacks"] = ctx.get_stat("optimistic_fallbacks")
+        kept = ctx.get_stat("records_kept")          # the last step's slice counts, downloaded now (outside the timed region)
+        if kept >= 0:
+            out["records_kept_over_R"] = round(kept / float(Q * R), 4)      # what the guess's safety margin costs the select's drain (1.0 = no surplus)
     if sharded_leg or wl == "c4":
         out["scaling"] = "strong"                            # the fixed N = 10M database over the GPUs (a one-GPU C2 line scales nothing)
     if pipe is not None:
@@ -1060,7 +1089,7 @@ def main():
                                           "value": Q * world / per_step}
         out["scaling_note"] = ("strong scaling of ONE %d-row database over the GPUs (BASELINE config 4).  The --gpus 1 line times C2 (N = 1M, the "
                                "configuration the metric is quoted on), so value(--gpus 1) is NOT this curve's one-GPU point: that is "
-                               "`scaling_reference_c4_one_gpu` in the --gpus 1 line (the same %d rows on one GPU, ~4.8 ms per step, ~2.1 M queries/s)" % (N, N))
+                               "`scaling_reference_c4_one_gpu` in the --gpus 1 --full line (the same %d rows on one GPU, ~4.8 ms per step, ~2.1 M queries/s)" % (N, N))
     if timing:
         span = timing.pop("step_gpu_span", None)
         rec_bytes = 8 if any(kv.replace(" ", "") == "compact_records=0" for kv in args.opt) else 1
@@ -1084,7 +1113,7 @@ def main():
         if not dry_dir:
             ctx.comm_destroy()
     ctx.close()
-    if world == 1 and not force:
+    if world == 1 and not force and args.full:
         def side(key, fn):           # a side measurement must never cost the main line
             try:
                 out[key] = fn()

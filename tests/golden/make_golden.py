@@ -13,7 +13,9 @@ For the small cases the first R entries of np.argsort(-ips', 1) are stored too
 (`idx`), pinning the canonical order itself.
 
 Also extracts the CIFAR-10 class vectors from the reference's label lists
-(data_list/cifar10/{database,test}.txt -- data files, stored as class indices).
+(data_list/cifar10/{database,test}.txt -- data files, stored as class indices), and records what
+tests/test_oracle_vs_reference.py and tests/test_evalio.py compare with (reference_live.npz, reference_files.npz),
+so that no test reads the reference itself.
 
 Usage:  python tests/golden/make_golden.py [case ...]
 """
@@ -96,8 +98,45 @@ def run_real_case(name):
     print("%-16s Q=%-5d N=%-9d R=%-6d map=%.17g skipped=%d" % (name, Q, N, R, m, int(np.isnan(ap).sum())))
 
 
+def reference_live():
+    """tests/test_oracle_vs_reference.py: the reference's mAP on that module's seeded cases (its LIVE_CASES), and the
+    name of the exception it raises for R > N."""
+    from tests import test_oracle_vs_reference as T
+    out = {}
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        for case in T.LIVE_CASES:
+            *_, database, query = T.live_inputs(*case)
+            out[T.live_key(*case)] = np.float64(MAPs(case[3]).get_maps_by_feature(database, query))
+    d, q, R = T.r_gt_n_inputs()
+    try:
+        MAPs(R).get_maps_by_feature(d, q)
+        out["r_gt_n_raises"] = np.array("")
+    except Exception as e:      # noqa: BLE001 -- recorded, the test asserts which
+        out["r_gt_n_raises"] = np.array(type(e).__name__)
+    np.savez_compressed(os.path.join(HERE, "reference_live.npz"), **out)
+
+
+def reference_files():
+    """tests/test_evalio.py: data_list/cifar10/test.txt verbatim (a data file), and of two configuration files only the
+    entries the evaluation reads (DATA.LABEL_DIM / DB_SIZE / TEST_SIZE / MAP_R, MODEL.HASH_DIM where set), re-emitted as YAML.
+    Every file is stored as its bytes (uint8)."""
+    import yaml
+    out = {"cifar10_test.txt": open(os.path.join(REF, "data_list/cifar10/test.txt"), "rb").read()}
+    for name in ("cifar_evaluation", "nuswide_step_1"):
+        with open(os.path.join(REF, "config", name + ".yaml")) as f:
+            y = yaml.safe_load(f)
+        keep = {"DATA": {k: y["DATA"][k] for k in ("LABEL_DIM", "DB_SIZE", "TEST_SIZE", "MAP_R") if k in y["DATA"]}}
+        if "HASH_DIM" in (y.get("MODEL") or {}):
+            keep["MODEL"] = {"HASH_DIM": y["MODEL"]["HASH_DIM"]}
+        out[name + ".yaml"] = yaml.safe_dump(keep).encode()
+    np.savez_compressed(os.path.join(HERE, "reference_files.npz"), **{k: np.frombuffer(v, np.uint8) for k, v in out.items()})
+
+
 if __name__ == "__main__":
     cifar_labels()
+    reference_live()
+    reference_files()
     from tests import cases
     names = sys.argv[1:] or (list(cases.CASES) + list(cases.REAL_CASES))
     for nm in names:

@@ -1,11 +1,9 @@
-"""The evaluation glue (hashgan_amd/evalio.py) against the reference's own data files where they
-exist (build container), and on synthetic inputs everywhere."""
+"""The evaluation glue (hashgan_amd/evalio.py) against the reference's own data files (as recorded under
+tests/golden/ by make_golden.py), and on synthetic inputs."""
 import os
 import numpy as np
 import pytest
 from hashgan_amd import evalio
-
-REF = "/root/reference"
 
 
 def test_read_label_list_and_stack(tmp_path):
@@ -31,17 +29,20 @@ def test_config_defaults_and_yaml(tmp_path):
     assert (c.HASH_DIM, c.LABEL_DIM, c.DB_SIZE, c.TEST_SIZE, c.MAP_R) == (64, 81, 168692, 5000, 5000)
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not os.path.exists(REF + "/config/cifar_evaluation.yaml"), reason="no /root/reference")
-def test_against_reference_files():
-    c = evalio.load_eval_config(REF + "/config/cifar_evaluation.yaml")
-    assert (c.LABEL_DIM, c.DB_SIZE, c.TEST_SIZE, c.MAP_R) == (10, 54000, 1000, 54000)
-    lab = evalio.read_label_list(REF + "/data_list/cifar10/test.txt")
-    assert lab.shape == (c.TEST_SIZE, c.LABEL_DIM) and (lab.sum(1) == 1).all()
+def test_against_reference_files(tmp_path):
+    """reference_files.npz: data_list/cifar10/test.txt verbatim, and of config/{cifar_evaluation,nuswide_step_1}.yaml the
+    entries the evaluation reads (DATA.LABEL_DIM / DB_SIZE / TEST_SIZE / MAP_R, MODEL.HASH_DIM where set) as YAML."""
     from tests import cases
+    ref = cases.load_golden("reference_files")
+    for key in ref:
+        (tmp_path / key).write_bytes(ref[key].tobytes())
+    c = evalio.load_eval_config(str(tmp_path / "cifar_evaluation.yaml"))
+    assert (c.LABEL_DIM, c.DB_SIZE, c.TEST_SIZE, c.MAP_R) == (10, 54000, 1000, 54000)
+    lab = evalio.read_label_list(str(tmp_path / "cifar10_test.txt"))
+    assert lab.shape == (c.TEST_SIZE, c.LABEL_DIM) and (lab.sum(1) == 1).all()
     z = np.load(os.path.join(cases.GOLDEN_DIR, "cifar10_labels.npz"))
     assert np.array_equal(lab.argmax(1), z["test_cls"])           # the committed fixture is this file
-    c = evalio.load_eval_config(REF + "/config/nuswide_step_1.yaml")
+    c = evalio.load_eval_config(str(tmp_path / "nuswide_step_1.yaml"))
     assert c.LABEL_DIM == 81 and c.MAP_R == 5000
 
 
