@@ -354,8 +354,9 @@ class Context:
         nq = pending[0] if pending else self.Q
         ap = np.empty(nq, dtype=np.float64)
         rel = np.empty(nq, dtype=np.int64)
-        check(self._lib.hg_map_end(self._h, _ptr(ap), _ptr(rel)))
-        self._in_flight = pending[1:]
+        rc = self._lib.hg_map_end(self._h, _ptr(ap), _ptr(rel))
+        self._in_flight = pending[1:]                    # (hg_map_end takes the step off its queue whatever it returns)
+        check(rc)
         return ap, rel
 
     # -- real-valued features ---------------------------------------------------

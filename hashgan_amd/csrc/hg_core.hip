@@ -175,7 +175,7 @@ static long long cache_stat(int which) {
     std::lock_guard<std::mutex> lk(c.m);
     return which == 0 ? (long long)c.dev_bytes : which == 1 ? (long long)c.pin_bytes : which == 2 ? c.hits : which == 3 ? c.misses : (long long)c.streams.size();
 }
-static int stream_create(int device, hipStream_t* out) {
+int stream_create(int device, hipStream_t* out) {
     *out = cache_take_stream(device);
     if (*out) return HG_OK;
     HG_HIP(host_timed(HP_STREAM, [&] { return hipStreamCreateWithFlags(out, hipStreamNonBlocking); }));
@@ -281,6 +281,7 @@ int hg_destroy(hg_ctx* c) {
     HostTimer t_destroy(HP_DESTROY);
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->stream_b) (void)hipStreamSynchronize(c->stream_b);
     c->t_collect();
     c->drop_graph();
     for (auto e : c->pool) (void)hipEventDestroy(e);
@@ -290,6 +291,7 @@ int hg_destroy(hg_ctx* c) {
                      &c->shapes, &c->ap, &c->rel, &c->stage_in, &c->badcnt, &c->qbad, &c->flist, &c->hwq, &c->dbf, &c->qf, &c->samp, &c->thr,
                      &c->sortA, &c->sortB, &c->gtab, &c->scores, &c->dbx, &c->qx, &c->bigq, &c->mbits2, &c->dbfx, &c->dbfb, &c->thr2, &c->xmax2, &c->dbx8, &c->dbx3, &c->dbx4, &c->sampx, &c->ap_recip, &c->part, &c->dbytes, &c->outblk, &c->beyond, &c->cntq, &c->hist2, &c->krows};
     for (auto* d : all) d->release();
+    c->release_step_b();
     for (auto& d : c->gathered) d.release();
     for (auto& d : c->scratch) d.release();
     c->comm_tmp.release(); c->gath_idx.release(); c->gath_dist.release();
@@ -304,6 +306,9 @@ int hg_destroy(hg_ctx* c) {
     if (c->stream2_ev) (void)hipEventDestroy(c->stream2_ev);
     if (c->stream2) { (void)hipStreamSynchronize(c->stream2); cache_give_stream(c->device, c->stream2); }
     for (auto& e : c->fstage_ev) if (e) (void)hipEventDestroy(e);
+    if (c->ev_pre) (void)hipEventDestroy(c->ev_pre);
+    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
+    if (c->stream_b) cache_give_stream(c->device, c->stream_b);                              // (synchronised above)
     if (c->stream && c->own_stream && !c->is_sub) cache_give_stream(c->device, c->stream);   // (synchronised above)
     delete c;
     return HG_OK;
@@ -927,6 +932,11 @@ int hg_set_option(hg_ctx* c, const char* key, int64_t value) {
     }
     c->cfg_epoch++;                                    // whatever changes: a captured step is rebuilt
     if (!strcmp(key, "step_graph")) { c->opt_graph = value != 0; return HG_OK; }
+    if (!strcmp(key, "step_streams")) {                // hg_map_begin: slot 1's blind steps on a second stream (2) or on the context's (1)
+        if (value < 1 || value > 2) return fail(HG_ERR_ARG, "step_streams must be 1 or 2");
+        c->opt_step_streams = value;
+        return HG_OK;
+    }
     if (!strcmp(key, "stage_sync")) { c->stage_sync = value != 0; return HG_OK; }
     if (!strcmp(key, "defer_verdict")) { c->defer_verdict = value != 0; return HG_OK; }
     if (!strcmp(key, "target_units")) {
@@ -1043,6 +1053,7 @@ int hg_trim(hg_ctx* c) {
                       &c->out_dist, &c->stage_in, &c->hwq, &c->samp, &c->sortA, &c->sortB, &c->gtab, &c->scores, &c->bigq, &c->mbits2,
                       &c->dbx, &c->qx, &c->dbfx, &c->dbfb, &c->sampx, &c->dbytes};   // the images are rebuilt on demand
     for (auto* d : work) d->release();
+    c->release_step_b();                               // (hg_map_begin's second workspace: its next step reserves it again)
     c->dbfx_valid = false;
     c->dbfb_valid = false;
     for (auto& d : c->gathered) d.release();
@@ -1144,6 +1155,7 @@ int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     }
     else if (!strcmp(key, "map_async_steps")) *value = c->map_async_steps;
     else if (!strcmp(key, "map_async_redone")) *value = c->map_async_redone;
+    else if (!strcmp(key, "map_overlapped_steps")) *value = c->map_overlapped;
     else if (!strcmp(key, "segments")) *value = c->geo.S;
     else if (!strcmp(key, "records_kept")) {
         // records the last bet's select pass left in the slices, over all live queries (a download of the slice counts: a
@@ -1185,6 +1197,7 @@ int hg_timing_enable(hg_ctx* c, int on) {
 int hg_timing_reset(hg_ctx* c) {
     if (!c) return fail(HG_ERR_ARG, "hg_timing_reset: null context");
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->stream_b) (void)hipStreamSynchronize(c->stream_b);
     c->t_collect();
     for (int i = 0; i < KI_COUNT; ++i) { c->t_ms[i] = 0; c->t_n[i] = 0; }
     return HG_OK;
@@ -1193,6 +1206,7 @@ int hg_timing_reset(hg_ctx* c) {
 int hg_timing_read(hg_ctx* c, int cap, const char** names, double* total_ms, int64_t* launches, int* n) {
     if (!c || !n) return fail(HG_ERR_ARG, "hg_timing_read: null argument");
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->stream_b) (void)hipStreamSynchronize(c->stream_b);
     c->t_collect();                                    // events recorded since the last read
     int k = 0;
     for (int i = 0; i < KI_COUNT && k < cap; ++i) {

@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 using namespace hg;
@@ -131,6 +132,7 @@ void cache_give_dev(int device, void* p, size_t bytes);              // (frees i
 void* cache_take_pin(size_t want, size_t* got);
 void cache_give_pin(void* p, size_t bytes);
 hipStream_t cache_take_stream(int device);                           // nullptr: none cached
+int stream_create(int device, hipStream_t* out);                    // from the cache, else a new non-blocking stream
 void cache_give_stream(int device, hipStream_t s);
 void cache_release_all();
 inline size_t cache_round(size_t bytes) {                            // sizes a later request can match: 4 KB up to 1 MB, then 1 MB
@@ -323,6 +325,44 @@ struct hg_ctx {
         std::vector<double> ap; std::vector<int64_t> rel;
     } mslot[2];
     int ms_head = 0, ms_n = 0;
+    // Slot 1's blind steps run on a second stream (option "step_streams" = 2), so that two consecutive steps overlap on the GPU:
+    // the tail of one (k_rank_lean, the download) and the sampled pass and guess of the next run beside the other's select.  Such
+    // a step writes a workspace of its own -- every buffer a bet writes, swapped in for the enqueue (swap_step) -- and reads
+    // the shared tables (database images, query tables, AP tables), which only ever change on the context's stream.
+    //   stream_b  waits, before the step, for everything on the context's stream but a blind slot-0 step in flight: ev_pre
+    //             (recorded just before that step, while pre_valid) or else ev_fork at the stream's tail;
+    //   stream    waits for stream_b's work (b_ev, while b_open) before anything but hg_map_begin / hg_map_end is enqueued (use()).
+    struct StepBufs {
+        DevBuf hist, hown, posbase, t, tguess, sstar, cnt_lt, quota, tie_before, n_lt, err, sl_start, sl_tie, sl_cnt, tot, failq,
+               cand, out_idx, out_dist, mbits, ap, rel, qbad, bigq, hwq, outblk;
+        i64 outblk_q = -1;
+    } ws_b;
+    hipStream_t stream_b = nullptr;
+    hipEvent_t ev_pre = nullptr, ev_fork = nullptr, b_ev = nullptr;
+    bool pre_valid = false, b_open = false;
+    bool swapped = false;      // ws_b and stream_b are swapped in (a slot-1 step is being enqueued)
+    i64 opt_step_streams = 2;  // "step_streams": 2 = slot 1's blind steps on stream_b, 1 = every step on the context's stream
+    i64 map_overlapped = 0;    // stat "map_overlapped_steps": blind steps enqueued on stream_b
+    void swap_step() {
+        StepBufs& w = ws_b;
+        std::swap(stream, stream_b);
+        std::swap(hist, w.hist); std::swap(hown, w.hown); std::swap(posbase, w.posbase); std::swap(t, w.t);
+        std::swap(tguess, w.tguess); std::swap(sstar, w.sstar); std::swap(cnt_lt, w.cnt_lt); std::swap(quota, w.quota);
+        std::swap(tie_before, w.tie_before); std::swap(n_lt, w.n_lt); std::swap(err, w.err); std::swap(sl_start, w.sl_start);
+        std::swap(sl_tie, w.sl_tie); std::swap(sl_cnt, w.sl_cnt); std::swap(tot, w.tot); std::swap(failq, w.failq);
+        std::swap(cand, w.cand); std::swap(out_idx, w.out_idx); std::swap(out_dist, w.out_dist); std::swap(mbits, w.mbits);
+        std::swap(ap, w.ap); std::swap(rel, w.rel); std::swap(qbad, w.qbad); std::swap(bigq, w.bigq); std::swap(hwq, w.hwq);
+        std::swap(outblk, w.outblk); std::swap(outblk_q, w.outblk_q);
+        swapped = !swapped;
+    }
+    void release_step_b() {
+        StepBufs& w = ws_b;
+        DevBuf* all[] = {&w.hist, &w.hown, &w.posbase, &w.t, &w.tguess, &w.sstar, &w.cnt_lt, &w.quota, &w.tie_before, &w.n_lt, &w.err,
+                         &w.sl_start, &w.sl_tie, &w.sl_cnt, &w.tot, &w.failq, &w.cand, &w.out_idx, &w.out_dist, &w.mbits, &w.ap, &w.rel,
+                         &w.qbad, &w.bigq, &w.hwq, &w.outblk};
+        for (auto* d : all) d->release();
+        w.outblk_q = -1;
+    }
     unsigned long long map_warm_cfg = 0, map_warm_epoch = 0;   // configuration of the last synchronous hg_map that won its bet outright
     i64 map_warm_R = -1;
     i64 map_async_steps = 0, map_async_redone = 0;
@@ -417,7 +457,13 @@ struct hg_ctx {
     std::vector<Pending> pending;
     std::vector<hipEvent_t> pool;
 
-    int use() { HG_HIP(hipSetDevice(device)); return HG_OK; }
+    // every entry point but hg_map_begin / hg_map_end: whatever it enqueues on the context's stream follows stream_b's work
+    int use() {
+        HG_HIP(hipSetDevice(device));
+        pre_valid = false;
+        if (b_open) { HG_HIP(hipStreamWaitEvent(stream, b_ev, 0)); b_open = false; }
+        return HG_OK;
+    }
 
     hipEvent_t get_event() {
         if (!pool.empty()) { hipEvent_t e = pool.back(); pool.pop_back(); return e; }
@@ -488,6 +534,10 @@ struct hg_ctx {
     }
     int sync() {
         HG_HIP(host_timed(HP_SYNC, [&] { return hipStreamSynchronize(stream); }));     // ("sync": waiting for the GPU -- kernels and copies included)
+        if (b_open && !swapped) {                      // (stream_b's work that the context's stream has not waited for)
+            HG_HIP(host_timed(HP_SYNC, [&] { return hipStreamSynchronize(stream_b); }));
+            b_open = false;
+        }
         if (pending.size() > 4096) t_collect();       // otherwise the elapsed times are read when somebody asks for them
         return HG_OK;
     }

@@ -1570,6 +1570,8 @@ int hg_map(hg_ctx* c, int64_t R, double* host_ap, int64_t* host_rel) {
     // (queries the fused rank kernel declines are fine when the step ranks them itself within the stream: leftovers_inline)
     if (c->optimistic && c->opt_fallbacks + c->opt_requeried + c->opt_rebets == fails0 && (c->opt_leftover == left0 || c->last_leftovers_inline) && !c->is_sub) {
         c->map_warm_cfg = c->cfg_epoch; c->map_warm_epoch = g_alloc_epoch; c->map_warm_R = R;
+        // slot 1's stream now, once per context (a stream costs milliseconds to create -- not inside a caller's pipeline)
+        if (c->opt_step_streams >= 2 && c->own_stream && !c->stream_b) HG_TRY(stream_create(c->device, &c->stream_b));
     } else {
         c->map_warm_R = -1;
     }
@@ -1583,10 +1585,59 @@ int hg_map(hg_ctx* c, int64_t R, double* host_ap, int64_t* host_rel) {
 // last synchronous hg_map with the same tables, options and R won its bet outright; otherwise hg_map_begin runs the whole call
 // itself (and keeps the results for hg_map_end).  A blind step that loses its bet is run again, synchronously, by hg_map_end:
 // results are those of hg_map in every case.
+// Two-stream form (step_streams = 2): the tables a blind step reads and a step would otherwise (re)build on first use -- the
+// query image after hg_set_queries kept the licence, the AP tables -- are built on the context's stream BEFORE the step, so a step
+// on stream_b never writes them and a fork point taken after this sees them.  *enqueued: something was.
+static int prepare_shared(hg_ctx* c, int64_t R, bool* enqueued) {
+    *enqueued = false;
+    if (c->opt_select_mfma && !c->qx_valid) { HG_TRY(ensure_mx_images(c, false)); *enqueued = true; }
+    const bool recip = c->opt_ap_recip && R <= (1ll << 20);
+    if (c->shapes_for_R != R || (recip && c->recip_for_R != R)) {
+        HG_TRY(set_R(c, R, 1, 0));
+        bool use_recip = false;
+        HG_TRY(ensure_ap_tables(c, &use_recip));
+        *enqueued = true;
+    }
+    return HG_OK;
+}
+
+// A blind step of slot 1 on stream_b, in the workspace ws_b.  Its stream first waits for everything on the context's stream
+// except a blind slot-0 step in flight (that one writes only the context's own workspace): ev_pre, recorded just before it, when
+// nothing else was enqueued since; else the stream's tail.  stream_b itself holds nothing else: its previous step was waited for
+// by hg_map_end, so the workspace is free.
+static int enqueue_bet_on_b(hg_ctx* c, hg_ctx::MapSlot& m, int64_t R, int stride, u32 need_cnt, bool tail_fork) {
+    if (!c->stream_b) HG_TRY(stream_create(c->device, &c->stream_b));
+    if (!c->ev_pre) HG_HIP(hipEventCreateWithFlags(&c->ev_pre, hipEventDisableTiming));
+    if (!c->ev_fork) HG_HIP(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    if (tail_fork || !c->pre_valid) {
+        HG_HIP(hipEventRecord(c->ev_fork, c->stream));
+        HG_HIP(hipStreamWaitEvent(c->stream_b, c->ev_fork, 0));
+    } else {
+        HG_HIP(hipStreamWaitEvent(c->stream_b, c->ev_pre, 0));
+    }
+    c->b_open = false;
+    const unsigned long long e0 = g_alloc_epoch.load();
+    c->swap_step();
+    int rc = ensure_out_block(c);                      // (ws_b's own err / ap / rel views; on first use)
+    if (rc == HG_OK) rc = enqueue_bet_with_ap(c, R, stride, need_cnt, m.pin);
+    if (rc == HG_OK && hipEventRecord(m.ev, c->stream) != hipSuccess) rc = fail(HG_ERR_HIP, "hg_map_begin: hipEventRecord failed");
+    c->swap_step();
+    if (rc != HG_OK) { (void)hipStreamSynchronize(c->stream_b); return rc; }
+    c->b_ev = m.ev;
+    c->b_open = true;
+    // ws_b's first reservations move no buffer the licence was given for (the context's own workspace is untouched)
+    if (c->map_warm_epoch == e0) c->map_warm_epoch = g_alloc_epoch;
+    c->map_overlapped++;
+    return HG_OK;
+}
+
 int hg_map_begin(hg_ctx* c, int64_t R) {
-    HG_TRY(need(c, ST_DB | ST_Q, "hg_map_begin", "hg_set_database + hg_set_queries"));
+    if (!c) return fail(HG_ERR_ARG, "hg_map_begin: null context");
+    if ((c->stage & (ST_DB | ST_Q)) != (ST_DB | ST_Q)) return fail(HG_ERR_STATE, "hg_map_begin called before hg_set_database + hg_set_queries");
+    HG_HIP(hipSetDevice(c->device));                   // (not use(): a blind step does not wait for the other slot's)
     if (c->ms_n == 2) return fail(HG_ERR_STATE, "hg_map_begin: two steps are in flight already (hg_map_end takes the oldest)");
-    hg_ctx::MapSlot& m = c->mslot[(c->ms_head + c->ms_n) & 1];
+    const int slot = (c->ms_head + c->ms_n) & 1;
+    hg_ctx::MapSlot& m = c->mslot[slot];
     m.R = R; m.Q = c->Q;
     m.q_gen = c->q_gen; m.db_gen = c->db_gen;
     int stride = 0;
@@ -1607,8 +1658,21 @@ int hg_map_begin(hg_ctx* c, int64_t R) {
         }
         if (!m.ev) HG_HIP(hipEventCreateWithFlags(&m.ev, hipEventDisableTiming));
         c->opt_runs++;
-        HG_TRY(enqueue_bet_with_ap(c, R, stride, need_cnt, m.pin));
-        HG_HIP(hipEventRecord(m.ev, c->stream));
+        // two streams unless the caller owns the stream (hg_set_stream) or per-kernel timing is on (its events assume one stream)
+        const bool two = c->opt_step_streams >= 2 && c->own_stream && c->timing == 0 && !c->capturing;
+        bool prepped = false;
+        if (two) HG_TRY(prepare_shared(c, R, &prepped));
+        if (two && slot == 1) {
+            HG_TRY(enqueue_bet_on_b(c, m, R, stride, need_cnt, prepped));
+        } else {
+            if (two) {                                 // the fork point of a slot-1 step enqueued while this one is in flight
+                if (!c->ev_pre) HG_HIP(hipEventCreateWithFlags(&c->ev_pre, hipEventDisableTiming));
+                HG_HIP(hipEventRecord(c->ev_pre, c->stream));
+            }
+            c->pre_valid = two;                        // (one stream: this step may build a shared table -- no fork point before it)
+            HG_TRY(enqueue_bet_with_ap(c, R, stride, need_cnt, m.pin));
+            HG_HIP(hipEventRecord(m.ev, c->stream));
+        }
         m.inline_ok = c->leftovers_inline;               // the step ranks what its fused kernel declines within the stream
         c->leftovers_inline = false;
         c->ap_staged = false;
@@ -1625,7 +1689,7 @@ int hg_map_begin(hg_ctx* c, int64_t R) {
 
 int hg_map_end(hg_ctx* c, double* host_ap, int64_t* host_rel) {
     if (!c) return fail(HG_ERR_ARG, "hg_map_end: null context");
-    HG_TRY(c->use());
+    HG_HIP(hipSetDevice(c->device));                   // (not use(): nothing is enqueued unless the step lost -- hg_map then joins)
     if (!c->ms_n) return fail(HG_ERR_STATE, "hg_map_end: no step in flight (hg_map_begin first)");
     hg_ctx::MapSlot& m = c->mslot[c->ms_head];
     c->ms_head ^= 1; --c->ms_n;                           // (taken off the queue whatever happens below)

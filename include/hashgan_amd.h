@@ -199,7 +199,9 @@ int hg_map(hg_ctx* ctx, int64_t R, double* host_ap, int64_t* host_rel);
  * results under the old step's name.  A new query table of the SAME size on an unchanged database and configuration keeps the licence
  * to enqueue blind, and hg_set_queries does not wait for the stream (the tables travel through a pinned block of the context's own):
  * a caller that hands over batch after batch -- hg_set_queries, hg_map_begin, the previous batch's hg_map_end -- keeps two steps in
- * flight.  Stats "map_async_steps" / "map_async_redone".  Test hook: option "handicap_next_bet" (0..64; not a configuration change)
+ * flight.  Option "step_streams" (2, the default): slot 1's blind steps run on a second stream of the context, in buffers of their
+ * own, so two consecutive steps overlap on the GPU; every other entry point first orders the context's stream behind it, and
+ * hg_synchronize waits for both (1: one stream).  Stats "map_async_steps" / "map_async_redone" / "map_overlapped_steps".  Test hook: option "handicap_next_bet" (0..64; not a configuration change)
  * puts the NEXT bet's guess that many deviations below the expected count, once: the bet loses. */
 int hg_map_begin(hg_ctx* ctx, int64_t R);
 int hg_map_end(hg_ctx* ctx, double* host_ap, int64_t* host_rel);
