@@ -231,10 +231,10 @@ int hg_shard_step(hg_ctx* c, int64_t R, int replica_world, double* host_ap, int6
     HG_TRY(hg_bet_eligible(c, R, world, &eligible));
     // (hg_merge_ranked's limits: lane r <-> shard r, the four queries of a block keep their [G][b + 1] record counts in LDS)
     if (!eligible || world > 64 || (size_t)4 * world * (c->b + 1) * 4 > 160u * 1024u) { *bet_lost = -1; return HG_OK; }   // nothing enqueued: the staged sequences apply
-    const bool sync0 = c->stage_sync;
-    c->stage_sync = false;                             // the stages only enqueue; hg_unpack_parts waits once
+    const i64 sync0 = c->opt.stage_sync;
+    c->opt.stage_sync = 0;                             // the stages only enqueue; hg_unpack_parts waits once
     const int rc = shard_step_enqueue(c, R, replica, world, rank, host_ap, host_rel, bet_lost);
-    c->stage_sync = sync0;
+    c->opt.stage_sync = sync0;
     return rc;
 }
 

@@ -242,6 +242,34 @@ int ensure_pin(hg_ctx* c, size_t need_b) {
     return HG_OK;
 }
 
+// The child context that reruns a few lost queries exactly (rerun_lost_queries, real_requery_lost), created on first use on the
+// parent's stream (ordered with its work).  It takes the parent's problem shape, database tables and options, with the call
+// protocol of a plain synchronous call and no timing; each caller then applies its own overrides and loads the nF lost queries.
+hg_ctx* requery_child(hg_ctx* c, i64 nF) {
+    if (!c->sub) {
+        c->sub = new hg_ctx();
+        c->sub->is_sub = true;
+        c->sub->device = c->device;
+        c->sub->stream = c->stream;
+    }
+    hg_ctx* s = c->sub;
+    s->N = c->N; s->b = c->b; s->C = c->C; s->n_total = c->n_total; s->NW = c->NW; s->NB = c->NB; s->LW = c->LW;
+    s->idx_base = c->idx_base; s->n_cu = c->n_cu; s->bpad = c->bpad;
+    s->opt = c->opt;
+    s->opt.stage_sync = 1; s->opt.defer_verdict = 0; s->opt.step_graph = 0; s->opt.step_streams = 2; s->opt.timing_every = 1;
+    s->timing = 0;
+    s->db.borrow(c->db);
+    s->dblab.borrow(c->dblab);
+    s->Q = nF;
+    return s;
+}
+
+// What the context and its requery child hold on the device (stat "device_bytes"; borrowed buffers and views are another's).
+static i64 device_bytes(hg_ctx* c) {
+    i64 total = 0;
+    c->for_each_buf([&](DevBuf& d, BufClass) { if (!d.borrowed) total += (i64)d.cap; });
+    return total + (c->sub ? device_bytes(c->sub) : 0);
+}
 
 // =============================================================================
 extern "C" {
@@ -285,17 +313,7 @@ int hg_destroy(hg_ctx* c) {
     c->t_collect();
     c->drop_graph();
     for (auto e : c->pool) (void)hipEventDestroy(e);
-    DevBuf* all[] = {&c->db, &c->dblab, &c->qc, &c->qlab, &c->hist, &c->hown, &c->posbase, &c->seglt, &c->segtie,
-                     &c->t, &c->tguess, &c->sstar, &c->cnt_lt, &c->quota, &c->tie_before, &c->n_lt, &c->err, &c->sl_start,
-                     &c->sl_tie, &c->sl_cnt, &c->tot, &c->failq, &c->cand, &c->out_idx, &c->out_dist, &c->mbits,
-                     &c->shapes, &c->ap, &c->rel, &c->stage_in, &c->badcnt, &c->qbad, &c->flist, &c->hwq, &c->dbf, &c->qf, &c->samp, &c->thr,
-                     &c->sortA, &c->sortB, &c->gtab, &c->scores, &c->dbx, &c->qx, &c->bigq, &c->mbits2, &c->dbfx, &c->dbfb, &c->thr2, &c->xmax2, &c->dbx8, &c->dbx3, &c->dbx4, &c->sampx, &c->ap_recip, &c->part, &c->dbytes, &c->outblk, &c->beyond, &c->cntq, &c->hist2, &c->krows};
-    for (auto* d : all) d->release();
-    c->release_step_b();
-    for (auto& d : c->gathered) d.release();
-    for (auto& d : c->scratch) d.release();
-    c->comm_tmp.release(); c->gath_idx.release(); c->gath_dist.release();
-    c->obuf[0].release(); c->obuf[1].release();
+    c->for_each_buf([](DevBuf& d, BufClass) { d.release(); });
     comm_release(c);
     if (c->sub) { hg_ctx* s = c->sub; c->sub = nullptr; (void)hg_destroy(s); }
     pin_free(c->pin, c->pin_cap);
@@ -353,7 +371,7 @@ int hg_set_database(hg_ctx* c, const uint64_t* codes, const uint64_t* labels, in
     c->dbx3_valid = false;
     c->dbx4_valid = false;
     c->dbx8_valid = false;
-    c->opt_consecutive_fail = c->shard_bet_fail = 0;    // a new database: earlier lost bets say nothing about it
+    c->bet_consecutive_fail = c->shard_bet_fail = 0;    // a new database: earlier lost bets say nothing about it
     c->cap_boost = c->real_cap_boost = 1;
     c->crowd_probed = false;
     c->cfg_epoch++;
@@ -553,8 +571,8 @@ int hg_set_database_f32(hg_ctx* c, const float* host_x, const int64_t* host_labe
     c->N = N; c->b = b; c->C = C; c->n_total = n_total;
     c->NW = (b + 31) / 32; c->NB = b + 1; c->LW = (C + 63) / 64;
     c->idx_base = (u32)idx_base;
-    if (c->opt_host_pack) {
-        HG_TRY(pack_on_host(c, host_x, host_labels, N, c->db, c->dblab, c->dbf, (int)c->opt_keep_floats, &c->dbf_resident,
+    if (c->opt.host_pack) {
+        HG_TRY(pack_on_host(c, host_x, host_labels, N, c->db, c->dblab, c->dbf, (int)c->opt.keep_floats, &c->dbf_resident,
                             bad_codes, bad_labels, c->census_db));
     } else {
         HG_TRY(pack_on_device(c, host_x, host_labels, N, c->db, c->dblab, c->dbf, bad_codes, bad_labels, c->census_db));
@@ -568,7 +586,7 @@ int hg_set_database_f32(hg_ctx* c, const float* host_x, const int64_t* host_labe
     c->dbx8_valid = false;
     c->dbfx_valid = false;
     c->dbfb_valid = false;
-    c->opt_consecutive_fail = c->shard_bet_fail = 0;
+    c->bet_consecutive_fail = c->shard_bet_fail = 0;
     c->cap_boost = c->real_cap_boost = 1;
     c->crowd_probed = false;
     c->cfg_epoch++;
@@ -603,7 +621,7 @@ int hg_set_queries_f32(hg_ctx* c, const float* host_x, const int64_t* host_label
     const i64 old_q = c->Q;
     const bool had_q = (c->stage & ST_Q) != 0;
     c->Q = Q;
-    if (c->opt_host_pack) {
+    if (c->opt.host_pack) {
         // the query table is small: its floats follow whenever the database's are there (the inner-product ranking needs both)
         const int saved_bpad = c->bpad;
         HG_TRY(pack_on_host(c, host_x, host_labels, Q, c->qc, c->qlab, c->qf, c->dbf_resident ? 1 : 0, &c->qf_resident,
@@ -732,7 +750,7 @@ extern "C++" int ensure_ap_tables(hg_ctx* c, bool* use_recip_out) {
         c->shapes_for_R = g.R;
     }
     // reciprocals of the ranks 1 .. R (k_ap's division in three multiply-adds); lists beyond 2^20 divide
-    const bool use_recip = c->opt_ap_recip && g.R <= (1ll << 20);
+    const bool use_recip = c->opt.ap_recip && g.R <= (1ll << 20);
     if (use_recip && c->recip_for_R != g.R) {
         // (AP_RECIP_SLACK more: ap_eval2's masked slots past the last rank still load a -- finite -- entry)
         HG_TRY(c->ap_recip.reserve((size_t)(g.R + 1 + AP_RECIP_SLACK) * 8));
@@ -754,7 +772,7 @@ extern "C++" int do_ap_range(hg_ctx* c, i64 q0, i64 nq, const u32* only) {      
     HG_TRY(ensure_ap_tables(c, &use_recip));
     c->t_begin(KI_AP);
     // few queries with long lists: four times the threads per query (see k_ap)
-    const bool wide = nq * 2 < (i64)c->n_cu * 8 && g.R > 2 * AP_CHUNK && c->opt_ap_wide;
+    const bool wide = nq * 2 < (i64)c->n_cu * 8 && g.R > 2 * AP_CHUNK && c->opt.ap_wide;
     if (nq > 0 && wide)
         hipLaunchKernelGGL(k_ap<512>, dim3((unsigned)nq), dim3(512), 0, c->stream, c->mbits.as<u64>() + (size_t)q0 * c->RW, c->RW, g.R,
                            c->shapes.as<ApShape>(), use_recip ? c->ap_recip.as<double>() : (const double*)nullptr,
@@ -923,6 +941,57 @@ int hg_set_stream(hg_ctx* c, void* stream) {
     return HG_OK;
 }
 
+// Every configuration key but the three hg_set_option handles first: the Options field it sets and the values it takes -- a flag
+// takes any value (nonzero = 1), a ranged key lo .. hi (else the text), select_packed any value as it is.
+namespace {
+struct OptionKey { const char* key; i64 Options::*field; bool flag; i64 lo, hi; const char* range; };
+constexpr i64 kMax = INT64_MAX;
+constexpr OptionKey flag(const char* k, i64 Options::*f) { return {k, f, true, 0, 1, nullptr}; }
+constexpr OptionKey ranged(const char* k, i64 Options::*f, i64 lo, i64 hi, const char* range) { return {k, f, false, lo, hi, range}; }
+const OptionKey kOptionKeys[] = {
+    ranged("target_units", &Options::target_units, 1, kMax, "target_units must be >= 1"),
+    ranged("min_segment", &Options::min_segment, 16, kMax, "min_segment must be >= 16"),
+    ranged("max_segments", &Options::max_segments, 1, kMax, "max_segments must be >= 1"),
+    ranged("sample_stride", &Options::sample_stride, 0, 1024, "sample_stride must be 0 (auto) .. 1024"),
+    ranged("guess_sigma", &Options::guess_sigma, 0, 64, "guess_sigma must be 0..64"),
+    ranged("cand_budget_x10", &Options::cand_budget_x10, 11, 1000, "cand_budget_x10 must be 11..1000"),
+    flag("second_bet", &Options::second_bet),
+    flag("crowd_probe", &Options::crowd_probe),
+    flag("select_mfma", &Options::select_mfma),
+    ranged("select_packed", &Options::select_packed, INT64_MIN, kMax, nullptr),
+    flag("compact_records", &Options::compact_records),
+    ranged("hist_mfma", &Options::hist_mfma, 0, 2, "hist_mfma must be 0, 1 or 2"),
+    ranged("rank_lds", &Options::rank_lds, 0, 2, "rank_lds must be 0, 1 or 2"),
+    ranged("rank_slices", &Options::rank_slices, 0, kMax, "rank_slices must be >= 0 (the smallest R it takes; 0: off)"),
+    ranged("rank_dense", &Options::rank_dense, 0, 2, "rank_dense must be 0 or 1 (2 is accepted and means 1)"),
+    ranged("rank_dense_gbm", &Options::rank_dense_gbm, -1, 1, "rank_dense_gbm must be -1, 0 or 1"),
+    ranged("dense_budget_mb", &Options::dense_budget_mb, 1, kMax, "dense_budget_mb must be >= 1"),
+    flag("all_rows_shortcut", &Options::all_rows_shortcut),
+    flag("fuse_ap", &Options::fuse_ap),
+    flag("inline_leftovers", &Options::inline_leftovers),
+    flag("ap_wide", &Options::ap_wide),
+    flag("ap_recip", &Options::ap_recip),
+#if HG_PROBES
+    ranged("probe_select", &Options::probe_select, INT64_MIN, kMax, nullptr),   // (libhashgan_amd_probe.so only: python -m hashgan_amd.build --probes)
+#endif
+    flag("stage_sync", &Options::stage_sync),
+    flag("defer_verdict", &Options::defer_verdict),
+    flag("staged_lists", &Options::staged_lists),
+    flag("step_graph", &Options::step_graph),
+    ranged("step_streams", &Options::step_streams, 1, 2, "step_streams must be 1 or 2"),
+    ranged("timing_every", &Options::timing_every, 1, 1024, "timing_every must be 1..1024"),
+    flag("host_pack", &Options::host_pack),
+    ranged("keep_floats", &Options::keep_floats, 0, 2, "keep_floats must be 0, 1 or 2"),
+    ranged("real_mfma", &Options::real_mfma, 0, 2, "real_mfma must be 0, 1 or 2"),
+    flag("real_sample_half", &Options::real_sample_half),
+    flag("real_second_sample", &Options::real_second_sample),
+    flag("real_sort_lds", &Options::real_sort_lds),
+    flag("real_groups", &Options::real_groups),
+    flag("real_map_lists", &Options::real_map_lists),
+    ranged("real_whole_rounds", &Options::real_whole_rounds, 0, 8, "real_whole_rounds must be 0 .. 8"),
+};
+}  // namespace
+
 int hg_set_option(hg_ctx* c, const char* key, int64_t value) {
     if (!c || !key) return fail(HG_ERR_ARG, "hg_set_option: null argument");
     if (!strcmp(key, "handicap_next_bet")) {           // test hook: not a configuration change (a blind hg_map_begin stays blind -- and loses)
@@ -930,140 +999,39 @@ int hg_set_option(hg_ctx* c, const char* key, int64_t value) {
         c->handicap_next = value;
         return HG_OK;
     }
-    c->cfg_epoch++;                                    // whatever changes: a captured step is rebuilt
-    if (!strcmp(key, "step_graph")) { c->opt_graph = value != 0; return HG_OK; }
-    if (!strcmp(key, "step_streams")) {                // hg_map_begin: slot 1's blind steps on a second stream (2) or on the context's (1)
-        if (value < 1 || value > 2) return fail(HG_ERR_ARG, "step_streams must be 1 or 2");
-        c->opt_step_streams = value;
+    if (!strcmp(key, "optimistic")) {                  // (a fresh start: the latches of lost bets are cleared)
+        c->opt.optimistic = value != 0;
+        c->bet_consecutive_fail = c->shard_bet_fail = 0;
+        c->cfg_epoch++;
         return HG_OK;
     }
-    if (!strcmp(key, "stage_sync")) { c->stage_sync = value != 0; return HG_OK; }
-    if (!strcmp(key, "defer_verdict")) { c->defer_verdict = value != 0; return HG_OK; }
-    if (!strcmp(key, "target_units")) {
-        if (value < 1) return fail(HG_ERR_ARG, "target_units must be >= 1");
-        c->target_units = value;
-    } else if (!strcmp(key, "min_segment")) {
-        if (value < 16) return fail(HG_ERR_ARG, "min_segment must be >= 16");
-        c->min_segment = value;
-    } else if (!strcmp(key, "max_segments")) {
-        if (value < 1) return fail(HG_ERR_ARG, "max_segments must be >= 1");
-        c->opt_max_segments = value;
-    } else if (!strcmp(key, "optimistic")) {
-        c->opt_enable = value != 0;
-        c->opt_consecutive_fail = c->shard_bet_fail = 0;
-    } else if (!strcmp(key, "sample_stride")) {
-        if (value < 0 || value > 1024) return fail(HG_ERR_ARG, "sample_stride must be 0 (auto) .. 1024");
-        c->opt_stride = value;
-    } else if (!strcmp(key, "guess_sigma")) {
-        if (value < 0 || value > 64) return fail(HG_ERR_ARG, "guess_sigma must be 0..64");
-        c->opt_sigma = value;
-    } else if (!strcmp(key, "staged_lists")) {
-        c->staged_lists = value != 0;
-    } else if (!strcmp(key, "all_rows_shortcut")) {
-        c->opt_all_rows = value != 0;
-    } else if (!strcmp(key, "timing_every")) {
-        if (value < 1 || value > 1024) return fail(HG_ERR_ARG, "timing_every must be 1..1024");
-        c->opt_timing_every = value;
-    } else if (!strcmp(key, "cap_boost")) {
+    if (!strcmp(key, "cap_boost")) {                   // run state: lost bets escalate it, every load resets it
         if (value < 1 || value > 4096) return fail(HG_ERR_ARG, "cap_boost must be 1..4096");
         // a caller that WIDENS the slices is retrying a lost sharded bet within the same call (sharded.evaluate_shard): that attempt
         // does not count towards hg_bet_eligible's "two calls in a row lost their bets"
         if (value > c->cap_boost && c->shard_bet_fail > 0) c->shard_bet_fail--;
         c->cap_boost = value;
-    } else if (!strcmp(key, "crowd_probe")) {
-        c->opt_crowd_probe = value != 0;
-    } else if (!strcmp(key, "fuse_ap")) {
-        c->opt_fuse_ap = value != 0;
-    } else if (!strcmp(key, "rank_dense")) {
-        if (value < 0 || value > 2) return fail(HG_ERR_ARG, "rank_dense must be 0 or 1 (2 is accepted and means 1)");
-        c->opt_rank_dense = value;
-    } else if (!strcmp(key, "inline_leftovers")) {
-        c->opt_inline_leftovers = value != 0;
-    } else if (!strcmp(key, "rank_slices")) {
-        if (value < 0) return fail(HG_ERR_ARG, "rank_slices must be >= 0 (the smallest R it takes; 0: off)");
-        c->opt_rank_slices = value;
-    } else if (!strcmp(key, "rank_dense_gbm")) {
-        if (value < -1 || value > 1) return fail(HG_ERR_ARG, "rank_dense_gbm must be -1, 0 or 1");
-        c->opt_rank_dense_gbm = value;
-    } else if (!strcmp(key, "dense_budget_mb")) {
-        if (value < 1) return fail(HG_ERR_ARG, "dense_budget_mb must be >= 1");
-        c->opt_dense_budget_mb = value;
-    } else if (!strcmp(key, "select_packed")) {
-        c->opt_select_packed = value;
-    } else if (!strcmp(key, "rank_lds")) {
-        // the bet's rank stage with a query's records resident in LDS: 2 = k_rank_lean where it applies, else k_rank_cnt (default);
-        // 1 = k_rank_cnt only; 0 = neither: k_rank_fused walks the records in global memory
-        if (value < 0 || value > 2) return fail(HG_ERR_ARG, "rank_lds must be 0, 1 or 2");
-        c->opt_rank_cnt = value >= 1;
-        c->opt_rank_lean = value >= 2;
-    } else if (!strcmp(key, "host_pack")) {
-        c->opt_host_pack = value != 0;
-    } else if (!strcmp(key, "keep_floats")) {
-        if (value < 0 || value > 2) return fail(HG_ERR_ARG, "keep_floats must be 0, 1 or 2");
-        c->opt_keep_floats = value;
-    } else if (!strcmp(key, "compact_records")) {
-        c->opt_compact = value != 0;
-    } else if (!strcmp(key, "second_bet")) {
-        c->opt_second_bet = value != 0;
-    } else if (!strcmp(key, "hist_mfma")) {
-        if (value < 0 || value > 2) return fail(HG_ERR_ARG, "hist_mfma must be 0, 1 or 2");
-        c->opt_hist_mfma = value;
-    } else if (!strcmp(key, "ap_recip")) {
-        c->opt_ap_recip = value != 0;
-    } else if (!strcmp(key, "select_mfma")) {
-        c->opt_select_mfma = value != 0;
-#if HG_PROBES
-    } else if (!strcmp(key, "probe_select")) {         // (libhashgan_amd_probe.so only: python -m hashgan_amd.build --probes)
-        c->opt_probe = value;
-#endif
-    } else if (!strcmp(key, "real_mfma")) {
-        if (value < 0 || value > 2) return fail(HG_ERR_ARG, "real_mfma must be 0, 1 or 2");
-        c->opt_real_mfma = value;
-    } else if (!strcmp(key, "real_sample_half")) {
-        c->opt_real_sample_h = value != 0;
-    } else if (!strcmp(key, "real_second_sample")) {
-        c->opt_real_second = value != 0;
-    } else if (!strcmp(key, "ap_wide")) {
-        c->opt_ap_wide = value != 0;
-    } else if (!strcmp(key, "real_map_lists")) {
-        c->opt_real_map_lists = value != 0;
-    } else if (!strcmp(key, "real_whole_rounds")) {
-        if (value < 0 || value > 8) return fail(HG_ERR_ARG, "real_whole_rounds must be 0 .. 8");
-        c->opt_real_rounds = value;
-    } else if (!strcmp(key, "real_groups")) {
-        c->opt_real_groups = value != 0;
-    } else if (!strcmp(key, "real_sort_lds")) {
-        c->opt_real_sort_lds = value != 0;
-    } else if (!strcmp(key, "cand_budget_x10")) {
-        if (value < 11 || value > 1000) return fail(HG_ERR_ARG, "cand_budget_x10 must be 11..1000");
-        c->cand_budget_x10 = value;
-    } else {
-        return fail(HG_ERR_ARG, "hg_set_option: unknown key '%s'", key);
+        c->cfg_epoch++;
+        return HG_OK;
     }
-    return HG_OK;
+    for (const OptionKey& k : kOptionKeys) {
+        if (strcmp(key, k.key)) continue;
+        if (!k.flag && (value < k.lo || value > k.hi)) return fail(HG_ERR_ARG, "%s", k.range);
+        c->opt.*k.field = k.flag ? value != 0 : value;
+        c->cfg_epoch++;                                // whatever changes: a captured step is rebuilt
+        return HG_OK;
+    }
+    return fail(HG_ERR_ARG, "hg_set_option: unknown key '%s'", key);
 }
 
 // Work buffers only grow (a big call leaves gigabytes behind for the next one to reuse); hg_trim
-// gives everything but the resident tables back.
+// gives everything but the loaded tables back (the images and AP tables are rebuilt on their next use).
 int hg_trim(hg_ctx* c) {
     if (!c) return fail(HG_ERR_ARG, "hg_trim: null context");
     HG_TRY(c->use());
     HG_TRY(c->sync());
-    DevBuf* work[] = {&c->hist, &c->seglt, &c->segtie, &c->sl_start, &c->sl_tie, &c->sl_cnt, &c->cand, &c->out_idx,
-                      &c->out_dist, &c->stage_in, &c->hwq, &c->samp, &c->sortA, &c->sortB, &c->gtab, &c->scores, &c->bigq, &c->mbits2,
-                      &c->dbx, &c->qx, &c->dbfx, &c->dbfb, &c->sampx, &c->dbytes};   // the images are rebuilt on demand
-    for (auto* d : work) d->release();
-    c->release_step_b();                               // (hg_map_begin's second workspace: its next step reserves it again)
-    c->dbfx_valid = false;
-    c->dbfb_valid = false;
-    for (auto& d : c->gathered) d.release();
-    for (auto& d : c->scratch) d.release();
-    c->gath_idx.release(); c->gath_dist.release();
-    c->obuf[0].release(); c->obuf[1].release();
-    c->dbx_valid = c->qx_valid = false;
-    c->dbx8.release(); c->dbx8_valid = false;
-    c->dbx3.release(); c->dbx3_valid = false;
-    c->dbx4.release(); c->dbx4_valid = false;
+    c->for_each_buf([](DevBuf& d, BufClass k) { if (k != BUF_TABLE) d.release(); });
+    c->forget_derived();
     if (c->sub) { hg_ctx* s = c->sub; c->sub = nullptr; (void)hg_destroy(s); }
     c->stage &= (ST_DB | ST_Q);
     c->lists_valid = false;
@@ -1092,11 +1060,11 @@ int hg_release_cache(void) {
 
 int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     if (!c || !key || !value) return fail(HG_ERR_ARG, "hg_get_stat: null argument");
-    if (!strcmp(key, "optimistic_runs")) *value = c->opt_runs;
-    else if (!strcmp(key, "optimistic_fallbacks")) *value = c->opt_fallbacks;
-    else if (!strcmp(key, "optimistic_requeried")) *value = c->opt_requeried;
-    else if (!strcmp(key, "optimistic_rebets")) *value = c->opt_rebets;
-    else if (!strcmp(key, "rank_leftovers")) *value = c->opt_leftover;
+    if (!strcmp(key, "optimistic_runs")) *value = c->bet_runs;
+    else if (!strcmp(key, "optimistic_fallbacks")) *value = c->bet_fallbacks;
+    else if (!strcmp(key, "optimistic_requeried")) *value = c->bet_requeried;
+    else if (!strcmp(key, "optimistic_rebets")) *value = c->bet_rebets;
+    else if (!strcmp(key, "rank_leftovers")) *value = c->rank_leftovers;
     else if (!strcmp(key, "select_variant")) *value = c->last_select;
     else if (!strcmp(key, "rank_variant")) *value = c->last_rank;
     else if (!strcmp(key, "ap_fused")) *value = c->ap_fused ? 1 : 0;
@@ -1109,20 +1077,7 @@ int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     // how the last real-valued ranking ran: bit 0 = bf16 filter + exact rescoring, bit 1 = ranked by the LDS-resident kernel,
     // bit 2 = record lists beyond the LDS ordered group by group (k_real_group_*), bit 3 = the filter ran in IEEE half (else bfloat16)
     else if (!strcmp(key, "real_path")) *value = (c->real_filtered ? 1 : 0) | (c->real_lds_ranked ? 2 : 0) | (c->real_grouped ? 4 : 0) | (c->real_filtered && c->dbfb_half ? 8 : 0);
-    else if (!strcmp(key, "device_bytes")) {
-        DevBuf* all[] = {&c->db, &c->dblab, &c->qc, &c->qlab, &c->hist, &c->hown, &c->posbase, &c->seglt, &c->segtie,
-                         &c->t, &c->tguess, &c->sstar, &c->cnt_lt, &c->quota, &c->tie_before, &c->n_lt, &c->err,
-                         &c->sl_start, &c->sl_tie, &c->sl_cnt, &c->tot, &c->failq, &c->cand, &c->out_idx, &c->out_dist,
-                         &c->mbits, &c->shapes, &c->ap, &c->rel, &c->stage_in, &c->badcnt, &c->qbad, &c->flist, &c->hwq,
-                         &c->dbf, &c->qf, &c->samp, &c->thr, &c->sortA, &c->sortB, &c->gtab, &c->scores, &c->dbx, &c->qx, &c->bigq, &c->mbits2,
-                         &c->dbfx, &c->dbfb, &c->thr2, &c->xmax2, &c->dbx8, &c->dbx3, &c->dbx4, &c->sampx, &c->ap_recip, &c->part, &c->dbytes, &c->outblk, &c->beyond, &c->cntq, &c->hist2, &c->krows,
-                         &c->comm_tmp, &c->gath_idx, &c->gath_dist, &c->obuf[0], &c->obuf[1]};
-        i64 total = 0;
-        for (auto* d : all) if (!d->borrowed) total += (i64)d->cap;
-        for (auto& d : c->gathered) if (!d.borrowed) total += (i64)d.cap;
-        for (auto& d : c->scratch) if (!d.borrowed) total += (i64)d.cap;
-        *value = total;
-    }
+    else if (!strcmp(key, "device_bytes")) *value = device_bytes(c);
 #ifdef HG_RANK_PROFILE
 #ifdef HG_RANK_PROFILE                        // (tools/rank_phase_profile.py: where k_rank_cnt left its phase timestamps)
     else if (!strcmp(key, "dbg_hwq_ptr")) *value = (int64_t)(uintptr_t)c->hwq.p;

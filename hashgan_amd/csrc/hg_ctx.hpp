@@ -217,13 +217,91 @@ void build_shape(int n, ApShape& sh);           // NumPy's pairwise-summation tr
 
 struct Pending { int id; hipEvent_t a, b; };
 
-struct hg_ctx {
+// The engine's options: one field per key of hg_set_option, named after the key, its default the initialiser.  The keys'
+// accepted values are in hg_set_option's table (hg_core.hip); DESIGN.md section 9 lists them with the tests that set them.
+struct Options {
+    // segments of the pair passes
+    i64 target_units = 16384;      // wavefront-sized units the pair passes are split into (segment count)
+    i64 min_segment = 256;         // shortest segment, rows
+    i64 max_segments = 2048;       // cap on the segment count (few queries)
+    // the one-shot bet
+    i64 optimistic = 1;            // one-shot calls may bet on a sampled threshold (verified, exact fallback)
+    i64 sample_stride = 0;         // sampling stride in row batches, 0 = auto
+    i64 guess_sigma = 5;           // safety margin of the guess, in standard deviations of the sample count (5: a query loses its bet
+                                   // about once in 3 million -- it is then rerun alone; 6 -> 5 keeps ~4 % fewer surplus records)
+    i64 cand_budget_x10 = 40;      // optimistic record budget per query, in tenths of R
+    i64 second_bet = 1;            // a lost one-shot bet is retried once with a wider margin before the exact sequence
+    i64 crowd_probe = 1;           // the first bet on a database measures how its near rows crowd (k_guess_direct's probe)
+    // kernels
+    i64 select_mfma = 1;           // optimistic select: 1 = matrix-core kernel (k_select_mx), 0 = vector-ALU k_select
+    i64 select_packed = 3;         // several distances per MFMA accumulator: 3 = k_select_mx3 (<= 64 bits, three) / k_select_mx4 (65..128 bits, two) with
+                                   // the batched drain, for one-byte records; anything else = k_select_mx (one distance per accumulator)
+    i64 compact_records = 1;       // one-byte compact records (matrix-core select, no lists wanted)
+    i64 hist_mfma = 2;             // histograms (sampled pass; full pass of the one-shot exact sequence) on the matrix cores -- 2: the integer instruction
+                                   // delivers the counter address (k_hist_i8, codes of <= 128 bits), 1: fp4 distances (k_hist_mx), 0: vector ALU
+    i64 rank_lds = 2;              // the bet's rank stage keeps a query's records in LDS: >= 1 the per-thread counting sort (k_rank_cnt) where it
+                                   // applies, 2 its lean form (k_rank_lean) for one-byte records without lists, <= 256 slices, <= 1024 pieces per query
+    i64 rank_slices = 7000;        // a bet's one-byte records with R >= this are ranked by k_rank_dense<slices>; 0: off (k_rank_cnt's tiles).
+                                   // Q = 10k, N = 1M: R = 5000 0.274 ms against k_rank_lean's 0.139 (fixed costs of the counter columns); R = 8000 0.318 / 0.372; R = 50 000 1.38 / 3.83
+    i64 rank_dense = 1;            // N/8 < R <= N on one shard through the byte matrix (k_dense_bytes + k_rank_dense, hg_rank_dense.hpp; codes of <= 126 bits, <= 128 classes); 0: off
+    i64 rank_dense_gbm = -1;       // k_rank_dense's bitmap in global memory (1) or LDS (0, where it fits); -1: by the blocks per CU
+    i64 dense_budget_mb = 16384;   // the byte matrix D holds at most this much (queries are chunked)
+    i64 all_rows_shortcut = 1;     // R = N: skip histogram and plan (every row is a member)
+    i64 fuse_ap = 1;               // AP from the rank kernel's epilogue (k_rank_cnt: the bitmap is still in LDS)
+    i64 inline_leftovers = 1;      // queries the fused rank kernel declined are ranked within the step's stream
+    i64 ap_wide = 1;               // k_ap with 512 threads per query when the queries are few and their lists long (0: always 128)
+    i64 ap_recip = 1;              // k_ap divides through the table of reciprocals (bit for bit the division; 0: divide)
+    i64 probe_select = 0;          // measurement probes of the matrix-core select kernels (SelArgs::probe; a key of the HG_PROBES build only)
+    // call protocol
+    i64 stage_sync = 1;            // staged calls synchronise the stream before returning
+    i64 defer_verdict = 0;         // hg_rank does not wait for the bet's verdict; hg_bet_verdict reads it later
+    i64 staged_lists = 1;          // staged hg_select materialises the idx/dist lists
+    i64 step_graph = 0;            // 1 = hg_map captures and replays its step (see run_oneshot)
+    i64 step_streams = 2;          // 2 = hg_map_begin's slot-1 blind steps on stream_b, 1 = every step on the context's stream
+    i64 timing_every = 1;          // level-1 timing records its events on every n-th one-shot step only
+    // hand-over of float32 / int64 arrays
+    i64 host_pack = 1;             // packed on the host by a thread pool before the upload (hg_host_pack.hpp); 0 = upload the raw arrays, pack on the GPU
+    i64 keep_floats = 2;           // database float table on the GPU -- 0 never, 1 always, 2 only if it is not a +-1 code
+    // real-valued ranking
+    i64 real_mfma = 2;             // 2 = bf16 filter on the matrix cores + exact rescoring of the survivors, 1 = exact float32 MFMA pass, 0 = vector ALU
+    i64 real_sample_half = 1;      // the sampled cut's scores in the filter's 16-bit arithmetic (k_real_sample_h) instead of exact float32 chains
+    i64 real_second_sample = 1;    // a second, counting sample four times as large tightens the sampled cut
+    i64 real_sort_lds = 1;         // sort + finish of the filter path in one LDS-resident kernel when the records fit
+    i64 real_groups = 1;           // record lists beyond the LDS are split by score range and ordered group by group in LDS (0: the four radix passes)
+    i64 real_map_lists = 0;        // hg_map_real also writes the ranked idx / score lists (hg_get_topr_real after it); 0: match bits and APs only, like hg_map
+    i64 real_whole_rounds = 3;     // the no-cut float32 MFMA pass (k_real_select_mx) cuts the database so that its blocks fill whole rounds of this many
+                                   // per CU; 0: the plain geometry
+};
+
+// What a device buffer of the context holds (hg_ctx::for_each_buf): hg_trim keeps the tables and frees the rest.
+enum BufClass {
+    BUF_TABLE,      // loaded by hg_set_*
+    BUF_DERIVED,    // built from the tables or R on first use, valid while a key says so (hg_ctx::forget_derived resets every key)
+    BUF_WORK,       // written by a call, reserved again by the next one
+};
+
+// The buffers a bet writes: the context's own (hg_ctx inherits them) and a second set (hg_ctx::ws_b) for the slot-1 steps of
+// hg_map_begin on the second stream.
+struct StepBufs {
+    DevBuf hist, hown, posbase, t, tguess, sstar, cnt_lt, quota, tie_before, n_lt, err, sl_start, sl_tie, sl_cnt, tot, failq,
+           cand, out_idx, out_dist, mbits, ap, rel, qbad, bigq, hwq;
+    DevBuf outblk;             // [verdict 16 B][ap Q x 8][rel Q x 4]: err, ap and rel are views of it (ensure_out_block), so a call's results come home in ONE copy
+    i64 outblk_q = -1;         // the Q those views were cut for
+    template <class F> void for_each_step_buf(F&& f) {
+        for (DevBuf* d : {&hist, &hown, &posbase, &t, &tguess, &sstar, &cnt_lt, &quota, &tie_before, &n_lt, &err, &sl_start, &sl_tie,
+                          &sl_cnt, &tot, &failq, &cand, &out_idx, &out_dist, &mbits, &ap, &rel, &qbad, &bigq, &hwq})
+            f(*d, BUF_WORK);
+        f(outblk, BUF_DERIVED);
+    }
+};
+
+struct hg_ctx : StepBufs {
     int device = 0;
     int n_cu = 256;            // compute units of the device
     hipStream_t stream = nullptr;
     bool own_stream = true;    // false: the stream belongs to the caller (hg_set_stream) or to the parent context
-    bool stage_sync = true;    // staged calls synchronise the stream before returning
     unsigned stage = ST_NONE;
+    Options opt;
 
     // problem
     i64 N = 0, Q = 0, R = 0, n_total = 0;
@@ -233,39 +311,14 @@ struct hg_ctx {
     Geo geo{};
     i64 RW = 0;
 
-    // options
-    i64 target_units = 16384;
-    i64 min_segment = 256;
-    i64 opt_max_segments = 2048;   // "max_segments"
-    i64 opt_enable = 1;        // one-shot calls may bet on a sampled threshold (verified, exact fallback)
-    i64 opt_stride = 0;        // sampling stride in row batches, 0 = auto
-    i64 opt_sigma = 5;         // safety margin of the guess, in standard deviations of the sample count (5: a query loses its bet
-                               // about once in 3 million -- it is then rerun alone; 6 -> 5 keeps ~4 % fewer surplus records)
-    i64 staged_lists = 1;      // staged hg_select materialises the idx/dist lists
-    i64 cand_budget_x10 = 40;  // optimistic record budget per query, in tenths of R
-    i64 opt_select_mfma = 1;   // optimistic select: 1 = matrix-core kernel (k_select_mx), 0 = vector-ALU k_select
-    i64 opt_probe = 0;         // measurement probes of the matrix-core select kernels (SelArgs::probe)
-    i64 opt_select_packed = 3; // several distances per MFMA accumulator: 3 = k_select_mx3 (<= 64 bits, three) / k_select_mx4 (65..128 bits, two) with
-                               // the batched drain, for one-byte records; anything else = k_select_mx (one distance per accumulator)
-    i64 opt_all_rows = 1;      // R = N: skip histogram and plan (every row is a member)
-    i64 opt_rank_cnt = 1;      // the bet's rank stage keeps a query's records in LDS and ranks them with the per-thread counting sort (k_rank_cnt / k_rank_lean) where it applies
-    i64 opt_rank_lean = 1;     // "rank_lean": ... in its lean form (k_rank_lean) for one-byte records without lists, <= 256 slices, <= 1024 pieces per query
     i64 real_grouped = 0;      // stat: the last real-valued ranking ordered its record lists group by group (k_real_group_*)
-    i64 opt_real_groups = 1;   // "real_groups": record lists beyond the LDS are split by score range and ordered group by group in LDS (0: the four radix passes)
     i64 real_cap_boost = 1;    // the same for the real-valued ranking's slices (run_real)
     bool crowd_probed = false; // the first bet on this database has measured how its near rows crowd (k_guess_direct's probe)
     i64 crowd_x100 = 0;        // stat "crowding_x100": that measure, x 100 (~200: rows in random order; ~100 x classes: stored class by class)
-    i64 opt_crowd_probe = 1;   // "crowd_probe"
     i64 cap_boost = 1;         // slice capacity multiplier a lost bet escalated to on this database (run_oneshot); 1 after every load
-    i64 opt_rank_dense = 1;    // "rank_dense": N/8 < R <= N on one shard through the byte matrix (k_dense_bytes + k_rank_dense, hg_rank_dense.hpp; codes of <= 126 bits, <= 128 classes); 0: off
     bool leftovers_expected = false;   // the last fused step on this context left queries to the general kernel
     bool last_leftovers_inline = false;   // (the last finished step did: finish_leftovers)
     bool leftovers_inline = false;     // ... and this step ranked its own within the stream (launch_rank_slices with the flags)
-    i64 opt_inline_leftovers = 1;      // "inline_leftovers"
-    i64 opt_rank_slices = 7000;    // "rank_slices": a bet's one-byte records with R >= this are ranked by k_rank_dense<slices>; 0: off (k_rank_cnt's tiles).
-                                   // Q = 10k, N = 1M: R = 5000 0.274 ms against k_rank_lean's 0.139 (fixed costs of the counter columns); R = 8000 0.318 / 0.372; R = 50 000 1.38 / 3.83
-    i64 opt_rank_dense_gbm = -1;   // "rank_dense_gbm": k_rank_dense's bitmap in global memory (1) or LDS (0, where it fits); -1: by the blocks per CU
-    i64 opt_dense_budget_mb = 16384;   // "dense_budget_mb": the byte matrix D holds at most this much (queries are chunked)
     bool dense_rank = false;   // run state of enqueue_all_rows: rank through the byte matrix
 
     // run state
@@ -274,41 +327,27 @@ struct hg_ctx {
     bool lists_valid = false;
     u32 cap = 0;               // optimistic slice capacity
     i64 crow = 0;              // record-row stride
-    i64 opt_runs = 0, opt_fallbacks = 0, opt_requeried = 0;
+    i64 bet_runs = 0, bet_fallbacks = 0, bet_requeried = 0;   // stats "optimistic_runs", "optimistic_fallbacks", "optimistic_requeried"
     int last_select = 0;       // stat "select_variant": 1 k_select, 2 k_select_dense, 3 k_select_mx, 5 k_select_mx3, 6 k_select_mx4
     int last_rank = 0;         // stat "rank_variant": 1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>
-    i64 opt_leftover = 0;      // stat "rank_leftovers": queries of fused steps that k_rank_cnt left to the general rank kernel
-    int opt_consecutive_fail = 0;   // one-shot bets lost in a row (this context only)
+    i64 rank_leftovers = 0;    // stat "rank_leftovers": queries of fused steps that k_rank_cnt left to the general rank kernel
+    int bet_consecutive_fail = 0;   // one-shot bets lost in a row (this context only)
     int shard_bet_fail = 0;         // sharded bets lost in a row: identical on every rank by construction
-    hg_ctx* sub = nullptr;     // child context (shares the database) that reruns single lost queries exactly
+    hg_ctx* sub = nullptr;     // child context (shares the database) that reruns single lost queries exactly (requery_child)
     bool is_sub = false;
 
-    // device state
-    DevBuf db, dblab, qc, qlab;
-    DevBuf beyond;             // one word: hg_guess_finish met a query whose cut lies beyond the planes its owner was sent
-    DevBuf dbx, qx;            // fp4 images of db / qc in MFMA fragment order for k_select_mx (built on first use)
-    bool dbx_valid = false, qx_valid = false;
-    DevBuf dbx8;               // i8 image of the database codes in A-fragment order (k_hist_i8), built on first use
-    bool dbx8_valid = false;
-    DevBuf dbx3;               // fp4 image for k_select_mx3 (48-row supertiles, three rows per accumulator), built on first use
-    bool dbx3_valid = false;
-    DevBuf dbx4;               // fp4 image for k_select_mx4 (32-row supertiles, two rows per accumulator; codes of 65..128 bits), built on first use
-    bool dbx4_valid = false;
+    // device state (the buffers themselves: for_each_buf)
+    bool dbx_valid = false, qx_valid = false, dbx8_valid = false, dbx3_valid = false, dbx4_valid = false;
     bool direct_rank = false;  // R = N: k_rank_fused computes distance and match bit per row itself (no records)
-    i64 opt_hist_mfma = 2;     // "hist_mfma": histograms (sampled pass; full pass of the one-shot exact sequence) on the matrix cores -- 2: the integer instruction delivers the counter address (k_hist_i8, codes of <= 128 bits), 1: fp4 distances (k_hist_mx), 0: vector ALU
     bool hist_pairs = false;   // the last FULL histogram pass ran per segment pair (k_hist_mx)
     bool exact_mx = false;     // the matrix-core select runs with the EXACT threshold (hg_hist + k_plan) instead of a guess
     bool rec8 = false;         // the record rows hold one-byte compact records (matrix-core select, no lists wanted)
-    i64 opt_compact = 1;       // "compact_records": allow them
-    i64 opt_second_bet = 1;    // "second_bet": a lost one-shot bet is retried once with a wider margin before the exact sequence
-    i64 opt_rebets = 0;
+    i64 bet_rebets = 0;        // stat "optimistic_rebets"
     bool err_zeroed = false;   // the guess kernel of a one-shot bet already cleared err
     // AP from the rank kernel's epilogue (k_rank_cnt: the bitmap is still in LDS) -- one launch less per step, and the general
     // rank kernel for the queries k_rank_cnt declines is launched only when the step's download says there are any
-    i64 opt_fuse_ap = 1;       // "fuse_ap"
     bool fuse_ap = false;      // request of the current enqueue (hg_map's bet)
     bool ap_fused = false;     // the last launch_rank left the AP of every query it ranked in c->ap / c->rel, leftovers counted in err[1]
-    i64 defer_verdict = 0;     // hg_rank does not wait for the bet's verdict; hg_bet_verdict reads it later
     bool verdict_pending = false, verdict_known = false;
     int verdict_flag = 0;
     // pinned landing zone for a one-shot call's results: AP, hit counts and the lost-bet flag come back with the
@@ -332,36 +371,16 @@ struct hg_ctx {
     //   stream_b  waits, before the step, for everything on the context's stream but a blind slot-0 step in flight: ev_pre
     //             (recorded just before that step, while pre_valid) or else ev_fork at the stream's tail;
     //   stream    waits for stream_b's work (b_ev, while b_open) before anything but hg_map_begin / hg_map_end is enqueued (use()).
-    struct StepBufs {
-        DevBuf hist, hown, posbase, t, tguess, sstar, cnt_lt, quota, tie_before, n_lt, err, sl_start, sl_tie, sl_cnt, tot, failq,
-               cand, out_idx, out_dist, mbits, ap, rel, qbad, bigq, hwq, outblk;
-        i64 outblk_q = -1;
-    } ws_b;
+    StepBufs ws_b;
     hipStream_t stream_b = nullptr;
     hipEvent_t ev_pre = nullptr, ev_fork = nullptr, b_ev = nullptr;
     bool pre_valid = false, b_open = false;
     bool swapped = false;      // ws_b and stream_b are swapped in (a slot-1 step is being enqueued)
-    i64 opt_step_streams = 2;  // "step_streams": 2 = slot 1's blind steps on stream_b, 1 = every step on the context's stream
     i64 map_overlapped = 0;    // stat "map_overlapped_steps": blind steps enqueued on stream_b
     void swap_step() {
-        StepBufs& w = ws_b;
+        std::swap(static_cast<StepBufs&>(*this), ws_b);
         std::swap(stream, stream_b);
-        std::swap(hist, w.hist); std::swap(hown, w.hown); std::swap(posbase, w.posbase); std::swap(t, w.t);
-        std::swap(tguess, w.tguess); std::swap(sstar, w.sstar); std::swap(cnt_lt, w.cnt_lt); std::swap(quota, w.quota);
-        std::swap(tie_before, w.tie_before); std::swap(n_lt, w.n_lt); std::swap(err, w.err); std::swap(sl_start, w.sl_start);
-        std::swap(sl_tie, w.sl_tie); std::swap(sl_cnt, w.sl_cnt); std::swap(tot, w.tot); std::swap(failq, w.failq);
-        std::swap(cand, w.cand); std::swap(out_idx, w.out_idx); std::swap(out_dist, w.out_dist); std::swap(mbits, w.mbits);
-        std::swap(ap, w.ap); std::swap(rel, w.rel); std::swap(qbad, w.qbad); std::swap(bigq, w.bigq); std::swap(hwq, w.hwq);
-        std::swap(outblk, w.outblk); std::swap(outblk_q, w.outblk_q);
         swapped = !swapped;
-    }
-    void release_step_b() {
-        StepBufs& w = ws_b;
-        DevBuf* all[] = {&w.hist, &w.hown, &w.posbase, &w.t, &w.tguess, &w.sstar, &w.cnt_lt, &w.quota, &w.tie_before, &w.n_lt, &w.err,
-                         &w.sl_start, &w.sl_tie, &w.sl_cnt, &w.tot, &w.failq, &w.cand, &w.out_idx, &w.out_dist, &w.mbits, &w.ap, &w.rel,
-                         &w.qbad, &w.bigq, &w.hwq, &w.outblk};
-        for (auto* d : all) d->release();
-        w.outblk_q = -1;
     }
     unsigned long long map_warm_cfg = 0, map_warm_epoch = 0;   // configuration of the last synchronous hg_map that won its bet outright
     i64 map_warm_R = -1;
@@ -373,45 +392,19 @@ struct hg_ctx {
     struct QStage { void* pin = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; } qstage[2];
     int qstage_next = 0;
     bool ap_staged = false;
-    DevBuf hist, hown, posbase, seglt, segtie;
-    DevBuf t, tguess, sstar, cnt_lt, quota, tie_before, n_lt, err;
-    DevBuf sl_start, sl_tie, sl_cnt, tot, failq;
-    DevBuf mbits2;             // hg_merge_ranked's output (swapped with mbits)
-    DevBuf part;               // hg_merge_ap_part's output: {AP, hits} of this rank's queries + its verdict
-    DevBuf obuf[2];            // owner-routed exchanges: [0] the blocks this rank sends (hg_pack_*_by_owner), [1] its answers as an owner (hg_guess_owned)
     bool ranked_local = false; // mbits holds this shard's bitmap in LOCAL rank order (hg_select_ranked)
-    DevBuf cand, out_idx, out_dist, mbits, shapes, ap_recip, ap, rel, stage_in, badcnt, qbad, flist, hwq, bigq;
-    DevBuf outblk;             // [verdict 16 B][ap Q x 8][rel Q x 4]: err, ap and rel are views of it (ensure_out_block), so a call's results come home in ONE copy
-    i64 outblk_q = -1;         // the Q those views were cut for
-    DevBuf dbytes;             // the byte matrix D[q][Npad] of the dense regime (k_dense_bytes)
-    DevBuf dbf, qf, samp, thr, sortA, sortB, scores, gtab;   // real-valued path
-    DevBuf dbfx;               // float features of the database in MFMA A-fragment order (k_real_select_mx), built on first use
-    bool dbfx_valid = false;
-    DevBuf sampx;              // float features of the sampled rows in MFMA A-fragment order (k_real_sample_mx), rebuilt per call
-    DevBuf cntq;               // real-valued path: the slices' record counts after the rescore, query-major [Q][S] (k_real_rank_lds reads a query's row in one piece)
-    DevBuf krows;              // real-valued path: the rows the filter kept, 4-byte row numbers [Q][S][cap] (k_real_select_bf writes, k_real_rescore reads)
-    DevBuf dbfb, thr2, xmax2;  // filter + rescore path (hg_real_bf.hpp): bf16 image of the database, lowered cuts, max row norm^2
-    bool dbfb_valid = false;
+    bool dbfx_valid = false, dbfb_valid = false;
     double real_expect = 0.0;  // rows per query the current real-valued attempt expects its cut to keep (real_attempt; picks the rescore's slices per wavefront)
-    bool dbfb_half = false;    // ... in IEEE half instead of bfloat16 (no feature of the database can overflow it: real_launch_select_bf)
-    DevBuf hist2;              // the second sample's counts [Q][RC_BINS] (k_real_sample_count)
-    i64 opt_real_second = 1;   // "real_second_sample": a second, counting sample four times as large tightens the sampled cut
-    i64 opt_real_rounds = 3;   // "real_whole_rounds": the no-cut float32 MFMA pass (k_real_select_mx) cuts the database so that its blocks fill whole rounds of this many per CU; 0: the plain geometry
-    i64 opt_real_map_lists = 0;   // "real_map_lists": hg_map_real also writes the ranked idx / score lists (hg_get_topr_real after it); 0: match bits and APs only, like hg_map
+    bool dbfb_half = false;    // dbfb is in IEEE half instead of bfloat16 (no feature of the database can overflow it: real_launch_select_bf)
     bool samp16 = false;       // the current attempt's sample scores are bfloat16 (k_real_sample_h -> k_real_guess_lds)
-    i64 opt_real_sample_h = 1; // "real_sample_half": the sampled cut's scores in the filter's 16-bit arithmetic (k_real_sample_h) instead of exact float32 chains
-    i64 opt_real_sort_lds = 1; // "real_sort_lds": sort + finish of the filter path in one LDS-resident kernel when the records fit
     bool real_no_cut = false;     // the current real_attempt takes every row (thr = -inf)
     bool real_filtered = false;   // the last real_select left unscored candidates that k_real_rescore completed
     i64 real_requeried = 0;       // queries that lost the first real-valued bet and were ranked again on their own (cumulative)
     i64 real_attempts = 0;        // statistics of the last real-valued ranking: attempts made (1 = the first bet held) ...
     i64 real_lds_ranked = 0;      // ... and whether the LDS-resident rank kernel produced its lists
-    i64 opt_real_mfma = 2;     // "real_mfma": 2 = bf16 filter on the matrix cores + exact rescoring of the survivors, 1 = exact float32 MFMA pass, 0 = vector ALU
     int bpad = 0;              // feature count padded to a multiple of 16 (0: no float tables loaded)
     i64 census_db[3] = {0, 0, 0}, census_q[3] = {0, 0, 0};
-    // hand-over of float32 / int64 arrays: packed on the host by a thread pool before the upload (hg_host_pack.hpp)
-    i64 opt_host_pack = 1;     // "host_pack": 0 = upload the raw arrays and pack on the GPU (k_pack_*)
-    i64 opt_keep_floats = 2;   // "keep_floats": database float table on the GPU -- 0 never, 1 always, 2 only if it is not a +-1 code
+    // hand-over of float32 / int64 arrays (options host_pack, keep_floats)
     hipStream_t stream2 = nullptr;   // the float table's uploads while the packing pool works (pack_on_host)
     hipEvent_t stream2_ev = nullptr;
     size_t fstage_cap = 0;
@@ -424,13 +417,55 @@ struct hg_ctx {
     bool real_lists_made = false;   // ... by the last attempt (hg_map_real skips them on the paths that rank in LDS)
     i64 shapes_for_R = -1;
     i64 recip_for_R = -1;      // ap_recip holds RN(1 / k) for k = 1 .. this
-    i64 opt_ap_recip = 1;      // "ap_recip": k_ap divides through the table of reciprocals (bit for bit the division; 0: divide)
-    i64 opt_ap_wide = 1;       // "ap_wide": k_ap with 512 threads per query when the queries are few and their lists long (0: always 128)
 
-    // collectives (RCCL over xGMI), one communicator per context; gathered[] are the landing zones of hg_allgather
+    // collectives (RCCL over xGMI), one communicator per context
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 1;
-    DevBuf gathered[4], scratch[4], comm_tmp, gath_idx, gath_dist;
+
+    // device buffers beyond the step's (StepBufs)
+    DevBuf db, dblab, qc, qlab;                 // the packed tables: database codes and label words, query codes and label words
+    DevBuf dbf, qf;                             // the float tables (hg_set_*_f32 with keep_floats)
+    DevBuf dbx, qx;            // fp4 images of db / qc in MFMA fragment order for k_select_mx (dbx_valid, qx_valid)
+    DevBuf dbx8;               // i8 image of the database codes in A-fragment order (k_hist_i8; dbx8_valid)
+    DevBuf dbx3;               // fp4 image for k_select_mx3 (48-row supertiles, three rows per accumulator; dbx3_valid)
+    DevBuf dbx4;               // fp4 image for k_select_mx4 (32-row supertiles, two rows per accumulator; codes of 65..128 bits; dbx4_valid)
+    DevBuf dbfx;               // float features of the database in MFMA A-fragment order (k_real_select_mx; dbfx_valid)
+    DevBuf dbfb, xmax2;        // filter + rescore path (hg_real_bf.hpp): 16-bit image of the database, max row norm^2 (dbfb_valid)
+    DevBuf shapes, ap_recip;   // k_ap's summation trees (shapes_for_R) and reciprocals (recip_for_R)
+    DevBuf seglt, segtie;
+    DevBuf mbits2;             // hg_merge_ranked's output (swapped with mbits)
+    DevBuf part;               // hg_merge_ap_part's output: {AP, hits} of this rank's queries + its verdict
+    DevBuf obuf[2];            // owner-routed exchanges: [0] the blocks this rank sends (hg_pack_*_by_owner), [1] its answers as an owner (hg_guess_owned)
+    DevBuf beyond;             // one word: hg_guess_finish met a query whose cut lies beyond the planes its owner was sent
+    DevBuf stage_in, badcnt;   // pack_on_device: the raw labels, the census counters
+    DevBuf flist;              // the lost queries a requery child reruns
+    DevBuf dbytes;             // the byte matrix D[q][Npad] of the dense regime (k_dense_bytes)
+    DevBuf samp, thr, sortA, sortB, scores, gtab;   // real-valued path
+    DevBuf sampx;              // float features of the sampled rows in MFMA A-fragment order (k_real_sample_mx), rebuilt per call
+    DevBuf cntq;               // real-valued path: the slices' record counts after the rescore, query-major [Q][S] (k_real_rank_lds reads a query's row in one piece)
+    DevBuf krows;              // real-valued path: the rows the filter kept, 4-byte row numbers [Q][S][cap] (k_real_select_bf writes, k_real_rescore reads)
+    DevBuf thr2;               // filter + rescore path: lowered cuts
+    DevBuf hist2;              // the second sample's counts [Q][RC_BINS] (k_real_sample_count)
+    DevBuf gathered[4], scratch[4], comm_tmp, gath_idx, gath_dist;   // hg_allgather's landing zones, hg_scratch, the collectives' own
+
+    // Every device buffer of the context, each once, with its class: hg_destroy, hg_trim and the stat "device_bytes" walk this.
+    template <class F> void for_each_buf(F&& f) {
+        for (DevBuf* d : {&db, &dblab, &qc, &qlab, &dbf, &qf}) f(*d, BUF_TABLE);
+        for (DevBuf* d : {&dbx, &qx, &dbx8, &dbx3, &dbx4, &dbfx, &dbfb, &xmax2, &shapes, &ap_recip}) f(*d, BUF_DERIVED);
+        for (DevBuf* d : {&seglt, &segtie, &mbits2, &part, &obuf[0], &obuf[1], &beyond, &stage_in, &badcnt, &flist, &dbytes, &samp, &thr,
+                          &sortA, &sortB, &scores, &gtab, &sampx, &cntq, &krows, &thr2, &hist2, &comm_tmp, &gath_idx, &gath_dist})
+            f(*d, BUF_WORK);
+        for (DevBuf& d : gathered) f(d, BUF_WORK);
+        for (DevBuf& d : scratch) f(d, BUF_WORK);
+        for_each_step_buf(f);
+        ws_b.for_each_step_buf(f);
+    }
+    // the keys of the BUF_DERIVED buffers: after this each is rebuilt on its next use
+    void forget_derived() {
+        dbx_valid = qx_valid = dbx8_valid = dbx3_valid = dbx4_valid = dbfx_valid = dbfb_valid = false;
+        shapes_for_R = recip_for_R = -1;
+        outblk_q = ws_b.outblk_q = -1;
+    }
 
     // one-shot step as a hipGraph: the bet's whole sequence (memsets, ~7 kernels, the result download) is captured the
     // second time hg_map sees the same problem and replayed afterwards -- one launch per step instead of ~15 enqueues,
@@ -445,7 +480,6 @@ struct hg_ctx {
         unsigned stage = 0; bool optimistic = false, lists_valid = false, ap_fused = false, rec8 = false; u32 cap = 0; i64 crow = 0, RW = 0; Geo geo{};
         std::vector<Pending> evs;          // event-record nodes inside the graph (kernel timing)
     } sg;
-    i64 opt_graph = 0;         // "step_graph": 1 = hg_map captures and replays its step (see run_oneshot); off by default
     unsigned long long cfg_epoch = 1;      // bumped by everything that changes what a step enqueues (tables, options, stream)
     bool capturing = false;
     i64 graph_replays = 0, graph_captures = 0;
@@ -475,9 +509,8 @@ struct hg_ctx {
         // 1: the select pass (the roofline kernel) and the step's span only -- every event pair costs the stream ~2-4 us
         // and only on one step in "timing_every" (the averages are over the sampled launches)
         return timing >= 2 || (timing == 1 && (id == KI_SELECT || id == KI_SELECT_MX || id == KI_STEP) &&
-                               (capturing || opt_timing_every <= 1 || t_seq % opt_timing_every == 0));
+                               (capturing || opt.timing_every <= 1 || t_seq % opt.timing_every == 0));
     }
-    i64 opt_timing_every = 1;  // "timing_every": level-1 timing records its events on every n-th one-shot step only
     i64 t_seq = 0;             // one-shot steps since timing was enabled
     // while a step is being captured the events become event-record nodes of the graph and stay with it
     std::vector<Pending>& t_list() { return capturing ? sg.evs : pending; }
@@ -543,7 +576,7 @@ struct hg_ctx {
     }
     // end of a staged call that only enqueued work: synchronise unless the caller orders everything on
     // one stream itself (hg_set_stream + stage_sync = 0, e.g. torch's current stream in sharded mode)
-    int stage_end() { return stage_sync ? sync() : HG_OK; }
+    int stage_end() { return opt.stage_sync ? sync() : HG_OK; }
     int check_launch(const char* what) {
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail(HG_ERR_HIP, "launch of %s failed: %s", what, hipGetErrorString(e));
@@ -567,6 +600,7 @@ inline int do_ap(hg_ctx* c) { return do_ap_range(c, 0, c->geo.Q); }
 int ensure_out_block(hg_ctx* c);                   // err / ap / rel as views of one block (before anything of the call is enqueued)
 int read_plan_flag(hg_ctx* c, int* flag);        // *err back to the host (synchronises)
 int launch_min_topr(hg_ctx* c, const u32* idx_all, const u8* dist_all, i64 n, int G);
+hg_ctx* requery_child(hg_ctx* c, i64 nF);       // c->sub, set up to rerun nF lost queries of c
 // hg_seq.hip
 int stage_ap_download(hg_ctx* c, void* dst = nullptr);   // {verdict, AP, hit counts} into pinned host memory behind everything enqueued so far (no synchronisation)
 void make_geometry(hg_ctx* c);

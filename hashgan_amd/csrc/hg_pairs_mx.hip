@@ -95,7 +95,7 @@ template <int NW, int LW> int launch_select_mx3_t(hg_ctx* c) {
     if (L.total > 64 * 1024)
         HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_select_mx3<NW, LW>), hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
     SelArgs a{c->exact_mx ? c->t.as<int>() : c->tguess.as<int>(), c->sl_start.as<u32>(), c->sl_tie.as<u32>(), c->sl_cnt.as<u32>(),
-              c->failq.as<u32>(), c->cap, c->crow, 1, c->sstar.as<int>(), (int)c->opt_probe};
+              c->failq.as<u32>(), c->cap, c->crow, 1, c->sstar.as<int>(), (int)c->opt.probe_select};
     c->t_begin(KI_SELECT_MX);
     hipLaunchKernelGGL((k_select_mx3<NW, LW>), dim3(padded_grid(g.nBlk)), dim3(64 * M3_WPB), (size_t)L.total, c->stream, c->qc.as<u32>(),
                        c->qlab.as<u64>(), c->qx.as<u8>(), c->db.as<u32>(), c->dbx3.as<u8>(), c->dblab.as<u64>(), a,
@@ -144,7 +144,7 @@ template <int NW> int launch_hist_i8_t(hg_ctx* c) {
 }  // namespace
 
 int launch_hist_mx(hg_ctx* c) {
-    if (c->opt_hist_mfma == 2 && c->NW <= 4) {
+    if (c->opt.hist_mfma == 2 && c->NW <= 4) {
         switch (c->NW) {
             case 1: return launch_hist_i8_t<1>(c);
             case 2: return launch_hist_i8_t<2>(c);

@@ -86,7 +86,7 @@ int ensure_filter_image(hg_ctx* c) {
         HG_TRY(c->sync());
         // (... and when the rows are not tiny either: half's error has an absolute floor -- subnormals, flushed or not -- that outgrows
         // the relative term once norms fall below ~0.1; bfloat16 has float32's exponents and no such floor)
-        c->dbfb_half = c->opt_real_mfma == 2 && xm >= 1.0f && xm < 1073741824.0f;         // 1 <= largest row norm^2 < 2^30 (inf and the NaN marker fail the test)
+        c->dbfb_half = c->opt.real_mfma == 2 && xm >= 1.0f && xm < 1073741824.0f;         // 1 <= largest row norm^2 < 2^30 (inf and the NaN marker fail the test)
         if (c->dbfb_half) hipLaunchKernelGGL(k_expand_dbf_bf16<true>, dim3(grid_for(n16 * (KP / 8))), dim3(256), 0, c->stream, c->dbf.as<float>(),
                                              c->dbfb.as<uint4>(), (i64)c->N, n16, KP, (i64)1);
         else hipLaunchKernelGGL(k_expand_dbf_bf16<false>, dim3(grid_for(n16 * (KP / 8))), dim3(256), 0, c->stream, c->dbf.as<float>(),
@@ -358,8 +358,8 @@ int real_sample_mx(hg_ctx* c, i64 M, i64 stride, i64 mstride) {
 }
 int real_sample(hg_ctx* c, i64 M, i64 stride, i64 mstride) {
     // with the 16-bit filter behind it the sample runs in the same arithmetic (its scores only place the cut); "real_mfma" 1 keeps the exact chains
-    if (c->bpad <= 128 && c->opt_real_mfma == 2 && c->opt_real_sample_h && c->geo.L % 16 == 0) return real_sample_h(c, M, stride, mstride);
-    if (c->bpad <= 128 && c->opt_real_mfma) return real_sample_mx(c, M, stride, mstride);
+    if (c->bpad <= 128 && c->opt.real_mfma == 2 && c->opt.real_sample_half && c->geo.L % 16 == 0) return real_sample_h(c, M, stride, mstride);
+    if (c->bpad <= 128 && c->opt.real_mfma) return real_sample_mx(c, M, stride, mstride);
     if (c->bpad > 128) {                                 // k_real_sample keeps the query in registers: the staged form beyond
         const Geo& g = c->geo;
         const i64 units = (M + 63) / 64 * g.nQT;
@@ -378,9 +378,9 @@ int real_select(hg_ctx* c) {
     c->real_filtered = false;
     // without a cut (every row a record: R = N, or after lost bets) a filter filters nothing and every pair would be rescored:
     // the exact float32 MFMA pass gives the scores at once (C1: 4.6 -> 4.0 ms per call)
-    const bool filter = c->opt_real_mfma == 2 && !(c->real_no_cut && c->bpad <= 128);
+    const bool filter = c->opt.real_mfma == 2 && !(c->real_no_cut && c->bpad <= 128);
     if ((filter || c->bpad > 128) && c->geo.L % 16 == 0) return real_select_bf(c);   // (the only pass for > 128 features)
-    if (c->opt_real_mfma && c->geo.L % 16 == 0) return real_select_mx(c);
+    if (c->opt.real_mfma && c->geo.L % 16 == 0) return real_select_mx(c);
     HG_DISPATCH_BP(real_launch_select, c)
 }
 
@@ -410,13 +410,13 @@ static int real_attempt(hg_ctx* c, int64_t R, bool bet, double sigma, double bud
             gg.nBlk = (int)((gg.nUnits + WPB - 1) / WPB);
         }
     }
-    if (!bet && c->bpad <= 128 && c->opt_real_mfma && c->opt_real_rounds > 0) {
+    if (!bet && c->bpad <= 128 && c->opt.real_mfma && c->opt.real_whole_rounds > 0) {
         // Every row a record through k_real_select_mx: blocks = (pairs of segments) x (256 queries), four wavefronts each, up to
         // three resident per CU (two beyond 64 features).  The plain geometry gave the CIFAR evaluation (1000 x 54 000) 376 blocks
         // for 256 CUs -- half the CUs with two, half with one; cut the database so that the blocks fill whole rounds instead.
         Geo& gg = c->geo;
         const i64 nQB = (gg.Q + WPB * 32 * RMX_QT - 1) / (WPB * 32 * RMX_QT);
-        const i64 per_cu = c->bpad <= 64 ? std::min<i64>(c->opt_real_rounds, 3) : std::min<i64>(c->opt_real_rounds, 2);
+        const i64 per_cu = c->bpad <= 64 ? std::min<i64>(c->opt.real_whole_rounds, 3) : std::min<i64>(c->opt.real_whole_rounds, 2);
         const i64 slots = (i64)c->n_cu * per_cu;
         const i64 nSP0 = (gg.S + 1) / 2;
         i64 k = (nSP0 * nQB + slots - 1) / slots;          // rounds the plain geometry touches
@@ -444,18 +444,18 @@ static int real_attempt(hg_ctx* c, int64_t R, bool bet, double sigma, double bud
     if (bet) {
         // sample so that about 64 of a query's top R rows are in it; guess the cut `sigma` deviations deep.  With a second, counting sample
         // behind it (256 expected hits) the first one only has to bracket the cut from below: half the rows do (REAL_FIRST_HITS_BRACKET)
-        const bool can16 = c->bpad <= 128 && c->opt_real_mfma == 2 && c->opt_real_sample_h && c->geo.L % 16 == 0;
+        const bool can16 = c->bpad <= 128 && c->opt.real_mfma == 2 && c->opt.real_sample_half && c->geo.L % 16 == 0;
         const i64 hits_b = REAL_FIRST_HITS_BRACKET;
         const i64 stride2 = (i64)((double)R / (double)(REAL_SAMPLE_HITS * REAL_SECOND_SAMPLE));
         i64 stride = (i64)((double)R / (double)hits_b);
-        bool second = can16 && c->opt_real_second && stride2 >= 1 && stride >= 2 * stride2 && (c->N + stride - 1) / stride <= RG_MMAX;
+        bool second = can16 && c->opt.real_second_sample && stride2 >= 1 && stride >= 2 * stride2 && (c->N + stride - 1) / stride <= RG_MMAX;
         if (!second) stride = (i64)((double)R / (double)REAL_SAMPLE_HITS);
         if (stride < 1) stride = 1;
         const i64 M = (c->N + stride - 1) / stride;
         const double fr = (double)R * (double)M / (double)c->N;
         const u32 rank_s = (u32)std::ceil(fr + sigma * std::sqrt(fr)) + 1u;
         // samp[q][mstride]: the matrix-core sample pass stores 16 samples at a time (rows 64-byte aligned), the vector kernels M densely
-        const i64 mstride = c->bpad <= 128 && c->opt_real_mfma ? (M + 15) / 16 * 16 : M;
+        const i64 mstride = c->bpad <= 128 && c->opt.real_mfma ? (M + 15) / 16 * 16 : M;
         HG_TRY(c->samp.reserve((size_t)g.Q * mstride * 4));
         // 16-bit sample scores when both ends take them: k_real_sample_h writes, k_real_guess_lds reads
         c->samp16 = M <= RG_MMAX && can16;
@@ -500,10 +500,10 @@ static int real_attempt(hg_ctx* c, int64_t R, bool bet, double sigma, double bud
     // 10k x R = 5000 and at the CIFAR evaluation alike); the global-memory passes gather the labels THROUGH the idx list and always write it
     // -- and only they reserve the lists then (and the second sort buffer: 0.43 GB each at the CIFAR evaluation, where a recycled context's
     // first call at the shape meets hipMalloc for whatever the block cache cannot serve)
-    const bool skip_lists = with_ap && !c->opt_real_map_lists && !c->is_sub;
+    const bool skip_lists = with_ap && !c->opt.real_map_lists && !c->is_sub;
     if (!skip_lists) { HG_TRY(c->out_idx.reserve(slots * 4)); HG_TRY(c->scores.reserve(slots * 4)); }
     c->real_lists_made = true;
-    if (c->real_filtered && bet && c->opt_real_sort_lds && g.S <= RK_SMAX && R <= RK_RMAX) {
+    if (c->real_filtered && bet && c->opt.real_sort_lds && g.S <= RK_SMAX && R <= RK_RMAX) {
         // a query's records fit the LDS of one workgroup: copy + select + counting passes + ranked list in one kernel
         constexpr int NA = 14336;
         HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_real_rank_lds<NA>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -549,7 +549,7 @@ static int real_attempt(hg_ctx* c, int64_t R, bool bet, double sigma, double bud
     const size_t lds = (size_t)(nwav + 1) * 256 * 4;
     const u64* in = c->cand.as<u64>();
     bool grouped = false;
-    if (c->opt_real_groups && g.S <= 8192 && !bet && c->crow <= (i64)RG_MAXG * RG_CAP) {
+    if (c->opt.real_groups && g.S <= 8192 && !bet && c->crow <= (i64)RG_MAXG * RG_CAP) {
         // every row a record (R = N on a CIFAR-sized database): split by score range into LDS-sized groups, order each group
         // in LDS (k_real_group_split / k_real_group_sort) -- two trips of the records through memory instead of the radix
         // passes' four, 3.1 -> 0.85 ms at C1; piled-up scores come back as bit 2 of the flag.  (A bet's list beyond the LDS --
@@ -645,25 +645,10 @@ static int real_requery_lost(hg_ctx* c, int64_t R, bool with_ap, bool* handled) 
     for (int q = 0; q < g.Q; ++q) if (bad[(size_t)q]) lost.push_back((u32)q);
     const i64 nF = (i64)lost.size();
     if (nF == 0 || nF * 16 > g.Q) return HG_OK;
-    if (!c->sub) {
-        c->sub = new hg_ctx();
-        c->sub->is_sub = true;
-        c->sub->device = c->device;
-        c->sub->stream = c->stream;                  // same stream: ordered with the parent's work
-    }
-    hg_ctx* s = c->sub;
-    s->N = c->N; s->b = c->b; s->C = c->C; s->n_total = c->n_total; s->NW = c->NW; s->NB = c->NB; s->LW = c->LW;
-    s->idx_base = c->idx_base; s->n_cu = c->n_cu;
-    s->target_units = c->target_units; s->min_segment = c->min_segment; s->opt_max_segments = c->opt_max_segments;
-    s->timing = 0;
-    s->bpad = c->bpad;
-    s->opt_real_mfma = c->opt_real_mfma; s->opt_real_sort_lds = c->opt_real_sort_lds; s->opt_real_groups = c->opt_real_groups;
+    hg_ctx* s = requery_child(c, nF);
     s->real_cap_boost = c->real_cap_boost;
-    s->db.borrow(c->db);
-    s->dblab.borrow(c->dblab);
     s->dbf.borrow(c->dbf); s->dbf_resident = true;
     s->dbfb.borrow(c->dbfb); s->xmax2.borrow(c->xmax2); s->dbfb_valid = c->dbfb_valid; s->dbfb_half = c->dbfb_half;
-    s->Q = nF;
     HG_TRY(c->flist.reserve((size_t)nF * 4));
     HG_HIP(hipMemcpyAsync(c->flist.p, lost.data(), (size_t)nF * 4, hipMemcpyHostToDevice, c->stream));
     HG_TRY(s->qf.reserve((size_t)nF * c->bpad * 4 + 256));

@@ -20,24 +20,24 @@ void make_geometry(hg_ctx* c) {
     g.Qpad = g.nQT * 64;
     g.NW = c->NW; g.NB = c->NB; g.LW = c->LW;
     g.N = c->N; g.R = c->R; g.idx_base = c->idx_base;
-    i64 S = (c->target_units + g.nQT - 1) / g.nQT;
+    i64 S = (c->opt.target_units + g.nQT - 1) / g.nQT;
     // few queries: more segments than fill the GPU twice only make every query's record row longer to walk
     // (Q = 64, N = 10M: 12500 slices per query cost the rank stage 3.4 ms; 2048 cost 0.1)
-    if (S > c->opt_max_segments) S = c->opt_max_segments;
-    const i64 maxS = (c->N + c->min_segment - 1) / c->min_segment;
+    if (S > c->opt.max_segments) S = c->opt.max_segments;
+    const i64 maxS = (c->N + c->opt.min_segment - 1) / c->opt.min_segment;
     if (S > maxS) S = maxS;
     if (S < 1) S = 1;
     i64 L = (c->N + S - 1) / S;
-    const i64 lq = (c->opt_select_packed >= 3 && c->NW <= 2) ? 96 : 32;   // k_select_mx walks segments in 32-row tiles, k_select_mx3 in 48-row supertiles
+    const i64 lq = (c->opt.select_packed >= 3 && c->NW <= 2) ? 96 : 32;   // k_select_mx walks segments in 32-row tiles, k_select_mx3 in 48-row supertiles
     L = (L + lq - 1) / lq * lq;
     if (L < lq) L = lq;
     S = (c->N + L - 1) / L;
     if (S < 1) S = 1;
-    if (c->opt_enable && c->opt_select_mfma && S >= 4) {
+    if (c->opt.optimistic && c->opt.select_mfma && S >= 4) {
         // k_select_mx runs (S / 2) x ceil(Q / 256 or 512) equal blocks, 4 or 2 resident per CU: pick the S near the
         // target that fills a whole number of such rounds, so the last round is not a nearly empty one
         const bool qt2 = c->NW <= 4;                                // mirrors launch_select_mx_t
-        const bool mx3 = c->opt_select_packed == 3 && c->NW <= 4;   // k_select_mx3 / k_select_mx4: blocks of 8 wavefronts x 64 queries, two per CU
+        const bool mx3 = c->opt.select_packed == 3 && c->NW <= 4;   // k_select_mx3 / k_select_mx4: blocks of 8 wavefronts x 64 queries, two per CU
         const i64 qblk = mx3 ? 64 * M3_WPB : qt2 ? 256 : 512;
         const i64 nQB = (c->Q + qblk - 1) / qblk;
         const i64 slots = (i64)c->n_cu * (mx3 ? 16 / M3_WPB : qt2 ? 4 : 2);
@@ -46,7 +46,7 @@ void make_geometry(hg_ctx* c) {
         // k_rank_lean takes at most 256 slices per query.  A target beyond that (few queries: C3's 2100 ask for 496 segments)
         // is cut to the whole rounds that 256 segments fill, when that is at least one: C3 396 -> 198 segments, one round of
         // blocks instead of two, k_rank_lean instead of k_rank_cnt: 0.277 -> 0.200 ms per step
-        if (mx3 && c->opt_rank_lean && S > 256 && 128 * nQB >= slots) {
+        if (mx3 && c->opt.rank_lds >= 2 && S > 256 && 128 * nQB >= slots) {
             k = 128 * nQB / slots;
             L = (c->N + 255) / 256;
             L = (L + lq - 1) / lq * lq;
@@ -85,7 +85,7 @@ Geo hist_geometry(const hg_ctx* c) {
 
 // histogram on the matrix cores: blocks = (pair of segments) x (256 queries); stride in tiles of 16 rows
 bool hist_mx_applies(const hg_ctx* c, int stride, bool pairs_ok) {
-    if (!c->opt_hist_mfma || !c->opt_select_mfma || c->NW > 8 || c->is_sub) return false;
+    if (!c->opt.hist_mfma || !c->opt.select_mfma || c->NW > 8 || c->is_sub) return false;
     {   // long segments (>= 65536 visited rows per pair) need one dword counter per query tile: with long codes the four
         // wavefronts' columns then exceed the CU's LDS -- the vector kernel, which shrinks its block, takes those
         const Geo& g = c->geo;
@@ -98,9 +98,9 @@ bool hist_mx_applies(const hg_ctx* c, int stride, bool pairs_ok) {
 
 // The record pass of the current sequence: which kernel takes it (the launchers live in hg_pairs_valu.hip / hg_pairs_mx.hip).
 // one-byte records {match, dist} (no index): only the matrix-core kernels of the bet produce them, and only when nobody wants the lists
-static bool select_takes_mx(const hg_ctx* c) { return c->optimistic && c->opt_select_mfma && c->cap < (1u << MX_POS_BITS); }
+static bool select_takes_mx(const hg_ctx* c) { return c->optimistic && c->opt.select_mfma && c->cap < (1u << MX_POS_BITS); }
 static bool records_are_bytes(const hg_ctx* c) {
-    return select_takes_mx(c) && c->opt_compact && !c->want_lists && c->LW <= 2 && c->cap % 16 == 0 && c->crow * 64 < (1ll << 31);
+    return select_takes_mx(c) && c->opt.compact_records && !c->want_lists && c->LW <= 2 && c->cap % 16 == 0 && c->crow * 64 < (1ll << 31);
 }
 // the record rows of the coming select: Q x crow slots of one byte or eight.  (Until round 6 eight bytes were reserved either way:
 // 2 GB at C2 for 0.25 GB of records -- and 14.9 GB once a class-sorted database had widened the slices, a hipMalloc that took
@@ -117,9 +117,9 @@ int launch_select(hg_ctx* c) {
     if (!c->optimistic && c->R * 4 >= c->n_total) { c->last_select = 2; return launch_select_dense(c, lw); }   // dense regime: most pairs are selected
     // three rows per accumulator + batched drain: codes of <= 64 bits, one-byte records (<= 128 classes).  (For <= 32 bits the
     // second k-half of every MFMA is empty, and it still beat round 2's two-rows-per-accumulator kernel: 0.69 vs 0.85 ms at b = 32.)
-    if (NW <= 2 && c->opt_select_packed == 3 && c->rec8 && c->geo.L % M3_ROWS == 0 && (lw == 1 || lw == 2)) { c->last_select = 5; return launch_select_mx3(c, lw); }
+    if (NW <= 2 && c->opt.select_packed == 3 && c->rec8 && c->geo.L % M3_ROWS == 0 && (lw == 1 || lw == 2)) { c->last_select = 5; return launch_select_mx3(c, lw); }
     // codes of 65..128 bits: two rows per accumulator (8-bit fields) and the same drain
-    if ((NW == 3 || NW == 4) && c->opt_select_packed == 3 && c->rec8 && c->geo.L % M4_ROWS == 0 && (lw == 1 || lw == 2)) { c->last_select = 6; return launch_select_mx4(c, lw); }
+    if ((NW == 3 || NW == 4) && c->opt.select_packed == 3 && c->rec8 && c->geo.L % M4_ROWS == 0 && (lw == 1 || lw == 2)) { c->last_select = 6; return launch_select_mx4(c, lw); }
     if (mx) { c->last_select = 3; return launch_select_mx(c, lw); }
     c->last_select = 1;
     return launch_select_valu(c, lw, c->optimistic);
@@ -278,7 +278,7 @@ int hg_plan(hg_ctx* c, int64_t R, const uint32_t* dev_hist_all, int G, int rank)
     HG_TRY(do_plan(c, R, dev_hist_all, G, rank));
     // the device flag says "R exceeds the rows in the gathered histograms"; R <= n_total was checked on
     // the host already, so an unsynchronised caller loses nothing by skipping the read-back
-    return c->stage_sync ? check_plan_flag(c) : HG_OK;
+    return c->opt.stage_sync ? check_plan_flag(c) : HG_OK;
 }
 
 // k_rank_fused in one of its modes: 0 = histogram + plan + placement in one launch (single shard),
@@ -286,7 +286,7 @@ int hg_plan(hg_ctx* c, int64_t R, const uint32_t* dev_hist_all, int G, int rank)
 // the dense regime through the byte matrix (hg_rank_dense.hpp): the counter columns always fit a block's LDS for codes of <= 126 bits
 static bool rank_dense_fits(const hg_ctx* c, int64_t R) {
     (void)R;
-    return c->opt_rank_dense && c->LW <= 2 && c->NW <= 4 && c->b <= 126 && c->N == c->n_total && !c->is_sub;
+    return c->opt.rank_dense && c->LW <= 2 && c->NW <= 4 && c->b <= 126 && c->N == c->n_total && !c->is_sub;
 }
 
 static void launch_dense_bytes(hg_ctx* c, u8* D, i64 Npad, int q0, int nq) {
@@ -326,16 +326,16 @@ static int launch_rank_dense(hg_ctx* c) {
     // (R = N = 1M: two blocks per query, 2 x 10 ms, against 37 ms of atomic ORs on a bitmap in global memory)
     i64 rw_part = 0;
     int kparts = 1;
-    if (blocks_lds == 0 && g.R * 4 >= c->N && c->opt_rank_dense_gbm != 1) {
+    if (blocks_lds == 0 && g.R * 4 >= c->N && c->opt.rank_dense_gbm != 1) {
         const i64 room = lds_cu - tot_gbm - 4096;
         kparts = (int)((c->RW * 8 + room - 1) / room);
         if (kparts >= 2 && kparts <= 8) rw_part = (c->RW + kparts - 1) / kparts; else kparts = 1;
     }
     const bool gbm = rw_part ? false
-                   : c->opt_rank_dense_gbm >= 0 ? c->opt_rank_dense_gbm != 0 || blocks_lds == 0 : (blocks_lds == 0 || (blocks_lds < 2 && g.R * 4 < c->N));
+                   : c->opt.rank_dense_gbm >= 0 ? c->opt.rank_dense_gbm != 0 || blocks_lds == 0 : (blocks_lds == 0 || (blocks_lds < 2 && g.R * 4 < c->N));
     const int total = gbm ? tot_gbm : rw_part ? rank_dense_layout(g.NB, rw_part, false).total : tot_lds;
     const i64 Npad = rank_dense_pieces(c->N) * RD_THREADS * 16;
-    i64 qchunk = (c->opt_dense_budget_mb << 20) / Npad;
+    i64 qchunk = (c->opt.dense_budget_mb << 20) / Npad;
     if (qchunk < 1) qchunk = 1;
     if (qchunk > g.Q) qchunk = g.Q;
     // (the byte matrix is a budget, not a need: when the device cannot give that much, fewer queries per chunk do)
@@ -347,7 +347,7 @@ static int launch_rank_dense(hg_ctx* c) {
         qchunk = (qchunk + 1) / 2;
     }
     bool use_recip = false;
-    const bool fuse = !gbm && !rw_part && blocks_lds >= 2 && c->fuse_ap && c->opt_fuse_ap && !c->want_lists;
+    const bool fuse = !gbm && !rw_part && blocks_lds >= 2 && c->fuse_ap && c->opt.fuse_ap && !c->want_lists;
     if (fuse) HG_TRY(ensure_ap_tables(c, &use_recip));
     const bool fused = fuse && use_recip;
     if (gbm) HG_HIP(hipMemsetAsync(c->mbits.p, 0, (size_t)g.Q * c->RW * 8, c->stream));
@@ -392,7 +392,7 @@ static int launch_rank_slices(hg_ctx* c, const u32* only) {
     const Geo& g = c->geo;
     const int sl_rows = slices_rows(c);
     const int total = rank_dense_layout(sl_rows + 1, c->RW, false).total;
-    const bool fuse = c->fuse_ap && c->opt_fuse_ap && (only || 160 * 1024 / total >= 2);
+    const bool fuse = c->fuse_ap && c->opt.fuse_ap && (only || 160 * 1024 / total >= 2);
     bool use_recip = false;
     if (fuse) HG_TRY(ensure_ap_tables(c, &use_recip));
     const bool fused = fuse && use_recip;
@@ -415,7 +415,7 @@ static int launch_rank_slices(hg_ctx* c, const u32* only) {
 // instead of a second host round trip (k_rank_fused + k_ap + three downloads: 0.08 ms of C5's 1.27).
 static int rank_leftovers_inline(hg_ctx* c, int mode, bool use_recip) {
     c->leftovers_inline = false;
-    if (c->leftovers_expected && mode == 0 && c->opt_inline_leftovers && use_recip && rank_slices_fits(c)) {
+    if (c->leftovers_expected && mode == 0 && c->opt.inline_leftovers && use_recip && rank_slices_fits(c)) {
         HG_TRY(launch_rank_slices(c, c->bigq.as<u32>()));
         c->leftovers_inline = true;
     }
@@ -429,7 +429,7 @@ struct LeanPlan { bool ok; int nbc, psp; i64 rb; };
 static LeanPlan rank_lean_plan(const hg_ctx* c, int mode) {
     const Geo& g = c->geo;
     LeanPlan l{false, 0, 1, 0};
-    if (!(c->optimistic && c->opt_rank_cnt && c->opt_rank_lean && (mode == 0 || mode == 3) && c->rec8 && !c->want_lists &&
+    if (!(c->optimistic && c->opt.rank_lds >= 2 && (mode == 0 || mode == 3) && c->rec8 && !c->want_lists &&
           g.S <= 256 && (c->cap & 15u) == 0 && c->cap <= 1024 && g.R <= 60000)) return l;
     const int nbc = rank_cnt_maxb(g.NB) + 2 < g.NB ? rank_cnt_maxb(g.NB) + 2 : 0;
     const int nbc_eff = nbc ? nbc : (g.NB < 128 ? g.NB : 128);
@@ -489,7 +489,7 @@ static int launch_rank(hg_ctx* c, int mode, int nbits, bool leftovers_only = fal
         if (lp.ok) {
             const RankLeanLds L = rank_lean_layout(g.NB, c->RW, g.S, (int)rb, nbc);
             HG_TRY(c->bigq.reserve((size_t)g.Qpad * 4));
-            const bool fuse = c->fuse_ap && c->opt_fuse_ap && mode == 0 && c->LW <= 2;
+            const bool fuse = c->fuse_ap && c->opt.fuse_ap && mode == 0 && c->LW <= 2;
             bool use_recip = false;
             if (fuse) HG_TRY(ensure_ap_tables(c, &use_recip));
             RankLdsArgs la{c->sl_cnt.as<u32>(), c->failq.as<u32>(), c->err.as<int>(), c->qbad.as<u32>(), c->bigq.as<u32>(),
@@ -511,11 +511,11 @@ static int launch_rank(hg_ctx* c, int mode, int nbits, bool leftovers_only = fal
             counted = true;
         }
     }
-    if (!counted && mode == 0 && g.R >= c->opt_rank_slices && c->opt_rank_slices > 0 && rank_slices_fits(c)) {
+    if (!counted && mode == 0 && g.R >= c->opt.rank_slices && c->opt.rank_slices > 0 && rank_slices_fits(c)) {
         // long lists of a bet (beyond k_rank_lean's LDS): k_rank_dense's two passes over the query's record slices, thread = part of a slice
         return launch_rank_slices(c, nullptr);
     }
-    if (!counted && c->optimistic && c->opt_rank_cnt && (mode == 0 || mode == 3)) {
+    if (!counted && c->optimistic && c->opt.rank_lds >= 1 && (mode == 0 || mode == 3)) {
         // per-thread counting sort (k_rank_cnt): byte counters for every distance + a tile of the records, <= 64 KiB per
         // block; lists longer than a tile are ranked tile by tile
         const double share = (double)c->N / (double)(c->n_total > 0 ? c->n_total : 1);
@@ -544,7 +544,7 @@ static int launch_rank(hg_ctx* c, int mode, int nbits, bool leftovers_only = fal
             HG_TRY(c->bigq.reserve((size_t)g.Qpad * 4));
             // hg_map's bet: the AP leaves with the ranking (the bitmap is in LDS), and the general kernel below is NOT launched --
             // the step's download carries the number of queries this kernel declined (err[1]); the host launches it only then
-            const bool fuse = c->fuse_ap && c->opt_fuse_ap && mode == 0 && !c->want_lists && c->LW <= 2;
+            const bool fuse = c->fuse_ap && c->opt.fuse_ap && mode == 0 && !c->want_lists && c->LW <= 2;
             bool use_recip = false;
             if (fuse) HG_TRY(ensure_ap_tables(c, &use_recip));
             RankLdsArgs la{c->sl_cnt.as<u32>(), c->failq.as<u32>(), c->err.as<int>(), c->qbad.as<u32>(), c->bigq.as<u32>(),
@@ -622,7 +622,7 @@ static int do_select(hg_ctx* c) {
 
 int hg_select(hg_ctx* c) {
     HG_TRY(need(c, ST_PLAN, "hg_select", "hg_plan"));
-    c->want_lists = c->staged_lists != 0;
+    c->want_lists = c->opt.staged_lists != 0;
     HG_TRY(do_select(c));
     return c->stage_end();
 }
@@ -648,7 +648,7 @@ static u32 slice_capacity(const hg_ctx* c, double mean) {
 
 static int auto_stride(hg_ctx* c, int64_t R) {
     (void)R;
-    return c->opt_stride > 0 ? (int)c->opt_stride : 24;
+    return c->opt.sample_stride > 0 ? (int)c->opt.sample_stride : 24;
 }
 
 int hg_bet_eligible(hg_ctx* c, int64_t R, int world, int* eligible) {
@@ -658,7 +658,7 @@ int hg_bet_eligible(hg_ctx* c, int64_t R, int world, int* eligible) {
     // computed from gathered data and therefore the same on every rank (one-shot calls keep their own counter)
     const int stride = auto_stride(c, R);
     const i64 per_shard = c->n_total / world;
-    *eligible = c->opt_enable && c->shard_bet_fail < 2 && stride >= 2 && R * 8 <= c->n_total && per_shard >= 65536;
+    *eligible = c->opt.optimistic && c->shard_bet_fail < 2 && stride >= 2 && R * 8 <= c->n_total && per_shard >= 65536;
     return HG_OK;
 }
 
@@ -685,14 +685,14 @@ int hg_guess(hg_ctx* c, int64_t R, const uint32_t* dev_hist_all, int G, int rank
     const Geo gh = hist_geometry(c);                   // the sampled pass ran on coarser segments
     HG_TRY(c->sstar.reserve(qb));
     hipLaunchKernelGGL(k_guess, dim3(grid_for(g.Q)), dim3(256), 0, c->stream, c->hown.as<u32>(), (const u32*)dev_hist_all, G,
-                       rank, c->hist.as<u32>(), gh.S, (int)(gh.L / g.L), (double)c->opt_sigma, (i64)c->n_total,
+                       rank, c->hist.as<u32>(), gh.S, (int)(gh.L / g.L), (double)c->opt.guess_sigma, (i64)c->n_total,
                        c->tguess.as<int>(), c->sstar.as<int>(), g);
     c->t_end();
     HG_TRY(c->check_launch("k_guess"));
     // a guessed cut keeps at most ~2.6 R rows over ALL shards; a shard's share is proportional to its size,
     // with the same 6-sigma headroom per slice as the one-shot bet
     const double share = (double)c->N / (double)c->n_total;
-    const double mean = 0.1 * (double)c->cand_budget_x10 * (double)c->cap_boost * (double)R * share / (double)g.S;
+    const double mean = 0.1 * (double)c->opt.cand_budget_x10 * (double)c->cap_boost * (double)R * share / (double)g.S;
     u32 cap = slice_capacity(c, mean);
     c->optimistic = true;
     c->cap = cap;
@@ -705,7 +705,7 @@ int hg_select_candidates(hg_ctx* c) {
     HG_TRY(need(c, ST_PLAN, "hg_select_candidates", "hg_guess"));
     if (!c->optimistic) return fail(HG_ERR_STATE, "hg_select_candidates: no guess in force (use hg_select after hg_plan)");
     const Geo& g = c->geo;
-    c->want_lists = c->staged_lists != 0 || c->LW > 2;  // decides the record format (hg_rank places them)
+    c->want_lists = c->opt.staged_lists != 0 || c->LW > 2;  // decides the record format (hg_rank places them)
     HG_TRY(reserve_records(c));
     HG_TRY(launch_select(c));
     const size_t plane = (size_t)g.NB * g.Qpad * 4;
@@ -789,7 +789,7 @@ static int merge_ranked_range(hg_ctx* c, const uint32_t* dev_hist_all, const uin
 int hg_merge_ranked(hg_ctx* c, const uint32_t* dev_hist_all, const uint64_t* dev_bits_all, int G, int* bet_lost) {
     if (!bet_lost) return fail(HG_ERR_ARG, "hg_merge_ranked: null argument");
     HG_TRY(merge_ranked_range(c, dev_hist_all, dev_bits_all, G, 0, c ? c->geo.Q : 0, "hg_merge_ranked"));
-    if (c->defer_verdict) {
+    if (c->opt.defer_verdict) {
         *bet_lost = -1;
         c->verdict_pending = true;
         c->verdict_known = false;
@@ -799,9 +799,9 @@ int hg_merge_ranked(hg_ctx* c, const uint32_t* dev_hist_all, const uint64_t* dev
     int flag = 0;
     HG_TRY(read_plan_flag(c, &flag));
     *bet_lost = flag;
-    c->opt_runs++;
+    c->bet_runs++;
     if (flag) {
-        c->opt_fallbacks++;
+        c->bet_fallbacks++;
         c->shard_bet_fail++;
         c->stage = ST_DB | ST_Q;
         return HG_OK;
@@ -813,9 +813,9 @@ int hg_merge_ranked(hg_ctx* c, const uint32_t* dev_hist_all, const uint64_t* dev
 
 // bookkeeping after the verdict of a staged bet is known
 static int settle_bet(hg_ctx* c, int flag) {
-    c->opt_runs++;
+    c->bet_runs++;
     if (flag) {
-        c->opt_fallbacks++;
+        c->bet_fallbacks++;
         c->shard_bet_fail++;
         c->stage = ST_DB | ST_Q;
         return HG_OK;
@@ -834,7 +834,7 @@ int hg_rank(hg_ctx* c, const uint32_t* dev_hist_all, int G, int rank, int* bet_l
     if (!bet_lost || G < 1 || (G > 1 && !dev_hist_all)) return fail(HG_ERR_ARG, "hg_rank: bad argument");
     const Geo& g = c->geo;
     c->G = G; c->rank = rank;
-    c->want_lists = c->staged_lists != 0 || c->LW > 2;
+    c->want_lists = c->opt.staged_lists != 0 || c->LW > 2;
     const size_t slots = (size_t)g.Q * g.R;
     HG_TRY(c->mbits.reserve((size_t)g.Q * c->RW * 8));
     HG_TRY(c->out_idx.reserve(c->want_lists ? slots * 4 : 16));
@@ -847,7 +847,7 @@ int hg_rank(hg_ctx* c, const uint32_t* dev_hist_all, int G, int rank, int* bet_l
     int nbits = 1;
     while ((1 << nbits) < g.NB) ++nbits;
     HG_TRY(launch_rank(c, 2, nbits));                // placement with the shared plan
-    if (c->defer_verdict) {
+    if (c->opt.defer_verdict) {
         // the caller goes on as if the bet held (match bits, exchange, AP) and asks hg_bet_verdict at the end,
         // together with its final download: no host round trip in the middle of the step
         *bet_lost = -1;
@@ -874,9 +874,9 @@ int hg_bet_verdict(hg_ctx* c, int* bet_lost) {
     else HG_TRY(read_plan_flag(c, &flag));
     c->verdict_known = false;
     *bet_lost = flag;
-    if (!flag) { c->opt_runs++; c->shard_bet_fail = 0; return HG_OK; }
-    c->opt_runs++;
-    c->opt_fallbacks++;
+    if (!flag) { c->bet_runs++; c->shard_bet_fail = 0; return HG_OK; }
+    c->bet_runs++;
+    c->bet_fallbacks++;
     c->shard_bet_fail++;
     c->lists_valid = false;
     c->stage = ST_DB | ST_Q;
@@ -934,9 +934,9 @@ int hg_unpack_parts(hg_ctx* c, const void* dev_parts_all, int G, int64_t width, 
     *bet_lost = flag;
     c->verdict_pending = false;
     c->verdict_known = false;
-    c->opt_runs++;                                     // the verdict comes from gathered data: the same on every rank
+    c->bet_runs++;                                     // the verdict comes from gathered data: the same on every rank
     if (flag) {
-        c->opt_fallbacks++;
+        c->bet_fallbacks++;
         c->shard_bet_fail++;
         c->lists_valid = false;
         c->stage = ST_DB | ST_Q;
@@ -981,7 +981,7 @@ int hg_guess_owned(hg_ctx* c, int64_t R, const void* dev_recv, int G, int rank, 
     HG_TRY(c->obuf[1].reserve((size_t)G * w.width * 16));
     c->t_begin(KI_GUESS);
     hipLaunchKernelGGL(k_guess_owner, dim3(grid_for(w.width)), dim3(256), 0, c->stream, (const u32*)dev_recv, w, sample_planes(c),
-                       owner_nq(w, rank), (double)c->opt_sigma, (i64)c->n_total, c->obuf[1].as<u32>(), g);
+                       owner_nq(w, rank), (double)c->opt.guess_sigma, (i64)c->n_total, c->obuf[1].as<u32>(), g);
     c->t_end();
     HG_TRY(c->check_launch("k_guess_owner"));
     *dev_ptr = c->obuf[1].p;
@@ -1012,7 +1012,7 @@ int hg_guess_finish(hg_ctx* c, int64_t R, const void* dev_answers, int G, int ra
     HG_TRY(c->check_launch("k_guess_finish"));
     // (the slices' budget: as hg_guess)
     const double share = (double)c->N / (double)c->n_total;
-    const double mean = 0.1 * (double)c->cand_budget_x10 * (double)c->cap_boost * (double)R * share / (double)g.S;
+    const double mean = 0.1 * (double)c->opt.cand_budget_x10 * (double)c->cap_boost * (double)R * share / (double)g.S;
     c->optimistic = true;
     c->cap = slice_capacity(c, mean);
     c->crow = (i64)g.S * c->cap;
@@ -1075,14 +1075,14 @@ int hg_merge_ap_owned(hg_ctx* c, const void* dev_recv, int G, int rank, void** d
 // and no slice may have overflowed.  The verified result is identical to the
 // exact path's; a failed bet reruns the exact path.
 static bool optimistic_eligible(hg_ctx* c, int64_t R, int* stride_out, u32* need_out) {
-    if (!c->opt_enable || c->opt_consecutive_fail >= 2) return false;
+    if (!c->opt.optimistic || c->bet_consecutive_fail >= 2) return false;
     if (R * 8 > c->N || c->N < 65536) return false;
     make_geometry(c);
     const int stride = auto_stride(c, R);
     if (stride < 2) return false;
     const i64 sampled = sampled_rows(c, stride);
     const double fr = (double)R * (double)sampled / (double)c->N;   // expected sample count at the true cut
-    const double need = fr + (double)c->opt_sigma * std::sqrt(fr) + 1.0;
+    const double need = fr + (double)c->opt.guess_sigma * std::sqrt(fr) + 1.0;
     *stride_out = stride;
     *need_out = (u32)std::ceil(need);
     return true;
@@ -1122,11 +1122,11 @@ static int enqueue_all_rows(hg_ctx* c, int64_t R) {
 
 static int enqueue_exact(hg_ctx* c, int64_t R) {
     // N/8 < R <= N through the byte matrix (k_dense_bytes + k_rank_dense: R = N/2 of N = 1M 68.8 -> 16.3 ms, C1 0.35 -> 0.19 ms)
-    if (R * 8 > c->N && c->opt_all_rows && rank_dense_fits(c, R)) {
+    if (R * 8 > c->N && c->opt.all_rows_shortcut && rank_dense_fits(c, R)) {
         c->dense_rank = true;
         return enqueue_all_rows(c, R);
     }
-    if (c->N == c->n_total && R == c->N && c->opt_all_rows && c->LW <= 2 && c->NW <= 8)
+    if (c->N == c->n_total && R == c->N && c->opt.all_rows_shortcut && c->LW <= 2 && c->NW <= 8)
         return enqueue_all_rows(c, R);                 // one-shot calls are single-shard; codes / label sets the byte matrix does not take: k_rank_fused walks the rows
     HG_TRY(do_hist(c, 1));
     HG_TRY(do_plan(c, R, nullptr, 1, 0));
@@ -1138,7 +1138,7 @@ static int enqueue_exact(hg_ctx* c, int64_t R) {
 // fixed-capacity slices -> the bet's rank stage, which cuts the ties at the quota.  Nothing is guessed, so the only way
 // this can fail is a slice overflowing its capacity (clustered rows): *err then, and the caller runs enqueue_exact.
 static bool exact_mx_applies(const hg_ctx* c, int64_t R) {
-    return c->opt_select_mfma && c->N == c->n_total && R * 8 <= c->N && c->N >= 65536 && !c->is_sub;
+    return c->opt.select_mfma && c->N == c->n_total && R * 8 <= c->N && c->N >= 65536 && !c->is_sub;
 }
 static int enqueue_exact_mx(hg_ctx* c, int64_t R) {
     HG_TRY(do_hist(c, 1, true, true));                 // per segment pair on the matrix cores where that applies
@@ -1146,7 +1146,7 @@ static int enqueue_exact_mx(hg_ctx* c, int64_t R) {
     const Geo& g = c->geo;
     // in all the slices hold R records + the ties of one segment beyond the quota, but unevenly: segments up to sstar carry
     // ALL their rows at distance t (the cut bucket is typically the fullest), later ones none -- budget like the bet does
-    const double mean = 0.1 * (double)c->cand_budget_x10 * (double)R / (double)g.S;
+    const double mean = 0.1 * (double)c->opt.cand_budget_x10 * (double)R / (double)g.S;
     u32 cap = (u32)std::ceil(mean + 6.0 * std::sqrt(mean) + 16.0);
     cap = (cap + 15u) & ~15u;
     c->optimistic = true;
@@ -1174,7 +1174,7 @@ static int enqueue_optimistic(hg_ctx* c, int64_t R, int stride, u32 need_cnt) {
     HG_TRY(c->err.reserve(16));
     HG_TRY(c->sstar.reserve(qb));
     // first bet on this database: the guess kernel also measures how the near rows crowd (err[2], err[3]) -- see below
-    const bool probe = c->opt_crowd_probe && !c->crowd_probed && c->cap_boost == 1 && !c->capturing && !c->is_sub;
+    const bool probe = c->opt.crowd_probe && !c->crowd_probed && c->cap_boost == 1 && !c->capturing && !c->is_sub;
     u32* crowd = probe ? c->err.as<u32>() + 2 : nullptr;
     if (probe) HG_HIP(hipMemsetAsync(crowd, 0, 8, c->stream));
     c->t_begin(KI_GUESS);
@@ -1182,7 +1182,7 @@ static int enqueue_optimistic(hg_ctx* c, int64_t R, int stride, u32 need_cnt) {
     {   // lanes per query by the number of sampled segments each has to sum
         const int ratio = (int)(gh.L / g.L);
         const u32 srows = (u32)sampled_rows(c, stride);
-        double sigma = (double)c->opt_sigma;
+        double sigma = (double)c->opt.guess_sigma;
         if (c->handicap_next && !c->capturing) { sigma = -(double)c->handicap_next; c->handicap_next = 0; }   // (test hook: this bet is meant to lose)
 #define HG_GUESS(P)                                                                                                     \
         hipLaunchKernelGGL(k_guess_direct<P>, dim3(grid_for(g.Qpad, WPB * (64 / P))), dim3(256), 0, c->stream,          \
@@ -1220,7 +1220,7 @@ static int enqueue_optimistic(hg_ctx* c, int64_t R, int stride, u32 need_cnt) {
     // distance bucket, and cumulative counts grow ~2x per bucket in the tail where the cut lies; clustered
     // codes grow faster) -- budget 4 R per query over the S segments plus 6 sigma per slice.  HBM is
     // plentiful (2.5 GB at C2); an overflow only costs the exact rerun.
-    const double mean = 0.1 * (double)c->cand_budget_x10 * (double)c->cap_boost * (double)R / (double)g.S;
+    const double mean = 0.1 * (double)c->opt.cand_budget_x10 * (double)c->cap_boost * (double)R / (double)g.S;
     u32 cap = slice_capacity(c, mean);
     c->optimistic = true;
     c->cap = cap;
@@ -1244,23 +1244,11 @@ static int rerun_lost_queries(hg_ctx* c, int64_t R, bool lists, bool with_ap, bo
     for (int q = 0; q < g.Q; ++q) if (bad[(size_t)q]) lost.push_back((u32)q);
     const i64 nF = (i64)lost.size();
     if (nF == 0 || nF * 8 > g.Q) return HG_OK;
-    if (!c->sub) {
-        c->sub = new hg_ctx();
-        c->sub->is_sub = true;
-        c->sub->device = c->device;
-        c->sub->stream = c->stream;                  // same stream: ordered with the parent's work
-    }
-    hg_ctx* s = c->sub;
-    s->N = c->N; s->b = c->b; s->C = c->C; s->n_total = c->n_total; s->NW = c->NW; s->NB = c->NB; s->LW = c->LW;
-    s->idx_base = c->idx_base;
-    s->target_units = c->target_units; s->min_segment = c->min_segment; s->opt_enable = 0;
+    hg_ctx* s = requery_child(c, nF);
+    s->opt.optimistic = 0;
     // a handful of queries: the per-segment bookkeeping (k_hist_reduce, k_seg_layout walk S segments per query) costs more than
     // the pair passes themselves -- 2048 segments: 0.8 ms of a 1 ms rerun; 256 keep every CU busy and cost 0.1
-    s->opt_max_segments = 256;
-    s->timing = 0;
-    s->db.borrow(c->db);
-    s->dblab.borrow(c->dblab);
-    s->Q = nF;
+    s->opt.max_segments = 256;
     HG_TRY(c->flist.reserve((size_t)nF * 4));
     HG_HIP(hipMemcpyAsync(c->flist.p, lost.data(), (size_t)nF * 4, hipMemcpyHostToDevice, c->stream));
     HG_TRY(s->qc.reserve((size_t)nF * c->NW * 4 + 64 * 4));
@@ -1287,7 +1275,7 @@ static int rerun_lost_queries(hg_ctx* c, int64_t R, bool lists, bool with_ap, bo
     }
     HG_TRY(c->check_launch("k_move_rows"));
     HG_TRY(c->sync());                               // `lost` (the H2D source) must outlive the copy
-    c->opt_requeried += nF;
+    c->bet_requeried += nF;
     *handled = true;
     return HG_OK;
 }
@@ -1383,7 +1371,7 @@ static int finish_leftovers(hg_ctx* c, int* flag) {
     const u32 nleft = ((const u32*)c->pin)[1];
     if ((nleft != 0) != c->leftovers_expected) { c->leftovers_expected = nleft != 0; c->cfg_epoch++; }
     if (!nleft) return HG_OK;
-    c->opt_leftover += nleft;
+    c->rank_leftovers += nleft;
     c->last_leftovers_inline = c->leftovers_inline;
     if (c->leftovers_inline) { c->leftovers_inline = false; return HG_OK; }     // k_rank_dense<slices> ranked them within the step
     const size_t Q = (size_t)c->geo.Q;
@@ -1411,18 +1399,18 @@ static int run_oneshot(hg_ctx* c, int64_t R, bool lists, bool with_ap) {
     const bool bet = optimistic_eligible(c, R, &stride, &need_cnt);
     int flag = 0;
     if (bet) {
-        c->opt_runs++;
+        c->bet_runs++;
         if (with_ap) {
             HG_TRY(ensure_pin(c, (size_t)c->Q * 12 + 16));
             auto& sg = c->sg;
             bool launched = false;
             // event-record nodes inside a graph turned out slow and unreliable on ROCm 7.2 (a replayed step took 1.9 ms
             // instead of 1.55, elapsed times came back for one replay in twenty): with kernel timing on, steps stay eager
-            if (c->opt_graph && !lists && !c->is_sub && c->timing == 0) {
+            if (c->opt.step_graph && !lists && !c->is_sub && c->timing == 0) {
                 const bool same = sg.exec && sg.epoch == g_alloc_epoch && sg.cfg == c->cfg_epoch && sg.R == R && sg.timing == c->timing;
                 const bool seen = sg.seen_epoch == g_alloc_epoch && sg.seen_cfg == c->cfg_epoch && sg.seen_R == R && sg.seen_timing == c->timing;
                 if (!same && seen) {
-                    if (capture_step(c, R, stride, need_cnt) != HG_OK) c->opt_graph = 0;      // not fatal: stay eager from now on
+                    if (capture_step(c, R, stride, need_cnt) != HG_OK) c->opt.step_graph = 0;      // not fatal: stay eager from now on
                 }
                 if (c->sg.exec && c->sg.epoch == g_alloc_epoch && c->sg.cfg == c->cfg_epoch && c->sg.R == R && c->sg.timing == c->timing) {
                     HG_HIP(hipGraphLaunch(sg.exec, c->stream));
@@ -1456,26 +1444,26 @@ static int run_oneshot(hg_ctx* c, int64_t R, bool lists, bool with_ap) {
             HG_TRY(enqueue_optimistic(c, R, stride, need_cnt));
             HG_TRY(read_plan_flag(c, &flag));
         }
-        if (!flag) { c->opt_consecutive_fail = 0; return HG_OK; }
+        if (!flag) { c->bet_consecutive_fail = 0; return HG_OK; }
         bool handled = false;                      // some queries lost their bet
         HG_TRY(rerun_lost_queries(c, R, lists, with_ap, &handled));
-        if (handled) { c->opt_consecutive_fail = 0; return HG_OK; }
+        if (handled) { c->bet_consecutive_fail = 0; return HG_OK; }
         // many queries lost.  Before paying for the exact two-pass sequence (3x the bet at C2), bet once more with
         // twice the safety margin and twice the record budget -- the verification is what makes either bet exact.
         // Still lost: the hits crowd into few segments (a database stored class by class: ten classes put ten times the
         // mean into a query's slices), which no margin on the CUT cures -- escalate the slices' capacity (x8, x64, until a
         // slice would hold its whole segment) and remember what worked for the next calls on this database.
-        if (c->opt_second_bet) {
-            const i64 sigma0 = c->opt_sigma, budget0 = c->cand_budget_x10, boost0 = c->cap_boost;
+        if (c->opt.second_bet) {
+            const i64 sigma0 = c->opt.guess_sigma, budget0 = c->opt.cand_budget_x10, boost0 = c->cap_boost;
             for (int attempt = 0; attempt < 3; ++attempt) {
                 if (attempt > 0) {
                     if (c->cap >= (u32)((c->geo.L + 15) & ~15ll)) break;               // a slice already holds a segment
                     if ((double)c->geo.Q * (double)c->crow * 8.0 * 8.0 > 64e9) break;  // the record rows would not fit comfortably
                     c->cap_boost = c->cap_boost * 8 > 4096 ? 4096 : c->cap_boost * 8;
                 }
-                c->opt_sigma = 2 * sigma0 + 2;
-                c->cand_budget_x10 = 2 * budget0;
-                c->opt_rebets++;
+                c->opt.guess_sigma = 2 * sigma0 + 2;
+                c->opt.cand_budget_x10 = 2 * budget0;
+                c->bet_rebets++;
                 c->want_lists = lists;
                 int rc;
                 if (with_ap) {
@@ -1488,8 +1476,8 @@ static int run_oneshot(hg_ctx* c, int64_t R, bool lists, bool with_ap) {
                     rc = enqueue_optimistic(c, R, stride, need_cnt);
                     if (rc == HG_OK) rc = read_plan_flag(c, &flag);
                 }
-                c->opt_sigma = sigma0;
-                c->cand_budget_x10 = budget0;
+                c->opt.guess_sigma = sigma0;
+                c->opt.cand_budget_x10 = budget0;
                 if (rc != HG_OK) { c->cap_boost = boost0; return rc; }
                 // held with twice the budget of a first bet at this boost: the next call's first bet gets that budget
                 // (a class-sorted database of tight clusters lost every first bet at x8 and won every second one)
@@ -1497,7 +1485,7 @@ static int run_oneshot(hg_ctx* c, int64_t R, bool lists, bool with_ap) {
                 // short this once, not that the slices are too small, and must not ratchet every later first bet's budget up
                 auto keep = [&] {
                     if (attempt > 0 && c->cap_boost < 4096) c->cap_boost *= 2;
-                    c->opt_consecutive_fail = 0;
+                    c->bet_consecutive_fail = 0;
                     c->cfg_epoch++;
                 };
                 if (!flag) { keep(); return HG_OK; }
@@ -1507,8 +1495,8 @@ static int run_oneshot(hg_ctx* c, int64_t R, bool lists, bool with_ap) {
             }
             c->cap_boost = boost0;                 // nothing helped: do not keep paying for big slices
         }
-        c->opt_fallbacks++;                        // still too many: exact path for all
-        c->opt_consecutive_fail++;
+        c->bet_fallbacks++;                        // still too many: exact path for all
+        c->bet_consecutive_fail++;
         c->want_lists = lists;
     }
     if (exact_mx_applies(c, R)) {
@@ -1562,16 +1550,16 @@ int hg_topr(hg_ctx* c, int64_t R) {
 
 int hg_map(hg_ctx* c, int64_t R, double* host_ap, int64_t* host_rel) {
     HG_TRY(need(c, ST_DB | ST_Q, "hg_map", "hg_set_database + hg_set_queries"));
-    const i64 fails0 = c->opt_fallbacks + c->opt_requeried + c->opt_rebets, left0 = c->opt_leftover;
+    const i64 fails0 = c->bet_fallbacks + c->bet_requeried + c->bet_rebets, left0 = c->rank_leftovers;
     c->last_leftovers_inline = false;
     HG_TRY(run_oneshot(c, R, false, true));
     HG_TRY(hg_get_ap(c, host_ap, host_rel));
     // what hg_map_begin may enqueue without looking back: this very step, when it just won its bet outright
     // (queries the fused rank kernel declines are fine when the step ranks them itself within the stream: leftovers_inline)
-    if (c->optimistic && c->opt_fallbacks + c->opt_requeried + c->opt_rebets == fails0 && (c->opt_leftover == left0 || c->last_leftovers_inline) && !c->is_sub) {
+    if (c->optimistic && c->bet_fallbacks + c->bet_requeried + c->bet_rebets == fails0 && (c->rank_leftovers == left0 || c->last_leftovers_inline) && !c->is_sub) {
         c->map_warm_cfg = c->cfg_epoch; c->map_warm_epoch = g_alloc_epoch; c->map_warm_R = R;
         // slot 1's stream now, once per context (a stream costs milliseconds to create -- not inside a caller's pipeline)
-        if (c->opt_step_streams >= 2 && c->own_stream && !c->stream_b) HG_TRY(stream_create(c->device, &c->stream_b));
+        if (c->opt.step_streams >= 2 && c->own_stream && !c->stream_b) HG_TRY(stream_create(c->device, &c->stream_b));
     } else {
         c->map_warm_R = -1;
     }
@@ -1590,8 +1578,8 @@ int hg_map(hg_ctx* c, int64_t R, double* host_ap, int64_t* host_rel) {
 // on stream_b never writes them and a fork point taken after this sees them.  *enqueued: something was.
 static int prepare_shared(hg_ctx* c, int64_t R, bool* enqueued) {
     *enqueued = false;
-    if (c->opt_select_mfma && !c->qx_valid) { HG_TRY(ensure_mx_images(c, false)); *enqueued = true; }
-    const bool recip = c->opt_ap_recip && R <= (1ll << 20);
+    if (c->opt.select_mfma && !c->qx_valid) { HG_TRY(ensure_mx_images(c, false)); *enqueued = true; }
+    const bool recip = c->opt.ap_recip && R <= (1ll << 20);
     if (c->shapes_for_R != R || (recip && c->recip_for_R != R)) {
         HG_TRY(set_R(c, R, 1, 0));
         bool use_recip = false;
@@ -1657,9 +1645,9 @@ int hg_map_begin(hg_ctx* c, int64_t R) {
             HG_HIP(pin_alloc(&m.pin, need_b, &m.cap));
         }
         if (!m.ev) HG_HIP(hipEventCreateWithFlags(&m.ev, hipEventDisableTiming));
-        c->opt_runs++;
+        c->bet_runs++;
         // two streams unless the caller owns the stream (hg_set_stream) or per-kernel timing is on (its events assume one stream)
-        const bool two = c->opt_step_streams >= 2 && c->own_stream && c->timing == 0 && !c->capturing;
+        const bool two = c->opt.step_streams >= 2 && c->own_stream && c->timing == 0 && !c->capturing;
         bool prepped = false;
         if (two) HG_TRY(prepare_shared(c, R, &prepped));
         if (two && slot == 1) {

@@ -282,7 +282,8 @@ int hg_synchronize(hg_ctx* ctx);
 int hg_set_stream(hg_ctx* ctx, void* hip_stream);
 
 /* ---- tuning and measurement -------------------------------------------------- */
-/* Engine options (33 keys; DESIGN.md section 9 lists every key with its default and the test that sets it):
+/* Engine options (39 keys, plus the test hook "handicap_next_bet" described at hg_map_begin; DESIGN.md section 9 lists every key with its
+ * default and the test that sets it):
  *   geometry      "target_units" (16384: wavefront-sized units the pair passes are split into), "min_segment" (256 rows), "max_segments" (2048)
  *   the bet       "optimistic" (1: one-shot calls bet on a sampled threshold -- verified on the device, exact fallback), "sample_stride" (0 = auto: every
  *                 24th tile of 16 rows), "guess_sigma" (5: margin of the guess in standard deviations of the sampled count), "cand_budget_x10" (40: record
@@ -306,12 +307,13 @@ int hg_set_stream(hg_ctx* ctx, void* hip_stream);
  *                 ALU), "real_sample_half" (1: the sampled cut's scores in the filter's 16-bit arithmetic -- they only place the cut; 0: exact float32 chains), "real_second_sample" (1: a second, counting sample four times as large tightens that cut), "real_sort_lds" (1: ranked by the LDS-resident kernel when the records fit), "real_groups" (1: lists beyond the LDS ordered group by group), "real_map_lists" (0; 1: hg_map_real also writes the ranked idx / score lists), "real_whole_rounds" (3: without a cut -- R = N -- the database is cut so that k_real_select_mx's blocks fill whole rounds of that many per CU; 0: the plain geometry)
  *   ("probe_select" exists only in the measurement build, python -m hashgan_amd.build --probes) */
 int hg_set_option(hg_ctx* ctx, const char* key, int64_t value);
-/* Counters and facts about the last call (22 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
+/* Counters and facts about the last call (23 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
  * "optimistic_requeried" (single queries rerun exactly after losing their bet), "optimistic_rebets" (second and widened bets), "last_optimistic",
  * "rank_leftovers" (queries the LDS-resident rank kernel left to the general one), "select_variant" (1 k_select, 2 k_select_dense, 3 k_select_mx,
  * 5 k_select_mx3, 6 k_select_mx4), "rank_variant" (1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>), "ap_fused",
  * "cap_boost", "crowding_x100", "segments", "records_kept" (records the last bet's select left in the slices: a download, not part of a step),
- * "device_bytes", "graph_replays", "map_async_steps" / "map_async_redone" (hg_map_begin: steps enqueued blind / of those, run again by hg_map_end);
+ * "device_bytes" (every device buffer the context and its requery child hold, the second stream's workspace included), "graph_replays", "map_async_steps" / "map_async_redone" / "map_overlapped_steps" (hg_map_begin: steps enqueued blind / of those, run again by hg_map_end /
+ * of those, run on the second stream);
  * "cut_beyond_planes" (1: the last hg_guess_finish met a query whose cut lies beyond the b/2 + 2 planes the owner-routed exchange carries -- its bet
  * cannot be won by wider slices; a download); real-valued path: "real_attempts", "real_requeried" (queries that lost the first cut and were ranked again on their own, cumulative), "real_cap_boost", "real_path" (bit 0 filter + rescoring, bit 1 ranked in LDS,
  * bit 2 lists ordered group by group). */
@@ -320,8 +322,9 @@ int hg_get_stat(hg_ctx* ctx, const char* key, int64_t* value);
  * {-1, 0, +1}, out[1] zeros, out[2] minus ones, out[3] = 1 if the float table is resident on the device -- from which the caller
  * tells +-1 codes (ranked by Hamming distance), {0,1} bits and real-valued features (ranked by inner product, metric.py:13) apart. */
 int hg_get_census(hg_ctx* ctx, int queries, int64_t out[4]);
-/* Work buffers only grow; hg_trim frees everything except the resident code/label/feature tables
- * (stat "device_bytes" reports what the context holds) and empties the process-wide block cache (hg_release_cache): the memory
+/* Work buffers only grow; hg_trim frees every device buffer except the loaded code/label/feature tables -- work buffers, the second
+ * stream's workspace, the images and AP tables built from the tables (rebuilt on their next use) and the requery child context --, so
+ * that stat "device_bytes" reports what the tables alone hold, and empties the process-wide block cache (hg_release_cache): the memory
  * goes back to the HIP runtime, e.g. for another framework in the same process. */
 int hg_trim(hg_ctx* ctx);
 /* Device blocks, pinned host blocks and streams that a destroyed or trimmed context gives up go to a process-wide cache and the

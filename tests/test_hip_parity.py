@@ -714,11 +714,14 @@ def test_failed_bet_falls_back_to_exact(ctx):
     ctx.set_option("optimistic", 1)
 
 
-def test_single_lost_query_is_rerun_alone(ctx):
-    """One query has 3000 exact duplicates of its code in one contiguous block of the database:
-    its slices overflow there (and those of the few queries whose code is within their threshold
-    of it); every other query's bet holds.  Only the lost queries are rerun (exactly) and patched
-    in; AP and the ranked lists equal the oracle's for the lost query and for ordinary ones."""
+_DEFAULTS = {"hist_mfma": 2, "ap_recip": 1}
+
+
+def _lost_queries_rerun_alone(ctx, opts):
+    """One query has 3000 exact duplicates of its code in one contiguous block of the database: its slices overflow there (and
+    those of the few queries whose code is within their threshold of it); every other query's bet holds.  Only the lost queries
+    are rerun (exactly, on the child context, with the parent's options `opts`) and patched in; AP and the ranked lists equal the
+    oracle's for the lost query and for ordinary ones.  Returns the count of queries rerun per call."""
     from hashgan_amd import synth
     Q, N, b, R, C = 256, 131072, 32, 4000, 10
     dl, _ = synth.onehot_labels(91, N, C)
@@ -732,13 +735,15 @@ def test_single_lost_query_is_rerun_alone(ctx):
         _, ap_ref, _, idx_ref, dist_ref = O.map_from_codes(qb[probe], db, ql[probe], dl, R)
     ctx.set_option("optimistic", 1)
     ctx.set_option("crowd_probe", 0)                 # (the first bet's crowding probe would widen the slices and nobody would lose)
+    for k, v in opts.items():
+        ctx.set_option(k, v)
     try:
         ctx.set_database(metric.pack_codes(db), metric.pack_labels(dl), b, C)
         ctx.set_queries(metric.pack_codes(qb), metric.pack_labels(ql))
         f0, p0 = ctx.get_stat("optimistic_fallbacks"), ctx.get_stat("optimistic_requeried")
         ap, rel = ctx.map(R)
         n_lost = ctx.get_stat("optimistic_requeried") - p0
-        assert ctx.get_stat("optimistic_fallbacks") == f0 and 1 <= n_lost < Q // 8
+        assert ctx.get_stat("optimistic_fallbacks") == f0 and n_lost >= 1
         assert np.array_equal(ap[probe], ap_ref, equal_nan=True)
         ctx.topr(R)                                      # same thing with the lists materialised
         assert ctx.get_stat("optimistic_requeried") == p0 + 2 * n_lost
@@ -747,19 +752,36 @@ def test_single_lost_query_is_rerun_alone(ctx):
         ctx.ap()
         ap2, _ = ctx.get_ap()
         assert np.array_equal(ap2[probe], ap_ref, equal_nan=True)
+        return n_lost
     finally:
         ctx.set_option("crowd_probe", 1)
+        for k in opts:
+            ctx.set_option(k, _DEFAULTS[k])
+
+
+def test_single_lost_query_is_rerun_alone(ctx):
+    n_lost = _lost_queries_rerun_alone(ctx, {})
+    assert 1 <= n_lost < 256 // 8
+
+
+def test_lost_queries_rerun_with_the_parents_kernel_options(ctx):
+    """The same with non-default kernel options: the child context reruns the lost queries with the parent's choices."""
+    _lost_queries_rerun_alone(ctx, {"hist_mfma": 1, "ap_recip": 0})
 
 
 def test_trim_frees_work_buffers_and_keeps_tables(ctx, case_cache):
+    """hg_trim gives back every buffer but the loaded tables: after map and topr it returns to what the tables alone hold."""
     c = case_cache("e_ragged")
     g = cases.load_golden("e_ragged")
     _load(ctx, c)
+    ctx.trim()
+    tables = ctx.get_stat("device_bytes")
     ap, _ = ctx.map(c["R"])
+    ctx.topr(c["R"])
     before = ctx.get_stat("device_bytes")
     ctx.trim()
     after = ctx.get_stat("device_bytes")
-    assert after < before
+    assert after < before and after == tables
     with pytest.raises(_native.HashganNativeError):
         ctx.get_ap()                       # results went with the buffers' stage
     ap2, _ = ctx.map(c["R"])               # tables are still loaded
@@ -778,6 +800,47 @@ def test_state_and_argument_errors(ctx, case_cache):
     assert e.value.code == _native.HG_ERR_ARG
     with pytest.raises(_native.HashganNativeError):
         ctx.set_option("no_such_option", 1)
+
+
+def _design_option_table():
+    """(key, default) of every row of DESIGN.md section 9's option table."""
+    import os
+    import re
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "DESIGN.md"), encoding="utf-8").read()
+    sec = text[text.index("## 9. Engine options"):text.index("## 10.")]
+    rows = []
+    for line in sec.splitlines():
+        m = re.match(r"\|\s*`([a-z0-9_]+)`[^|]*\|\s*([^|]*)\|", line)
+        if m:
+            rows.append((m.group(1), int(re.match(r"-?\d+", m.group(2).strip().replace("\u2212", "-")).group(0))))
+    return rows
+
+
+def test_every_documented_option_is_accepted_at_its_default_and_ranges_hold():
+    """hg_set_option's table against DESIGN.md section 9: every key listed there is accepted at its documented default, the ranged
+    keys refuse a value beyond either end (HG_ERR_ARG), and an unknown key is refused."""
+    rows = _design_option_table()
+    assert len(rows) == 39 and len({k for k, _ in rows}) == 39
+    bad = {"target_units": [0], "min_segment": [15], "max_segments": [0], "sample_stride": [-1, 1025], "guess_sigma": [-1, 65],
+           "cand_budget_x10": [10, 1001], "cap_boost": [0, 4097], "hist_mfma": [-1, 3], "rank_lds": [-1, 3], "rank_slices": [-1],
+           "rank_dense": [-1, 3], "rank_dense_gbm": [-2, 2], "dense_budget_mb": [0], "step_streams": [0, 3], "timing_every": [0, 1025],
+           "keep_floats": [-1, 3], "real_mfma": [-1, 3], "real_whole_rounds": [-1, 9], "handicap_next_bet": [-1, 65]}
+    c = _native.Context(0)
+    try:
+        for key, default in rows:
+            c.set_option(key, default)
+        for key, values in bad.items():
+            for v in values:
+                with pytest.raises(_native.HashganNativeError) as e:
+                    c.set_option(key, v)
+                assert e.value.code == _native.HG_ERR_ARG, (key, v)
+        for key, v in (("rank_dense", 2), ("select_packed", -7), ("select_packed", 1 << 40), ("fuse_ap", 5), ("handicap_next_bet", 0)):
+            c.set_option(key, v)                       # the edges that are accepted
+        with pytest.raises(_native.HashganNativeError) as e:
+            c.set_option("no_such_option", 1)
+        assert e.value.code == _native.HG_ERR_ARG
+    finally:
+        c.close()
 
 
 def test_longest_code_and_largest_distance(ctx):

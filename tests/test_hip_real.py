@@ -245,11 +245,11 @@ def test_features_that_follow_the_labels_in_a_class_sorted_database():
         c.close()
 
 
-def test_a_few_lost_queries_are_ranked_again_on_their_own():
+def _lost_queries_ranked_again(opts):
     """Two of 240 queries have their whole top R in one stretch of the database (near-copies of themselves stored together): their
     slices overflow whatever the cut -- and those long rows crowd a few other queries' lists too --, the rest win their bet.
-    Only the losers run again (a child context on the same tables, stat "real_requeried"), the call itself stays at one
-    attempt, and every list and AP is the oracle's bit for bit."""
+    Only the losers run again (a child context on the same tables and options, stat "real_requeried") and every list and AP is
+    the oracle's bit for bit.  Returns the queries ranked again per call and the attempts of the first call."""
     rng = np.random.default_rng(17)
     Q, N, b, R, C = 240, 150000, 32, 1500, 7
     dbf = np.tanh(rng.standard_normal((N, b))).astype(np.float32)
@@ -265,16 +265,63 @@ def test_a_few_lost_queries_are_ranked_again_on_their_own():
         m, ap_ref, idx_ref, score_ref = RM.map_from_features(qf, dbf, ql, dl, R)
     c = _native.Context(0)
     try:
+        for k, v in opts.items():
+            c.set_option(k, v)
         c.set_database_f32(dbf, dl)
         c.set_queries_f32(qf, ql)
         n0 = c.get_stat("real_requeried")
         ap, rel = c.map_real(R)
         assert np.array_equal(ap, ap_ref, equal_nan=True)
         n1 = c.get_stat("real_requeried") - n0
-        assert c.get_stat("real_attempts") == 1 and 2 <= n1 <= 15, (c.get_stat("real_attempts"), n1)
+        attempts = c.get_stat("real_attempts")
+        assert n1 >= 1
         idx, score = c.topr_real(R)
         assert np.array_equal(idx, idx_ref) and np.array_equal(score.view(np.uint32), score_ref.view(np.uint32))
         assert c.get_stat("real_requeried") - n0 == 2 * n1
+        return n1, attempts
+    finally:
+        c.close()
+
+
+def test_a_few_lost_queries_are_ranked_again_on_their_own():
+    """... with the default options the call itself stays at one attempt."""
+    n1, attempts = _lost_queries_ranked_again({})
+    assert attempts == 1 and 2 <= n1 <= 15, (attempts, n1)
+
+
+def test_lost_queries_are_ranked_again_with_the_parents_options():
+    """... and with non-default options of the sampled cut, which the child context runs with too."""
+    _lost_queries_ranked_again({"real_sample_half": 0, "real_second_sample": 0})
+
+
+def test_trim_returns_to_the_tables():
+    """hg_trim after a real-valued ranking that took the filter path (R << N: sampled cut, 16-bit filter, exact rescoring) gives
+    back every buffer but the loaded tables: the context holds what it held after loading them and trimming."""
+    rng = np.random.default_rng(7)
+    Q, N, b, R, C = 12, 70000, 64, 700, 10
+    dbf = np.tanh(rng.standard_normal((N, b))).astype(np.float32)
+    qf = np.tanh(rng.standard_normal((Q, b))).astype(np.float32)
+    dl = np.eye(C, dtype=np.int64)[rng.integers(0, C, N)]
+    ql = np.eye(C, dtype=np.int64)[rng.integers(0, C, Q)]
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        m, ap_ref, idx_ref, score_ref = RM.map_from_features(qf, dbf, ql, dl, R)
+    c = _native.Context(0)
+    try:
+        c.set_database_f32(dbf, dl)
+        c.set_queries_f32(qf, ql)
+        c.trim()
+        tables = c.get_stat("device_bytes")
+        ap, _ = c.map_real(R)
+        assert c.get_stat("real_path") & 1, "the filter path"
+        idx, score = c.topr_real(R)
+        assert c.get_stat("device_bytes") > tables
+        c.trim()
+        assert c.get_stat("device_bytes") == tables
+        assert np.array_equal(ap, ap_ref, equal_nan=True)
+        assert np.array_equal(idx, idx_ref) and np.array_equal(score.view(np.uint32), score_ref.view(np.uint32))
+        ap2, _ = c.map_real(R)                     # the tables are still there
+        assert np.array_equal(ap2, ap_ref, equal_nan=True)
     finally:
         c.close()
 

@@ -161,6 +161,42 @@ def test_one_and_two_streams_identical(c2):
             ctx.close()
 
 
+@pytest.mark.gpu
+def test_device_bytes_count_the_second_workspace(c2):
+    """Batch after batch through hg_map_begin / hg_map_end with one and with two streams: the second stream's workspace is held by
+    the context (stat "device_bytes" counts it), and hg_trim gives it back -- both contexts then hold their tables alone, what
+    they held after loading them and trimming."""
+    c, _ = c2
+    R = c["R"]
+    fwd, rev = slice(None), slice(None, None, -1)
+    held, tables, trimmed = {}, {}, {}
+    for streams in (1, 2):
+        ctx = _native.Context(0)
+        try:
+            _load(ctx, c)
+            ctx.set_option("step_streams", streams)
+            ctx.trim()
+            tables[streams] = ctx.get_stat("device_bytes")
+            ctx.map(R)                                     # (warm: the next begin may enqueue blind)
+            for k in range(3):
+                _queries(ctx, c, fwd)
+                ctx.map_begin(R)
+                _queries(ctx, c, rev)
+                ctx.map_begin(R)
+                ctx.map_end()
+                ctx.map_end()
+            ctx.synchronize()
+            if streams == 2:
+                assert ctx.get_stat("map_overlapped_steps") >= 1
+            held[streams] = ctx.get_stat("device_bytes")
+            ctx.trim()
+            trimmed[streams] = ctx.get_stat("device_bytes")
+        finally:
+            ctx.close()
+    assert held[2] > held[1], held
+    assert trimmed[1] == trimmed[2] == tables[1] == tables[2], (trimmed, tables)
+
+
 class _FailingEnd:
     """Stand-in for the library: hg_map_end fails (as when a lost step's tables were replaced)."""
 
