@@ -295,12 +295,44 @@ struct StepBufs {
     }
 };
 
-struct hg_ctx : StepBufs {
+// What the enqueue of a step leaves behind on the host for the entry points after it.  hg_ctx inherits it, and a captured step
+// (hg_ctx::StepGraph) keeps the copy its replays restore by one assignment.
+struct StepState {
+    unsigned stage = ST_NONE;
+    Geo geo{};
+    i64 RW = 0;
+    bool optimistic = false;   // records come from a guessed threshold (fixed-capacity slices)
+    bool lists_valid = false;
+    bool rec8 = false;         // the record rows hold one-byte compact records (matrix-core select, no lists wanted)
+    u32 cap = 0;               // optimistic slice capacity
+    i64 crow = 0;              // record-row stride
+    // AP from the rank kernel's epilogue (k_rank_cnt: the bitmap is still in LDS) -- one launch less per step, and the general
+    // rank kernel for the queries k_rank_cnt declines is launched only when the step's download says there are any
+    bool ap_fused = false;     // the last launch_rank left the AP of every query it ranked in c->ap / c->rel, leftovers counted in err[1]
+    bool leftovers_inline = false;     // ... and the step ranked those leftovers itself within the stream (rank_leftovers_inline)
+    int last_select = 0;       // stat "select_variant": 1 k_select, 2 k_select_dense, 3 k_select_mx, 5 k_select_mx3, 6 k_select_mx4
+    int last_rank = 0;         // stat "rank_variant": 1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>
+};
+
+// What one enqueue of a step is asked to do.  Built by the entry point and passed down by const reference to the launchers; a
+// level that knows more (the guess kernel has cleared the verdict word, the sequence cuts at the exact threshold) hands a copy
+// on, so a request ends with its call.  The staged entry points pass the default.
+struct StepReq {
+    bool fuse_ap = false;      // AP from the rank kernel's epilogue wanted (hg_map), where option "fuse_ap" and the kernel allow it
+    enum Rows { RECORDS, BYTES, DIRECT } rows = RECORDS;   // the rank stage's rows: the select's records, the byte matrix (k_dense_bytes
+                               // + k_rank_dense), or the database rows themselves (R = N: k_rank_fused computes distance and match bit per row)
+    bool exact_cut = false;    // the matrix-core select and the LDS rank kernels cut at the EXACT threshold c->t (hg_hist + k_plan), not the guess c->tguess
+    bool err_zeroed = false;   // the guess kernel in front of the rank stage already cleared the verdict word
+    i64 guess_sigma = 0;       // the bet's margin and record budget for this attempt (options "guess_sigma", "cand_budget_x10"; a second
+    i64 cand_budget_x10 = 0;   // bet widens both)
+    void* dst = nullptr;       // pinned block the results go to (hg_map_begin's slot); nullptr: the context's own
+};
+
+struct hg_ctx : StepBufs, StepState {
     int device = 0;
     int n_cu = 256;            // compute units of the device
     hipStream_t stream = nullptr;
     bool own_stream = true;    // false: the stream belongs to the caller (hg_set_stream) or to the parent context
-    unsigned stage = ST_NONE;
     Options opt;
 
     // problem
@@ -308,8 +340,6 @@ struct hg_ctx : StepBufs {
     int b = 0, C = 0, NW = 0, NB = 0, LW = 0;
     u32 idx_base = 0;
     int G = 1, rank = 0;
-    Geo geo{};
-    i64 RW = 0;
 
     i64 real_grouped = 0;      // stat: the last real-valued ranking ordered its record lists group by group (k_real_group_*)
     i64 real_cap_boost = 1;    // the same for the real-valued ranking's slices (run_real)
@@ -317,19 +347,11 @@ struct hg_ctx : StepBufs {
     i64 crowd_x100 = 0;        // stat "crowding_x100": that measure, x 100 (~200: rows in random order; ~100 x classes: stored class by class)
     i64 cap_boost = 1;         // slice capacity multiplier a lost bet escalated to on this database (run_oneshot); 1 after every load
     bool leftovers_expected = false;   // the last fused step on this context left queries to the general kernel
-    bool last_leftovers_inline = false;   // (the last finished step did: finish_leftovers)
-    bool leftovers_inline = false;     // ... and this step ranked its own within the stream (launch_rank_slices with the flags)
-    bool dense_rank = false;   // run state of enqueue_all_rows: rank through the byte matrix
+    bool last_leftovers_inline = false;   // ... and the last finished step had ranked its own within the stream (finish_leftovers)
 
-    // run state
-    bool optimistic = false;   // records come from a guessed threshold (fixed-capacity slices)
+    // run state (what a step leaves behind: StepState)
     bool want_lists = true;
-    bool lists_valid = false;
-    u32 cap = 0;               // optimistic slice capacity
-    i64 crow = 0;              // record-row stride
     i64 bet_runs = 0, bet_fallbacks = 0, bet_requeried = 0;   // stats "optimistic_runs", "optimistic_fallbacks", "optimistic_requeried"
-    int last_select = 0;       // stat "select_variant": 1 k_select, 2 k_select_dense, 3 k_select_mx, 5 k_select_mx3, 6 k_select_mx4
-    int last_rank = 0;         // stat "rank_variant": 1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>
     i64 rank_leftovers = 0;    // stat "rank_leftovers": queries of fused steps that k_rank_cnt left to the general rank kernel
     int bet_consecutive_fail = 0;   // one-shot bets lost in a row (this context only)
     int shard_bet_fail = 0;         // sharded bets lost in a row: identical on every rank by construction
@@ -338,16 +360,8 @@ struct hg_ctx : StepBufs {
 
     // device state (the buffers themselves: for_each_buf)
     bool dbx_valid = false, qx_valid = false, dbx8_valid = false, dbx3_valid = false, dbx4_valid = false;
-    bool direct_rank = false;  // R = N: k_rank_fused computes distance and match bit per row itself (no records)
     bool hist_pairs = false;   // the last FULL histogram pass ran per segment pair (k_hist_mx)
-    bool exact_mx = false;     // the matrix-core select runs with the EXACT threshold (hg_hist + k_plan) instead of a guess
-    bool rec8 = false;         // the record rows hold one-byte compact records (matrix-core select, no lists wanted)
     i64 bet_rebets = 0;        // stat "optimistic_rebets"
-    bool err_zeroed = false;   // the guess kernel of a one-shot bet already cleared err
-    // AP from the rank kernel's epilogue (k_rank_cnt: the bitmap is still in LDS) -- one launch less per step, and the general
-    // rank kernel for the queries k_rank_cnt declines is launched only when the step's download says there are any
-    bool fuse_ap = false;      // request of the current enqueue (hg_map's bet)
-    bool ap_fused = false;     // the last launch_rank left the AP of every query it ranked in c->ap / c->rel, leftovers counted in err[1]
     bool verdict_pending = false, verdict_known = false;
     int verdict_flag = 0;
     // pinned landing zone for a one-shot call's results: AP, hit counts and the lost-bet flag come back with the
@@ -476,8 +490,7 @@ struct hg_ctx : StepBufs {
         unsigned long long epoch = 0, cfg = 0, seen_epoch = 0, seen_cfg = 0;   // key of exec / of the last eager step
         i64 R = -1, seen_R = -1;
         int timing = -1, seen_timing = -1;
-        // host-side state the captured enqueue functions leave behind
-        unsigned stage = 0; bool optimistic = false, lists_valid = false, ap_fused = false, rec8 = false; u32 cap = 0; i64 crow = 0, RW = 0; Geo geo{};
+        StepState left;                    // what the captured enqueue left behind on the host
         std::vector<Pending> evs;          // event-record nodes inside the graph (kernel timing)
     } sg;
     unsigned long long cfg_epoch = 1;      // bumped by everything that changes what a step enqueues (tables, options, stream)
@@ -603,6 +616,7 @@ int launch_min_topr(hg_ctx* c, const u32* idx_all, const u8* dist_all, i64 n, in
 hg_ctx* requery_child(hg_ctx* c, i64 nF);       // c->sub, set up to rerun nF lost queries of c
 // hg_seq.hip
 int stage_ap_download(hg_ctx* c, void* dst = nullptr);   // {verdict, AP, hit counts} into pinned host memory behind everything enqueued so far (no synchronisation)
+int wait_verdict(hg_ctx* c, bool staged, int* flag);     // waits for the stream; the verdict word from the context's pinned block (staged) or by a download of its own
 void make_geometry(hg_ctx* c);
 Geo hist_geometry(const hg_ctx* c);
 int set_R(hg_ctx* c, int64_t R, int G, int rank);
@@ -613,9 +627,10 @@ int launch_select_dense(hg_ctx* c, int lw);      // k_select_dense<NW, LW>
 // hg_pairs_mx.hip (k_select_mx: hg_pairs_mx1.hip)
 int ensure_mx_images(hg_ctx* c, bool need_db);  // fp4 images of database / query codes, built on first use
 int launch_hist_mx(hg_ctx* c);                   // k_hist_i8 / k_hist_mx
-int launch_select_mx(hg_ctx* c, int lw);         // k_select_mx<NW, LW, QT, COMPACT>
-int launch_select_mx3(hg_ctx* c, int lw);        // k_select_mx3 (codes of <= 64 bits, one-byte records)
-int launch_select_mx4(hg_ctx* c, int lw);        // k_select_mx4 (codes of 65..128 bits, one-byte records)
+// (cut: each query's threshold -- c->tguess, or c->t for StepReq::exact_cut)
+int launch_select_mx(hg_ctx* c, int lw, const int* cut);    // k_select_mx<NW, LW, QT, COMPACT>
+int launch_select_mx3(hg_ctx* c, int lw, const int* cut);   // k_select_mx3 (codes of <= 64 bits, one-byte records)
+int launch_select_mx4(hg_ctx* c, int lw, const int* cut);   // k_select_mx4 (codes of 65..128 bits, one-byte records)
 int preload_valu(); int preload_mx(); int preload_mx1(); int preload_real(); int preload_seq();   // one per translation unit with kernels (hg_preload)
 // hg_comm.hip
 void comm_release(hg_ctx* c);                    // destroys the context's communicator, if any

@@ -71,7 +71,7 @@ template <int NW> int launch_hist_mx_t(hg_ctx* c) {
 
 // codes of 33..64 bits, compact records: three rows per accumulator and the batched drain (k_select_mx3);
 // blocks = (pair of segments) x (256 queries); the query image is k_select_mx's
-template <int NW, int LW> int launch_select_mx3_t(hg_ctx* c) {
+template <int NW, int LW> int launch_select_mx3_t(hg_ctx* c, const int* cut) {
     HG_TRY(ensure_mx_images(c, false));
     if (!c->dbx3_valid) {
         const i64 n48 = (c->N + M3_ROWS - 1) / M3_ROWS * M3_ROWS + M3_WS_MAX * M3_ROWS;     // + one window of zero rows: the last segment's last window may run past the end
@@ -94,7 +94,7 @@ template <int NW, int LW> int launch_select_mx3_t(hg_ctx* c) {
     const Mx3Lds L = mx3_lds_layout(NW, LW);
     if (L.total > 64 * 1024)
         HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_select_mx3<NW, LW>), hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-    SelArgs a{c->exact_mx ? c->t.as<int>() : c->tguess.as<int>(), c->sl_start.as<u32>(), c->sl_tie.as<u32>(), c->sl_cnt.as<u32>(),
+    SelArgs a{cut, c->sl_start.as<u32>(), c->sl_tie.as<u32>(), c->sl_cnt.as<u32>(),
               c->failq.as<u32>(), c->cap, c->crow, 1, c->sstar.as<int>(), (int)c->opt.probe_select};
     c->t_begin(KI_SELECT_MX);
     hipLaunchKernelGGL((k_select_mx3<NW, LW>), dim3(padded_grid(g.nBlk)), dim3(64 * M3_WPB), (size_t)L.total, c->stream, c->qc.as<u32>(),
@@ -159,7 +159,7 @@ int launch_hist_mx(hg_ctx* c) {
 namespace {
 // codes of 65..128 bits, compact records: two rows per accumulator and the batched drain (k_select_mx4);
 // blocks = (pair of segments) x (512 queries); the query image is k_select_mx's
-template <int NW, int LW> int launch_select_mx4_t(hg_ctx* c) {
+template <int NW, int LW> int launch_select_mx4_t(hg_ctx* c, const int* cut) {
     HG_TRY(ensure_mx_images(c, false));
     if (!c->dbx4_valid) {
         const i64 n32 = (c->N + M4_ROWS - 1) / M4_ROWS * M4_ROWS + M4_WS * M4_ROWS;     // + one window of zero rows: the last segment's last window may run past the end
@@ -181,7 +181,7 @@ template <int NW, int LW> int launch_select_mx4_t(hg_ctx* c) {
     const Mx4Lds L = mx4_lds_layout(NW, LW);
     if (L.total > 64 * 1024)
         HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_select_mx4<NW, LW>), hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-    SelArgs a{c->exact_mx ? c->t.as<int>() : c->tguess.as<int>(), c->sl_start.as<u32>(), c->sl_tie.as<u32>(), c->sl_cnt.as<u32>(),
+    SelArgs a{cut, c->sl_start.as<u32>(), c->sl_tie.as<u32>(), c->sl_cnt.as<u32>(),
               c->failq.as<u32>(), c->cap, c->crow, 1, c->sstar.as<int>(), 0};
     c->t_begin(KI_SELECT_MX);
     hipLaunchKernelGGL((k_select_mx4<NW, LW>), dim3(padded_grid(g.nBlk)), dim3(64 * M4_WPB), (size_t)L.total, c->stream, c->qc.as<u32>(),
@@ -192,16 +192,16 @@ template <int NW, int LW> int launch_select_mx4_t(hg_ctx* c) {
 }
 }  // namespace
 
-int launch_select_mx4(hg_ctx* c, int lw) {           // codes of 65..128 bits, one-byte records, <= 128 classes
+int launch_select_mx4(hg_ctx* c, int lw, const int* cut) {           // codes of 65..128 bits, one-byte records, <= 128 classes
     if (c->NW < 3 || c->NW > 4 || lw < 1 || lw > 2) return fail(HG_ERR_ARG, "k_select_mx4 takes codes of 65..128 bits and 1..128 classes");
-    if (c->NW == 3) return lw == 1 ? launch_select_mx4_t<3, 1>(c) : launch_select_mx4_t<3, 2>(c);
-    return lw == 1 ? launch_select_mx4_t<4, 1>(c) : launch_select_mx4_t<4, 2>(c);
+    if (c->NW == 3) return lw == 1 ? launch_select_mx4_t<3, 1>(c, cut) : launch_select_mx4_t<3, 2>(c, cut);
+    return lw == 1 ? launch_select_mx4_t<4, 1>(c, cut) : launch_select_mx4_t<4, 2>(c, cut);
 }
 
-int launch_select_mx3(hg_ctx* c, int lw) {           // codes of <= 64 bits, one-byte records, <= 128 classes
+int launch_select_mx3(hg_ctx* c, int lw, const int* cut) {           // codes of <= 64 bits, one-byte records, <= 128 classes
     if (c->NW > 2 || lw < 1 || lw > 2) return fail(HG_ERR_ARG, "k_select_mx3 takes codes of <= 64 bits and 1..128 classes");
-    if (c->NW == 1) return lw == 1 ? launch_select_mx3_t<1, 1>(c) : launch_select_mx3_t<1, 2>(c);
-    return lw == 1 ? launch_select_mx3_t<2, 1>(c) : launch_select_mx3_t<2, 2>(c);
+    if (c->NW == 1) return lw == 1 ? launch_select_mx3_t<1, 1>(c, cut) : launch_select_mx3_t<1, 2>(c, cut);
+    return lw == 1 ? launch_select_mx3_t<2, 1>(c, cut) : launch_select_mx3_t<2, 2>(c, cut);
 }
 
 // hg_preload: the runtime loads a translation unit's code object when one of its kernels is first needed (milliseconds);

@@ -521,12 +521,8 @@ static int real_attempt(hg_ctx* c, int64_t R, bool bet, double sigma, double bud
             c->stage = ST_DB | ST_Q | ST_SELECT | ST_MATCH;
             HG_TRY(do_ap(c));
             HG_TRY(stage_ap_download(c));
-            HG_TRY(c->sync());
-            flag = *(const int*)c->pin;
-            c->stage = ST_DB | ST_Q | ST_SELECT;
-        } else {
-            HG_TRY(read_plan_flag(c, &flag));
         }
+        HG_TRY(wait_verdict(c, with_ap, &flag));
         if (!(flag & 2)) {
             c->real_lds_ranked = 1;
             c->real_lists_made = !skip_lists;
@@ -581,12 +577,9 @@ static int real_attempt(hg_ctx* c, int64_t R, bool bet, double sigma, double bud
             c->stage = ST_DB | ST_Q | ST_SELECT | ST_MATCH;
             HG_TRY(do_ap(c));
             HG_TRY(stage_ap_download(c));
-            HG_TRY(c->sync());
-            flag = *(const int*)c->pin;
-            c->stage = ST_DB | ST_Q | ST_SELECT;
-        } else {
-            HG_TRY(read_plan_flag(c, &flag));
         }
+        HG_TRY(wait_verdict(c, with_ap, &flag));
+        if (with_ap) c->stage = ST_DB | ST_Q | ST_SELECT;
         if (flag & 4) {
             HG_HIP(hipMemsetAsync(c->err.p, 0, 4, c->stream));
         } else {

@@ -102,6 +102,8 @@ static bool select_takes_mx(const hg_ctx* c) { return c->optimistic && c->opt.se
 static bool records_are_bytes(const hg_ctx* c) {
     return select_takes_mx(c) && c->opt.compact_records && !c->want_lists && c->LW <= 2 && c->cap % 16 == 0 && c->crow * 64 < (1ll << 31);
 }
+// the ranked idx / dist lists are written: somebody asked for them, or k_match gathers the labels through the idx list (> 128 classes)
+static bool lists_needed(const hg_ctx* c) { return c->want_lists || c->LW > 2; }
 // the record rows of the coming select: Q x crow slots of one byte or eight.  (Until round 6 eight bytes were reserved either way:
 // 2 GB at C2 for 0.25 GB of records -- and 14.9 GB once a class-sorted database had widened the slices, a hipMalloc that took
 // between 0.4 ms and 3.5 s.)
@@ -109,18 +111,21 @@ static int reserve_records(hg_ctx* c) {
     return c->cand.reserve((size_t)c->geo.Q * (size_t)c->crow * (records_are_bytes(c) ? 1 : 8) + 64);
 }
 
-int launch_select(hg_ctx* c) {
+static const int* cut_of(const hg_ctx* c, const StepReq& req) { return req.exact_cut ? c->t.as<int>() : c->tguess.as<int>(); }
+
+static int launch_select(hg_ctx* c, const StepReq& req) {
     const int NW = c->NW;
+    const int* cut = cut_of(c, req);
     const int lw = c->LW <= 2 ? c->LW : 0;           // > 128 classes: match bits come from k_match
     const bool mx = select_takes_mx(c);
     c->rec8 = records_are_bytes(c);
     if (!c->optimistic && c->R * 4 >= c->n_total) { c->last_select = 2; return launch_select_dense(c, lw); }   // dense regime: most pairs are selected
     // three rows per accumulator + batched drain: codes of <= 64 bits, one-byte records (<= 128 classes).  (For <= 32 bits the
     // second k-half of every MFMA is empty, and it still beat round 2's two-rows-per-accumulator kernel: 0.69 vs 0.85 ms at b = 32.)
-    if (NW <= 2 && c->opt.select_packed == 3 && c->rec8 && c->geo.L % M3_ROWS == 0 && (lw == 1 || lw == 2)) { c->last_select = 5; return launch_select_mx3(c, lw); }
+    if (NW <= 2 && c->opt.select_packed == 3 && c->rec8 && c->geo.L % M3_ROWS == 0 && (lw == 1 || lw == 2)) { c->last_select = 5; return launch_select_mx3(c, lw, cut); }
     // codes of 65..128 bits: two rows per accumulator (8-bit fields) and the same drain
-    if ((NW == 3 || NW == 4) && c->opt.select_packed == 3 && c->rec8 && c->geo.L % M4_ROWS == 0 && (lw == 1 || lw == 2)) { c->last_select = 6; return launch_select_mx4(c, lw); }
-    if (mx) { c->last_select = 3; return launch_select_mx(c, lw); }
+    if ((NW == 3 || NW == 4) && c->opt.select_packed == 3 && c->rec8 && c->geo.L % M4_ROWS == 0 && (lw == 1 || lw == 2)) { c->last_select = 6; return launch_select_mx4(c, lw, cut); }
+    if (mx) { c->last_select = 3; return launch_select_mx(c, lw, cut); }
     c->last_select = 1;
     return launch_select_valu(c, lw, c->optimistic);
 }
@@ -260,14 +265,14 @@ static int do_plan(hg_ctx* c, int64_t R, const uint32_t* dev_hist_all, int G, in
     return HG_OK;
 }
 
+static int plan_overrun(hg_ctx* c) {                  // k_plan's verdict on an exact sequence
+    c->stage = ST_DB | ST_Q | ST_HIST;
+    return fail(HG_ERR_ARG, "R=%lld exceeds the rows present in the gathered histograms", (long long)c->R);
+}
 static int check_plan_flag(hg_ctx* c) {
     int err = 0;
     HG_TRY(read_plan_flag(c, &err));
-    if (err) {
-        c->stage = ST_DB | ST_Q | ST_HIST;
-        return fail(HG_ERR_ARG, "R=%lld exceeds the rows present in the gathered histograms", (long long)c->R);
-    }
-    return HG_OK;
+    return err ? plan_overrun(c) : HG_OK;
 }
 
 int hg_plan(hg_ctx* c, int64_t R, const uint32_t* dev_hist_all, int G, int rank) {
@@ -284,8 +289,7 @@ int hg_plan(hg_ctx* c, int64_t R, const uint32_t* dev_hist_all, int G, int rank)
 // k_rank_fused in one of its modes: 0 = histogram + plan + placement in one launch (single shard),
 // 1 = histogram phase (several shards, before the exchange), 2 = placement phase (after k_plan).
 // the dense regime through the byte matrix (hg_rank_dense.hpp): the counter columns always fit a block's LDS for codes of <= 126 bits
-static bool rank_dense_fits(const hg_ctx* c, int64_t R) {
-    (void)R;
+static bool rank_dense_fits(const hg_ctx* c) {
     return c->opt.rank_dense && c->LW <= 2 && c->NW <= 4 && c->b <= 126 && c->N == c->n_total && !c->is_sub;
 }
 
@@ -310,7 +314,7 @@ static void launch_dense_bytes(hg_ctx* c, u8* D, i64 Npad, int q0, int nq) {
 #undef HG_DENSE_BYTES
 }
 
-static int launch_rank_dense(hg_ctx* c) {
+static int launch_rank_dense(hg_ctx* c, const StepReq& req) {
     const Geo& g = c->geo;
     HG_TRY(c->err.reserve(16));
     HG_TRY(c->qbad.reserve((size_t)g.Qpad * 4));
@@ -347,7 +351,7 @@ static int launch_rank_dense(hg_ctx* c) {
         qchunk = (qchunk + 1) / 2;
     }
     bool use_recip = false;
-    const bool fuse = !gbm && !rw_part && blocks_lds >= 2 && c->fuse_ap && c->opt.fuse_ap && !c->want_lists;
+    const bool fuse = !gbm && !rw_part && blocks_lds >= 2 && req.fuse_ap && c->opt.fuse_ap && !c->want_lists;
     if (fuse) HG_TRY(ensure_ap_tables(c, &use_recip));
     const bool fused = fuse && use_recip;
     if (gbm) HG_HIP(hipMemsetAsync(c->mbits.p, 0, (size_t)g.Q * c->RW * 8, c->stream));
@@ -380,19 +384,19 @@ static int launch_rank_dense(hg_ctx* c) {
 
 // k_rank_dense<slices> (hg_rank_dense.hpp) over the bet's one-byte records: the whole launch (long lists), or only the queries
 // flagged in `only` (what k_rank_lean declined -- then always with the AP from the epilogue: a handful of blocks)
-static int slices_rows(const hg_ctx* c) {
+static int slices_rows(const hg_ctx* c, const StepReq& req) {
     // the bet's cut never exceeds b/2 + 1 -- enqueue_optimistic's sampled pass stops there --, so b/2 + 2 counter rows cover its records
-    return (!c->exact_mx && c->geo.NB / 2 + 2 < c->geo.NB) ? c->geo.NB / 2 + 2 : c->geo.NB;
+    return (!req.exact_cut && c->geo.NB / 2 + 2 < c->geo.NB) ? c->geo.NB / 2 + 2 : c->geo.NB;
 }
-static bool rank_slices_fits(const hg_ctx* c) {
-    return c->optimistic && c->rec8 && !c->want_lists && c->geo.S <= RD_THREADS && slices_rows(c) <= 126 &&
-           rank_dense_layout(slices_rows(c) + 1, c->RW, false).total <= 160 * 1024;
+static bool rank_slices_fits(const hg_ctx* c, const StepReq& req) {
+    return c->optimistic && c->rec8 && !c->want_lists && c->geo.S <= RD_THREADS && slices_rows(c, req) <= 126 &&
+           rank_dense_layout(slices_rows(c, req) + 1, c->RW, false).total <= 160 * 1024;
 }
-static int launch_rank_slices(hg_ctx* c, const u32* only) {
+static int launch_rank_slices(hg_ctx* c, const StepReq& req, const u32* only) {
     const Geo& g = c->geo;
-    const int sl_rows = slices_rows(c);
+    const int sl_rows = slices_rows(c, req);
     const int total = rank_dense_layout(sl_rows + 1, c->RW, false).total;
-    const bool fuse = c->fuse_ap && c->opt.fuse_ap && (only || 160 * 1024 / total >= 2);
+    const bool fuse = req.fuse_ap && c->opt.fuse_ap && (only || 160 * 1024 / total >= 2);
     bool use_recip = false;
     if (fuse) HG_TRY(ensure_ap_tables(c, &use_recip));
     const bool fused = fuse && use_recip;
@@ -413,25 +417,31 @@ static int launch_rank_slices(hg_ctx* c, const u32* only) {
 // The last fused step on this context had queries its rank kernel declined (one of C5's 10 000 spans more distances than
 // k_rank_lean places): rank the flagged ones right behind it, in the same stream -- a launch of mostly returning blocks --
 // instead of a second host round trip (k_rank_fused + k_ap + three downloads: 0.08 ms of C5's 1.27).
-static int rank_leftovers_inline(hg_ctx* c, int mode, bool use_recip) {
+static int rank_leftovers_inline(hg_ctx* c, const StepReq& req, int mode, bool use_recip) {
     c->leftovers_inline = false;
-    if (c->leftovers_expected && mode == 0 && c->opt.inline_leftovers && use_recip && rank_slices_fits(c)) {
-        HG_TRY(launch_rank_slices(c, c->bigq.as<u32>()));
+    if (c->leftovers_expected && mode == 0 && c->opt.inline_leftovers && use_recip && rank_slices_fits(c, req)) {
+        HG_TRY(launch_rank_slices(c, req, c->bigq.as<u32>()));
         c->leftovers_inline = true;
     }
     return HG_OK;
 }
 
+// Every record of a bet lies within its query's cut (the guess; the exact threshold of enqueue_exact_mx), and a list
+// reaching further down than the 16 (32) distances the LDS rank kernels place leaves them anyway: byte counters for the 18 (34)
+// distances up to the cut are all they need (round 3: b/2 + 2 of them -- 8.7 KB of LDS at b = 64, 16.9 KB at b = 128); a
+// query with a record below them goes to k_rank_fused.  0: a counter for every distance (short codes), and no cut to read.
+static int cut_counters(const Geo& g) { return rank_cnt_maxb(g.NB) + 2 < g.NB ? rank_cnt_maxb(g.NB) + 2 : 0; }
+
 // Which LDS-resident rank kernel a bet's one-byte records will meet -- decided from what is known BEFORE the select runs (R, the
 // slices' capacity, the segment count, options), because the select writes the interleaved record layout (SelArgs::il) only for
 // the kernel that reads it, k_rank_lean (k_rank_fused, the general kernel behind every path, reads both layouts).
-struct LeanPlan { bool ok; int nbc, psp; i64 rb; };
+struct LeanPlan { bool ok; int psp; i64 rb; };
 static LeanPlan rank_lean_plan(const hg_ctx* c, int mode) {
     const Geo& g = c->geo;
-    LeanPlan l{false, 0, 1, 0};
+    LeanPlan l{false, 1, 0};
     if (!(c->optimistic && c->opt.rank_lds >= 2 && (mode == 0 || mode == 3) && c->rec8 && !c->want_lists &&
           g.S <= 256 && (c->cap & 15u) == 0 && c->cap <= 1024 && g.R <= 60000)) return l;
-    const int nbc = rank_cnt_maxb(g.NB) + 2 < g.NB ? rank_cnt_maxb(g.NB) + 2 : 0;
+    const int nbc = cut_counters(g);
     const int nbc_eff = nbc ? nbc : (g.NB < 128 ? g.NB : 128);
     // room for every piece of the row when that fits HG_RANK_WAVES blocks per CU; else for the usual list (2.2 R + padding)
     const double share = (double)c->N / (double)(c->n_total > 0 ? c->n_total : 1);
@@ -450,15 +460,22 @@ static LeanPlan rank_lean_plan(const hg_ctx* c, int mode) {
     if (rb > all) rb = all;
     if (rb > 16 * RL_MAX_PIECES) rb = 16 * RL_MAX_PIECES;      // a thread keeps at most four pieces of its query's list
     const RankLeanLds L = rank_lean_layout(g.NB, c->RW, g.S, (int)rb, nbc);
-    l.nbc = nbc; l.psp = psp; l.rb = rb;
+    l.psp = psp; l.rb = rb;
     l.ok = nbc_eff <= 63 && L.total <= 64 * 1024 && rb >= 16 && (rb >= least || rb == all);
     return l;
 }
+static int nbits_for(int NB) {
+    int nbits = 1;
+    while ((1 << nbits) < NB) ++nbits;
+    return nbits;
+}
 // leftovers_only: the second half of a fused step -- k_rank_cnt has run (with its AP epilogue) and flagged in bigq the queries
 // it declined; rank just those with the general kernel
-static int launch_rank(hg_ctx* c, int mode, int nbits, bool leftovers_only = false) {
+static int launch_rank(hg_ctx* c, int mode, const StepReq& req, bool leftovers_only = false) {
     const Geo& g = c->geo;
-    if (c->dense_rank && mode == 0) return launch_rank_dense(c);
+    if (req.rows == StepReq::BYTES && mode == 0) return launch_rank_dense(c, req);
+    const int nbits = nbits_for(g.NB);
+    const bool lists = lists_needed(c);
     int nwav = (c->optimistic ? 3 * c->R : c->R) >= 16384 ? 16 : 4;   // k_rank_fused's wavefronts per query, by the records per query (~ 3R / R)
     if (leftovers_only && c->R >= 1024) nwav = 16;   // a handful of blocks (mode 0: no hwq): what counts is one block's latency
     const size_t fixed_words = (size_t)(nwav + 1) * g.NB + 8;
@@ -471,9 +488,8 @@ static int launch_rank(hg_ctx* c, int mode, int nbits, bool leftovers_only = fal
     HG_TRY(c->hwq.reserve((size_t)4096 * 16 * 4 + (size_t)g.Q * nwav * g.NB * 4));
 #endif
     if (mode == 0 && !leftovers_only) {
-        if (c->optimistic) { if (!c->err_zeroed) HG_HIP(hipMemsetAsync(c->err.p, 0, 8, c->stream)); }
+        if (c->optimistic) { if (!req.err_zeroed) HG_HIP(hipMemsetAsync(c->err.p, 0, 8, c->stream)); }
         else HG_HIP(hipMemsetAsync(c->failq.p, 0, (size_t)g.Qpad * 4, c->stream));
-        c->err_zeroed = false;
     }
     const u32* only = nullptr;
     bool counted = false;
@@ -481,15 +497,16 @@ static int launch_rank(hg_ctx* c, int mode, int nbits, bool leftovers_only = fal
     if (!leftovers_only) c->last_rank = 1;                // k_rank_fused unless one of the LDS-resident kernels takes the lists
     if (leftovers_only) { only = c->bigq.as<u32>(); counted = true; }
     const LeanPlan lp = rank_lean_plan(c, mode);
+    const int nbc = cut_counters(g);
+    const int* cut = nbc ? cut_of(c, req) : nullptr;
     if (!counted) {
         // the lean counting sort (k_rank_lean): the whole record row in one coalesced read, piecewise compaction, chunks in registers
-        const int nbc = lp.nbc, psp = lp.psp;
+        const int psp = lp.psp;
         const i64 rb = lp.rb;
-        const int* cut = nbc ? (c->exact_mx ? c->t.as<int>() : c->tguess.as<int>()) : nullptr;
         if (lp.ok) {
             const RankLeanLds L = rank_lean_layout(g.NB, c->RW, g.S, (int)rb, nbc);
             HG_TRY(c->bigq.reserve((size_t)g.Qpad * 4));
-            const bool fuse = c->fuse_ap && c->opt.fuse_ap && mode == 0 && c->LW <= 2;
+            const bool fuse = req.fuse_ap && c->opt.fuse_ap && mode == 0 && c->LW <= 2;
             bool use_recip = false;
             if (fuse) HG_TRY(ensure_ap_tables(c, &use_recip));
             RankLdsArgs la{c->sl_cnt.as<u32>(), c->failq.as<u32>(), c->err.as<int>(), c->qbad.as<u32>(), c->bigq.as<u32>(),
@@ -504,16 +521,16 @@ static int launch_rank(hg_ctx* c, int mode, int nbits, bool leftovers_only = fal
             c->last_rank = 6;
             if (fuse) {
                 c->ap_fused = true;
-                HG_TRY(rank_leftovers_inline(c, mode, use_recip));
+                HG_TRY(rank_leftovers_inline(c, req, mode, use_recip));
                 return HG_OK;
             }
             only = c->bigq.as<u32>();                // k_rank_fused below ranks what this path declined
             counted = true;
         }
     }
-    if (!counted && mode == 0 && g.R >= c->opt.rank_slices && c->opt.rank_slices > 0 && rank_slices_fits(c)) {
+    if (!counted && mode == 0 && g.R >= c->opt.rank_slices && c->opt.rank_slices > 0 && rank_slices_fits(c, req)) {
         // long lists of a bet (beyond k_rank_lean's LDS): k_rank_dense's two passes over the query's record slices, thread = part of a slice
-        return launch_rank_slices(c, nullptr);
+        return launch_rank_slices(c, req, nullptr);
     }
     if (!counted && c->optimistic && c->opt.rank_lds >= 1 && (mode == 0 || mode == 3)) {
         // per-thread counting sort (k_rank_cnt): byte counters for every distance + a tile of the records, <= 64 KiB per
@@ -522,33 +539,27 @@ static int launch_rank(hg_ctx* c, int mode, int nbits, bool leftovers_only = fal
         i64 r2 = (i64)(2.5 * (double)c->R * share) + 256;         // a tile of the records: the usual list (1.3 - 2 R) in one
         if (r2 < 4096) r2 = 4096;                                  // (small R: the guess's margin is relatively larger)
         r2 = r2 / 64 * 64;
-        // every record of a bet lies within its query's cut (the guess; the exact threshold of the exact_mx sequence), and a
-        // list reaching further down than the 16 (32) distances this kernel places leaves it anyway: byte counters for the
-        // 18 (34) distances up to the cut are all it needs (round 3: b/2 + 2 of them -- 8.7 KB of LDS at b = 64, 16.9 KB at
-        // b = 128); a query with a record below them goes to k_rank_fused
-        const int nbc = rank_cnt_maxb(g.NB) + 2 < g.NB ? rank_cnt_maxb(g.NB) + 2 : 0;
-        const int* cut = nbc ? (c->exact_mx ? c->t.as<int>() : c->tguess.as<int>()) : nullptr;
-        RankCntLds L = rank_cnt_layout(g.NB, c->RW, g.S, (int)r2, c->want_lists ? 1 : 0, nbc);
+        RankCntLds L = rank_cnt_layout(g.NB, c->RW, g.S, (int)r2, lists ? 1 : 0, nbc);
         {   // one block more per CU when trimming the record tile by a few percent (never below 2.2 R) makes it fit
             const int per_cu = (int)(160 * 1024 / ((L.total + 511) & ~511));
             const i64 want = (160 * 1024 / (per_cu + 1)) & ~511ll;
             const i64 r3 = (r2 - (L.total - want)) / 64 * 64;
             // (the kernel is compiled for HG_RANK_WAVES wavefronts per SIMD = blocks per CU: more LDS room than that buys nothing)
-            if (per_cu + 1 <= HG_RANK_WAVES && L.total > want && r3 >= (i64)(2.2 * (double)c->R * share) + 256 && r3 >= 4096 && !c->want_lists) {
+            if (per_cu + 1 <= HG_RANK_WAVES && L.total > want && r3 >= (i64)(2.2 * (double)c->R * share) + 256 && r3 >= 4096 && !lists) {
                 r2 = r3;
                 L = rank_cnt_layout(g.NB, c->RW, g.S, (int)r2, 0, nbc);
             }
         }
-        while (L.total > 64 * 1024 && r2 > 64) { r2 -= 64; L = rank_cnt_layout(g.NB, c->RW, g.S, (int)r2, c->want_lists ? 1 : 0, nbc); }
+        while (L.total > 64 * 1024 && r2 > 64) { r2 -= 64; L = rank_cnt_layout(g.NB, c->RW, g.S, (int)r2, lists ? 1 : 0, nbc); }
         if (L.total <= 64 * 1024 && r2 >= 4096) {
             HG_TRY(c->bigq.reserve((size_t)g.Qpad * 4));
             // hg_map's bet: the AP leaves with the ranking (the bitmap is in LDS), and the general kernel below is NOT launched --
             // the step's download carries the number of queries this kernel declined (err[1]); the host launches it only then
-            const bool fuse = c->fuse_ap && c->opt.fuse_ap && mode == 0 && !c->want_lists && c->LW <= 2;
+            const bool fuse = req.fuse_ap && c->opt.fuse_ap && mode == 0 && !lists && c->LW <= 2;
             bool use_recip = false;
             if (fuse) HG_TRY(ensure_ap_tables(c, &use_recip));
             RankLdsArgs la{c->sl_cnt.as<u32>(), c->failq.as<u32>(), c->err.as<int>(), c->qbad.as<u32>(), c->bigq.as<u32>(),
-                           c->cap, c->crow, c->want_lists ? 1 : 0, c->rec8 ? 1 : 0, c->RW, (int)r2, mode, c->hwq.as<u32>(), c->hown.as<u32>(),
+                           c->cap, c->crow, lists ? 1 : 0, c->rec8 ? 1 : 0, c->RW, (int)r2, mode, c->hwq.as<u32>(), c->hown.as<u32>(),
                            c->t.as<int>(), c->cnt_lt.as<u32>(), c->quota.as<u32>(), c->tie_before.as<u32>(), c->posbase.as<u32>(), nbc,
                            fuse ? c->shapes.as<ApShape>() : nullptr, fuse && use_recip ? c->ap_recip.as<double>() : nullptr,
                            c->ap.as<double>(), c->rel.as<u32>(), fuse ? c->err.as<u32>() + 1 : nullptr, cut};
@@ -558,7 +569,7 @@ static int launch_rank(hg_ctx* c, int mode, int nbits, bool leftovers_only = fal
             c->t_end();
             HG_TRY(c->check_launch("k_rank_cnt"));
             c->last_rank = 3;
-            if (fuse) { c->ap_fused = true; if (c->rec8) HG_TRY(rank_leftovers_inline(c, mode, use_recip)); return HG_OK; }
+            if (fuse) { c->ap_fused = true; if (c->rec8) HG_TRY(rank_leftovers_inline(c, req, mode, use_recip)); return HG_OK; }
             only = c->bigq.as<u32>();                // k_rank_fused below ranks what this path declined
             counted = true;
         }
@@ -566,8 +577,8 @@ static int launch_rank(hg_ctx* c, int mode, int nbits, bool leftovers_only = fal
     RankArgs ra{c->sl_cnt.as<u32>(), c->tot.as<u32>(), c->failq.as<u32>(), c->err.as<int>(), c->qbad.as<u32>(),
                 mode, c->hwq.as<u32>(), c->hown.as<u32>(), c->t.as<int>(), c->cnt_lt.as<u32>(), c->quota.as<u32>(),
                 c->tie_before.as<u32>(), c->posbase.as<u32>(),
-                c->optimistic ? c->cap : 256u, c->crow, c->optimistic ? 0 : 1, c->want_lists ? 1 : 0, bits_lds, c->RW, only,
-                c->direct_rank ? 1 : 0, c->rec8 ? 1 : 0, c->db.as<u32>(), c->dblab.as<u64>(), c->qc.as<u32>(), c->qlab.as<u64>()};
+                c->optimistic ? c->cap : 256u, c->crow, c->optimistic ? 0 : 1, lists ? 1 : 0, bits_lds, c->RW, only,
+                req.rows == StepReq::DIRECT ? 1 : 0, c->rec8 ? 1 : 0, c->db.as<u32>(), c->dblab.as<u64>(), c->qc.as<u32>(), c->qlab.as<u64>()};
     const size_t lds_bytes = (fixed_words + (bits_lds ? 2 * (size_t)c->RW : 0)) * 4;
     c->t_begin(mode == 1 ? KI_CAND_HIST : KI_RANK_FUSED);
     if (nwav == 16)
@@ -581,39 +592,37 @@ static int launch_rank(hg_ctx* c, int mode, int nbits, bool leftovers_only = fal
 }
 
 // record pass + ordering (+ gather-based label match when labels are too wide for the record pass)
-static int do_select(hg_ctx* c) {
+static int do_select(hg_ctx* c, const StepReq& req) {
     const Geo& g = c->geo;
     const size_t slots = (size_t)g.Q * g.R;
-    if (c->LW > 2) c->want_lists = true;                  // k_match gathers through the idx list
+    const bool lists = lists_needed(c);
     HG_TRY(reserve_records(c));
     HG_TRY(c->mbits.reserve((size_t)g.Q * c->RW * 8));
-    HG_TRY(c->out_idx.reserve(c->want_lists ? slots * 4 : 16));
-    HG_TRY(c->out_dist.reserve(c->want_lists ? slots : 16));
-    if (c->want_lists && c->G > 1) {  // slots of other shards stay IDX_NONE / 0xFF
+    HG_TRY(c->out_idx.reserve(lists ? slots * 4 : 16));
+    HG_TRY(c->out_dist.reserve(lists ? slots : 16));
+    if (lists && c->G > 1) {  // slots of other shards stay IDX_NONE / 0xFF
         HG_HIP(hipMemsetAsync(c->out_idx.p, 0xFF, slots * 4, c->stream));
         HG_HIP(hipMemsetAsync(c->out_dist.p, 0xFF, slots, c->stream));
     }
-    HG_TRY(launch_select(c));
-    int nbits = 1;
-    while ((1 << nbits) < g.NB) ++nbits;
+    HG_TRY(launch_select(c, req));
     if (c->optimistic || c->G == 1) {
         // one block per query: verify (optimistic) + plan + order.  Exact single-shard rows hold
         // precisely the top R, so the same counting plan reproduces t and the bucket starts.
-        HG_TRY(launch_rank(c, 0, nbits));
+        HG_TRY(launch_rank(c, 0, req));
     } else {
         const size_t lds_words = (size_t)g.NB + 2 * (size_t)c->RW;
         const int bits_lds = WPB * lds_words * 4 <= 64 * 1024;
         if (!bits_lds) HG_HIP(hipMemsetAsync(c->mbits.p, 0, (size_t)g.Q * c->RW * 8, c->stream));
         OrdArgs oa{c->t.as<int>(), c->cnt_lt.as<u32>(), c->quota.as<u32>(), c->tie_before.as<u32>(), c->posbase.as<u32>(),
-                   c->tot.as<u32>(), c->crow, c->want_lists ? 1 : 0, bits_lds, c->RW};
+                   c->tot.as<u32>(), c->crow, lists ? 1 : 0, bits_lds, c->RW};
         c->t_begin(KI_ORDER);
         hipLaunchKernelGGL(k_order, dim3(grid_for(g.Q, WPB)), dim3(256),
                            (size_t)WPB * (g.NB + (bits_lds ? 2 * (size_t)c->RW : 0)) * 4, c->stream, c->cand.as<u64>(), oa,
-                           c->out_idx.as<u32>(), c->out_dist.as<u8>(), c->mbits.as<u32>(), nbits, g);
+                           c->out_idx.as<u32>(), c->out_dist.as<u8>(), c->mbits.as<u32>(), nbits_for(g.NB), g);
         c->t_end();
         HG_TRY(c->check_launch("k_order"));
     }
-    c->lists_valid = c->want_lists;
+    c->lists_valid = lists;
     c->stage = (c->stage & (ST_DB | ST_Q | ST_HIST | ST_PLAN)) | ST_PLAN | ST_SELECT;
     if (c->LW <= 2) c->stage |= ST_MATCH;                 // match bits came with the records
     else HG_TRY(do_match(c));
@@ -623,7 +632,7 @@ static int do_select(hg_ctx* c) {
 int hg_select(hg_ctx* c) {
     HG_TRY(need(c, ST_PLAN, "hg_select", "hg_plan"));
     c->want_lists = c->opt.staged_lists != 0;
-    HG_TRY(do_select(c));
+    HG_TRY(do_select(c, StepReq{}));
     return c->stage_end();
 }
 
@@ -707,12 +716,10 @@ int hg_select_candidates(hg_ctx* c) {
     const Geo& g = c->geo;
     c->want_lists = c->opt.staged_lists != 0 || c->LW > 2;  // decides the record format (hg_rank places them)
     HG_TRY(reserve_records(c));
-    HG_TRY(launch_select(c));
+    HG_TRY(launch_select(c, StepReq{}));
     const size_t plane = (size_t)g.NB * g.Qpad * 4;
     HG_HIP(hipMemsetAsync(c->hown.as<char>() + plane, 0, TAIL_WORDS * 4, c->stream));
-    int nbits = 1;
-    while ((1 << nbits) < g.NB) ++nbits;
-    HG_TRY(launch_rank(c, 1, nbits));                // per-wave and shard histograms of the records
+    HG_TRY(launch_rank(c, 1, StepReq{}));                // per-wave and shard histograms of the records
     return c->stage_end();
 }
 
@@ -735,12 +742,10 @@ int hg_select_ranked(hg_ctx* c) {
     if (wide) HG_HIP(hipMemsetAsync(c->out_idx.p, 0xFF, slots * 4, c->stream));    // slots past the shard's own records: IDX_NONE
     HG_TRY(c->err.reserve(16));
     HG_HIP(hipMemsetAsync(c->err.p, 0, 4, c->stream));
-    HG_TRY(launch_select(c));
+    HG_TRY(launch_select(c, StepReq{}));
     const size_t plane = (size_t)g.NB * g.Qpad * 4;
     HG_HIP(hipMemsetAsync(c->hown.as<char>() + plane, 0, TAIL_WORDS * 4, c->stream));
-    int nbits = 1;
-    while ((1 << nbits) < g.NB) ++nbits;
-    HG_TRY(launch_rank(c, 3, nbits));
+    HG_TRY(launch_rank(c, 3, StepReq{}));
     c->lists_valid = false;
     c->ranked_local = true;
     c->stage = ST_DB | ST_Q | ST_PLAN | ST_SELECT;
@@ -844,9 +849,7 @@ int hg_rank(hg_ctx* c, const uint32_t* dev_hist_all, int G, int rank, int* bet_l
         HG_HIP(hipMemsetAsync(c->out_dist.p, 0xFF, slots, c->stream));
     }
     HG_TRY(launch_plan(c, dev_hist_all));
-    int nbits = 1;
-    while ((1 << nbits) < g.NB) ++nbits;
-    HG_TRY(launch_rank(c, 2, nbits));                // placement with the shared plan
+    HG_TRY(launch_rank(c, 2, StepReq{}));                // placement with the shared plan
     if (c->opt.defer_verdict) {
         // the caller goes on as if the bet held (match bits, exchange, AP) and asks hg_bet_verdict at the end,
         // together with its final download: no host round trip in the middle of the step
@@ -1074,24 +1077,20 @@ int hg_merge_ap_owned(hg_ctx* c, const void* dev_recv, int G, int rank, void** d
 // superset with it, then verify: the records' exact histogram must contain R rows
 // and no slice may have overflowed.  The verified result is identical to the
 // exact path's; a failed bet reruns the exact path.
-static bool optimistic_eligible(hg_ctx* c, int64_t R, int* stride_out, u32* need_out) {
+static bool optimistic_eligible(hg_ctx* c, int64_t R, int* stride_out) {
     if (!c->opt.optimistic || c->bet_consecutive_fail >= 2) return false;
     if (R * 8 > c->N || c->N < 65536) return false;
     make_geometry(c);
     const int stride = auto_stride(c, R);
     if (stride < 2) return false;
-    const i64 sampled = sampled_rows(c, stride);
-    const double fr = (double)R * (double)sampled / (double)c->N;   // expected sample count at the true cut
-    const double need = fr + (double)c->opt.guess_sigma * std::sqrt(fr) + 1.0;
     *stride_out = stride;
-    *need_out = (u32)std::ceil(need);
     return true;
 }
 
 // R = N on one shard (the reference's CIFAR-10 setting): every row is a member of every ranked list, so nothing
 // has to be selected or written down -- the ranking kernel walks the shard's rows directly, computing each row's
 // distance and match bit from the codes and labels in both of its passes (counting, then stable placement).
-static int enqueue_all_rows(hg_ctx* c, int64_t R) {
+static int enqueue_all_rows(hg_ctx* c, int64_t R, const StepReq& req, StepReq::Rows rows) {
     make_geometry(c);
     HG_TRY(set_R(c, R, 1, 0));
     const Geo& g = c->geo;
@@ -1106,31 +1105,24 @@ static int enqueue_all_rows(hg_ctx* c, int64_t R) {
     c->optimistic = false;
     c->crow = R;
     c->cap = 0;
-    int nbits = 1;
-    while ((1 << nbits) < g.NB) ++nbits;
-    c->direct_rank = true;
     c->rec8 = false;
     c->last_select = 0;                                // no record pass at all
-    const int rc = launch_rank(c, 0, nbits);
-    c->direct_rank = false;
-    c->dense_rank = false;
-    HG_TRY(rc);
+    StepReq walk = req;
+    walk.rows = rows;
+    HG_TRY(launch_rank(c, 0, walk));
     c->lists_valid = c->want_lists;
     c->stage = ST_DB | ST_Q | ST_PLAN | ST_SELECT | ST_MATCH;
     return HG_OK;
 }
 
-static int enqueue_exact(hg_ctx* c, int64_t R) {
+static int enqueue_exact(hg_ctx* c, int64_t R, const StepReq& req) {
     // N/8 < R <= N through the byte matrix (k_dense_bytes + k_rank_dense: R = N/2 of N = 1M 68.8 -> 16.3 ms, C1 0.35 -> 0.19 ms)
-    if (R * 8 > c->N && c->opt.all_rows_shortcut && rank_dense_fits(c, R)) {
-        c->dense_rank = true;
-        return enqueue_all_rows(c, R);
-    }
+    if (R * 8 > c->N && c->opt.all_rows_shortcut && rank_dense_fits(c)) return enqueue_all_rows(c, R, req, StepReq::BYTES);
     if (c->N == c->n_total && R == c->N && c->opt.all_rows_shortcut && c->LW <= 2 && c->NW <= 8)
-        return enqueue_all_rows(c, R);                 // one-shot calls are single-shard; codes / label sets the byte matrix does not take: k_rank_fused walks the rows
+        return enqueue_all_rows(c, R, req, StepReq::DIRECT);   // one-shot calls are single-shard; codes / label sets the byte matrix does not take: k_rank_fused walks the rows
     HG_TRY(do_hist(c, 1));
     HG_TRY(do_plan(c, R, nullptr, 1, 0));
-    return do_select(c);
+    return do_select(c, req);
 }
 
 // The exact sequence with its second pass on the matrix cores (one shard, R << N): full histogram -> plan (exact
@@ -1140,7 +1132,7 @@ static int enqueue_exact(hg_ctx* c, int64_t R) {
 static bool exact_mx_applies(const hg_ctx* c, int64_t R) {
     return c->opt.select_mfma && c->N == c->n_total && R * 8 <= c->N && c->N >= 65536 && !c->is_sub;
 }
-static int enqueue_exact_mx(hg_ctx* c, int64_t R) {
+static int enqueue_exact_mx(hg_ctx* c, int64_t R, const StepReq& req) {
     HG_TRY(do_hist(c, 1, true, true));                 // per segment pair on the matrix cores where that applies
     HG_TRY(do_plan(c, R, nullptr, 1, 0));              // c->t, c->sstar; leaves optimistic = false, crow = R
     const Geo& g = c->geo;
@@ -1150,17 +1142,15 @@ static int enqueue_exact_mx(hg_ctx* c, int64_t R) {
     u32 cap = (u32)std::ceil(mean + 6.0 * std::sqrt(mean) + 16.0);
     cap = (cap + 15u) & ~15u;
     c->optimistic = true;
-    c->exact_mx = true;
     c->cap = cap;
     c->crow = (i64)g.S * cap;
     HG_HIP(hipMemsetAsync(c->failq.p, 0, (size_t)g.Qpad * 4, c->stream));
-    const int rc = do_select(c);
-    c->exact_mx = false;
-    return rc;
+    StepReq exact = req;
+    exact.exact_cut = true;
+    return do_select(c, exact);
 }
 
-static int enqueue_optimistic(hg_ctx* c, int64_t R, int stride, u32 need_cnt) {
-    (void)need_cnt;
+static int enqueue_optimistic(hg_ctx* c, int64_t R, int stride, const StepReq& req) {
     // the guess stops at the cut, far below b/2 when R <= N/8 on any data whose queries resemble the database: the
     // sampled pass writes only those planes (130 -> 68 MB per launch at C2).  A cut beyond them reads as a thin
     // sample -- everything is taken, the slices overflow, the exact sequence answers.
@@ -1182,7 +1172,7 @@ static int enqueue_optimistic(hg_ctx* c, int64_t R, int stride, u32 need_cnt) {
     {   // lanes per query by the number of sampled segments each has to sum
         const int ratio = (int)(gh.L / g.L);
         const u32 srows = (u32)sampled_rows(c, stride);
-        double sigma = (double)c->opt.guess_sigma;
+        double sigma = (double)req.guess_sigma;
         if (c->handicap_next && !c->capturing) { sigma = -(double)c->handicap_next; c->handicap_next = 0; }   // (test hook: this bet is meant to lose)
 #define HG_GUESS(P)                                                                                                     \
         hipLaunchKernelGGL(k_guess_direct<P>, dim3(grid_for(g.Qpad, WPB * (64 / P))), dim3(256), 0, c->stream,          \
@@ -1197,7 +1187,6 @@ static int enqueue_optimistic(hg_ctx* c, int64_t R, int stride, u32 need_cnt) {
     }
     c->t_end();
     HG_TRY(c->check_launch("k_guess_direct"));
-    c->err_zeroed = true;                              // launch_rank need not clear the lost-bet flag again
     if (probe) {
         // One host round trip, once per database: sum over the queries of (fullest sampled segment) * segments / (their total)
         // is ~2 for rows in random order (the maximum of ~50 small Poisson counts) and ~the number of classes for a database
@@ -1220,16 +1209,16 @@ static int enqueue_optimistic(hg_ctx* c, int64_t R, int stride, u32 need_cnt) {
     // distance bucket, and cumulative counts grow ~2x per bucket in the tail where the cut lies; clustered
     // codes grow faster) -- budget 4 R per query over the S segments plus 6 sigma per slice.  HBM is
     // plentiful (2.5 GB at C2); an overflow only costs the exact rerun.
-    const double mean = 0.1 * (double)c->opt.cand_budget_x10 * (double)c->cap_boost * (double)R / (double)g.S;
+    const double mean = 0.1 * (double)req.cand_budget_x10 * (double)c->cap_boost * (double)R / (double)g.S;
     u32 cap = slice_capacity(c, mean);
     c->optimistic = true;
     c->cap = cap;
     c->crow = (i64)g.S * cap;
     c->stage = ST_DB | ST_Q | ST_PLAN;
-    return do_select(c);
+    StepReq guessed = req;
+    guessed.err_zeroed = true;                         // k_guess_direct cleared the lost-bet flag: launch_rank need not
+    return do_select(c, guessed);
 }
-
-static int enqueue_exact(hg_ctx* c, int64_t R);
 
 // Lost bets are per query (a short superset, an overflowed slice).  When only a few queries lost,
 // rerun just those through the exact sequence in a child context that borrows the database
@@ -1262,7 +1251,7 @@ static int rerun_lost_queries(hg_ctx* c, int64_t R, bool lists, bool with_ap, bo
     HG_TRY(c->check_launch("k_move_rows"));
     s->stage = ST_DB | ST_Q;
     s->want_lists = lists;
-    HG_TRY(enqueue_exact(s, R));
+    HG_TRY(enqueue_exact(s, R, StepReq{}));
     if (with_ap) HG_TRY(do_ap(s));
     move(s->mbits.p, c->mbits.p, c->RW * 8, 0);
     if (with_ap) {
@@ -1294,6 +1283,15 @@ static __global__ __launch_bounds__(256) void k_copy_out(const uint4* __restrict
     if (i < tail_dwords) ((u32*)(dst + n16))[i] = ((const u32*)(src + n16))[i];
 }
 
+// the copy-engine form: {verdict, leftover count}, APs and hit counts wherever the three live
+static int download_results(hg_ctx* c, char* pb) {    // pb: [flag: 16 B][ap Q x 8][rel Q x 4]
+    const size_t Q = (size_t)c->geo.Q;
+    HG_HIP(hipMemcpyAsync(pb, c->err.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HG_HIP(hipMemcpyAsync(pb + 16, c->ap.p, Q * 8, hipMemcpyDeviceToHost, c->stream));
+    HG_HIP(hipMemcpyAsync(pb + 16 + Q * 8, c->rel.p, Q * 4, hipMemcpyDeviceToHost, c->stream));
+    return HG_OK;
+}
+
 extern "C++" int stage_ap_download(hg_ctx* c, void* dst) {      // dst: a pinned block of its own (hg_map_begin), else (nullptr) the context's
     const size_t Q = (size_t)c->geo.Q;
     if (!dst) HG_TRY(ensure_pin(c, Q * 12 + 16));
@@ -1310,32 +1308,47 @@ extern "C++" int stage_ap_download(hg_ctx* c, void* dst) {      // dst: a pinned
         hipLaunchKernelGGL(k_copy_out, dim3((n16 + 255) / 256 + (n16 % 256 == 0 && tail ? 1 : 0)), dim3(256), 0, c->stream, (const uint4*)base, (uint4*)pb, n16, tail);
         return c->check_launch("k_copy_out");
     }
-    HG_HIP(hipMemcpyAsync(pb, c->err.p, 8, hipMemcpyDeviceToHost, c->stream));
-    HG_HIP(hipMemcpyAsync(pb + 16, c->ap.p, Q * 8, hipMemcpyDeviceToHost, c->stream));
-    HG_HIP(hipMemcpyAsync(pb + 16 + Q * 8, c->rel.p, Q * 4, hipMemcpyDeviceToHost, c->stream));
+    return download_results(c, pb);
+}
+
+extern "C++" int wait_verdict(hg_ctx* c, bool staged, int* flag) {
+    if (!staged) return read_plan_flag(c, flag);
+    HG_TRY(c->sync());
+    *flag = *(const int*)c->pin;
     return HG_OK;
 }
 
-static int enqueue_bet_with_ap(hg_ctx* c, int64_t R, int stride, u32 need_cnt, void* dst = nullptr) {
+// One attempt at a step, enqueued: the sequence of its kind, then -- for hg_map -- the APs (unless a rank kernel's epilogue left
+// them) and their way home.  Pure enqueue for a bet whose buffers are warm, so a bet can run under stream capture.
+enum Attempt { AT_BET, AT_EXACT_MX, AT_EXACT };
+static int enqueue_attempt(hg_ctx* c, Attempt kind, int64_t R, int stride, const StepReq& req, bool with_ap) {
     c->t_step_begin();
-    c->fuse_ap = true;
-    const int rc = enqueue_optimistic(c, R, stride, need_cnt);
-    c->fuse_ap = false;
-    HG_TRY(rc);
-    if (c->ap_fused) { c->ap_staged = false; c->stage |= ST_AP; }     // k_rank_cnt's epilogue left the APs (leftovers: run_oneshot)
-    else HG_TRY(do_ap(c));
-    HG_TRY(stage_ap_download(c, dst));         // [flag, leftover count: 16 B][ap Q x 8][rel Q x 4]
+    HG_TRY(kind == AT_BET ? enqueue_optimistic(c, R, stride, req) : kind == AT_EXACT_MX ? enqueue_exact_mx(c, R, req) : enqueue_exact(c, R, req));
+    if (with_ap) {
+        if (c->ap_fused) { c->ap_staged = false; c->stage |= ST_AP; }     // the rank kernel's epilogue left the APs (leftovers: finish_leftovers)
+        else HG_TRY(do_ap(c));
+        if (kind == AT_EXACT) c->ap_fused = false;     // (no leftovers on this path: nothing for finish_leftovers)
+        HG_TRY(stage_ap_download(c, req.dst));         // [flag, leftover count: 16 B][ap Q x 8][rel Q x 4]; C1 (R = N through the byte matrix): 0.17 -> 0.14 ms per call
+    }
     c->t_step_end();
     return HG_OK;
 }
+// the bet as the options ask for it
+static StepReq bet_request(const hg_ctx* c, bool fuse_ap, void* dst = nullptr) {
+    StepReq req;
+    req.fuse_ap = fuse_ap;
+    req.guess_sigma = c->opt.guess_sigma;
+    req.cand_budget_x10 = c->opt.cand_budget_x10;
+    req.dst = dst;
+    return req;
+}
 
-// Second sighting of the same step (same tables, options, R, timing level; no buffer moved since): capture it.
-static int capture_step(hg_ctx* c, int64_t R, int stride, u32 need_cnt) {
+static int capture_step(hg_ctx* c, int64_t R, int stride, const StepReq& req) {
     c->drop_graph();
     const unsigned long long epoch0 = g_alloc_epoch.load();
     HG_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
     c->capturing = true;
-    const int rc = enqueue_bet_with_ap(c, R, stride, need_cnt);
+    const int rc = enqueue_attempt(c, AT_BET, R, stride, req, true);
     c->capturing = false;
     hipGraph_t gr = nullptr;
     const hipError_t e = hipStreamEndCapture(c->stream, &gr);
@@ -1356,8 +1369,7 @@ static int capture_step(hg_ctx* c, int64_t R, int stride, u32 need_cnt) {
     auto& sg = c->sg;
     sg.graph = gr; sg.exec = ex;
     sg.epoch = g_alloc_epoch; sg.cfg = c->cfg_epoch; sg.R = R; sg.timing = c->timing;
-    sg.stage = c->stage; sg.optimistic = c->optimistic; sg.lists_valid = c->lists_valid; sg.cap = c->cap; sg.crow = c->crow;
-    sg.RW = c->RW; sg.geo = c->geo; sg.ap_fused = c->ap_fused; sg.rec8 = c->rec8;
+    sg.left = *c;                                      // (the context's StepState)
     c->graph_captures++;
     return HG_OK;
 }
@@ -1374,75 +1386,77 @@ static int finish_leftovers(hg_ctx* c, int* flag) {
     c->rank_leftovers += nleft;
     c->last_leftovers_inline = c->leftovers_inline;
     if (c->leftovers_inline) { c->leftovers_inline = false; return HG_OK; }     // k_rank_dense<slices> ranked them within the step
-    const size_t Q = (size_t)c->geo.Q;
-    int nbits = 1;
-    while ((1 << nbits) < c->geo.NB) ++nbits;
-    HG_TRY(launch_rank(c, 0, nbits, true));
+    HG_TRY(launch_rank(c, 0, StepReq{}, true));
     HG_TRY(do_ap_range(c, 0, c->geo.Q, c->bigq.as<u32>()));
-    char* pb = (char*)c->pin;
-    HG_HIP(hipMemcpyAsync(pb, c->err.p, 8, hipMemcpyDeviceToHost, c->stream));
-    HG_HIP(hipMemcpyAsync(pb + 16, c->ap.p, Q * 8, hipMemcpyDeviceToHost, c->stream));
-    HG_HIP(hipMemcpyAsync(pb + 16 + Q * 8, c->rel.p, Q * 4, hipMemcpyDeviceToHost, c->stream));
-    HG_TRY(c->sync());
-    *flag = *(const int*)c->pin;
+    HG_TRY(download_results(c, (char*)c->pin));
+    return wait_verdict(c, true, flag);
+}
+
+// What follows every enqueued attempt of a one-shot call: wait, read the verdict (the bet was lost, a slice overflowed, R
+// exceeds the rows), and for hg_map rank what a fused step left over; ap_staged: the pinned block holds the call's results.
+static int await_attempt(hg_ctx* c, bool with_ap, int* flag) {
+    HG_TRY(wait_verdict(c, with_ap, flag));
+    if (with_ap) {
+        HG_TRY(finish_leftovers(c, flag));
+        c->ap_staged = *flag == 0;
+    }
+    return HG_OK;
+}
+static int run_attempt(hg_ctx* c, Attempt kind, int64_t R, int stride, const StepReq& req, bool with_ap, int* flag) {
+    static const bool trace = getenv("HG_STEP_TRACE") != nullptr;        // debugging: where a slow step spent its time
+    const auto tp0 = std::chrono::steady_clock::now();
+    HG_TRY(enqueue_attempt(c, kind, R, stride, req, with_ap));
+    const auto tp1 = std::chrono::steady_clock::now();
+    HG_TRY(await_attempt(c, with_ap, flag));
+    if (trace) {
+        const auto tp2 = std::chrono::steady_clock::now();
+        const double e = std::chrono::duration<double, std::milli>(tp1 - tp0).count(), w = std::chrono::duration<double, std::milli>(tp2 - tp1).count();
+        if (e + w > 2.0) fprintf(stderr, "[hg] slow step: enqueue %.3f ms, wait %.3f ms (t_seq %lld, pending events %zu, pool %zu)\n", e, w, (long long)c->t_seq, c->pending.size(), c->pool.size());
+    }
     return HG_OK;
 }
 
+// hg_map's first bet as a captured step (option "step_graph"): the second sighting of the same step (same tables, options, R,
+// timing level; no buffer moved since) captures it, later ones replay it.  *launched = false: the caller runs it eagerly.
+static int replay_bet(hg_ctx* c, int64_t R, int stride, const StepReq& req, bool* launched, int* flag) {
+    auto& sg = c->sg;
+    *launched = false;
+    const auto current = [&] { return sg.exec && sg.epoch == g_alloc_epoch && sg.cfg == c->cfg_epoch && sg.R == R && sg.timing == c->timing; };
+    const bool seen = sg.seen_epoch == g_alloc_epoch && sg.seen_cfg == c->cfg_epoch && sg.seen_R == R && sg.seen_timing == c->timing;
+    if (!current() && seen && capture_step(c, R, stride, req) != HG_OK) c->opt.step_graph = 0;      // not fatal: stay eager from now on
+    if (!current()) return HG_OK;
+    HG_HIP(hipGraphLaunch(sg.exec, c->stream));
+    HG_TRY(set_R(c, R, 1, 0));
+    static_cast<StepState&>(*c) = sg.left;             // what the captured enqueue left behind on the host side
+    c->graph_replays++;
+    *launched = true;
+    HG_TRY(await_attempt(c, true, flag));
+    c->t_collect_graph();
+    return HG_OK;
+}
+
+// The escalation ladder of a one-shot call: the bet -> (few queries lost: those alone, exactly) -> wider bets -> the exact
+// threshold with the matrix-core select -> the exact sequence.
 static int run_oneshot(hg_ctx* c, int64_t R, bool lists, bool with_ap) {
     c->real_lists = false;
     int stride = 0;
-    u32 need_cnt = 0;
     if (R < 1 || R > c->n_total)
         return fail(HG_ERR_ARG, "R=%lld outside 1..N (N=%lld rows in the database)", (long long)R, (long long)c->n_total);
     c->want_lists = lists;
     if (with_ap && !c->is_sub) HG_TRY(ensure_out_block(c));
-    const bool bet = optimistic_eligible(c, R, &stride, &need_cnt);
     int flag = 0;
-    if (bet) {
+    if (optimistic_eligible(c, R, &stride)) {
+        const StepReq req = bet_request(c, with_ap);
         c->bet_runs++;
-        if (with_ap) {
-            HG_TRY(ensure_pin(c, (size_t)c->Q * 12 + 16));
+        if (with_ap) HG_TRY(ensure_pin(c, (size_t)c->Q * 12 + 16));
+        bool launched = false;
+        // event-record nodes inside a graph turned out slow and unreliable on ROCm 7.2 (a replayed step took 1.9 ms
+        // instead of 1.55, elapsed times came back for one replay in twenty): with kernel timing on, steps stay eager
+        if (with_ap && c->opt.step_graph && !lists && !c->is_sub && c->timing == 0) HG_TRY(replay_bet(c, R, stride, req, &launched, &flag));
+        if (!launched) {
+            HG_TRY(run_attempt(c, AT_BET, R, stride, req, with_ap, &flag));
             auto& sg = c->sg;
-            bool launched = false;
-            // event-record nodes inside a graph turned out slow and unreliable on ROCm 7.2 (a replayed step took 1.9 ms
-            // instead of 1.55, elapsed times came back for one replay in twenty): with kernel timing on, steps stay eager
-            if (c->opt.step_graph && !lists && !c->is_sub && c->timing == 0) {
-                const bool same = sg.exec && sg.epoch == g_alloc_epoch && sg.cfg == c->cfg_epoch && sg.R == R && sg.timing == c->timing;
-                const bool seen = sg.seen_epoch == g_alloc_epoch && sg.seen_cfg == c->cfg_epoch && sg.seen_R == R && sg.seen_timing == c->timing;
-                if (!same && seen) {
-                    if (capture_step(c, R, stride, need_cnt) != HG_OK) c->opt.step_graph = 0;      // not fatal: stay eager from now on
-                }
-                if (c->sg.exec && c->sg.epoch == g_alloc_epoch && c->sg.cfg == c->cfg_epoch && c->sg.R == R && c->sg.timing == c->timing) {
-                    HG_HIP(hipGraphLaunch(sg.exec, c->stream));
-                    HG_TRY(c->sync());
-                    c->t_collect_graph();
-                    // what the captured enqueue functions leave behind on the host side
-                    HG_TRY(set_R(c, R, 1, 0));
-                    c->geo = sg.geo; c->RW = sg.RW; c->stage = sg.stage; c->optimistic = sg.optimistic; c->lists_valid = sg.lists_valid;
-                    c->cap = sg.cap; c->crow = sg.crow; c->err_zeroed = false; c->ap_fused = sg.ap_fused; c->rec8 = sg.rec8;
-                    c->graph_replays++;
-                    launched = true;
-                }
-            }
-            if (!launched) {
-                static const bool trace = getenv("HG_STEP_TRACE") != nullptr;        // debugging: where a slow step spent its time
-                const auto tp0 = std::chrono::steady_clock::now();
-                HG_TRY(enqueue_bet_with_ap(c, R, stride, need_cnt));
-                const auto tp1 = std::chrono::steady_clock::now();
-                HG_TRY(c->sync());
-                if (trace) {
-                    const auto tp2 = std::chrono::steady_clock::now();
-                    const double e = std::chrono::duration<double, std::milli>(tp1 - tp0).count(), w = std::chrono::duration<double, std::milli>(tp2 - tp1).count();
-                    if (e + w > 2.0) fprintf(stderr, "[hg] slow step: enqueue %.3f ms, wait %.3f ms (t_seq %lld, pending events %zu, pool %zu)\n", e, w, (long long)c->t_seq, c->pending.size(), c->pool.size());
-                }
-                sg.seen_epoch = g_alloc_epoch; sg.seen_cfg = c->cfg_epoch; sg.seen_R = R; sg.seen_timing = c->timing;
-            }
-            flag = *(const int*)c->pin;
-            HG_TRY(finish_leftovers(c, &flag));
-            c->ap_staged = flag == 0;
-        } else {
-            HG_TRY(enqueue_optimistic(c, R, stride, need_cnt));
-            HG_TRY(read_plan_flag(c, &flag));
+            if (with_ap) { sg.seen_epoch = g_alloc_epoch; sg.seen_cfg = c->cfg_epoch; sg.seen_R = R; sg.seen_timing = c->timing; }
         }
         if (!flag) { c->bet_consecutive_fail = 0; return HG_OK; }
         bool handled = false;                      // some queries lost their bet
@@ -1454,30 +1468,18 @@ static int run_oneshot(hg_ctx* c, int64_t R, bool lists, bool with_ap) {
         // mean into a query's slices), which no margin on the CUT cures -- escalate the slices' capacity (x8, x64, until a
         // slice would hold its whole segment) and remember what worked for the next calls on this database.
         if (c->opt.second_bet) {
-            const i64 sigma0 = c->opt.guess_sigma, budget0 = c->opt.cand_budget_x10, boost0 = c->cap_boost;
+            StepReq wide = req;
+            wide.guess_sigma = 2 * req.guess_sigma + 2;
+            wide.cand_budget_x10 = 2 * req.cand_budget_x10;
+            const i64 boost0 = c->cap_boost;
             for (int attempt = 0; attempt < 3; ++attempt) {
                 if (attempt > 0) {
                     if (c->cap >= (u32)((c->geo.L + 15) & ~15ll)) break;               // a slice already holds a segment
                     if ((double)c->geo.Q * (double)c->crow * 8.0 * 8.0 > 64e9) break;  // the record rows would not fit comfortably
                     c->cap_boost = c->cap_boost * 8 > 4096 ? 4096 : c->cap_boost * 8;
                 }
-                c->opt.guess_sigma = 2 * sigma0 + 2;
-                c->opt.cand_budget_x10 = 2 * budget0;
                 c->bet_rebets++;
-                c->want_lists = lists;
-                int rc;
-                if (with_ap) {
-                    rc = enqueue_bet_with_ap(c, R, stride, need_cnt);
-                    if (rc == HG_OK) rc = c->sync();
-                    flag = *(const int*)c->pin;
-                    if (rc == HG_OK) rc = finish_leftovers(c, &flag);
-                    c->ap_staged = rc == HG_OK && flag == 0;
-                } else {
-                    rc = enqueue_optimistic(c, R, stride, need_cnt);
-                    if (rc == HG_OK) rc = read_plan_flag(c, &flag);
-                }
-                c->opt.guess_sigma = sigma0;
-                c->opt.cand_budget_x10 = budget0;
+                const int rc = run_attempt(c, AT_BET, R, stride, wide, with_ap, &flag);
                 if (rc != HG_OK) { c->cap_boost = boost0; return rc; }
                 // held with twice the budget of a first bet at this boost: the next call's first bet gets that budget
                 // (a class-sorted database of tight clusters lost every first bet at x8 and won every second one)
@@ -1497,50 +1499,15 @@ static int run_oneshot(hg_ctx* c, int64_t R, bool lists, bool with_ap) {
         }
         c->bet_fallbacks++;                        // still too many: exact path for all
         c->bet_consecutive_fail++;
-        c->want_lists = lists;
     }
     if (exact_mx_applies(c, R)) {
-        c->want_lists = lists;
-        c->t_step_begin();
-        HG_TRY(enqueue_exact_mx(c, R));
-        if (with_ap) {
-            HG_TRY(do_ap(c));
-            HG_TRY(stage_ap_download(c));
-            c->t_step_end();
-            HG_TRY(c->sync());
-            flag = *(const int*)c->pin;
-            c->ap_staged = flag == 0;
-        } else {
-            c->t_step_end();
-            HG_TRY(read_plan_flag(c, &flag));
-        }
-        if (!flag) return HG_OK;
-        c->want_lists = lists;                         // a slice overflowed: the vector-ALU select with exact-sized slices
+        HG_TRY(run_attempt(c, AT_EXACT_MX, R, 0, StepReq{}, with_ap, &flag));
+        if (!flag) return HG_OK;                   // (else a slice overflowed: the vector-ALU select with exact-sized slices)
     }
-    c->t_step_begin();
-    c->ap_fused = false;
-    c->fuse_ap = with_ap && !lists;
-    const int rce = enqueue_exact(c, R);
-    c->fuse_ap = false;
-    HG_TRY(rce);
-    if (with_ap) {
-        if (c->ap_fused) { c->ap_staged = false; c->stage |= ST_AP; }     // a rank kernel's epilogue left the APs
-        else HG_TRY(do_ap(c));
-    }
-    c->ap_fused = false;                               // (no leftovers on this path: nothing for finish_leftovers)
-    if (with_ap) {                                     // C1 (R = N through the byte matrix): 0.17 -> 0.14 ms per call
-        HG_TRY(stage_ap_download(c));
-        c->t_step_end();
-        HG_TRY(c->sync());
-        if (*(const int*)c->pin) {
-            c->stage = ST_DB | ST_Q | ST_HIST;
-            return fail(HG_ERR_ARG, "R=%lld exceeds the rows present in the gathered histograms", (long long)c->R);
-        }
-        c->ap_staged = true;
-        return HG_OK;
-    }
-    c->t_step_end();
-    return check_plan_flag(c);
+    StepReq exact;
+    exact.fuse_ap = with_ap && !lists;
+    HG_TRY(run_attempt(c, AT_EXACT, R, 0, exact, with_ap, &flag));
+    return flag ? plan_overrun(c) : HG_OK;
 }
 
 int hg_topr(hg_ctx* c, int64_t R) {
@@ -1593,7 +1560,7 @@ static int prepare_shared(hg_ctx* c, int64_t R, bool* enqueued) {
 // except a blind slot-0 step in flight (that one writes only the context's own workspace): ev_pre, recorded just before it, when
 // nothing else was enqueued since; else the stream's tail.  stream_b itself holds nothing else: its previous step was waited for
 // by hg_map_end, so the workspace is free.
-static int enqueue_bet_on_b(hg_ctx* c, hg_ctx::MapSlot& m, int64_t R, int stride, u32 need_cnt, bool tail_fork) {
+static int enqueue_bet_on_b(hg_ctx* c, hg_ctx::MapSlot& m, int64_t R, int stride, bool tail_fork) {
     if (!c->stream_b) HG_TRY(stream_create(c->device, &c->stream_b));
     if (!c->ev_pre) HG_HIP(hipEventCreateWithFlags(&c->ev_pre, hipEventDisableTiming));
     if (!c->ev_fork) HG_HIP(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
@@ -1607,7 +1574,7 @@ static int enqueue_bet_on_b(hg_ctx* c, hg_ctx::MapSlot& m, int64_t R, int stride
     const unsigned long long e0 = g_alloc_epoch.load();
     c->swap_step();
     int rc = ensure_out_block(c);                      // (ws_b's own err / ap / rel views; on first use)
-    if (rc == HG_OK) rc = enqueue_bet_with_ap(c, R, stride, need_cnt, m.pin);
+    if (rc == HG_OK) rc = enqueue_attempt(c, AT_BET, R, stride, bet_request(c, true, m.pin), true);
     if (rc == HG_OK && hipEventRecord(m.ev, c->stream) != hipSuccess) rc = fail(HG_ERR_HIP, "hg_map_begin: hipEventRecord failed");
     c->swap_step();
     if (rc != HG_OK) { (void)hipStreamSynchronize(c->stream_b); return rc; }
@@ -1629,13 +1596,12 @@ int hg_map_begin(hg_ctx* c, int64_t R) {
     m.R = R; m.Q = c->Q;
     m.q_gen = c->q_gen; m.db_gen = c->db_gen;
     int stride = 0;
-    u32 need_cnt = 0;
     bool blind = c->map_warm_R == R && c->map_warm_cfg == c->cfg_epoch && c->map_warm_epoch == g_alloc_epoch && !c->is_sub;
     if (blind) {
         c->real_lists = false;
         c->want_lists = false;
         HG_TRY(ensure_out_block(c));
-        blind = optimistic_eligible(c, R, &stride, &need_cnt) && c->map_warm_epoch == g_alloc_epoch;
+        blind = optimistic_eligible(c, R, &stride) && c->map_warm_epoch == g_alloc_epoch;
     }
     if (blind) {
         const size_t need_b = (size_t)c->Q * 12 + 16;
@@ -1651,14 +1617,14 @@ int hg_map_begin(hg_ctx* c, int64_t R) {
         bool prepped = false;
         if (two) HG_TRY(prepare_shared(c, R, &prepped));
         if (two && slot == 1) {
-            HG_TRY(enqueue_bet_on_b(c, m, R, stride, need_cnt, prepped));
+            HG_TRY(enqueue_bet_on_b(c, m, R, stride, prepped));
         } else {
             if (two) {                                 // the fork point of a slot-1 step enqueued while this one is in flight
                 if (!c->ev_pre) HG_HIP(hipEventCreateWithFlags(&c->ev_pre, hipEventDisableTiming));
                 HG_HIP(hipEventRecord(c->ev_pre, c->stream));
             }
             c->pre_valid = two;                        // (one stream: this step may build a shared table -- no fork point before it)
-            HG_TRY(enqueue_bet_with_ap(c, R, stride, need_cnt, m.pin));
+            HG_TRY(enqueue_attempt(c, AT_BET, R, stride, bet_request(c, true, m.pin), true));
             HG_HIP(hipEventRecord(m.ev, c->stream));
         }
         m.inline_ok = c->leftovers_inline;               // the step ranks what its fused kernel declines within the stream

@@ -1335,6 +1335,67 @@ def test_fused_step_hands_wide_lists_to_the_general_kernel(ctx):
     assert np.array_equal(ap3[probe], ap3_ref, equal_nan=True)
 
 
+def test_replayed_step_keeps_its_inline_leftovers():
+    """The workload of test_fused_step_hands_wide_lists_to_the_general_kernel with `step_graph` = 1: the captured step holds the
+    inline k_rank_dense<slices> launch for the two queries k_rank_lean declines, and every replay restores what the captured
+    enqueue left on the host -- that the step ranked its leftovers itself included.  So a replay is never followed by the
+    second round trip (k_rank_fused + k_ap + downloads, which clears ap_fused), its numbers are the eager step's and the
+    oracle's, and hg_map_begin may go on enqueueing blind."""
+    from hashgan_amd import synth
+    Q, N, b, R, C = 192, 100000, 64, 2000, 10
+    dl, _ = synth.onehot_labels(71, N, C)
+    ql, _ = synth.onehot_labels(72, Q, C)
+    db = synth.random_bits(73, N, b)
+    qb = synth.random_bits(74, Q, b)
+    rng = np.random.default_rng(75)
+    for qi, base in ((7, 20000), (130, 60000)):            # rows at EVERY distance 0..21 from two queries, 30 each
+        k = 0
+        for d in range(22):
+            for _ in range(30):
+                row = qb[qi].copy()
+                row[rng.choice(b, d, replace=False)] ^= 1
+                db[base + 7 * k] = row
+                k += 1
+    probe = [0, 7, 8, 129, 130, 191]
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        _, ap_ref, *_ = O.map_from_codes(qb[probe], db, ql[probe], dl, R)
+    ctx = _native.Context(0)
+    try:
+        ctx.set_option("optimistic", 1)
+        ctx.set_option("max_segments", 200)
+        ctx.set_database(metric.pack_codes(db), metric.pack_labels(dl), b, C)
+        ctx.set_queries(metric.pack_codes(qb), metric.pack_labels(ql))
+        ctx.map(R)                                        # finds the leftovers; from now on a step expects them
+        l0 = ctx.get_stat("rank_leftovers")
+        ap, rel = ctx.map(R)                              # the eager step, leftovers ranked within its stream
+        assert ctx.get_stat("ap_fused") == 1 and ctx.get_stat("rank_leftovers") - l0 >= 2
+        assert np.array_equal(ap[probe], ap_ref, equal_nan=True)
+        ctx.set_option("step_graph", 1)
+        g0 = ctx.get_stat("graph_replays")
+        for _ in range(4):                                # a sighting, then the call that captures (and replays at once)
+            ctx.map(R)
+            if ctx.get_stat("graph_replays") > g0:
+                break
+        assert ctx.get_stat("graph_replays") == g0 + 1
+        for i in range(3):
+            l1 = ctx.get_stat("rank_leftovers")
+            apg, relg = ctx.map(R)
+            print("replay", i + 2, "ap_fused", ctx.get_stat("ap_fused"), "leftovers", ctx.get_stat("rank_leftovers") - l1)
+            assert ctx.get_stat("graph_replays") == g0 + 2 + i
+            assert ctx.get_stat("ap_fused") == 1 and ctx.get_stat("rank_leftovers") - l1 >= 2
+            assert np.array_equal(apg, ap, equal_nan=True) and np.array_equal(relg, rel)
+            assert np.array_equal(apg[probe], ap_ref, equal_nan=True)
+        n0, r0 = ctx.get_stat("map_async_steps"), ctx.get_stat("map_async_redone")
+        for _ in range(2):
+            ctx.map_begin(R)
+            apb, relb = ctx.map_end()
+            assert np.array_equal(apb, ap, equal_nan=True) and np.array_equal(relb, rel)
+        assert ctx.get_stat("map_async_steps") - n0 == 2 and ctx.get_stat("map_async_redone") == r0
+    finally:
+        ctx.close()
+
+
 @pytest.mark.parametrize("b", [65, 80, 96, 97, 100, 127, 128])
 def test_long_codes_take_the_packed_matrix_core_select(b):
     """Codes of 65..128 bits: hg_map's bet selects with k_select_mx4 (two rows per fp4 accumulator, 8-bit fields -- the
