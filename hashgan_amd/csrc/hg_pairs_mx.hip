@@ -8,11 +8,8 @@
 #include "hg_hist_mx.hpp"
 #include "hg_hist_i8.hpp"
 
-namespace {
-}  // namespace
-
-// the fp4 images of the codes in MFMA fragment order (k_select_mx, k_hist_mx; k_select_mx3 shares the query image), built on
-// first use.  need_db = false: the query image only (k_select_mx3 has its own database image)
+// the fp4 images of the codes in MFMA fragment order (k_select_mx, k_hist_mx; k_select_mx3 / mx4 share the query image), built on
+// first use.  need_db = false: the query image only (k_select_mx3 / mx4 have their own database images)
 int ensure_mx_images(hg_ctx* c, const bool need_db) {
     const int NW = c->NW, NM = (NW + 1) / 2;
     if (need_db && !c->dbx_valid) {
@@ -69,39 +66,47 @@ template <int NW> int launch_hist_mx_t(hg_ctx* c) {
     return c->check_launch("k_hist_mx");
 }
 
-// codes of 33..64 bits, compact records: three rows per accumulator and the batched drain (k_select_mx3);
-// blocks = (pair of segments) x (256 queries); the query image is k_select_mx's
-template <int NW, int LW> int launch_select_mx3_t(hg_ctx* c, const int* cut) {
+// The packed record pass of the optimistic step (k_select_mx3 / k_select_mx4, one-byte records through the batched drain of
+// hg_packed_drain.hpp); blocks = (pair of segments) x (512 queries); the query image is k_select_mx's.  P = the packing's
+// traits; `image` is its database image (P::IMG_WORDS code words of 16 bytes per row), built here on first use.
+template <class P, class Expand, class Kernel>
+int launch_select_packed(hg_ctx* c, const int* cut, const int NW, const int LW, DevBuf& image, bool& image_valid, Expand expand,
+                         const char* expand_name, Kernel kernel, const char* kernel_name) {
     HG_TRY(ensure_mx_images(c, false));
-    if (!c->dbx3_valid) {
-        const i64 n48 = (c->N + M3_ROWS - 1) / M3_ROWS * M3_ROWS + M3_WS_MAX * M3_ROWS;     // + one window of zero rows: the last segment's last window may run past the end
-        HG_TRY(c->dbx3.reserve((size_t)(n48 > 0 ? n48 : M3_ROWS) * 32));
-        const i64 items = n48 * 2;
+    if (!image_valid) {
+        const i64 n = (c->N + P::ROWS - 1) / P::ROWS * P::ROWS + P::WS_MAX * P::ROWS;     // + one window of zero rows: the last segment's last window may run past the end
+        HG_TRY(image.reserve((size_t)n * P::IMG_WORDS * 16));
+        const i64 items = n * P::IMG_WORDS;
         c->t_begin(KI_PACK);
-        if (items) hipLaunchKernelGGL(k_expand_db3, dim3(grid_for(items)), dim3(256), 0, c->stream, c->db.as<u32>(),
-                                      c->dbx3.as<uint4>(), (i64)c->N, n48, NW);
+        hipLaunchKernelGGL(expand, dim3(grid_for(items)), dim3(256), 0, c->stream, c->db.as<u32>(), image.as<uint4>(), (i64)c->N, n, NW);
         c->t_end();
-        HG_TRY(c->check_launch("k_expand_db3"));
-        c->dbx3_valid = true;
+        HG_TRY(c->check_launch(expand_name));
+        image_valid = true;
     }
     Geo g = c->geo;
     const int nSP = (g.S + 1) / 2;
-    const int nQB = (g.Q + 64 * M3_WPB - 1) / (64 * M3_WPB);
+    const int nQB = (g.Q + 64 * P::WPB - 1) / (64 * P::WPB);
     g.nQT = nQB;
     g.nUnits = (i64)nSP * nQB;
-    g.wpb = M3_WPB;
+    g.wpb = P::WPB;
     g.nBlk = (int)g.nUnits;
-    const Mx3Lds L = mx3_lds_layout(NW, LW);
+    const PackedLds L = packed_lds_layout<P>(NW, LW);
     if (L.total > 64 * 1024)
-        HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_select_mx3<NW, LW>), hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
+        HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
     SelArgs a{cut, c->sl_start.as<u32>(), c->sl_tie.as<u32>(), c->sl_cnt.as<u32>(),
               c->failq.as<u32>(), c->cap, c->crow, 1, c->sstar.as<int>(), (int)c->opt.probe_select};
     c->t_begin(KI_SELECT_MX);
-    hipLaunchKernelGGL((k_select_mx3<NW, LW>), dim3(padded_grid(g.nBlk)), dim3(64 * M3_WPB), (size_t)L.total, c->stream, c->qc.as<u32>(),
-                       c->qlab.as<u64>(), c->qx.as<u8>(), c->db.as<u32>(), c->dbx3.as<u8>(), c->dblab.as<u64>(), a,
+    hipLaunchKernelGGL(kernel, dim3(padded_grid(g.nBlk)), dim3(64 * P::WPB), (size_t)L.total, c->stream, c->qc.as<u32>(),
+                       c->qlab.as<u64>(), c->qx.as<u8>(), c->db.as<u32>(), image.as<u8>(), c->dblab.as<u64>(), a,
                        c->cand.as<u8>(), g);
     c->t_end();
-    return c->check_launch("k_select_mx3");
+    return c->check_launch(kernel_name);
+}
+template <int NW, int LW> int launch_select_mx3_t(hg_ctx* c, const int* cut) {      // codes of <= 64 bits: three rows per accumulator
+    return launch_select_packed<M3Pack>(c, cut, NW, LW, c->dbx3, c->dbx3_valid, k_expand_db3, "k_expand_db3", &k_select_mx3<NW, LW>, "k_select_mx3");
+}
+template <int NW, int LW> int launch_select_mx4_t(hg_ctx* c, const int* cut) {      // codes of 65..128 bits: two rows per accumulator
+    return launch_select_packed<M4Pack>(c, cut, NW, LW, c->dbx4, c->dbx4_valid, k_expand_db4, "k_expand_db4", &k_select_mx4<NW, LW>, "k_select_mx4");
 }
 
 // the same pass with the integer matrix instruction delivering the counter addresses (hg_hist_i8.hpp); codes of <= 128 bits
@@ -155,42 +160,6 @@ int launch_hist_mx(hg_ctx* c) {
     HG_DISPATCH_NW(launch_hist_mx_t, c)
 }
 
-
-namespace {
-// codes of 65..128 bits, compact records: two rows per accumulator and the batched drain (k_select_mx4);
-// blocks = (pair of segments) x (512 queries); the query image is k_select_mx's
-template <int NW, int LW> int launch_select_mx4_t(hg_ctx* c, const int* cut) {
-    HG_TRY(ensure_mx_images(c, false));
-    if (!c->dbx4_valid) {
-        const i64 n32 = (c->N + M4_ROWS - 1) / M4_ROWS * M4_ROWS + M4_WS * M4_ROWS;     // + one window of zero rows: the last segment's last window may run past the end
-        HG_TRY(c->dbx4.reserve((size_t)n32 * 64));
-        const i64 items = n32 * 4;
-        c->t_begin(KI_PACK);
-        hipLaunchKernelGGL(k_expand_db4, dim3(grid_for(items)), dim3(256), 0, c->stream, c->db.as<u32>(), c->dbx4.as<uint4>(), (i64)c->N, n32, NW);
-        c->t_end();
-        HG_TRY(c->check_launch("k_expand_db4"));
-        c->dbx4_valid = true;
-    }
-    Geo g = c->geo;
-    const int nSP = (g.S + 1) / 2;
-    const int nQB = (g.Q + 64 * M4_WPB - 1) / (64 * M4_WPB);
-    g.nQT = nQB;
-    g.nUnits = (i64)nSP * nQB;
-    g.wpb = M4_WPB;
-    g.nBlk = (int)g.nUnits;
-    const Mx4Lds L = mx4_lds_layout(NW, LW);
-    if (L.total > 64 * 1024)
-        HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_select_mx4<NW, LW>), hipFuncAttributeMaxDynamicSharedMemorySize, L.total));
-    SelArgs a{cut, c->sl_start.as<u32>(), c->sl_tie.as<u32>(), c->sl_cnt.as<u32>(),
-              c->failq.as<u32>(), c->cap, c->crow, 1, c->sstar.as<int>(), 0};
-    c->t_begin(KI_SELECT_MX);
-    hipLaunchKernelGGL((k_select_mx4<NW, LW>), dim3(padded_grid(g.nBlk)), dim3(64 * M4_WPB), (size_t)L.total, c->stream, c->qc.as<u32>(),
-                       c->qlab.as<u64>(), c->qx.as<u8>(), c->db.as<u32>(), c->dbx4.as<u8>(), c->dblab.as<u64>(), a,
-                       c->cand.as<u8>(), g);
-    c->t_end();
-    return c->check_launch("k_select_mx4");
-}
-}  // namespace
 
 int launch_select_mx4(hg_ctx* c, int lw, const int* cut) {           // codes of 65..128 bits, one-byte records, <= 128 classes
     if (c->NW < 3 || c->NW > 4 || lw < 1 || lw > 2) return fail(HG_ERR_ARG, "k_select_mx4 takes codes of 65..128 bits and 1..128 classes");

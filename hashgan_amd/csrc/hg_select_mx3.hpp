@@ -20,18 +20,10 @@
 // The database image dbx3 (k_expand_db3) is k_select_mx's fp4 image with that row permutation and -1.0 for a set bit,
 // so the query image qx (+1 / -1 for a clear / set bit) is shared with the other matrix-core kernels.
 //
-// Drain (one-byte compact records only: hg_mx_drain.hpp explains rings and slices).  Per supertile and query tile every
-// lane with a hit appends ONE 12-byte entry {A | query tag | lane-half | supertile | buffer, B | slice position & 15, C} to the
-// wavefront's queue (ring buffer in LDS, slot = rank among the pushing lanes).  The emit works the queue off in batches
-// of exactly 64 entries -- every lane busy -- and entries that do not fill a batch WAIT for the next window: the packed
-// codes and labels the emit needs are triple-buffered, so an entry may be emitted one window late, and the
-// owner-side flush of the 16-record rings lags one window accordingly (it flushes what was pushed before the window
-// that just ended).  A block is eight wavefronts = one segment pair x 512 queries sharing windows of four supertiles (192
-// rows per lane-half; two for 65..128 classes); ~140 entries per window and wavefront at C2.
-// Bursts (a ring that could overflow: > 16 records of one slice pending) drain everything and, if one supertile alone
-// still brings too many, the lane walks its own hits straight to global memory -- rare, slow, exact.
+// Drain: the batched drain of hg_packed_drain.hpp with the 12-byte entries of M3Pack below.  A block is eight wavefronts =
+// one segment pair x 512 queries sharing windows of four supertiles (192 rows per lane-half; two for 65..128 classes).
 #pragma once
-#include "hg_select_mx.hpp"
+#include "hg_packed_drain.hpp"
 
 namespace hg {
 
@@ -47,8 +39,6 @@ constexpr int M3_ROWS = 48;                // rows per supertile and lane-half
 #endif
 __host__ __device__ constexpr int m3_ws(int LW) { return LW <= 1 ? HG_M3_WS : 2; }
 constexpr int M3_WS_MAX = HG_M3_WS > 2 ? HG_M3_WS : 2;
-constexpr int M3_QCAP = 128;               // queue entries per wavefront (ring buffer; a power of two)
-constexpr int M3_RING = 16;                // records per slice ring
 #ifndef HG_M3_WPB
 #define HG_M3_WPB 8
 #endif
@@ -98,12 +88,6 @@ __device__ __forceinline__ u32 m3_ffbl(const u32 x) {
     asm("v_ffbl_b32 %0, %1" : "=v"(d) : "v"(x));
     return d;
 }
-// (x & K) | y in one op
-__device__ __forceinline__ u32 m3_and_or(const u32 x, const u32 k, const u32 y) {
-    u32 d;
-    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "n"(k), "v"(y));
-    return d;
-}
 // x * 0x421 for x < 2^22 (the C word's six hit bits -> contiguous): the full-rate 24-bit multiply (the compiler turns __umul24 by a
 // constant back into the quarter-rate v_mul_lo_u32)
 __device__ __forceinline__ u32 m3_mul24_421(const u32 x) {
@@ -112,279 +96,46 @@ __device__ __forceinline__ u32 m3_mul24_421(const u32 x) {
     return d;
 }
 
-struct Mx3Lds {                // byte offsets inside the block's dynamic LDS
-    int a, abuf;               // A fragments: 2 buffers of abuf bytes
-    int cl, clbuf, labels;     // packed codes + labels of a window's rows (both halves): 3 buffers of clbuf bytes; labels inside a buffer
-    int qcodes, qlabels;       // the block's query tables
-    int queue;                 // per-wave queues: [QCAP] entries of 12 bytes {A, B, C} (ONE address per entry; round 4 kept {A, B} and {C} in two arrays: 0.627 vs 0.615 ms)
-    int rings;                 // per-wave slice rings
-    int total;
-};
-__host__ __device__ inline Mx3Lds mx3_lds_layout(int NW, int LW) {
-    Mx3Lds l;
-    const int M3_WS = m3_ws(LW), M3_WROWS = M3_WS * M3_ROWS;
-    l.a = 0;
-    l.abuf = M3_WS * 3 * 1024;
-    l.cl = 2 * l.abuf;
-    l.labels = 2 * M3_WROWS * NW * 4;
-    l.clbuf = (l.labels + 2 * M3_WROWS * LW * 8 + 15) & ~15;
-    l.qcodes = l.cl + 3 * l.clbuf;
-    l.qlabels = l.qcodes + M3_WPB * 64 * NW * 4;
-    l.queue = l.qlabels + M3_WPB * 64 * LW * 8;
-    l.rings = l.queue + M3_WPB * M3_QCAP * 12;
-    l.total = l.rings + M3_WPB * 64 * M3_QT * M3_RING;
-    return l;
-}
-
-template <int NW, int LW>
-struct Mx3Drain {
-    static constexpr int QT = M3_QT, CB = NW * 4, LB = LW * 8;
-    static constexpr int M3_WS = m3_ws(LW), M3_WROWS = M3_WS * M3_ROWS;
-    u8* lds;
-    Mx3Lds L;
-    u32 ring_base;                       // LDS address of the wavefront's first ring
-    u32 q12_base;                        // this wavefront's queue: LDS address of its first 12-byte entry (kept opaque: ONE address per entry)
-    u8* rings;                           // this wavefront's rings: slice (t, lane) at (t * 64 + lane) * M3_RING
-    int wave, lane;
-    u32 cap;                             // slice capacity (records), a multiple of 16
-    u8* tb0;                             // the wavefront's first slice (t = 0, lane 0); tile t adds t * 32 * crow
-    i64 crow;
-    u32 lane_off;                        // byte offset of the lane's slices relative to that (the launcher keeps 64 * crow below 2^31)
-    u32 cnt[QT];                         // records of slice (t, lane) pushed so far (may exceed cap: the surplus is dropped at the flush)
-    u32 prev[QT];                        // ... pushed before the current window: those are in the rings for sure
-    u32 flushed[QT];                     // ... written to global memory (a multiple of 8)
-    u32 qhead, qfill, old;               // queue: first entry, entries, entries pushed before the current window (wave-uniform)
-    int probe;
-
-    __device__ __forceinline__ void init(u8* lds_, const Mx3Lds& L_, int wave_, int lane_, int qb, int sp, u32 cap_, i64 crow_, u8* cand8, int probe_) {
-        lds = lds_; L = L_; wave = wave_; lane = lane_; cap = cap_; crow = crow_; probe = probe_;
-        q12_base = (u32)(L.queue + wave * (M3_QCAP * 12));
-        asm volatile("" : "+s"(q12_base));
-        rings = lds + L.rings + wave * (64 * QT * M3_RING);
-        ring_base = (u32)(uintptr_t)(__attribute__((address_space(3))) u8*)rings;
-        const int h = lane >> 5, j = lane & 31;
-        lane_off = (u32)j * (u32)crow + (u32)h * cap;
-        tb0 = cand8 + (i64)(qb * M3_WPB + wave) * 64 * crow + (i64)(2 * sp) * cap;
-        qhead = qfill = old = 0;
-#pragma unroll
-        for (int t = 0; t < QT; ++t) cnt[t] = prev[t] = flushed[t] = 0;
+// The packing's traits for the batched drain (hg_packed_drain.hpp).  A queue entry is 12 bytes, ONE address per entry (round 4
+// kept {A, B} and {C} in two arrays: 0.627 vs 0.615 ms):
+//     e[0] = {query tag t * 32 + j : 6 | A : 21 | lane-half : 1 | supertile : 2 | buffer : 2},  e[1] = {0 : 6 | B : 21 | position : 5},  e[2] = C
+struct M3Pack {
+    static constexpr int QT = M3_QT, ROWS = M3_ROWS, WPB = M3_WPB, WORDS = 3, ENTRY = 12, CHUNKS = 3;
+    static constexpr int WS_MAX = M3_WS_MAX, FLUSH = HG_M3_FLUSH;
+    static constexpr int IMG_WORDS = 2;                               // code words of a row in the image dbx3
+    static constexpr bool OPAQUE_QBASE = true;                        // the three words of an entry share ONE address register
+    static __host__ __device__ constexpr int ws(int LW) { return m3_ws(LW); }
+    static __device__ __forceinline__ void load(const u8* lds, u32 qbase, u32 i, u32 (&e)[3]) {
+        const u32* p = (const u32*)(lds + (qbase + i * 12u));
+        e[0] = p[0]; e[1] = p[1]; e[2] = p[2];
     }
-    // ring of slice (t, lane): half * 64 + t * 32 + query-in-tile -- the low six bits are the tag a queue entry carries
-    __device__ __forceinline__ int ring_index(const int t) const { return (lane >> 5) * 64 + t * 32 + (lane & 31); }
-    __device__ __forceinline__ u8* slice(const int t) const { return tb0 + (i64)t * 32 * crow + lane_off; }
-
-    // ---- owner side: completed 8-record pieces below limit[t] leave the ring with one aligned 8-byte store each ----
-    // (a slice that is already full keeps advancing: its surplus pieces land on its last piece -- the query is flagged
-    // as lost at the end of the kernel, what its slice holds no longer matters, only that the stores stay inside it)
-    __device__ __forceinline__ void flush_to(const u32 (&limit)[QT]) {
-        bool need = false;
-#pragma unroll
-        for (int t = 0; t < QT; ++t) need |= limit[t] - flushed[t] >= 8u;
-        while (__any(need)) {                                         // a second pass only if some slice had 16 pending
-            need = false;
-#pragma unroll
-            for (int t = 0; t < QT; ++t) {
-                const u32 f = flushed[t];
-                if (limit[t] - f >= 8u) {
-                    const u8* ring = rings + ring_index(t) * M3_RING;
-                    u8* tb = tb0 + (i64)t * 32 * crow;                // wave-uniform base; the lane's part fits 32 bits
-                    *(u64*)(tb + (lane_off + min(f, cap - 8u))) = *(const u64*)(ring + (f & 8u));
-                    flushed[t] = f + 8u;
-                    need |= limit[t] - f >= 16u;
-                }
-            }
-        }
-        wave_lds_sync();                                              // ring reads done before an emit reuses the slots
+    static __device__ __forceinline__ void store(u8* lds, u32 qbase, u32 slot, const u32 (&e)[3]) {
+        u32* p = (u32*)(lds + (qbase + slot * 12u));
+        p[0] = e[0]; p[1] = e[1]; p[2] = e[2];
     }
-
-    // ---- emit: n <= 64 entries from the head of the queue, one per lane ----
-    __device__ __forceinline__ void emit_batch(const u32 n) {
-        wave_lds_sync();
-        if ((u32)lane < n && !(kProbes && (probe & 8))) {
-            const u32 i = (qhead + (u32)lane) & (M3_QCAP - 1);
-            const u32* e = (const u32*)(lds + (q12_base + i * 12u));
-            const u32 a = e[0], b = e[1], c = e[2];
-            // entry: a = {query tag t * 32 + j : 6 | A : 21 | lane-half : 1 | supertile : 2 | buffer : 2}, b = {0 : 6 | B : 21 | position : 5}
-            const u32 x = a & 63u, h = (a >> 27) & 1u, st = (a >> 28) & 3u, sel = a >> 30;
-            u32 pos = b >> 27;                                        // slice position & 15 of the entry's first hit
-            // flat hit mask of the supertile: bit P <-> row P.  b holds B at bits 6..26 and the position above them, nothing below:
-            // b << 15 IS B's rows 0..10 at bits 21..31; the C word's six bits become contiguous through one 24-bit multiply
-            u32 xlo = m3_lshl_or(b, 15, __builtin_amdgcn_ubfe(a, 6, 21));
-            u32 xhi = ((m3_mul24_421(c) >> 6) & 0xFC00u) | __builtin_amdgcn_ubfe(b, 17, 10);
-            const u32 ql = (u32)wave * 64u + x;                       // the entry's query, block-local
-            u32 qcw[NW];
-            u64 qlw[LW];
-#pragma unroll
-            for (int k = 0; k < NW; ++k) qcw[k] = ((const u32*)(lds + L.qcodes + ql * CB))[k];
-#pragma unroll
-            for (int k = 0; k < LW; ++k) qlw[k] = ((const u64*)(lds + L.qlabels + ql * LB))[k];
-            const u32 ring = ring_base + (h * 64u + x) * M3_RING;     // LDS address (the block's dynamic LDS starts at 0), a multiple of 16
-            // LDS byte offsets of the code / label words of the supertile's row 0 (buffer sel, lane-half h, supertile st)
-            const u32 row0 = h * M3_WROWS + st * M3_ROWS;
-            const u32 code0 = (u32)L.cl + sel * (u32)L.clbuf + row0 * CB;
-            const u32 lab0 = (u32)L.cl + sel * (u32)L.clbuf + (u32)L.labels + row0 * LB;
-            while (xlo | xhi) {
-                const u32 P = min(m3_ffbl(xlo), m3_ffbl(xhi) | 32u);  // lowest set bit = earliest row (v_ffbl of 0 is ~0)
-                const u32 lo1 = xlo - 1u;
-                xhi &= xhi - (xlo == 0u ? 1u : 0u);
-                xlo &= lo1;
-                const u32* rp = (const u32*)(lds + (code0 + P * CB));
-                u32 d = 0;
-#pragma unroll
-                for (int k = 0; k < NW; ++k) d += __builtin_popcount(qcw[k] ^ rp[k]);
-                const u64* lp = (const u64*)(lds + (lab0 + P * LB));
-                u64 any = 0;
-#pragma unroll
-                for (int k = 0; k < LW; ++k) any |= lp[k] & qlw[k];
-                if (!(kProbes && (probe & 4))) *(u8 __attribute__((address_space(3)))*)(uintptr_t)m3_and_or(pos, M3_RING - 1, ring) = make_rec8(d, any != 0);
-                ++pos;
-            }
-        }
-        wave_lds_sync();
-        qhead = (qhead + n) & (M3_QCAP - 1);
-        qfill -= n;
-        old = old > n ? old - n : 0u;
+    static __device__ __forceinline__ u64 flat(const u32 (&w)[3]) {
+        const u32 a21 = (w[0] >> 6) & 0x1FFFFFu, b21 = (w[1] >> 6) & 0x1FFFFFu, c6 = ((w[2] * 0x421u) >> 16) & 0x3Fu;
+        return (u64)a21 | ((u64)b21 << 21) | ((u64)c6 << 42);
     }
-    __device__ __forceinline__ void emit_all() {
-        while (qfill) emit_batch(qfill < 64u ? qfill : 64u);
-    }
-
-    // ---- rare: the lane writes the hits of one of its own supertile masks straight to global memory ----
-    // (its ring's leftovers first, so the slice stays in index order; every record also passes through the ring, whose
-    // last partial piece is then what a later flush expects)
-    __device__ __forceinline__ void direct_walk(const int t, const u32 wa, const u32 wb, const u32 wc, const int st, const u32 sel) {
-        const u8* ring_r = rings + ring_index(t) * M3_RING;
-        u8* ring = rings + ring_index(t) * M3_RING;
-        u8* out = slice(t);
-        for (u32 p = flushed[t]; p < cnt[t]; ++p) if (p < cap) out[p] = ring_r[p & (M3_RING - 1)];
-        const u32 a21 = (wa >> 6) & 0x1FFFFFu, b21 = (wb >> 6) & 0x1FFFFFu, c6 = ((wc * 0x421u) >> 16) & 0x3Fu;
-        u64 x = (u64)a21 | ((u64)b21 << 21) | ((u64)c6 << 42);
-        const int ql = wave * 64 + t * 32 + (lane & 31);
-        u32 qcw[NW];
-        u64 qlw[LW];
-#pragma unroll
-        for (int k = 0; k < NW; ++k) qcw[k] = ((const u32*)(lds + L.qcodes + ql * CB))[k];
-#pragma unroll
-        for (int k = 0; k < LW; ++k) qlw[k] = ((const u64*)(lds + L.qlabels + ql * LB))[k];
-        const u8* clb = lds + L.cl + sel * L.clbuf;
-        const u32 row0 = (u32)(lane >> 5) * M3_WROWS + (u32)st * M3_ROWS;
-        u32 pos = cnt[t];
-        while (x) {
-            const u32 P = (u32)__builtin_ctzll(x);
-            x &= x - 1ull;
-            const u32* rp = (const u32*)(clb + (row0 + P) * CB);
-            u32 d = 0;
-#pragma unroll
-            for (int k = 0; k < NW; ++k) d += __builtin_popcount(qcw[k] ^ rp[k]);
-            const u64* lp = (const u64*)(clb + L.labels + (row0 + P) * LB);
-            u64 any = 0;
-#pragma unroll
-            for (int k = 0; k < LW; ++k) any |= lp[k] & qlw[k];
-            const u8 rec = make_rec8(d, any != 0);
-            if (pos < cap) out[pos] = rec;
-            ring[pos & (M3_RING - 1)] = rec;
-            ++pos;
+    // the same mask for the emit, as two 32-bit halves.  e[1] holds B at bits 6..26 and the position above them, nothing below:
+    // e[1] << 15 IS B's rows 0..10 at bits 21..31; the C word's six bits become contiguous through one 24-bit multiply
+    struct Mask {
+        u32 xlo, xhi;
+        __device__ __forceinline__ Mask(const u32 (&e)[3]) {
+            xlo = m3_lshl_or(e[1], 15, __builtin_amdgcn_ubfe(e[0], 6, 21));
+            xhi = ((m3_mul24_421(e[2]) >> 6) & 0xFC00u) | __builtin_amdgcn_ubfe(e[1], 17, 10);
         }
-        cnt[t] = pos;
-        prev[t] = pos;
-        flushed[t] = pos & ~7u;
-    }
-
-    // Rare: the queue cannot take this supertile's entries, or some slice would have more than M3_RING unflushed records.
-    // Everything queued is emitted and flushed; slices that still cannot take their hits go the direct route and their
-    // words are cleared.
-    __device__ __forceinline__ void make_room(u32 (&w)[QT][3], const int st, const u32 sel) {
-        emit_all();
-#pragma unroll
-        for (int t = 0; t < QT; ++t) prev[t] = cnt[t];
-        flush_to(prev);
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            const u32 want = cnt[t] + (u32)__builtin_popcount(w[t][0]) + (u32)__builtin_popcount(w[t][1]) + (u32)__builtin_popcount(w[t][2]);
-            if (want - flushed[t] > (u32)M3_RING) {
-                direct_walk(t, w[t][0], w[t][1], w[t][2], st, sel);
-                w[t][0] = w[t][1] = w[t][2] = 0u;
-            }
+        __device__ __forceinline__ bool any() const { return (xlo | xhi) != 0u; }
+        __device__ __forceinline__ u32 pop() {
+            const u32 P = min(m3_ffbl(xlo), m3_ffbl(xhi) | 32u);      // (v_ffbl of 0 is ~0)
+            const u32 lo1 = xlo - 1u;
+            xhi &= xhi - (xlo == 0u ? 1u : 0u);
+            xlo &= lo1;
+            return P;
         }
-        wave_lds_sync();
-    }
-
-    // The hit words of one supertile: w[t] = {A, B, C} of query tile t.  st = supertile of the window, sel = the
-    // window's codes/labels buffer.
-    __device__ __forceinline__ void push(u32 (&w)[QT][3], const int st, const u32 sel) {
-        u32 any[QT], want[QT];
-        u64 bal[QT];
-        {
-            bool over = false;
-#pragma unroll
-            for (int t = 0; t < QT; ++t) {
-                want[t] = cnt[t] + (u32)__builtin_popcount(w[t][0]) + (u32)__builtin_popcount(w[t][1]) + (u32)__builtin_popcount(w[t][2]);
-                over |= want[t] - flushed[t] > (u32)M3_RING;
-            }
-            if (__builtin_expect(__any(over) != 0, 0)) {              // rare: afterwards every ring takes what is left of the words
-                make_room(w, st, sel);
-#pragma unroll
-                for (int t = 0; t < QT; ++t)
-                    want[t] = cnt[t] + (u32)__builtin_popcount(w[t][0]) + (u32)__builtin_popcount(w[t][1]) + (u32)__builtin_popcount(w[t][2]);
-            }
-        }
-        // (the hit flags and ballots have ONE definition, behind the rare branch: no second compare for the stores' exec mask)
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            any[t] = w[t][0] | w[t][1] | w[t][2];
-            bal[t] = __ballot(any[t] != 0u);
-        }
-        u32 nz = 0;
-#pragma unroll
-        for (int t = 0; t < QT; ++t) nz += (u32)__builtin_popcountll(bal[t]);
-        if (__builtin_expect(qfill + nz > (u32)M3_QCAP, 0)) {         // a full queue: work off whole batches (never wasted work);
-            while (qfill >= 64u) emit_batch(64u);                     // a dense supertile (up to 128 entries) needs it empty
-            if (qfill + nz > (u32)M3_QCAP) emit_batch(qfill);
-        }
-        const u32 desc = ((u32)st << 28) | (sel << 30);
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            const u64 b = bal[t];
-            const u32 slot = (qhead + qfill + __builtin_amdgcn_mbcnt_hi((u32)(b >> 32), __builtin_amdgcn_mbcnt_lo((u32)b, 0u))) & (M3_QCAP - 1);
-            if (__builtin_amdgcn_inverse_ballot_w64(b)) {             // (the ballot IS the exec mask: no second compare)
-                const u32 ea = w[t][0] | ((u32)(lane & 31) | ((u32)t << 5) | ((u32)(lane >> 5) << 27)) | desc;
-                const u32 eb = w[t][1] | (cnt[t] << 27);
-                u32* e = (u32*)(lds + (q12_base + slot * 12u));
-                e[0] = ea; e[1] = eb; e[2] = w[t][2];
-            }
-            cnt[t] = want[t];
-            qfill += (u32)__builtin_popcountll(b);
-        }
-    }
-
-    // End of a window: entries pushed before it must be emitted now (their codes/labels buffer is recycled next); of
-    // this window's, whole batches only.  Then the owners flush what was pushed before this window.
-    __device__ __forceinline__ void end_window(const bool do_flush) {
-        while (qfill >= 64u) emit_batch(64u);
-        if (old) emit_batch(qfill);
-        old = qfill;
-        if (do_flush) flush_to(prev);
-#pragma unroll
-        for (int t = 0; t < QT; ++t) prev[t] = cnt[t];
-    }
-
-    // End of the kernel: everything out; the last partial piece of a slice leaves as a whole 8-byte store (slots past
-    // cnt are inside the slice's capacity, a multiple of 16).
-    __device__ __forceinline__ void finish() {
-        emit_all();
-        flush_to(cnt);
-#pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            const u32 f = flushed[t];
-            if (cnt[t] > f) {
-                const u8* ring = rings + ring_index(t) * M3_RING;
-                *(u64*)(slice(t) + min(f, cap - 8u)) = *(const u64*)(ring + (f & 8u));
-            }
-        }
-    }
+    };
 };
 
-// Geo as set by the launcher: g.nQT = query blocks (of 64 M3_WPB queries) per segment pair, g.nBlk = blocks; g.L % 48 == 0.
 template <int NW, int LW>
 #ifndef HG_M3_WAVES
 #define HG_M3_WAVES 4
@@ -398,29 +149,19 @@ void k_select_mx3(const u32* __restrict__ qc, const u64* __restrict__ qlab, cons
     constexpr int QT = M3_QT, WQ = 32 * QT;
     constexpr int CB = NW * 4, LB = LW * 8;
     constexpr int M3_WS = m3_ws(LW), M3_WROWS = M3_WS * M3_ROWS;      // this label width's window
-    const Mx3Lds L = mx3_lds_layout(NW, LW);
+    const PackedLds L = packed_lds_layout<M3Pack>(NW, LW);
 
     const int lb = logical_block(g.nBlk);
     if (lb < 0) return;                                   // whole block: no barrier is skipped by a part of it
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int nQB = g.nQT;
-    const int sp = lb / nQB;                             // segment pair
-    const int qb = lb - sp * nQB;                        // block of 256 queries
-    const int h = lane >> 5, j = lane & 31;
-
-    const int s = 2 * sp + h;                            // this lane's segment
-    const bool seg_ok = s < g.S;
-    const i64 lo0 = (i64)(2 * sp) * g.L, lo1 = lo0 + g.L;
-    const i64 len0 = (lo0 + g.L < g.N ? g.L : g.N - lo0);
-    const i64 len1 = lo1 >= g.N ? 0 : (lo1 + g.L < g.N ? g.L : g.N - lo1);
-    const i64 mylen = h ? len1 : len0;
-    const i64 minlen = len0 < len1 ? len0 : len1;
-    const i64 nwin = ((len0 > len1 ? len0 : len1) + M3_WROWS - 1) / M3_WROWS;
-    const i64 NG = (g.N + M3_ROWS - 1) / M3_ROWS;        // supertiles in the image
+    const PackedBlock<LW, M3Pack> blk(lb, lane, g);                 // segment pair, query block, the two segments' rows
+    const int h = blk.h, j = blk.j, s = blk.s;
+    const bool seg_ok = blk.seg_ok;
+    const i64 lo0 = blk.lo0, lo1 = blk.lo1, nwin = blk.nwin, NG = blk.NG;
 
     // ---- query side: LDS tables for the emit, B fragments, C = the bias, harvest masks ----
-    const int q0w = (qb * M3_WPB + wave) * WQ;               // first query of this wavefront
+    const int q0w = (blk.qb * M3_WPB + wave) * WQ;               // first query of this wavefront
     {
         u32* qcl = (u32*)(mxlds + L.qcodes + wave * WQ * CB);
         for (int e = lane; e < WQ * NW; e += 64) {
@@ -437,8 +178,8 @@ void k_select_mx3(const u32* __restrict__ qc, const u64* __restrict__ qlab, cons
     f32x16 cv[QT];
     u32 K[QT][3];
     bool far[QT];
-    Mx3Drain<NW, LW> dr;
-    dr.init(mxlds, L, wave, lane, qb, sp, a.cap, a.crow, cand8, a.probe);
+    PackedDrain<NW, LW, M3Pack> dr;
+    dr.init(mxlds, L, wave, lane, blk.qb, blk.sp, a.cap, a.crow, cand8, a.probe);
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
         const int q = q0w + t * 32 + j;
@@ -462,7 +203,7 @@ void k_select_mx3(const u32* __restrict__ qc, const u64* __restrict__ qlab, cons
         }
     }
 
-    // ---- window staging: global -> LDS, the four waves split the copy instructions ----
+    // ---- window staging: global -> LDS, the block's wavefronts split the copy instructions ----
     const int ah = (j >> 2) & 1;                                     // lane-half (segment) that A row j feeds
     const int ar = (j & 3) + 4 * (j >> 3);                           // the accumulator register of that row
     const i64 ag0 = (ah ? lo1 : lo0) / M3_ROWS;                      // first supertile of that segment
@@ -590,8 +331,8 @@ void k_select_mx3(const u32* __restrict__ qc, const u64* __restrict__ qlab, cons
 #endif
             // rows past the end of the lane's segment (ragged last window, unpaired last segment) never count
             const i64 base_row = win * M3_WROWS + st * M3_ROWS;
-            if (minlen - base_row < M3_ROWS) {
-                const i64 left = mylen - base_row;                   // valid rows of this lane in the supertile
+            if (blk.minlen - base_row < M3_ROWS) {
+                const i64 left = blk.mylen - base_row;                   // valid rows of this lane in the supertile
                 const int la = left < 0 ? 0 : left > 21 ? 21 : (int)left, lb2 = left < 21 ? 0 : left > 42 ? 21 : (int)left - 21;
                 const u32 ka = ((1u << la) - 1u) << 6, kb = ((1u << lb2) - 1u) << 6;
                 u32 kc = 0;
@@ -603,7 +344,7 @@ void k_select_mx3(const u32* __restrict__ qc, const u64* __restrict__ qlab, cons
             __builtin_amdgcn_sched_barrier(0);
         }
         // the owners flush every fourth supertile (192 rows: ~1.2 records per slice at C2; every second one cost 4 % more)
-        if (!(kProbes && (a.probe & 2))) dr.end_window(((win + 1) * M3_WS) % HG_M3_FLUSH == 0);
+        if (!(kProbes && (a.probe & 2))) dr.end_window(((win + 1) * M3_WS) % M3Pack::FLUSH == 0);
         clsel = clnext;
     }
     dr.finish();

@@ -38,9 +38,10 @@ void make_geometry(hg_ctx* c) {
         // target that fills a whole number of such rounds, so the last round is not a nearly empty one
         const bool qt2 = c->NW <= 4;                                // mirrors launch_select_mx_t
         const bool mx3 = c->opt.select_packed == 3 && c->NW <= 4;   // k_select_mx3 / k_select_mx4: blocks of 8 wavefronts x 64 queries, two per CU
-        const i64 qblk = mx3 ? 64 * M3_WPB : qt2 ? 256 : 512;
+        const int mx3_wpb = c->NW <= 2 ? M3Pack::WPB : M4Pack::WPB;
+        const i64 qblk = mx3 ? 64 * mx3_wpb : qt2 ? 256 : 512;
         const i64 nQB = (c->Q + qblk - 1) / qblk;
-        const i64 slots = (i64)c->n_cu * (mx3 ? 16 / M3_WPB : qt2 ? 4 : 2);
+        const i64 slots = (i64)c->n_cu * (mx3 ? 16 / mx3_wpb : qt2 ? 4 : 2);
         i64 k = (S / 2 * nQB + slots / 2) / slots;
         if (k < 1) k = 1;
         // k_rank_lean takes at most 256 slices per query.  A target beyond that (few queries: C3's 2100 ask for 496 segments)
