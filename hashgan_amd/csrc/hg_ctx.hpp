@@ -6,7 +6,7 @@
 //   hg_pairs_valu.hip  launchers of the vector-ALU pair passes (k_hist, k_select, k_select_dense)
 //   hg_pairs_mx.hip    launchers of the matrix-core pair passes (k_select_mx3 / mx4, k_hist_mx, k_hist_i8) and their images
 //   hg_pairs_mx1.hip   launcher of k_select_mx (every code length: the longest compile)
-//   hg_real.hip        real-valued (float32 inner product) ranking
+//   hg_real.hip        real-valued (float32 inner product) ranking: a ladder of attempts, each with one RealReq down and one RealState (hg_ctx::real) up
 //   hg_comm.hip        RCCL collectives (library dlopen'ed on first use)
 //
 // No torch, no CPU compute path: every entry point either runs HIP kernels or fails.
@@ -328,6 +328,31 @@ struct StepReq {
     void* dst = nullptr;       // pinned block the results go to (hg_map_begin's slot); nullptr: the context's own
 };
 
+// What one attempt of the real-valued ranking (hg_real.hip) is asked to do.  Built by real_attempt and passed down by const reference
+// to the sample and select stages and their launchers; the stage that places the cut writes what it learns into the attempt's copy
+// before the stages after it see it, so a request ends with its attempt.
+struct RealReq {
+    i64 R = 0;
+    bool bet = false;          // cut at a sampled threshold `sigma` deviations deep, slices sized for `budget` x R records per query
+    double sigma = 0.0, budget = 0.0;
+    bool with_ap = false;      // hg_map_real: APs wanted
+    // derived by the attempt for the levels below it
+    bool no_cut = false;       // every row a record (thr = -inf)
+    double expect = 0.0;       // rows per query the cut is expected to keep (a second sample lowers it; picks the rescore's slices per wavefront)
+    bool samp16 = false;       // the sample's scores are 16-bit (k_real_sample_h writes, k_real_guess_lds reads)
+    bool skip_lists = false;   // the kernels that rank in LDS leave the idx / score lists out (match bits and APs only)
+};
+
+// What an attempt of the real-valued ranking leaves behind on the host: real_attempt begins by assigning a fresh one (keeping the
+// count), so nothing survives from an earlier attempt or call.  Stat "real_path" is computed from it.
+struct RealState {
+    bool filtered = false;     // the select left unscored candidates that k_real_rescore completed (filter + rescore)
+    bool lds_ranked = false;   // the LDS-resident rank kernel produced the lists
+    bool grouped = false;      // the record lists were ordered group by group (k_real_group_*)
+    bool lists_made = false;   // out_idx / scores hold the ranked lists (hg_map_real skips them on the paths that rank in LDS)
+    i64 attempts = 0;          // stat "real_attempts": attempts of the last call (1 = the first bet held)
+};
+
 struct hg_ctx : StepBufs, StepState {
     int device = 0;
     int n_cu = 256;            // compute units of the device
@@ -341,11 +366,10 @@ struct hg_ctx : StepBufs, StepState {
     u32 idx_base = 0;
     int G = 1, rank = 0;
 
-    i64 real_grouped = 0;      // stat: the last real-valued ranking ordered its record lists group by group (k_real_group_*)
-    i64 real_cap_boost = 1;    // the same for the real-valued ranking's slices (run_real)
     bool crowd_probed = false; // the first bet on this database has measured how its near rows crowd (k_guess_direct's probe)
     i64 crowd_x100 = 0;        // stat "crowding_x100": that measure, x 100 (~200: rows in random order; ~100 x classes: stored class by class)
     i64 cap_boost = 1;         // slice capacity multiplier a lost bet escalated to on this database (run_oneshot); 1 after every load
+    i64 real_cap_boost = 1;    // the same for the real-valued ranking's slices (real_ladder)
     bool leftovers_expected = false;   // the last fused step on this context left queries to the general kernel
     bool last_leftovers_inline = false;   // ... and the last finished step had ranked its own within the stream (finish_leftovers)
 
@@ -408,14 +432,8 @@ struct hg_ctx : StepBufs, StepState {
     bool ap_staged = false;
     bool ranked_local = false; // mbits holds this shard's bitmap in LOCAL rank order (hg_select_ranked)
     bool dbfx_valid = false, dbfb_valid = false;
-    double real_expect = 0.0;  // rows per query the current real-valued attempt expects its cut to keep (real_attempt; picks the rescore's slices per wavefront)
-    bool dbfb_half = false;    // dbfb is in IEEE half instead of bfloat16 (no feature of the database can overflow it: real_launch_select_bf)
-    bool samp16 = false;       // the current attempt's sample scores are bfloat16 (k_real_sample_h -> k_real_guess_lds)
-    bool real_no_cut = false;     // the current real_attempt takes every row (thr = -inf)
-    bool real_filtered = false;   // the last real_select left unscored candidates that k_real_rescore completed
+    bool dbfb_half = false;    // dbfb is in IEEE half instead of bfloat16 (no feature of the database can overflow it: ensure_filter_image)
     i64 real_requeried = 0;       // queries that lost the first real-valued bet and were ranked again on their own (cumulative)
-    i64 real_attempts = 0;        // statistics of the last real-valued ranking: attempts made (1 = the first bet held) ...
-    i64 real_lds_ranked = 0;      // ... and whether the LDS-resident rank kernel produced its lists
     int bpad = 0;              // feature count padded to a multiple of 16 (0: no float tables loaded)
     i64 census_db[3] = {0, 0, 0}, census_q[3] = {0, 0, 0};
     // hand-over of float32 / int64 arrays (options host_pack, keep_floats)
@@ -427,8 +445,8 @@ struct hg_ctx : StepBufs, StepState {
     void* hpk = nullptr;       // pinned staging for the packed tables
     size_t hpk_cap = 0;
     bool dbf_resident = false, qf_resident = false;   // float tables as loaded: entries outside {-1,0,+1}, zeros, minus ones
-    bool real_lists = false;
-    bool real_lists_made = false;   // ... by the last attempt (hg_map_real skips them on the paths that rank in LDS)
+    RealState real;            // what the last attempt of a real-valued ranking left behind
+    bool real_lists = false;   // hg_get_topr_real may hand out out_idx / scores: cleared where run_real begins, set once its ladder has succeeded
     i64 shapes_for_R = -1;
     i64 recip_for_R = -1;      // ap_recip holds RN(1 / k) for k = 1 .. this
 

@@ -106,6 +106,35 @@ def test_every_row_ranked_group_by_group(kind):
         c.close()
 
 
+def test_the_path_of_a_call_is_not_carried_over_from_the_call_before():
+    """Stat real_path describes the LAST call: an every-row call that ranked group by group (bit 2), then on the same context a
+    bet that the LDS rank kernel finishes at its first attempt -- bit 1 set, bit 2 clear, and the oracle's lists both times."""
+    rng = np.random.default_rng(41)
+    Q, N, b, C, R = 12, 70000, 64, 10, 2000
+    dbf, qf = np.tanh(rng.standard_normal((N, b))).astype(np.float32), np.tanh(rng.standard_normal((Q, b))).astype(np.float32)
+    dl = (rng.random((N, C)) < 0.2).astype(np.int64)
+    ql = (rng.random((Q, C)) < 0.2).astype(np.int64)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        _, _, idx_all, score_all = RM.map_from_features(qf, dbf, ql.astype(np.int8), dl.astype(np.int8), N)
+        _, _, idx_ref, score_ref = RM.map_from_features(qf, dbf, ql.astype(np.int8), dl.astype(np.int8), R)
+    c = _native.Context(0)
+    try:
+        c.set_database_f32(dbf, dl)
+        c.set_queries_f32(qf, ql)
+        idx, score = c.topr_real(N)
+        assert (c.get_stat("real_path") >> 2) & 1
+        assert np.array_equal(idx, idx_all) and np.array_equal(score.view(np.uint32), score_all.view(np.uint32))
+        idx, score = c.topr_real(R)
+        assert np.array_equal(idx, idx_ref) and np.array_equal(score.view(np.uint32), score_ref.view(np.uint32))
+        assert c.get_stat("real_attempts") == 1
+        path = c.get_stat("real_path")
+        assert (path >> 1) & 1, "the bet was not ranked in LDS"
+        assert ((path >> 2) & 1) == 0, "bit 2 of real_path is the call before's"
+    finally:
+        c.close()
+
+
 @pytest.mark.parametrize("Q,N,b", [(70, 20011, 64), (33, 9000, 128), (100, 4999, 20)])
 def test_every_row_a_record_leaves_in_whole_lines(Q, N, b):
     """No cut (R = N, metric.py:14 with MAP_R = DB_SIZE): k_real_select_mx turns a tile's records through LDS and stores whole

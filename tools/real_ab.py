@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The real-valued call at the C2 shape under engine options: tools/real_ab.py [key=value ...] -> ms per call, per-kernel averages,
-and the APs' equality with the unfused sequence (real_fused_scores=0)."""
+"""The real-valued call at the C2 shape under engine options: tools/real_ab.py [key=value ...] -> for the default options and then for
+each key=value on its own: ms per call, per-kernel averages, and whether the APs equal those of the default options."""
 import sys, time
 import numpy as np
 sys.path.insert(0, __file__.rsplit("/", 2)[0])
