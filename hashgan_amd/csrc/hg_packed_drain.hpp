@@ -7,7 +7,7 @@
 // in the kernel's own header, with the entry format).  Everything else is here, once.
 //
 // Drain (one-byte compact records only: hg_mx_drain.hpp explains rings and slices).  Per supertile and query tile every
-// lane with a hit appends ONE entry {A | query tag | lane-half | supertile | buffer, B | slice position & 15, further
+// lane with a hit appends ONE entry {A | query tag | row index of the supertile, B | slice position & 15, further
 // words} to the wavefront's queue (ring buffer in LDS, slot = rank among the pushing lanes).  The emit works the queue
 // off in batches of exactly 64 entries -- every lane busy -- and entries that do not fill a batch WAIT for the next
 // window: the packed codes and labels the emit needs are triple-buffered, so an entry may be emitted one window late,
@@ -21,7 +21,7 @@
 //     QT, ROWS, WPB      query tiles (of 32) per wavefront, rows per supertile and lane-half, wavefronts per block
 //     WORDS, ENTRY       hit words per entry, bytes of an entry in the LDS queue
 //     CHUNKS, IMG_WORDS  1 KiB chunks of A fragments per supertile; 16-byte code words per row of the database image
-//     ws(LW), WS_MAX     supertiles per window for LW label words (<= 4: two bits of a queue entry); the largest
+//     ws(LW), WS_MAX     supertiles per window for LW label words (1, 2 or 4: the row index of a queue entry has five bits); the largest
 //     FLUSH              the owners flush their rings every this many supertiles (a multiple of the window)
 //     load / store       a queue entry <-> its words; OPAQUE_QBASE: the queue's LDS address is hidden from the optimiser
 //     flat(words)        the supertile's hit mask, bit P <-> row P (the direct route)
@@ -41,9 +41,21 @@ __device__ __forceinline__ u32 pk_and_or(const u32 x, const u32 k, const u32 y) 
     return d;
 }
 
+// (x << SH) | y and a | b | c in one op each, c wave-uniform: a queue entry's two tagged words cost the push one op apiece
+template <int SH> __device__ __forceinline__ u32 pk_lshl_or(const u32 x, const u32 y) {
+    u32 d;
+    asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(d) : "v"(x), "n"(SH), "v"(y));
+    return d;
+}
+__device__ __forceinline__ u32 pk_or3_s(const u32 a, const u32 b, const u32 c) {
+    u32 d;
+    asm("v_or3_b32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(c));
+    return d;
+}
+
 struct PackedLds {             // byte offsets inside the block's dynamic LDS
     int a, abuf;               // A fragments: 2 buffers of abuf bytes
-    int cl, clbuf, labels;     // packed codes + labels of a window's rows (both halves): 3 buffers of clbuf bytes; labels inside a buffer
+    int cl, labels;            // packed codes of the staged rows, one array [3 buffers][2 lane-halves][window rows]; their labels, a second array indexed alike
     int qcodes, qlabels;       // the block's query tables
     int queue;                 // per-wave queues: [PK_QCAP] entries of P::ENTRY bytes
     int rings;                 // per-wave slice rings
@@ -55,9 +67,8 @@ template <class P> __host__ __device__ inline PackedLds packed_lds_layout(int NW
     l.a = 0;
     l.abuf = WS * P::CHUNKS * 1024;
     l.cl = 2 * l.abuf;
-    l.labels = 2 * WROWS * NW * 4;
-    l.clbuf = (l.labels + 2 * WROWS * LW * 8 + 15) & ~15;
-    l.qcodes = l.cl + 3 * l.clbuf;
+    l.labels = l.cl + 6 * WROWS * NW * 4;
+    l.qcodes = (l.labels + 6 * WROWS * LW * 8 + 15) & ~15;
     l.qlabels = l.qcodes + P::WPB * 64 * NW * 4;
     l.queue = l.qlabels + P::WPB * 64 * LW * 8;
     l.rings = l.queue + P::WPB * PK_QCAP * P::ENTRY;
@@ -69,6 +80,7 @@ template <int NW, int LW, class P>
 struct PackedDrain {
     static constexpr int QT = P::QT, NH = P::WORDS, CB = NW * 4, LB = LW * 8;
     static constexpr int ROWS = P::ROWS, WROWS = P::ws(LW) * ROWS;
+    static_assert((P::ws(LW) & (P::ws(LW) - 1)) == 0 && 6 * P::ws(LW) <= 32, "an entry's row index: {buffer, lane-half, supertile} in five bits, the half one of them");
     u8* lds;
     PackedLds L;
     u32 ring_base;                       // LDS address of the wavefront's first ring
@@ -139,23 +151,23 @@ struct PackedDrain {
             const u32 i = (qhead + (u32)lane) & (PK_QCAP - 1);
             u32 e[NH];
             P::load(lds, qbase, i, e);
-            // every packing's entry: e[0] = {query tag t * 32 + j : 6 | hit bits | lane-half : 1 | supertile : 2 | buffer : 2},
-            // e[1] = {hit bits | position : 5}
-            const u32 x = e[0] & 63u, h = (e[0] >> 27) & 1u, st = (e[0] >> 28) & 3u, sel = e[0] >> 30;
+            // every packing's entry: e[0] = {query tag t * 32 + j : 6 | hit bits | idx : 5}, e[1] = {hit bits | position : 5};
+            // idx = (buffer * 2 + lane-half) * WS + supertile numbers the supertile's rows among the staged ones, codes and labels alike
+            const u32 x = e[0] & 63u, idx = e[0] >> 27, h = (idx / (u32)P::ws(LW)) & 1u;
             u32 pos = e[1] >> 27;                                     // slice position & 15 of the entry's first hit
             typename P::Mask m(e);
             const u32 ql = (u32)wave * 64u + x;                       // the entry's query, block-local
             u32 qcw[NW];
             u64 qlw[LW];
+            // (plain LDS addresses -- the block's dynamic LDS starts at 0 -- spare the add of the array's symbol)
 #pragma unroll
-            for (int k = 0; k < NW; ++k) qcw[k] = ((const u32*)(lds + L.qcodes + ql * CB))[k];
+            for (int k = 0; k < NW; ++k) qcw[k] = ((const u32 __attribute__((address_space(3)))*)(uintptr_t)((u32)L.qcodes + ql * CB))[k];
 #pragma unroll
-            for (int k = 0; k < LW; ++k) qlw[k] = ((const u64*)(lds + L.qlabels + ql * LB))[k];
+            for (int k = 0; k < LW; ++k) qlw[k] = ((const u64 __attribute__((address_space(3)))*)(uintptr_t)((u32)L.qlabels + ql * LB))[k];
             const u32 ring = ring_base + (h * 64u + x) * PK_RING;     // LDS address (the block's dynamic LDS starts at 0), a multiple of 16
-            // LDS byte offsets of the code / label words of the supertile's row 0 (buffer sel, lane-half h, supertile st)
-            const u32 row0 = h * WROWS + st * ROWS;
-            const u32 code0 = (u32)L.cl + sel * (u32)L.clbuf + row0 * CB;
-            const u32 lab0 = (u32)L.cl + sel * (u32)L.clbuf + (u32)L.labels + row0 * LB;
+            // LDS byte offsets of the code / label words of the supertile's row 0
+            const u32 code0 = (u32)L.cl + idx * (u32)(ROWS * CB);
+            const u32 lab0 = (u32)L.labels + idx * (u32)(ROWS * LB);
             while (m.any()) {
                 const u32 row = m.pop();                              // lowest set bit = earliest row
                 const u32* rp = (const u32*)(lds + (code0 + row * CB));
@@ -195,17 +207,18 @@ struct PackedDrain {
         for (int k = 0; k < NW; ++k) qcw[k] = ((const u32*)(lds + L.qcodes + ql * CB))[k];
 #pragma unroll
         for (int k = 0; k < LW; ++k) qlw[k] = ((const u64*)(lds + L.qlabels + ql * LB))[k];
-        const u8* clb = lds + L.cl + sel * L.clbuf;
-        const u32 row0 = (u32)(lane >> 5) * WROWS + (u32)st * ROWS;
+        const u32 row0 = (sel * 2u + (u32)(lane >> 5)) * WROWS + (u32)st * ROWS;
+        const u8* codes = lds + L.cl;
+        const u8* labels = lds + L.labels;
         u32 pos = cnt[t];
         while (x) {
             const u32 row = (u32)(sizeof(x) == 8 ? __builtin_ctzll(x) : __builtin_ctz((u32)x));
             x &= x - 1;
-            const u32* rp = (const u32*)(clb + (row0 + row) * CB);
+            const u32* rp = (const u32*)(codes + (row0 + row) * CB);
             u32 d = 0;
 #pragma unroll
             for (int k = 0; k < NW; ++k) d += __builtin_popcount(qcw[k] ^ rp[k]);
-            const u64* lp = (const u64*)(clb + L.labels + (row0 + row) * LB);
+            const u64* lp = (const u64*)(labels + (row0 + row) * LB);
             u64 any = 0;
 #pragma unroll
             for (int k = 0; k < LW; ++k) any |= lp[k] & qlw[k];
@@ -242,7 +255,7 @@ struct PackedDrain {
     // The hit words of one supertile: w[t] = the words of query tile t.  st = supertile of the window, sel = the
     // window's codes/labels buffer.
     __device__ __forceinline__ void push(u32 (&w)[QT][NH], const int st, const u32 sel) {
-        u32 any[QT], want[QT];
+        u32 want[QT];
         u64 bal[QT];
         {
             bool over = false;
@@ -257,14 +270,10 @@ struct PackedDrain {
                 for (int t = 0; t < QT; ++t) want[t] = plus_hits(cnt[t], w[t]);
             }
         }
-        // (the hit flags and ballots have ONE definition, behind the rare branch: no second compare for the stores' exec mask)
+        // (a lane has a hit where its count moves -- the popcounts are needed anyway; ONE definition, behind the rare branch: no second
+        // compare for the stores' exec mask)
 #pragma unroll
-        for (int t = 0; t < QT; ++t) {
-            any[t] = w[t][0];
-#pragma unroll
-            for (int k = 1; k < NH; ++k) any[t] |= w[t][k];
-            bal[t] = __ballot(any[t] != 0u);
-        }
+        for (int t = 0; t < QT; ++t) bal[t] = __ballot(want[t] != cnt[t]);
         u32 nz = 0;
 #pragma unroll
         for (int t = 0; t < QT; ++t) nz += (u32)__builtin_popcountll(bal[t]);
@@ -272,15 +281,18 @@ struct PackedDrain {
             while (qfill >= 64u) emit_batch(64u);                     // a dense supertile (up to 128 entries) needs it empty
             if (qfill + nz > (u32)PK_QCAP) emit_batch(qfill);
         }
-        const u32 desc = ((u32)st << 28) | (sel << 30);
+        // the entry's row index (buffer * 2 + half) * WS + supertile: the wave-uniform part is scalar, the half's rides in the lane's constant
+        const u32 desc = (sel * (u32)(2 * P::ws(LW)) + (u32)st) << 27;
+        const u32 half = (u32)(lane >> 5) * (u32)P::ws(LW);
 #pragma unroll
         for (int t = 0; t < QT; ++t) {
             const u64 b = bal[t];
             const u32 slot = (qhead + qfill + __builtin_amdgcn_mbcnt_hi((u32)(b >> 32), __builtin_amdgcn_mbcnt_lo((u32)b, 0u))) & (PK_QCAP - 1);
             if (__builtin_amdgcn_inverse_ballot_w64(b)) {             // (the ballot IS the exec mask: no second compare)
                 u32 e[NH];
-                e[0] = w[t][0] | ((u32)(lane & 31) | ((u32)t << 5) | ((u32)(lane >> 5) << 27)) | desc;
-                e[1] = w[t][1] | (cnt[t] << 27);
+                // (the lane's part is the same for every tile; the tile's bit joins the scalar part)
+                e[0] = pk_or3_s(w[t][0], (u32)(lane & 31) | (half << 27), desc | ((u32)t << 5));
+                e[1] = pk_lshl_or<27>(cnt[t], w[t][1]);
 #pragma unroll
                 for (int k = 2; k < NH; ++k) e[k] = w[t][k];
                 P::store(lds, qbase, slot, e);

@@ -29,7 +29,7 @@ namespace hg {
 
 constexpr int M3_QT = 2;                   // query tiles (of 32) per wavefront
 constexpr int M3_ROWS = 48;                // rows per supertile and lane-half
-// Supertiles per window (<= 4: two bits of a queue entry).  A window costs LDS -- 3 KiB of A fragments per supertile, twice,
+// Supertiles per window (1, 2 or 4: a queue entry numbers the supertile among those of three windows x two lane-halves in five bits).  A window costs LDS -- 3 KiB of A fragments per supertile, twice,
 // and the packed codes + labels of its rows three times -- and buys fewer barriers, flushes and window ends per row.
 // Eight wavefronts share it: 79 KB per block with 4 supertiles and one label word (two blocks per CU, four wavefronts per
 // SIMD); two label words (65..128 classes) get 2 supertiles (67 KB).  Measured at C2, 8 wavefronts per block: 2 supertiles
@@ -98,7 +98,7 @@ __device__ __forceinline__ u32 m3_mul24_421(const u32 x) {
 
 // The packing's traits for the batched drain (hg_packed_drain.hpp).  A queue entry is 12 bytes, ONE address per entry (round 4
 // kept {A, B} and {C} in two arrays: 0.627 vs 0.615 ms):
-//     e[0] = {query tag t * 32 + j : 6 | A : 21 | lane-half : 1 | supertile : 2 | buffer : 2},  e[1] = {0 : 6 | B : 21 | position : 5},  e[2] = C
+//     e[0] = {query tag t * 32 + j : 6 | A : 21 | row index (buffer * 2 + lane-half) * WS + supertile : 5},  e[1] = {0 : 6 | B : 21 | position : 5},  e[2] = C
 struct M3Pack {
     static constexpr int QT = M3_QT, ROWS = M3_ROWS, WPB = M3_WPB, WORDS = 3, ENTRY = 12, CHUNKS = 3;
     static constexpr int WS_MAX = M3_WS_MAX, FLUSH = HG_M3_FLUSH;
@@ -220,7 +220,6 @@ void k_select_mx3(const u32* __restrict__ qc, const u64* __restrict__ qlab, cons
     const u32 lane16 = (u32)lane * 16u;
     auto stage_window = [&](const i64 win, const int abuf, const int clsel) {
         u8* sa = mxlds + L.a + abuf * L.abuf;
-        u8* scl = mxlds + L.cl + clsel * L.clbuf;
 #pragma unroll
         for (int k = 0; k < (M3_WS * 3 + M3_WPB - 1) / M3_WPB; ++k) {
             const int c = wave + k * M3_WPB;
@@ -242,7 +241,7 @@ void k_select_mx3(const u32* __restrict__ qc, const u64* __restrict__ qlab, cons
                 const i64 lim = g.N * rowb;
                 const u8* tab = is_lab ? (const u8*)dblab : (const u8*)db;
                 // rows past the table: anything (masked); the last chunk may overhang the table by < 16 B (allocation slack, see k_select_mx)
-                u8* dst = scl + (is_lab ? L.labels : 0) + hh * M3_WROWS * rowb + piece * 1024;
+                u8* dst = mxlds + (is_lab ? L.labels : L.cl) + (clsel * 2 + hh) * M3_WROWS * rowb + piece * 1024;
                 if (piece * 1024 + (int)lane16 < M3_WROWS * rowb) {
                     // (the lane's offset is made opaque here: hoisted out of the window loop, `table + lane offset` is a 64-bit value per
                     // table that lives across the whole kernel -- and, spilled, comes back behind an s_waitcnt vmcnt(0) that also

@@ -30,7 +30,7 @@ constexpr int M4_ROWS = 32;                // rows per supertile and lane-half
 #ifndef HG_M4_WS
 #define HG_M4_WS 2
 #endif
-constexpr int M4_WS = HG_M4_WS;            // supertiles per window (<= 4: two bits of a queue entry)
+constexpr int M4_WS = HG_M4_WS;            // supertiles per window (1, 2 or 4: five bits of a queue entry number the staged supertiles)
 constexpr int M4_WPB = 8;                  // wavefronts per block: they share the staged window
 constexpr int M4_NM = 2;                   // MFMAs (64-bit granules) per tile: codes of 65..128 bits
 
@@ -59,7 +59,7 @@ static __global__ __launch_bounds__(256) void k_expand_db4(const u32* __restrict
 }
 
 // The packing's traits for the batched drain (hg_packed_drain.hpp).  A queue entry is one u64 {e[1], e[0]}:
-//     e[0] = {query tag t * 32 + j : 6 | 0 | A : 16 | 0 : 4 | lane-half : 1 | supertile : 2 | buffer : 2},  e[1] = {.. B : 16 .. | position : 5}
+//     e[0] = {query tag t * 32 + j : 6 | 0 | A : 16 | 0 : 4 | row index (buffer * 2 + lane-half) * WS + supertile : 5},  e[1] = {.. B : 16 .. | position : 5}
 struct M4Pack {
     static constexpr int QT = M4_QT, ROWS = M4_ROWS, WPB = M4_WPB, WORDS = 2, ENTRY = 8, CHUNKS = 2 * M4_NM;
     static constexpr int WS_MAX = M4_WS, FLUSH = 4;
@@ -178,7 +178,6 @@ void k_select_mx4(const u32* __restrict__ qc, const u64* __restrict__ qlab, cons
     const u32 lane16 = (u32)lane * 16u;
     auto stage_window = [&](const i64 win, const int abuf, const int clsel) {
         u8* sa = mxlds + L.a + abuf * L.abuf;
-        u8* scl = mxlds + L.cl + clsel * L.clbuf;
 #pragma unroll
         for (int k = 0; k < (M4_WS * CPS + M4_WPB - 1) / M4_WPB; ++k) {
             const int c = wave + k * M4_WPB;
@@ -200,7 +199,7 @@ void k_select_mx4(const u32* __restrict__ qc, const u64* __restrict__ qlab, cons
                 const i64 lim = g.N * rowb;
                 const u8* tab = is_lab ? (const u8*)dblab : (const u8*)db;
                 // rows past the table: anything (masked); the last chunk may overhang the table by < 16 B (allocation slack, see k_select_mx)
-                u8* dst = scl + (is_lab ? L.labels : 0) + hh * WROWS * rowb + piece * 1024;
+                u8* dst = mxlds + (is_lab ? L.labels : L.cl) + (clsel * 2 + hh) * WROWS * rowb + piece * 1024;
                 if (piece * 1024 + (int)lane16 < WROWS * rowb) {
                     u32 l16 = lane16;                                // (opaque: see k_select_mx3's staging -- no hoisted 64-bit `table + lane offset` to spill)
                     asm volatile("" : "+v"(l16));
