@@ -37,6 +37,7 @@ _SIGNATURES = {
     "hg_get_packed": [_p, C.c_int, _p, _p],
     "hg_hist": [_p],
     "hg_hist_buffer": [_p, C.POINTER(_p), C.POINTER(_i64)],
+    "hg_rel_hist": [_p],
     "hg_plan": [_p, _i64, _p, C.c_int, C.c_int],
     "hg_select": [_p],
     "hg_bet_eligible": [_p, _i64, C.c_int, C.POINTER(C.c_int)],
@@ -71,6 +72,7 @@ _SIGNATURES = {
     "hg_get_match": [_p, _p],
     "hg_get_ap": [_p, _p, _p],
     "hg_get_hist": [_p, _p],
+    "hg_get_rel_hist": [_p, _p, _p],
     "hg_comm_unique_id": [_p],
     "hg_comm_init": [_p, _p, C.c_int, C.c_int],
     "hg_comm_destroy": [_p],
@@ -221,6 +223,10 @@ class Context:
     # -- stages -----------------------------------------------------------------
     def hist(self):
         check(self._lib.hg_hist(self._h))
+
+    def rel_hist(self):
+        """One pass over the pairs: rows per (distance, query) and how many of them share a label with the query."""
+        check(self._lib.hg_rel_hist(self._h))
 
     def hist_buffer(self):
         p, n = _p(), _i64()
@@ -397,6 +403,14 @@ class Context:
         h = np.empty((self.b + 1, self.Q), dtype=np.uint32)
         check(self._lib.hg_get_hist(self._h, _ptr(h)))
         return h
+
+    def get_rel_hist(self):
+        """-> (all, rel), uint32 [b+1, Q] each, of this shard (after rel_hist())."""
+        shape = ((self.b or 0) + 1, self.Q or 0)          # (nothing loaded yet: the library says so)
+        a = np.empty(shape, dtype=np.uint32)
+        r = np.empty(shape, dtype=np.uint32)
+        check(self._lib.hg_get_rel_hist(self._h, _ptr(a), _ptr(r)))
+        return a, r
 
     # -- collectives (RCCL) -------------------------------------------------------
     def comm_init(self, unique_id, rank, world):

@@ -23,7 +23,8 @@ int fail(int code, const char* fmt, ...) {
 
 const char* const kKernelNames[KI_COUNT] = {"k_hist", "k_hist_reduce", "k_plan", "k_seg_counts", "k_seg_layout", "k_guess",
                                             "k_select", "k_rank_hist", "k_order", "k_rank_fused", "k_match", "k_ap", "k_merge", "k_pack",
-                                            "k_real_sample", "k_real_guess", "k_real_select", "k_radix_pass", "k_real_finish", "k_select_mx", "k_rank_cnt", "rccl_allgather", "step_gpu_span", "k_real_rescore"};
+                                            "k_real_sample", "k_real_guess", "k_real_select", "k_radix_pass", "k_real_finish", "k_select_mx", "k_rank_cnt", "rccl_allgather", "step_gpu_span", "k_real_rescore",
+                                            "k_hist_rel", "k_hist_rel_reduce"};
 // Flatten NumPy's pairwise-summation tree for a chunk of n elements (n <= 8192):
 // numpy/_core/src/umath/loops_utils.h.src, pairwise_sum: n <= 128 is a leaf,
 // otherwise split at n/2 rounded down to a multiple of 8.
@@ -883,6 +884,16 @@ int hg_get_hist(hg_ctx* c, uint32_t* host_hist) {
     return c->sync();
 }
 
+int hg_get_rel_hist(hg_ctx* c, uint32_t* host_all, uint32_t* host_rel) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_rel_hist", "hg_rel_hist"));
+    if (!c->rh_done || c->rh_q_gen != c->q_gen || c->rh_db_gen != c->db_gen)
+        return fail(HG_ERR_STATE, "hg_get_rel_hist called before hg_rel_hist (on the tables loaded now)");
+    const size_t row = (size_t)c->rh_Q * 4, pitch = (size_t)c->rh_Qpad * 4;
+    if (host_all) HG_HIP(hipMemcpy2DAsync(host_all, row, c->rh_all.p, pitch, row, (size_t)c->rh_NB, hipMemcpyDeviceToHost, c->stream));
+    if (host_rel) HG_HIP(hipMemcpy2DAsync(host_rel, row, c->rh_rel.p, pitch, row, (size_t)c->rh_NB, hipMemcpyDeviceToHost, c->stream));
+    return c->sync();
+}
+
 
 // Context-owned device scratch (grows only) and a stream-ordered device-to-device copy: what an in-process
 // communicator (virtual shards of one GPU in the tests) needs to do hg_allgather's job without RCCL.
@@ -1067,6 +1078,7 @@ int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "rank_leftovers")) *value = c->rank_leftovers;
     else if (!strcmp(key, "select_variant")) *value = c->last_select;
     else if (!strcmp(key, "rank_variant")) *value = c->last_rank;
+    else if (!strcmp(key, "rel_hist_variant")) *value = c->last_rel_hist;
     else if (!strcmp(key, "ap_fused")) *value = c->ap_fused ? 1 : 0;
     else if (!strcmp(key, "cap_boost")) *value = c->cap_boost;
     else if (!strcmp(key, "crowding_x100")) *value = c->crowd_x100;

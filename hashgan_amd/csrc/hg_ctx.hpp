@@ -209,7 +209,7 @@ struct DevBuf {
 
 enum KernelId { KI_HIST = 0, KI_HIST_REDUCE, KI_PLAN, KI_SEG_COUNTS, KI_SEG_LAYOUT, KI_GUESS, KI_SELECT, KI_CAND_HIST,
                 KI_ORDER, KI_RANK_FUSED, KI_MATCH, KI_AP, KI_MERGE, KI_PACK, KI_REAL_SAMPLE, KI_REAL_GUESS, KI_REAL_SELECT,
-                KI_RADIX, KI_REAL_FINISH, KI_SELECT_MX, KI_RANK_LDS, KI_COMM, KI_STEP, KI_REAL_RESCORE, KI_COUNT };
+                KI_RADIX, KI_REAL_FINISH, KI_SELECT_MX, KI_RANK_LDS, KI_COMM, KI_STEP, KI_REAL_RESCORE, KI_HIST_REL, KI_HIST_REL_REDUCE, KI_COUNT };
 enum Stage { ST_NONE = 0, ST_DB = 1, ST_Q = 2, ST_HIST = 4, ST_PLAN = 8, ST_SELECT = 16, ST_MATCH = 32, ST_AP = 64 };
 extern const char* const kKernelNames[KI_COUNT];
 
@@ -386,6 +386,11 @@ struct hg_ctx : StepBufs, StepState {
     bool dbx_valid = false, qx_valid = false, dbx8_valid = false, dbx3_valid = false, dbx4_valid = false;
     bool hist_pairs = false;   // the last FULL histogram pass ran per segment pair (k_hist_mx)
     i64 bet_rebets = 0;        // stat "optimistic_rebets"
+    // the relevant-row histogram (hg_rel_hist): rh_all / rh_rel hold the tables of the queries and database of these generations
+    bool rh_done = false;
+    unsigned long long rh_q_gen = 0, rh_db_gen = 0;
+    i64 rh_Q = 0, rh_Qpad = 0, rh_NB = 0;
+    int last_rel_hist = 0;     // stat "rel_hist_variant": 1 k_hist_rel (0: no pass yet)
     bool verdict_pending = false, verdict_known = false;
     int verdict_flag = 0;
     // pinned landing zone for a one-shot call's results: AP, hit counts and the lost-bet flag come back with the
@@ -459,6 +464,7 @@ struct hg_ctx : StepBufs, StepState {
     DevBuf dbf, qf;                             // the float tables (hg_set_*_f32 with keep_floats)
     DevBuf dbx, qx;            // fp4 images of db / qc in MFMA fragment order for k_select_mx (dbx_valid, qx_valid)
     DevBuf dbx8;               // i8 image of the database codes in A-fragment order (k_hist_i8; dbx8_valid)
+    DevBuf rh_part, rh_all, rh_rel;   // hg_rel_hist: per-segment counters [S][2 NB][Qpad], the tables all / rel [NB][Qpad] (rh_done)
     DevBuf dbx3;               // fp4 image for k_select_mx3 (48-row supertiles, three rows per accumulator; dbx3_valid)
     DevBuf dbx4;               // fp4 image for k_select_mx4 (32-row supertiles, two rows per accumulator; codes of 65..128 bits; dbx4_valid)
     DevBuf dbfx;               // float features of the database in MFMA A-fragment order (k_real_select_mx; dbfx_valid)
@@ -485,7 +491,7 @@ struct hg_ctx : StepBufs, StepState {
         for (DevBuf* d : {&db, &dblab, &qc, &qlab, &dbf, &qf}) f(*d, BUF_TABLE);
         for (DevBuf* d : {&dbx, &qx, &dbx8, &dbx3, &dbx4, &dbfx, &dbfb, &xmax2, &shapes, &ap_recip}) f(*d, BUF_DERIVED);
         for (DevBuf* d : {&seglt, &segtie, &mbits2, &part, &obuf[0], &obuf[1], &beyond, &stage_in, &badcnt, &flist, &dbytes, &samp, &thr,
-                          &sortA, &sortB, &scores, &gtab, &sampx, &cntq, &krows, &thr2, &hist2, &comm_tmp, &gath_idx, &gath_dist})
+                          &sortA, &sortB, &scores, &gtab, &sampx, &cntq, &krows, &thr2, &hist2, &comm_tmp, &gath_idx, &gath_dist, &rh_part, &rh_all, &rh_rel})
             f(*d, BUF_WORK);
         for (DevBuf& d : gathered) f(d, BUF_WORK);
         for (DevBuf& d : scratch) f(d, BUF_WORK);
@@ -495,6 +501,7 @@ struct hg_ctx : StepBufs, StepState {
     // the keys of the BUF_DERIVED buffers: after this each is rebuilt on its next use
     void forget_derived() {
         dbx_valid = qx_valid = dbx8_valid = dbx3_valid = dbx4_valid = dbfx_valid = dbfb_valid = false;
+        rh_done = false;               // (hg_trim releases the tables with the other work buffers)
         shapes_for_R = recip_for_R = -1;
         outblk_q = ws_b.outblk_q = -1;
     }
@@ -640,6 +647,7 @@ Geo hist_geometry(const hg_ctx* c);
 int set_R(hg_ctx* c, int64_t R, int G, int rank);
 // hg_pairs_valu.hip
 int launch_hist(hg_ctx* c);                      // k_hist<NW>
+int launch_hist_rel(hg_ctx* c, const Geo& g);    // k_hist_rel<NW, LW> into c->rh_part (g: the full pass's geometry)
 int launch_select_valu(hg_ctx* c, int lw, bool optimistic);   // k_select<NW, LW, OPT>
 int launch_select_dense(hg_ctx* c, int lw);      // k_select_dense<NW, LW>
 // hg_pairs_mx.hip (k_select_mx: hg_pairs_mx1.hip)

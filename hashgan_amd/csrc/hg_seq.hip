@@ -6,6 +6,7 @@
 #include "hg_select_mx3.hpp"
 #include "hg_select_mx4.hpp"
 #include "hg_hist_mx.hpp"
+#include "hg_hist_rel.hpp"
 #include "hg_rank_cnt.hpp"
 #include "hg_rank_lean.hpp"
 #include "hg_rank_dense.hpp"
@@ -197,6 +198,37 @@ static int do_hist(hg_ctx* c, int stride, bool reduce = true, bool pairs_ok = fa
 int hg_hist(hg_ctx* c) {
     HG_TRY(need(c, ST_DB | ST_Q, "hg_hist", "hg_set_database + hg_set_queries"));
     HG_TRY(do_hist(c, 1));
+    return c->stage_end();
+}
+
+// The relevant-row histogram (hg_hist_rel.hpp): one pass over the pairs leaves all[d][q] (rows at distance d) and rel[d][q] (those
+// that share a label with the query) in buffers of its own.  The geometry is the full pass's (do_hist(c, 1)), taken on a copy: the
+// step state -- stage, geometry, hist / hown, hist_pairs -- stays what the last call left, so a plan, a select or a step in flight
+// goes on as if this call had not happened.
+int hg_rel_hist(hg_ctx* c) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_rel_hist", "hg_set_database + hg_set_queries"));
+    const Geo kept = c->geo;
+    make_geometry(c);
+    const Geo g = c->geo;
+    c->geo = kept;
+    c->rh_done = false;
+    const unsigned long long e0 = g_alloc_epoch.load();
+    const size_t plane = (size_t)g.NB * g.Qpad * 4;
+    HG_TRY(c->rh_part.reserve(2 * plane * g.S));
+    HG_TRY(c->rh_all.reserve(plane));
+    HG_TRY(c->rh_rel.reserve(plane));
+    // (first reservations move no buffer hg_map_begin's licence to enqueue blind was given for)
+    if (c->map_warm_epoch == e0) c->map_warm_epoch = g_alloc_epoch;
+    HG_TRY(launch_hist_rel(c, g));
+    c->last_rel_hist = 1;
+    c->t_begin(KI_HIST_REL_REDUCE);
+    hipLaunchKernelGGL(k_hist_rel_reduce, dim3(grid_for((i64)g.NB * g.Qpad)), dim3(256), 0, c->stream, c->rh_part.as<u32>(),
+                       c->rh_all.as<u32>(), c->rh_rel.as<u32>(), g);
+    c->t_end();
+    HG_TRY(c->check_launch("k_hist_rel_reduce"));
+    c->rh_done = true;
+    c->rh_q_gen = c->q_gen; c->rh_db_gen = c->db_gen;
+    c->rh_Q = g.Q; c->rh_Qpad = g.Qpad; c->rh_NB = g.NB;
     return c->stage_end();
 }
 

@@ -3,6 +3,10 @@ Not in the reference (lib/metric.py only has mAP); these are the standard compan
 literature HashGAN's paper reports: precision/recall at the top k, and precision within Hamming
 radius r.  The ranking, label matching and histograms run on the GPU (hashgan_amd._native); the
 host only reduces small per-query vectors.
+
+Everything a Hamming-ball lookup is judged by -- ball sizes, hits inside the ball, the recall denominator, for every radius at
+once -- comes from one table: per query and distance d, the rows at distance d and how many of them share a label with the
+query (Context.rel_hist, one pass over the pairs; no ranking, no lists, nothing of size Q x N on the host).
 """
 import numpy as np
 
@@ -21,6 +25,46 @@ def _load(eng, q_codes, db_codes, q_labels, db_labels):
     return eng.ctx
 
 
+def _tables(ctx):
+    """The relevant-row histogram of the loaded tables -> (all, rel), int64 [Q, b+1]."""
+    ctx.rel_hist()
+    a, r = ctx.get_rel_hist()
+    return a.T.astype(np.int64), r.T.astype(np.int64)
+
+
+def lookup_histograms(q_codes, db_codes, q_labels, db_labels, device=0):
+    """Per query and Hamming distance d: the database rows at distance d, and those of them that share a label with the
+    query.  -> (all_hist, rel_hist), int64 [Q, b+1]"""
+    eng = metric._Shared.get(device)
+    with eng.lock:
+        return _tables(_load(eng, q_codes, db_codes, q_labels, db_labels))
+
+
+def curves_from_histograms(all_hist, rel_hist):
+    """Lookup curves over the Hamming radius r = 0..b from the two tables (NumPy only).
+    ball[q, r] = rows within r, hit[q, r] = relevant rows within r, total_rel[q] = hit[q, b];
+    precision[r] = mean over ALL queries of hit / ball (0 where the ball is empty);
+    recall[r] = mean of hit / total_rel over the queries that have relevant rows (NaN for every r if none has).
+    -> dict(precision, recall, ball, hit, total_rel)"""
+    all_hist = np.asarray(all_hist, dtype=np.int64)
+    rel_hist = np.asarray(rel_hist, dtype=np.int64)
+    if all_hist.ndim != 2 or all_hist.shape != rel_hist.shape:
+        raise ValueError("all_hist and rel_hist must be [Q, b+1] tables of the same shape")
+    ball = np.cumsum(all_hist, axis=1)
+    hit = np.cumsum(rel_hist, axis=1)
+    total_rel = hit[:, -1].copy()
+    precision = np.where(ball > 0, hit / np.maximum(ball, 1), 0.0).mean(0)
+    ok = total_rel > 0
+    recall = (hit[ok] / total_rel[ok, None]).mean(0) if ok.any() else np.full(all_hist.shape[1], np.nan)
+    return {"precision": precision, "recall": recall, "ball": ball, "hit": hit, "total_rel": total_rel}
+
+
+def hamming_radius_curves(q_codes, db_codes, q_labels, db_labels, device=0):
+    """The lookup P-R curve: (recall[r], precision[r]) for r = 0..b, with the per-query ball, hit and total_rel tables
+    (curves_from_histograms of lookup_histograms)."""
+    return curves_from_histograms(*lookup_histograms(q_codes, db_codes, q_labels, db_labels, device))
+
+
 def precision_recall_at_k(q_codes, db_codes, q_labels, db_labels, ks, device=0):
     """Mean precision@k and recall@k over the queries, Hamming ranking with the canonical tie order.
     recall uses the number of relevant rows in the WHOLE database; queries without any are skipped
@@ -32,12 +76,12 @@ def precision_recall_at_k(q_codes, db_codes, q_labels, db_labels, ks, device=0):
     eng = metric._Shared.get(device)
     with eng.lock:
         ctx = _load(eng, q_codes, db_codes, q_labels, db_labels)
-        ctx.topr(int(ks[-1]))
+        ctx.topr(int(ks[-1]))                                            # ranked once, for the hits at k
         match = ctx.get_match()
+        total_rel = _tables(ctx)[1].sum(1)                               # relevant rows in the whole database, per query
     cum = np.cumsum(match.astype(np.int64), axis=1)                      # [Q, kmax]
     hits = cum[:, ks - 1]
     precision = (hits / ks[None, :]).mean(0)
-    total_rel = ((np.asarray(q_labels) != 0).astype(np.int64) @ (np.asarray(db_labels) != 0).astype(np.int64).T > 0).sum(1)
     ok = total_rel > 0
     recall = (hits[ok] / total_rel[ok, None]).mean(0) if ok.any() else np.full(len(ks), np.nan)
     return precision, recall
@@ -49,15 +93,10 @@ def precision_within_radius(q_codes, db_codes, q_labels, db_labels, radius=2, de
     convention).  -> (mean precision, per-query ball sizes)"""
     eng = metric._Shared.get(device)
     with eng.lock:
-        ctx = _load(eng, q_codes, db_codes, q_labels, db_labels)
-        ctx.hist()
-        ball = ctx.get_hist()[:radius + 1].astype(np.int64).sum(0)      # rows within the radius, per query
-        if ball.max() == 0:
-            return 0.0, ball
-        ctx.topr(int(ball.max()))                                        # every ball is a prefix of its ranked list
-        idx, dist = ctx.get_topr()
-        match = ctx.get_match()
-    inside = dist <= radius
-    hits = (match.astype(bool) & inside).sum(1)
+        all_hist, rel_hist = _tables(_load(eng, q_codes, db_codes, q_labels, db_labels))
+    ball = all_hist[:, :radius + 1].sum(1)                               # rows within the radius, per query
+    if ball.max() == 0:
+        return 0.0, ball
+    hits = rel_hist[:, :radius + 1].sum(1)
     prec = np.where(ball > 0, hits / np.maximum(ball, 1), 0.0)
     return float(prec.mean()), ball

@@ -108,6 +108,11 @@ int hg_hist(hg_ctx* ctx);
 /* The exchange unit of every histogram stage: uint32 [b+1][Qpad] followed by 64 tail words
  * ([0] "a slice overflowed" flag, [1] rows the pass visited). */
 int hg_hist_buffer(hg_ctx* ctx, void** dev_ptr, int64_t* nbytes);
+/* The relevant-row histogram of this shard, for hash-lookup metrics (precision / recall as functions of the Hamming radius): one
+ * pass over the pairs counts, per query and distance d, the rows at distance d (all) and those of them that share a label with
+ * the query (rel) -- no ranking, no lists.  Tables of its own: the staged pipeline's state (hg_hist's histogram, a plan, a step
+ * of hg_map_begin in flight) is left as it was.  Additive over shards; a database or query reload invalidates the tables. */
+int hg_rel_hist(hg_ctx* ctx);                                            /* needs database + queries */
 int hg_plan(hg_ctx* ctx, int64_t R, const uint32_t* dev_hist_all, int G, int rank);
 int hg_select(hg_ctx* ctx);
 int hg_match(hg_ctx* ctx);
@@ -225,6 +230,7 @@ int hg_get_topr(hg_ctx* ctx, uint32_t* host_idx, uint8_t* host_dist);   /* [Q][R
 int hg_get_match(hg_ctx* ctx, uint8_t* host_imatch);                    /* [Q][R] of 0/1 */
 int hg_get_ap(hg_ctx* ctx, double* host_ap, int64_t* host_rel);         /* [Q]; ap = NaN where rel == 0 */
 int hg_get_hist(hg_ctx* ctx, uint32_t* host_hist);                      /* [b+1][Q] of this shard */
+int hg_get_rel_hist(hg_ctx* ctx, uint32_t* host_all, uint32_t* host_rel); /* [b+1][Q] each, this shard (after hg_rel_hist) */
 
 /* ---- collectives: RCCL over xGMI, one process per GPU (the reference has no counterpart --
  * main.py:260-263 only sets CUDA_VISIBLE_DEVICES) --------------------------------------------------------
@@ -307,10 +313,10 @@ int hg_set_stream(hg_ctx* ctx, void* hip_stream);
  *                 ALU), "real_sample_half" (1: the sampled cut's scores in the filter's 16-bit arithmetic -- they only place the cut; 0: exact float32 chains), "real_second_sample" (1: a second, counting sample four times as large tightens that cut), "real_sort_lds" (1: ranked by the LDS-resident kernel when the records fit), "real_groups" (1: lists beyond the LDS ordered group by group), "real_map_lists" (0; 1: hg_map_real also writes the ranked idx / score lists), "real_whole_rounds" (3: without a cut -- R = N -- the database is cut so that k_real_select_mx's blocks fill whole rounds of that many per CU; 0: the plain geometry)
  *   ("probe_select" exists only in the measurement build, python -m hashgan_amd.build --probes) */
 int hg_set_option(hg_ctx* ctx, const char* key, int64_t value);
-/* Counters and facts about the last call (23 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
+/* Counters and facts about the last call (24 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
  * "optimistic_requeried" (single queries rerun exactly after losing their bet), "optimistic_rebets" (second and widened bets), "last_optimistic",
  * "rank_leftovers" (queries the LDS-resident rank kernel left to the general one), "select_variant" (1 k_select, 2 k_select_dense, 3 k_select_mx,
- * 5 k_select_mx3, 6 k_select_mx4), "rank_variant" (1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>), "ap_fused",
+ * 5 k_select_mx3, 6 k_select_mx4), "rank_variant" (1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>), "rel_hist_variant" (the kernel of the last hg_rel_hist: 1 k_hist_rel, the vector-ALU pass -- the only one so far, whatever "hist_mfma" says; 0: no pass yet), "ap_fused",
  * "cap_boost", "crowding_x100", "segments", "records_kept" (records the last bet's select left in the slices: a download, not part of a step),
  * "device_bytes" (every device buffer the context and its requery child hold, the second stream's workspace included), "graph_replays", "map_async_steps" / "map_async_redone" / "map_overlapped_steps" (hg_map_begin: steps enqueued blind / of those, run again by hg_map_end /
  * of those, run on the second stream);
