@@ -38,6 +38,8 @@ _SIGNATURES = {
     "hg_hist": [_p],
     "hg_hist_buffer": [_p, C.POINTER(_p), C.POINTER(_i64)],
     "hg_rel_hist": [_p],
+    "hg_grade_hist": [_p],
+    "hg_graded": [_p, _p, C.c_int, _p, _p, C.c_int],
     "hg_plan": [_p, _i64, _p, C.c_int, C.c_int],
     "hg_select": [_p],
     "hg_bet_eligible": [_p, _i64, C.c_int, C.POINTER(C.c_int)],
@@ -73,6 +75,9 @@ _SIGNATURES = {
     "hg_get_ap": [_p, _p, _p],
     "hg_get_hist": [_p, _p],
     "hg_get_rel_hist": [_p, _p, _p],
+    "hg_get_grade_hist": [_p, _p],
+    "hg_get_graded": [_p, _p, _p, _p, _p],
+    "hg_get_grades": [_p, _p],
     "hg_comm_unique_id": [_p],
     "hg_comm_init": [_p, _p, C.c_int, C.c_int],
     "hg_comm_destroy": [_p],
@@ -228,6 +233,21 @@ class Context:
         """One pass over the pairs: rows per (distance, query) and how many of them share a label with the query."""
         check(self._lib.hg_rel_hist(self._h))
 
+    def grade_hist(self):
+        """One pass over the label pairs: rows per (grade, query), grade = labels shared with the query."""
+        check(self._lib.hg_grade_hist(self._h))
+
+    def graded(self, ks, gain, disc, keep_grades=False):
+        """Graded sums along the ranked lists of the last topr() / topr_real() at the ascending cut-offs ks; gain [C+1] and
+        disc [max(ks)] are float64 tables (disc[i-1] for rank i).  Results: get_graded(), get_grades()."""
+        ks = _carray(ks, np.int64).ravel()
+        gain = _carray(gain, np.float64).ravel()
+        disc = _carray(disc, np.float64).ravel()
+        if len(gain) != (self.C or 0) + 1 or (len(ks) and len(disc) < int(ks[-1])):
+            raise ValueError("gain must have C + 1 entries and disc max(ks)")
+        check(self._lib.hg_graded(self._h, _ptr(ks), len(ks), _ptr(gain), _ptr(disc), 1 if keep_grades else 0))
+        self._graded_nk = len(ks)
+
     def hist_buffer(self):
         p, n = _p(), _i64()
         check(self._lib.hg_hist_buffer(self._h, C.byref(p), C.byref(n)))
@@ -373,9 +393,12 @@ class Context:
         self.R = int(R)
         return ap, rel
 
-    def topr_real(self, R):
+    def topr_real(self, R, download=True):
+        """download=False: the lists stay on the device (for graded())."""
         check(self._lib.hg_topr_real(self._h, int(R)))
         self.R = int(R)
+        if not download:
+            return None
         idx = np.empty((self.Q, self.R), dtype=np.uint32)
         score = np.empty((self.Q, self.R), dtype=np.float32)
         check(self._lib.hg_get_topr_real(self._h, _ptr(idx), _ptr(score)))
@@ -411,6 +434,26 @@ class Context:
         r = np.empty(shape, dtype=np.uint32)
         check(self._lib.hg_get_rel_hist(self._h, _ptr(a), _ptr(r)))
         return a, r
+
+    def get_graded(self):
+        """-> (gsum int64, hits int64, dcg float64, wsum float64), [Q, nk] each (after graded())."""
+        shape = (self.Q or 0, getattr(self, "_graded_nk", 0))
+        gsum, hits = np.empty(shape, dtype=np.int64), np.empty(shape, dtype=np.int64)
+        dcg, wsum = np.empty(shape, dtype=np.float64), np.empty(shape, dtype=np.float64)
+        check(self._lib.hg_get_graded(self._h, _ptr(gsum), _ptr(hits), _ptr(dcg), _ptr(wsum)))
+        return gsum, hits, dcg, wsum
+
+    def get_grades(self):
+        """-> uint8 [Q, R]: the grade of every rank (after graded(..., keep_grades=True))."""
+        g = np.empty((self.Q or 0, self.R or 0), dtype=np.uint8)
+        check(self._lib.hg_get_grades(self._h, _ptr(g)))
+        return g
+
+    def get_grade_hist(self):
+        """-> uint32 [C+1, Q] of this shard (after grade_hist())."""
+        h = np.empty(((self.C or 0) + 1, self.Q or 0), dtype=np.uint32)
+        check(self._lib.hg_get_grade_hist(self._h, _ptr(h)))
+        return h
 
     # -- collectives (RCCL) -------------------------------------------------------
     def comm_init(self, unique_id, rank, world):

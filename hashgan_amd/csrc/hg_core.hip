@@ -24,7 +24,7 @@ int fail(int code, const char* fmt, ...) {
 const char* const kKernelNames[KI_COUNT] = {"k_hist", "k_hist_reduce", "k_plan", "k_seg_counts", "k_seg_layout", "k_guess",
                                             "k_select", "k_rank_hist", "k_order", "k_rank_fused", "k_match", "k_ap", "k_merge", "k_pack",
                                             "k_real_sample", "k_real_guess", "k_real_select", "k_radix_pass", "k_real_finish", "k_select_mx", "k_rank_cnt", "rccl_allgather", "step_gpu_span", "k_real_rescore",
-                                            "k_hist_rel", "k_hist_rel_reduce"};
+                                            "k_hist_rel", "k_hist_rel_reduce", "k_graded", "k_grade_hist", "k_grade_hist_reduce"};
 // Flatten NumPy's pairwise-summation tree for a chunk of n elements (n <= 8192):
 // numpy/_core/src/umath/loops_utils.h.src, pairwise_sum: n <= 128 is a leaf,
 // otherwise split at n/2 rounded down to a multiple of 8.
@@ -813,6 +813,7 @@ int hg_merge_topr(hg_ctx* c, const uint32_t* dev_idx_all, const uint8_t* dev_dis
                        (const u8*)dev_dist_all, c->out_idx.as<u32>(), c->out_dist.as<u8>(), n, G);
     c->t_end();
     HG_TRY(c->check_launch("k_min_topr"));
+    c->gr_done = c->gr_kept = false;                   // (the lists are no longer the ones hg_graded walked)
     return c->stage_end();
 }
 
@@ -891,6 +892,37 @@ int hg_get_rel_hist(hg_ctx* c, uint32_t* host_all, uint32_t* host_rel) {
     const size_t row = (size_t)c->rh_Q * 4, pitch = (size_t)c->rh_Qpad * 4;
     if (host_all) HG_HIP(hipMemcpy2DAsync(host_all, row, c->rh_all.p, pitch, row, (size_t)c->rh_NB, hipMemcpyDeviceToHost, c->stream));
     if (host_rel) HG_HIP(hipMemcpy2DAsync(host_rel, row, c->rh_rel.p, pitch, row, (size_t)c->rh_NB, hipMemcpyDeviceToHost, c->stream));
+    return c->sync();
+}
+
+int hg_get_graded(hg_ctx* c, int64_t* host_gsum, int64_t* host_hits, double* host_dcg, double* host_wsum) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_graded", "hg_graded"));
+    if (!c->gr_done || c->gr_q_gen != c->q_gen || c->gr_db_gen != c->db_gen)
+        return fail(HG_ERR_STATE, "hg_get_graded called before hg_graded (on the ranked lists and tables held now)");
+    const size_t plane = (size_t)c->gr_Q * c->gr_nk * 8;
+    const char* o = c->gr_out.as<char>();
+    void* dst[4] = {host_gsum, host_hits, host_dcg, host_wsum};
+    for (int i = 0; i < 4; ++i)
+        if (dst[i]) HG_HIP(hipMemcpyAsync(dst[i], o + i * plane, plane, hipMemcpyDeviceToHost, c->stream));
+    return c->sync();
+}
+
+int hg_get_grades(hg_ctx* c, uint8_t* host_grades) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_grades", "hg_graded"));
+    if (!c->gr_done || !c->gr_kept || c->gr_q_gen != c->q_gen || c->gr_db_gen != c->db_gen)
+        return fail(HG_ERR_STATE, "hg_get_grades: the last hg_graded on these lists did not keep the grade bytes (keep_grades = 0), or there was none");
+    if (!host_grades) return fail(HG_ERR_ARG, "hg_get_grades: null pointer");
+    HG_HIP(hipMemcpyAsync(host_grades, c->gr_grades.p, (size_t)c->gr_Q * c->gr_R, hipMemcpyDeviceToHost, c->stream));
+    return c->sync();
+}
+
+int hg_get_grade_hist(hg_ctx* c, uint32_t* host_hist) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_grade_hist", "hg_grade_hist"));
+    if (!c->gh_done || c->gh_q_gen != c->q_gen || c->gh_db_gen != c->db_gen)
+        return fail(HG_ERR_STATE, "hg_get_grade_hist called before hg_grade_hist (on the tables loaded now)");
+    if (!host_hist) return fail(HG_ERR_ARG, "hg_get_grade_hist: null pointer");
+    const size_t row = (size_t)c->gh_Q * 4, pitch = (size_t)c->gh_Qpad * 4;
+    HG_HIP(hipMemcpy2DAsync(host_hist, row, c->gh_tab.p, pitch, row, (size_t)c->gh_G, hipMemcpyDeviceToHost, c->stream));
     return c->sync();
 }
 

@@ -209,7 +209,8 @@ struct DevBuf {
 
 enum KernelId { KI_HIST = 0, KI_HIST_REDUCE, KI_PLAN, KI_SEG_COUNTS, KI_SEG_LAYOUT, KI_GUESS, KI_SELECT, KI_CAND_HIST,
                 KI_ORDER, KI_RANK_FUSED, KI_MATCH, KI_AP, KI_MERGE, KI_PACK, KI_REAL_SAMPLE, KI_REAL_GUESS, KI_REAL_SELECT,
-                KI_RADIX, KI_REAL_FINISH, KI_SELECT_MX, KI_RANK_LDS, KI_COMM, KI_STEP, KI_REAL_RESCORE, KI_HIST_REL, KI_HIST_REL_REDUCE, KI_COUNT };
+                KI_RADIX, KI_REAL_FINISH, KI_SELECT_MX, KI_RANK_LDS, KI_COMM, KI_STEP, KI_REAL_RESCORE, KI_HIST_REL, KI_HIST_REL_REDUCE,
+                KI_GRADED, KI_GRADE_HIST, KI_GRADE_HIST_REDUCE, KI_COUNT };
 enum Stage { ST_NONE = 0, ST_DB = 1, ST_Q = 2, ST_HIST = 4, ST_PLAN = 8, ST_SELECT = 16, ST_MATCH = 32, ST_AP = 64 };
 extern const char* const kKernelNames[KI_COUNT];
 
@@ -391,6 +392,15 @@ struct hg_ctx : StepBufs, StepState {
     unsigned long long rh_q_gen = 0, rh_db_gen = 0;
     i64 rh_Q = 0, rh_Qpad = 0, rh_NB = 0;
     int last_rel_hist = 0;     // stat "rel_hist_variant": 1 k_hist_rel (0: no pass yet)
+    // graded relevance (hg_graded.hpp).  gr_out holds hg_graded's four [Q][nk] tables of the ranked lists it found: any later ranking
+    // (set_R), a merge into the lists, a reload (generations) and hg_trim end that.  gh_tab is hg_grade_hist's table, kept like rh_all.
+    bool gr_done = false, gr_kept = false;     // gr_kept: gr_grades holds the grade bytes [Q][R] of that pass
+    unsigned long long gr_q_gen = 0, gr_db_gen = 0;
+    i64 gr_Q = 0, gr_R = 0;
+    int gr_nk = 0;
+    bool gh_done = false;
+    unsigned long long gh_q_gen = 0, gh_db_gen = 0;
+    i64 gh_Q = 0, gh_Qpad = 0, gh_G = 0;
     bool verdict_pending = false, verdict_known = false;
     int verdict_flag = 0;
     // pinned landing zone for a one-shot call's results: AP, hit counts and the lost-bet flag come back with the
@@ -465,6 +475,8 @@ struct hg_ctx : StepBufs, StepState {
     DevBuf dbx, qx;            // fp4 images of db / qc in MFMA fragment order for k_select_mx (dbx_valid, qx_valid)
     DevBuf dbx8;               // i8 image of the database codes in A-fragment order (k_hist_i8; dbx8_valid)
     DevBuf rh_part, rh_all, rh_rel;   // hg_rel_hist: per-segment counters [S][2 NB][Qpad], the tables all / rel [NB][Qpad] (rh_done)
+    DevBuf gr_tab, gr_out, gr_grades;   // hg_graded: [ks 64 x i64][gain C + 1][disc kmax], the tables gsum / hits / dcg / wsum [Q][nk] each, grade bytes [Q][R]
+    DevBuf gh_part, gh_tab;    // hg_grade_hist: per-segment counters [S][C + 1][Qpad], the table [C + 1][Qpad] (gh_done)
     DevBuf dbx3;               // fp4 image for k_select_mx3 (48-row supertiles, three rows per accumulator; dbx3_valid)
     DevBuf dbx4;               // fp4 image for k_select_mx4 (32-row supertiles, two rows per accumulator; codes of 65..128 bits; dbx4_valid)
     DevBuf dbfx;               // float features of the database in MFMA A-fragment order (k_real_select_mx; dbfx_valid)
@@ -491,7 +503,8 @@ struct hg_ctx : StepBufs, StepState {
         for (DevBuf* d : {&db, &dblab, &qc, &qlab, &dbf, &qf}) f(*d, BUF_TABLE);
         for (DevBuf* d : {&dbx, &qx, &dbx8, &dbx3, &dbx4, &dbfx, &dbfb, &xmax2, &shapes, &ap_recip}) f(*d, BUF_DERIVED);
         for (DevBuf* d : {&seglt, &segtie, &mbits2, &part, &obuf[0], &obuf[1], &beyond, &stage_in, &badcnt, &flist, &dbytes, &samp, &thr,
-                          &sortA, &sortB, &scores, &gtab, &sampx, &cntq, &krows, &thr2, &hist2, &comm_tmp, &gath_idx, &gath_dist, &rh_part, &rh_all, &rh_rel})
+                          &sortA, &sortB, &scores, &gtab, &sampx, &cntq, &krows, &thr2, &hist2, &comm_tmp, &gath_idx, &gath_dist, &rh_part, &rh_all, &rh_rel,
+                          &gr_tab, &gr_out, &gr_grades, &gh_part, &gh_tab})
             f(*d, BUF_WORK);
         for (DevBuf& d : gathered) f(d, BUF_WORK);
         for (DevBuf& d : scratch) f(d, BUF_WORK);
@@ -502,6 +515,7 @@ struct hg_ctx : StepBufs, StepState {
     void forget_derived() {
         dbx_valid = qx_valid = dbx8_valid = dbx3_valid = dbx4_valid = dbfx_valid = dbfb_valid = false;
         rh_done = false;               // (hg_trim releases the tables with the other work buffers)
+        gr_done = gr_kept = gh_done = false;
         shapes_for_R = recip_for_R = -1;
         outblk_q = ws_b.outblk_q = -1;
     }

@@ -7,6 +7,7 @@
 #include "hg_select_mx4.hpp"
 #include "hg_hist_mx.hpp"
 #include "hg_hist_rel.hpp"
+#include "hg_graded.hpp"
 #include "hg_rank_cnt.hpp"
 #include "hg_rank_lean.hpp"
 #include "hg_rank_dense.hpp"
@@ -232,6 +233,110 @@ int hg_rel_hist(hg_ctx* c) {
     return c->stage_end();
 }
 
+// Graded relevance along the ranked lists (hg_graded.hpp): per query and cut-off k of `host_ks`, the sum of the grades, the ranks with a
+// grade, the discounted gain and the sum WAP averages, from the idx lists the last ranking left in out_idx -- hg_topr, a staged
+// select with lists, hg_topr_real.  Reads the lists and the label tables, writes buffers of its own: stage, geometry and match bits
+// stay the ranking's.  The host tables are copied before the call returns (it synchronises whatever "stage_sync" says).
+int hg_graded(hg_ctx* c, const int64_t* host_ks, int nk, const double* host_gain, const double* host_disc, int keep_grades) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_graded", "hg_set_database + hg_set_queries"));
+    c->gr_done = c->gr_kept = false;
+    if (c->idx_base != 0 || c->N != c->n_total)
+        return fail(HG_ERR_STATE, "hg_graded: the context holds rows [%lld, %lld) of %lld: graded sums need the whole database in one context (lists of a shard are partial)",
+                    (long long)c->idx_base, (long long)(c->idx_base + c->N), (long long)c->n_total);
+    if (!(c->stage & ST_SELECT) || !(c->lists_valid || c->real_lists))
+        return fail(HG_ERR_STATE, "hg_graded: no ranked lists on the device (hg_map and hg_map_real write none): call hg_topr / hg_topr_real first");
+    if (c->C > GR_MAX_C) return fail(HG_ERR_ARG, "hg_graded: C=%d classes (a grade is a byte: at most %d)", c->C, GR_MAX_C);
+    if (!host_ks || !host_gain || !host_disc) return fail(HG_ERR_ARG, "hg_graded: null pointer");
+    if (nk < 1 || nk > GR_MAX_K) return fail(HG_ERR_ARG, "hg_graded: %d cut-offs (1..%d)", nk, GR_MAX_K);
+    const i64 Q = c->geo.Q, R = c->geo.R;
+    for (int j = 0; j < nk; ++j)
+        if (host_ks[j] < 1 || host_ks[j] > R || (j > 0 && host_ks[j] <= host_ks[j - 1]))
+            return fail(HG_ERR_ARG, "hg_graded: ks must be strictly ascending within 1..R (R=%lld; ks[%d]=%lld)", (long long)R, j, (long long)host_ks[j]);
+    const i64 kmax = host_ks[nk - 1];
+    const size_t o_gain = GR_MAX_K * 8, o_disc = o_gain + (size_t)(c->C + 1) * 8, tab = o_disc + (size_t)kmax * 8;
+    const size_t plane = (size_t)Q * nk * 8;
+    const unsigned long long e0 = g_alloc_epoch.load();
+    HG_TRY(c->gr_tab.reserve(tab));
+    HG_TRY(c->gr_out.reserve(4 * plane));
+    if (keep_grades) HG_TRY(c->gr_grades.reserve((size_t)Q * R));
+    // (first reservations move no buffer hg_map_begin's licence to enqueue blind was given for)
+    if (c->map_warm_epoch == e0) c->map_warm_epoch = g_alloc_epoch;
+    char* t = c->gr_tab.as<char>();
+    HG_HIP(hipMemcpyAsync(t, host_ks, (size_t)nk * 8, hipMemcpyHostToDevice, c->stream));
+    HG_HIP(hipMemcpyAsync(t + o_gain, host_gain, (size_t)(c->C + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HG_HIP(hipMemcpyAsync(t + o_disc, host_disc, (size_t)kmax * 8, hipMemcpyHostToDevice, c->stream));
+    char* o = c->gr_out.as<char>();
+    GradedArgs a;
+    a.idx = c->out_idx.as<u32>(); a.dblab = c->dblab.as<u64>(); a.qlab = c->qlab.as<u64>();
+    a.ks = (const i64*)t; a.gain = (const double*)(t + o_gain); a.disc = (const double*)(t + o_disc);
+    a.gsum = (i64*)o; a.hits = (i64*)(o + plane); a.dcg = (double*)(o + 2 * plane); a.wsum = (double*)(o + 3 * plane);
+    a.grades = keep_grades ? c->gr_grades.as<u8>() : nullptr;
+    a.R = R; a.N = c->N; a.nk = nk; a.LW = c->LW;
+    a.lastmask = c->C % 64 ? (1ull << (c->C % 64)) - 1ull : ~0ull;
+    c->t_begin(KI_GRADED);
+    hipLaunchKernelGGL(k_graded, dim3((unsigned)Q), dim3(GR_THREADS), 0, c->stream, a);
+    c->t_end();
+    HG_TRY(c->check_launch("k_graded"));
+    HG_TRY(c->sync());                                 // (the host tables are the caller's)
+    c->gr_done = true; c->gr_kept = keep_grades != 0;
+    c->gr_q_gen = c->q_gen; c->gr_db_gen = c->db_gen;
+    c->gr_Q = Q; c->gr_R = R; c->gr_nk = nk;
+    return HG_OK;
+}
+
+// The grade histogram of this shard (hg_graded.hpp): rows per (grade, query) in one pass over the label pairs.  Like hg_rel_hist: the
+// full pass's geometry on a copy, buffers of its own, the step state left as it was.
+extern "C++" {
+template <int LWT> static int launch_grade_hist_t(hg_ctx* c, Geo g, int G, u64 lastmask) {
+    // LDS: wpb * G * 64 * 4 bytes (C = 255: two wavefronts, 128 KiB)
+    int wpb = WPB;
+    while (wpb > 1 && (size_t)wpb * G * 256 > 160u * 1024u) wpb >>= 1;
+    g.wpb = wpb;
+    g.nBlk = (int)((g.nUnits + wpb - 1) / wpb);
+    const size_t lds = (size_t)wpb * G * 256;
+    static std::atomic<unsigned long long> lds_allowed{0};
+    if (lds > 64 * 1024 && !(lds_allowed.load() >> (c->device & 63) & 1ull)) {
+        HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grade_hist<LWT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        lds_allowed.fetch_or(1ull << (c->device & 63));
+    }
+    c->t_begin(KI_GRADE_HIST);
+    hipLaunchKernelGGL((k_grade_hist<LWT>), dim3(padded_grid(g.nBlk)), dim3(64 * wpb), lds, c->stream, c->qlab.as<u64>(),
+                       c->dblab.as<u64>(), c->gh_part.as<u32>(), g, G, lastmask);
+    c->t_end();
+    return c->check_launch("k_grade_hist");
+}
+}  // extern "C++"
+
+int hg_grade_hist(hg_ctx* c) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_grade_hist", "hg_set_database + hg_set_queries"));
+    if (c->C > GR_MAX_C) return fail(HG_ERR_ARG, "hg_grade_hist: C=%d classes (a grade is a byte: at most %d)", c->C, GR_MAX_C);
+    const Geo kept = c->geo;
+    make_geometry(c);
+    const Geo g = c->geo;
+    c->geo = kept;
+    c->gh_done = false;
+    const int G = c->C + 1;
+    const unsigned long long e0 = g_alloc_epoch.load();
+    const i64 plane = (i64)G * g.Qpad;
+    HG_TRY(c->gh_part.reserve((size_t)plane * 4 * g.S));
+    HG_TRY(c->gh_tab.reserve((size_t)plane * 4));
+    if (c->map_warm_epoch == e0) c->map_warm_epoch = g_alloc_epoch;
+    const u64 lastmask = c->C % 64 ? (1ull << (c->C % 64)) - 1ull : ~0ull;
+    switch (c->LW) {
+        case 1: HG_TRY(launch_grade_hist_t<1>(c, g, G, lastmask)); break;
+        case 2: HG_TRY(launch_grade_hist_t<2>(c, g, G, lastmask)); break;
+        default: HG_TRY(launch_grade_hist_t<0>(c, g, G, lastmask)); break;
+    }
+    c->t_begin(KI_GRADE_HIST_REDUCE);
+    hipLaunchKernelGGL(k_grade_hist_reduce, dim3(grid_for(plane)), dim3(256), 0, c->stream, c->gh_part.as<u32>(), c->gh_tab.as<u32>(), plane, g.S);
+    c->t_end();
+    HG_TRY(c->check_launch("k_grade_hist_reduce"));
+    c->gh_done = true;
+    c->gh_q_gen = c->q_gen; c->gh_db_gen = c->db_gen;
+    c->gh_Q = g.Q; c->gh_Qpad = g.Qpad; c->gh_G = G;
+    return c->stage_end();
+}
+
 int hg_hist_buffer(hg_ctx* c, void** dev_ptr, int64_t* nbytes) {
     HG_TRY(need(c, ST_DB | ST_Q, "hg_hist_buffer", "hg_hist / hg_sample_hist / hg_select_candidates"));
     if (!c->hown.p) return fail(HG_ERR_STATE, "hg_hist_buffer: no histogram computed yet");
@@ -245,6 +350,7 @@ extern "C++" int set_R(hg_ctx* c, int64_t R, int G, int rank) {
     if (R < 1 || R > c->n_total)
         return fail(HG_ERR_ARG, "R=%lld outside 1..N (N=%lld rows in the database)", (long long)R, (long long)c->n_total);
     c->R = R; c->G = G; c->rank = rank;
+    c->gr_done = c->gr_kept = false;                   // every ranking comes through here: hg_graded's tables were the previous lists'
     c->geo.R = R;
     c->RW = (R + 63) / 64;
     return HG_OK;

@@ -7,6 +7,11 @@ host only reduces small per-query vectors.
 Everything a Hamming-ball lookup is judged by -- ball sizes, hits inside the ball, the recall denominator, for every radius at
 once -- comes from one table: per query and distance d, the rows at distance d and how many of them share a label with the
 query (Context.rel_hist, one pass over the pairs; no ranking, no lists, nothing of size Q x N on the host).
+
+Graded relevance for multi-label data (NUS-WIDE, COCO): the grade of a retrieved row is the number of labels it shares with the
+query, and ACG@k, NDCG@k and WAP@k are read from four [Q, len(ks)] tables the GPU sums along the ranked lists (Context.graded) and
+the grade histogram of the whole database (Context.grade_hist), which stands for the ideal ordering: graded_relevance_at_k for
+binary codes and for real-valued features, graded_from_tables for the reduction alone, grade_histograms for the table.
 """
 import numpy as np
 
@@ -63,6 +68,146 @@ def hamming_radius_curves(q_codes, db_codes, q_labels, db_labels, device=0):
     """The lookup P-R curve: (recall[r], precision[r]) for r = 0..b, with the per-query ball, hit and total_rel tables
     (curves_from_histograms of lookup_histograms)."""
     return curves_from_histograms(*lookup_histograms(q_codes, db_codes, q_labels, db_labels, device))
+
+
+MAX_CLASSES = 255      # a grade is a byte on the GPU
+MAX_CUTOFFS = 64
+
+
+def _check_ks(ks, N):
+    """-> int64 array; strictly ascending values in 1..N, at most MAX_CUTOFFS of them."""
+    ks = np.asarray(ks)
+    if ks.ndim != 1 or ks.size == 0:
+        raise ValueError("ks must be a non-empty list of cut-offs")
+    if ks.dtype.kind not in "iu":
+        raise ValueError("ks must be integers")
+    ks = ks.astype(np.int64)
+    if ks.size > MAX_CUTOFFS:
+        raise ValueError("at most %d cut-offs per call (have %d)" % (MAX_CUTOFFS, ks.size))
+    if (np.diff(ks) <= 0).any():
+        raise ValueError("ks must be strictly ascending")
+    if ks[0] < 1 or (N is not None and ks[-1] > N):
+        raise ValueError("every k must be in 1..N")
+    return ks
+
+
+def gain_table(gain, C):
+    """float64 [C + 1]: "exp" -> 2^g - 1, "linear" -> g, or the given C + 1 values; must be non-decreasing in g."""
+    if C > MAX_CLASSES:
+        raise ValueError("graded relevance takes up to %d classes (have %d)" % (MAX_CLASSES, C))
+    if isinstance(gain, str):
+        g = np.arange(C + 1, dtype=np.float64)
+        if gain == "exp":
+            tab = np.exp2(g) - 1.0
+        elif gain == "linear":
+            tab = g
+        else:
+            raise ValueError('gain must be "exp", "linear" or an array of C + 1 values')
+    else:
+        tab = np.array(gain, dtype=np.float64)
+        if tab.shape != (C + 1,):
+            raise ValueError("gain must have C + 1 = %d values" % (C + 1))
+    if not np.isfinite(tab).all() or (np.diff(tab) < 0).any():
+        raise ValueError("gain must be finite and non-decreasing in the grade")
+    return tab
+
+
+def discount_table(kmax):
+    """float64 [kmax]: 1 / log2(1 + i) for the ranks i = 1..kmax."""
+    return 1.0 / np.log2(np.arange(2, int(kmax) + 2, dtype=np.float64))
+
+
+def graded_from_tables(gsum, hits, dcg, wsum, grade_hist, ks, gain, disc):
+    """ACG@k, NDCG@k and WAP@k from the device tables (NumPy only).  gsum, hits, dcg, wsum: [Q, len(ks)] (Context.get_graded);
+    grade_hist: [Q, C + 1] rows of the whole database per grade; gain [C + 1], disc [>= max(ks)] the tables the GPU was given.
+    IDCG@k is the DCG of the database sorted by grade descending: walking the grades from C down, grade g occupies the next
+    grade_hist[q, g] positions and contributes gain[g] times the discounts of those of them that lie within k -- O(Q C) per k.
+    NDCG = DCG / IDCG (NaN where IDCG is 0), WAP = wsum / hits (NaN where hits is 0); means: ACG over all queries, NDCG over
+    those with IDCG > 0, WAP over those with a hit within k, NaN when none is left.
+    -> dict(acg, ndcg, wap [len(ks)], per_query=dict(acg, dcg, idcg, ndcg, wap, hits [Q, len(ks)], total_rel [Q]))"""
+    grade_hist = np.asarray(grade_hist, dtype=np.int64)
+    if grade_hist.ndim != 2:
+        raise ValueError("grade_hist must be a [Q, C + 1] table")
+    Q, G = grade_hist.shape
+    gain = gain_table(gain, G - 1)
+    ks = _check_ks(ks, None)
+    disc = np.asarray(disc, dtype=np.float64)
+    if disc.ndim != 1 or disc.size < ks[-1]:
+        raise ValueError("disc must hold a discount for every rank up to max(ks)")
+    gsum, hits = np.asarray(gsum, dtype=np.int64), np.asarray(hits, dtype=np.int64)
+    dcg, wsum = np.asarray(dcg, dtype=np.float64), np.asarray(wsum, dtype=np.float64)
+    for a in (gsum, hits, dcg, wsum):
+        if a.shape != (Q, ks.size):
+            raise ValueError("gsum, hits, dcg and wsum must be [Q, len(ks)] tables")
+    cum = np.concatenate([[0.0], np.cumsum(disc[:ks[-1]])])             # cum[n] = discounts of the ranks 1..n
+    above = np.zeros(Q, dtype=np.int64)                                  # rows with a higher grade than the one being placed
+    idcg = np.zeros((Q, ks.size), dtype=np.float64)
+    for g in range(G - 1, -1, -1):
+        start = np.minimum(above[:, None], ks[None, :])
+        above = above + grade_hist[:, g]
+        end = np.minimum(above[:, None], ks[None, :])
+        idcg += gain[g] * (cum[end] - cum[start])
+    has = idcg > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ndcg = np.where(has, dcg / idcg, np.nan)
+        wap = np.where(hits > 0, wsum / hits, np.nan)
+    acg = gsum / ks[None, :]
+
+    def mean_where(x, ok):
+        return np.array([x[ok[:, j], j].mean() if ok[:, j].any() else np.nan for j in range(ks.size)])
+
+    return {"acg": acg.mean(0) if Q else np.full(ks.size, np.nan), "ndcg": mean_where(ndcg, has), "wap": mean_where(wap, hits > 0),
+            "per_query": {"acg": acg, "dcg": dcg, "idcg": idcg, "ndcg": ndcg, "wap": wap, "hits": hits,
+                          "total_rel": grade_hist[:, 1:].sum(1)}}
+
+
+def _check_graded_inputs(q, db, q_labels, db_labels):
+    q, db, q_labels, db_labels = np.asarray(q), np.asarray(db), np.asarray(q_labels), np.asarray(db_labels)
+    metric._check_shapes(q, db, q_labels, db_labels, 1)
+    if db_labels.shape[1] > MAX_CLASSES:
+        raise ValueError("graded relevance takes up to %d classes (have %d)" % (MAX_CLASSES, db_labels.shape[1]))
+    return q, db, q_labels, db_labels
+
+
+def grade_histograms(q_codes, db_codes, q_labels, db_labels, device=0):
+    """Per query and grade g = 0..C: the database rows that share exactly g labels with the query.  -> int64 [Q, C + 1]"""
+    q_codes, db_codes, q_labels, db_labels = _check_graded_inputs(q_codes, db_codes, q_labels, db_labels)
+    eng = metric._Shared.get(device)
+    with eng.lock:
+        ctx = _load(eng, q_codes, db_codes, q_labels, db_labels)
+        ctx.grade_hist()
+        return ctx.get_grade_hist().T.astype(np.int64)
+
+
+def graded_relevance_at_k(q, db, q_labels, db_labels, ks, gain="exp", features=False, device=0):
+    """ACG@k, NDCG@k and WAP@k with grade = number of labels a retrieved row shares with the query, at the strictly ascending
+    cut-offs ks (at most 64, each in 1..N).  gain: "exp" (2^g - 1), "linear" (g) or C + 1 non-decreasing values; the discount is
+    1 / log2(1 + rank).  features=False: q and db are binary codes ({0,1} or +-1), ranked by Hamming distance, ties by index;
+    features=True: real-valued features (up to 255), ranked by float32 inner product descending, ties by index, as
+    MAPs.get_maps_by_feature ranks them.  The ranking, the sums along the lists and the grade histogram run on the GPU; nothing of
+    size Q x k or Q x N comes to the host.  -> graded_from_tables' dict"""
+    q, db, q_labels, db_labels = _check_graded_inputs(q, db, q_labels, db_labels)
+    ks = _check_ks(ks, db.shape[0])
+    tab = gain_table(gain, db_labels.shape[1])
+    if features and db.shape[1] > 255:
+        raise ValueError("inner-product ranking supports up to 255 features (have %d)" % db.shape[1])
+    disc = discount_table(ks[-1])
+    eng = metric._Shared.get(device)
+    with eng.lock:
+        if features:
+            metric._load_database(eng, db, db_labels, "reference", floats=1)
+            if eng.ctx.set_queries_f32(q, q_labels)[1]:
+                raise ValueError("labels must be {0,1} indicator matrices")
+            ctx = eng.ctx
+            ctx.topr_real(int(ks[-1]), download=False)
+        else:
+            ctx = _load(eng, q, db, q_labels, db_labels)
+            ctx.topr(int(ks[-1]))
+        ctx.graded(ks, tab, disc)
+        gsum, hits, dcg, wsum = ctx.get_graded()
+        ctx.grade_hist()
+        hist = ctx.get_grade_hist().T
+    return graded_from_tables(gsum, hits, dcg, wsum, hist, ks, tab, disc)
 
 
 def precision_recall_at_k(q_codes, db_codes, q_labels, db_labels, ks, device=0):

@@ -113,6 +113,12 @@ int hg_hist_buffer(hg_ctx* ctx, void** dev_ptr, int64_t* nbytes);
  * the query (rel) -- no ranking, no lists.  Tables of its own: the staged pipeline's state (hg_hist's histogram, a plan, a step
  * of hg_map_begin in flight) is left as it was.  Additive over shards; a database or query reload invalidates the tables. */
 int hg_rel_hist(hg_ctx* ctx);                                            /* needs database + queries */
+/* The grade histogram of this shard, for graded relevance on multi-label data (grade = labels a row shares with the query): one pass
+ * over the query x database label pairs -- no codes, no ranking -- counts, per query and grade g = 0..C, the rows with that grade.
+ * The ideal ordering NDCG divides by is "the database sorted by grade", so IDCG at any k follows from this table.  C <= 255
+ * (HG_ERR_ARG beyond).  Same rules as hg_rel_hist: a table of its own, the staged pipeline's state and a step of hg_map_begin in
+ * flight are left as they were; additive over shards; a database or query reload invalidates it; hg_trim frees it. */
+int hg_grade_hist(hg_ctx* ctx);                                          /* needs database + queries */
 int hg_plan(hg_ctx* ctx, int64_t R, const uint32_t* dev_hist_all, int G, int rank);
 int hg_select(hg_ctx* ctx);
 int hg_match(hg_ctx* ctx);
@@ -231,6 +237,23 @@ int hg_get_match(hg_ctx* ctx, uint8_t* host_imatch);                    /* [Q][R
 int hg_get_ap(hg_ctx* ctx, double* host_ap, int64_t* host_rel);         /* [Q]; ap = NaN where rel == 0 */
 int hg_get_hist(hg_ctx* ctx, uint32_t* host_hist);                      /* [b+1][Q] of this shard */
 int hg_get_rel_hist(hg_ctx* ctx, uint32_t* host_all, uint32_t* host_rel); /* [b+1][Q] each, this shard (after hg_rel_hist) */
+int hg_get_grade_hist(hg_ctx* ctx, uint32_t* host_hist);                /* [C+1][Q] of this shard (after hg_grade_hist) */
+
+/* ---- graded relevance along the ranked lists (ACG, NDCG, WAP at k) -------------
+ * hg_graded walks the ranked index lists the last ranking left on the device -- hg_topr, a staged hg_select with lists, hg_topr_real;
+ * HG_ERR_STATE after anything that writes none (hg_map, hg_map_real): call hg_topr / hg_topr_real first -- and leaves, per query and
+ * cut-off k = ks[j], with g_i = popcount(query labels & labels of the row at rank i):
+ *   gsum = sum_{i<=k} g_i,  hits = #{i<=k : g_i > 0},  dcg = sum_{i<=k} gain[g_i] * disc[i-1],  wsum = sum_{i<=k, g_i>0} (sum_{m<=i} g_m) / i
+ * ks: nk (1..64) strictly ascending values in 1..R of the lists; gain: C + 1 doubles; disc: ks[nk-1] doubles (disc[i-1] belongs to rank i);
+ * C <= 255; anything else HG_ERR_ARG.  The host arrays are copied before the call returns.  Indices outside the table count as grade 0.
+ * The context must hold the whole database (idx_base 0, N = n_total; HG_ERR_STATE otherwise).  The summation order depends on ks
+ * alone (chunks of 256 ranks cut at every k, fixed trees inside), so equal inputs give equal bits; float64 throughout, no atomics.
+ * keep_grades != 0 also keeps the grade bytes of every rank for hg_get_grades.  The results belong to the lists they were computed on:
+ * any later ranking, hg_merge_topr, a database or query reload and hg_trim invalidate them (the getters then return HG_ERR_STATE, as
+ * they do before the first pass).  The ranking's own state -- stage, match bits, APs -- is untouched. */
+int hg_graded(hg_ctx* ctx, const int64_t* host_ks, int nk, const double* host_gain, const double* host_disc, int keep_grades);
+int hg_get_graded(hg_ctx* ctx, int64_t* host_gsum, int64_t* host_hits, double* host_dcg, double* host_wsum);   /* [Q][nk] each; null: skipped */
+int hg_get_grades(hg_ctx* ctx, uint8_t* host_grades);                   /* [Q][R]; HG_ERR_STATE unless the last hg_graded kept them */
 
 /* ---- collectives: RCCL over xGMI, one process per GPU (the reference has no counterpart --
  * main.py:260-263 only sets CUDA_VISIBLE_DEVICES) --------------------------------------------------------
