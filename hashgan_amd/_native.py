@@ -40,6 +40,7 @@ _SIGNATURES = {
     "hg_rel_hist": [_p],
     "hg_grade_hist": [_p],
     "hg_graded": [_p, _p, C.c_int, _p, _p, C.c_int],
+    "hg_tie_ap": [_p, _p, C.c_int],
     "hg_plan": [_p, _i64, _p, C.c_int, C.c_int],
     "hg_select": [_p],
     "hg_bet_eligible": [_p, _i64, C.c_int, C.POINTER(C.c_int)],
@@ -78,6 +79,7 @@ _SIGNATURES = {
     "hg_get_grade_hist": [_p, _p],
     "hg_get_graded": [_p, _p, _p, _p, _p],
     "hg_get_grades": [_p, _p],
+    "hg_get_tie_ap": [_p, _p, _p, _p, _p, _p, _p, _p],
     "hg_comm_unique_id": [_p],
     "hg_comm_init": [_p, _p, C.c_int, C.c_int],
     "hg_comm_destroy": [_p],
@@ -247,6 +249,13 @@ class Context:
             raise ValueError("gain must have C + 1 entries and disc max(ks)")
         check(self._lib.hg_graded(self._h, _ptr(ks), len(ks), _ptr(gain), _ptr(disc), 1 if keep_grades else 0))
         self._graded_nk = len(ks)
+
+    def tie_ap(self, Rs):
+        """Tie-aware AP at the strictly ascending cut-offs Rs (1..N, at most 64) from the relevant-row histogram, which is
+        computed first unless the tables of the loaded queries and database are there.  Results: get_tie_ap()."""
+        Rs = _carray(Rs, np.int64).ravel()
+        check(self._lib.hg_tie_ap(self._h, _ptr(Rs), len(Rs)))
+        self._tie_nR = len(Rs)
 
     def hist_buffer(self):
         p, n = _p(), _i64()
@@ -442,6 +451,14 @@ class Context:
         dcg, wsum = np.empty(shape, dtype=np.float64), np.empty(shape, dtype=np.float64)
         check(self._lib.hg_get_graded(self._h, _ptr(gsum), _ptr(hits), _ptr(dcg), _ptr(wsum)))
         return gsum, hits, dcg, wsum
+
+    def get_tie_ap(self):
+        """-> dict(ap, p_hit, ap_min, ap_max, rel_exp float64, rel_lo, rel_hi int64), [Q, nR] each (after tie_ap())."""
+        shape = (self.Q or 0, getattr(self, "_tie_nR", 0))
+        f = [np.empty(shape, dtype=np.float64) for _ in range(5)]
+        i = [np.empty(shape, dtype=np.int64) for _ in range(2)]
+        check(self._lib.hg_get_tie_ap(self._h, *[_ptr(x) for x in f + i]))
+        return dict(zip(("ap", "p_hit", "ap_min", "ap_max", "rel_exp", "rel_lo", "rel_hi"), f + i))
 
     def get_grades(self):
         """-> uint8 [Q, R]: the grade of every rank (after graded(..., keep_grades=True))."""

@@ -24,7 +24,7 @@ int fail(int code, const char* fmt, ...) {
 const char* const kKernelNames[KI_COUNT] = {"k_hist", "k_hist_reduce", "k_plan", "k_seg_counts", "k_seg_layout", "k_guess",
                                             "k_select", "k_rank_hist", "k_order", "k_rank_fused", "k_match", "k_ap", "k_merge", "k_pack",
                                             "k_real_sample", "k_real_guess", "k_real_select", "k_radix_pass", "k_real_finish", "k_select_mx", "k_rank_cnt", "rccl_allgather", "step_gpu_span", "k_real_rescore",
-                                            "k_hist_rel", "k_hist_rel_reduce", "k_graded", "k_grade_hist", "k_grade_hist_reduce"};
+                                            "k_hist_rel", "k_hist_rel_reduce", "k_graded", "k_grade_hist", "k_grade_hist_reduce", "k_tie_ap"};
 // Flatten NumPy's pairwise-summation tree for a chunk of n elements (n <= 8192):
 // numpy/_core/src/umath/loops_utils.h.src, pairwise_sum: n <= 128 is a leaf,
 // otherwise split at n/2 rounded down to a multiple of 8.
@@ -926,6 +926,18 @@ int hg_get_grade_hist(hg_ctx* c, uint32_t* host_hist) {
     return c->sync();
 }
 
+int hg_get_tie_ap(hg_ctx* c, double* host_ap_exp, double* host_p_hit, double* host_ap_min, double* host_ap_max, double* host_rel_exp,
+                  int64_t* host_rel_lo, int64_t* host_rel_hi) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_tie_ap", "hg_tie_ap"));
+    if (!c->ta_done || c->ta_q_gen != c->q_gen || c->ta_db_gen != c->db_gen)
+        return fail(HG_ERR_STATE, "hg_get_tie_ap called before hg_tie_ap (on the tables loaded now)");
+    const size_t plane = (size_t)c->ta_Q * c->ta_nR * 8;
+    const char* o = c->ta_out.as<char>();
+    void* dst[7] = {host_ap_exp, host_p_hit, host_ap_min, host_ap_max, host_rel_exp, host_rel_lo, host_rel_hi};
+    for (int i = 0; i < 7; ++i)
+        if (dst[i]) HG_HIP(hipMemcpyAsync(dst[i], o + i * plane, plane, hipMemcpyDeviceToHost, c->stream));
+    return c->sync();
+}
 
 // Context-owned device scratch (grows only) and a stream-ordered device-to-device copy: what an in-process
 // communicator (virtual shards of one GPU in the tests) needs to do hg_allgather's job without RCCL.

@@ -8,6 +8,7 @@
 #include "hg_hist_mx.hpp"
 #include "hg_hist_rel.hpp"
 #include "hg_graded.hpp"
+#include "hg_tie_ap.hpp"
 #include "hg_rank_cnt.hpp"
 #include "hg_rank_lean.hpp"
 #include "hg_rank_dense.hpp"
@@ -335,6 +336,48 @@ int hg_grade_hist(hg_ctx* c) {
     c->gh_q_gen = c->q_gen; c->gh_db_gen = c->db_gen;
     c->gh_Q = g.Q; c->gh_Qpad = g.Qpad; c->gh_G = G;
     return c->stage_end();
+}
+
+// Tie-aware AP at the cut-offs `host_Rs` (hg_tie_ap.hpp): expectation, hit probability, minimum and maximum of AP@R over the orders
+// inside the tie groups, from hg_rel_hist's two tables alone.  Runs that pass when the tables of the current generations are not
+// there and reuses them otherwise.  Like hg_graded: buffers of its own, the step state left as it was, the host array copied
+// before the call returns (it synchronises whatever "stage_sync" says).
+int hg_tie_ap(hg_ctx* c, const int64_t* host_Rs, int nR) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_tie_ap", "hg_set_database + hg_set_queries"));
+    c->ta_done = false;
+    if (c->idx_base != 0 || c->N != c->n_total)
+        return fail(HG_ERR_STATE, "hg_tie_ap: the context holds rows [%lld, %lld) of %lld: the cut at R needs the tables of the whole database in one context",
+                    (long long)c->idx_base, (long long)(c->idx_base + c->N), (long long)c->n_total);
+    if (!host_Rs) return fail(HG_ERR_ARG, "hg_tie_ap: null pointer");
+    if (nR < 1 || nR > TA_MAX_R) return fail(HG_ERR_ARG, "hg_tie_ap: %d cut-offs (1..%d)", nR, TA_MAX_R);
+    for (int j = 0; j < nR; ++j)
+        if (host_Rs[j] < 1 || host_Rs[j] > c->N || (j > 0 && host_Rs[j] <= host_Rs[j - 1]))
+            return fail(HG_ERR_ARG, "hg_tie_ap: Rs must be strictly ascending within 1..N (N=%lld; Rs[%d]=%lld)", (long long)c->N, j, (long long)host_Rs[j]);
+    if (c->NB > TA_THREADS) return fail(HG_ERR_ARG, "hg_tie_ap: b=%d bits (at most %d)", c->b, TA_THREADS - 1);
+    if (!c->rh_done || c->rh_q_gen != c->q_gen || c->rh_db_gen != c->db_gen) HG_TRY(hg_rel_hist(c));
+    const i64 Q = c->rh_Q;
+    const size_t plane = (size_t)Q * nR * 8;
+    const unsigned long long e0 = g_alloc_epoch.load();
+    HG_TRY(c->ta_tab.reserve(TA_MAX_R * 8));
+    HG_TRY(c->ta_out.reserve(7 * plane));
+    // (first reservations move no buffer hg_map_begin's licence to enqueue blind was given for)
+    if (c->map_warm_epoch == e0) c->map_warm_epoch = g_alloc_epoch;
+    HG_HIP(hipMemcpyAsync(c->ta_tab.p, host_Rs, (size_t)nR * 8, hipMemcpyHostToDevice, c->stream));
+    char* o = c->ta_out.as<char>();
+    TieApArgs a;
+    a.all = c->rh_all.as<u32>(); a.rel = c->rh_rel.as<u32>(); a.Rs = c->ta_tab.as<i64>();
+    a.ap_exp = (double*)o; a.p_hit = (double*)(o + plane); a.ap_min = (double*)(o + 2 * plane); a.ap_max = (double*)(o + 3 * plane);
+    a.rel_exp = (double*)(o + 4 * plane); a.rel_lo = (i64*)(o + 5 * plane); a.rel_hi = (i64*)(o + 6 * plane);
+    a.Qpad = c->rh_Qpad; a.NB = (int)c->rh_NB; a.nR = nR;
+    c->t_begin(KI_TIE_AP);
+    hipLaunchKernelGGL(k_tie_ap, dim3((unsigned)Q, (unsigned)nR), dim3(TA_THREADS), 0, c->stream, a);
+    c->t_end();
+    HG_TRY(c->check_launch("k_tie_ap"));
+    HG_TRY(c->sync());                                 // (the host array is the caller's)
+    c->ta_done = true;
+    c->ta_q_gen = c->q_gen; c->ta_db_gen = c->db_gen;
+    c->ta_Q = Q; c->ta_nR = nR;
+    return HG_OK;
 }
 
 int hg_hist_buffer(hg_ctx* c, void** dev_ptr, int64_t* nbytes) {

@@ -12,6 +12,12 @@ Graded relevance for multi-label data (NUS-WIDE, COCO): the grade of a retrieved
 query, and ACG@k, NDCG@k and WAP@k are read from four [Q, len(ks)] tables the GPU sums along the ranked lists (Context.graded) and
 the grade histogram of the whole database (Context.grade_hist), which stands for the ideal ordering: graded_relevance_at_k for
 binary codes and for real-valued features, graded_from_tables for the reduction alone, grade_histograms for the table.
+
+Tie-aware mAP (He, Cakir, Bargal, Sclaroff, "Hashing as Tie-Aware Learning to Rank", CVPR 2018): a b-bit code has b + 1 distances,
+so AP@R depends on how the rows happen to be ordered inside each tie group.  tie_aware_map gives the expectation of the reference's
+AP@R over all those orders, the probability that the top R hold a hit, and the exact minimum and maximum, per query -- a function
+of the relevant-row histogram and R alone (Context.tie_ap), no ranking and no lists; tie_aware_precision_recall_at_k the expected
+precision and recall at k from the same call.  Shuffling the database rows leaves every one of these bits unchanged.
 """
 import numpy as np
 
@@ -208,6 +214,58 @@ def graded_relevance_at_k(q, db, q_labels, db_labels, ks, gain="exp", features=F
         ctx.grade_hist()
         hist = ctx.get_grade_hist().T
     return graded_from_tables(gsum, hits, dcg, wsum, hist, ks, tab, disc)
+
+
+def _tie_tables(q_codes, db_codes, q_labels, db_labels, Rs, device):
+    """-> (Rs int64, Context.get_tie_ap()'s dict, total_rel int64 [Q]); argument errors before any GPU use."""
+    q_codes, db_codes, q_labels, db_labels = np.asarray(q_codes), np.asarray(db_codes), np.asarray(q_labels), np.asarray(db_labels)
+    metric._check_shapes(q_codes, db_codes, q_labels, db_labels, 1)
+    Rs = _check_ks(Rs, db_codes.shape[0])
+    eng = metric._Shared.get(device)
+    with eng.lock:
+        ctx = _load(eng, q_codes, db_codes, q_labels, db_labels)
+        ctx.tie_ap(Rs)                                                   # (runs the histogram pass: the tables are new)
+        t = ctx.get_tie_ap()
+        total_rel = ctx.get_rel_hist()[1].astype(np.int64).sum(0)
+    return Rs, t, total_rel
+
+
+def tie_aware_map(q_codes, db_codes, q_labels, db_labels, Rs, device=0):
+    """Tie-aware mAP@R of a Hamming ranking at the strictly ascending cut-offs Rs (at most 64, each in 1..N), binary codes
+    ({0,1} or +-1).  Per query and R, over uniformly random orders inside every group of rows at equal distance:
+      ap       the expectation of the reference's AP@R given that the top R hold a relevant row (NaN when they never do),
+      p_hit    the probability that they do (the reference skips a query whose top R hold none),
+      ap_min, ap_max   the exact extremes of AP@R over all those orders (NaN when no order has a hit),
+      rel_exp, rel_lo, rel_hi   expectation and extremes of the number of relevant rows among the top R,
+      total_rel   relevant rows in the whole database.
+    The per-query values are exact (float64 rounding aside).  map[j] = sum_q p_hit * ap / sum_q p_hit (NaN when the denominator is
+    0): the reference's mAP is the mean of AP over the queries that have a hit, so whenever every p_hit is 0 or 1 -- the set of
+    averaged queries does not depend on the order -- map[j] IS the expectation of the reference's mAP@R over the tie orders; with a
+    p_hit strictly between 0 and 1 the number of averaged queries is itself random and map[j] is the ratio of the expectations
+    of the reference's numerator and denominator, not the expectation of their ratio.
+    -> dict(map [nR], per_query=dict(ap, p_hit, ap_min, ap_max, rel_exp, rel_lo, rel_hi [Q, nR], total_rel [Q]))"""
+    Rs, t, total_rel = _tie_tables(q_codes, db_codes, q_labels, db_labels, Rs, device)
+    w = t["p_hit"]
+    den = w.sum(0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        m = np.where(den > 0, np.where(w > 0, w * t["ap"], 0.0).sum(0) / den, np.nan)
+    pq = dict(t)
+    pq["total_rel"] = total_rel
+    return {"map": m, "per_query": pq}
+
+
+def tie_aware_precision_recall_at_k(q_codes, db_codes, q_labels, db_labels, ks, device=0):
+    """Expected precision@k and recall@k over the tie orders of a Hamming ranking: per query rel_exp / k and rel_exp / total_rel
+    with rel_exp the expected number of relevant rows among the top k, averaged like precision_recall_at_k does -- precision over
+    all queries, recall over the queries that have relevant rows in the whole database (NaN if none has).  ks: strictly ascending,
+    at most 64, each in 1..N.  The same device call as tie_aware_map: no ranking, no lists.
+    -> (precision [len(ks)], recall [len(ks)])"""
+    ks, t, total_rel = _tie_tables(q_codes, db_codes, q_labels, db_labels, ks, device)
+    rel_exp = t["rel_exp"]
+    precision = (rel_exp / ks[None, :]).mean(0)
+    ok = total_rel > 0
+    recall = (rel_exp[ok] / total_rel[ok, None]).mean(0) if ok.any() else np.full(len(ks), np.nan)
+    return precision, recall
 
 
 def precision_recall_at_k(q_codes, db_codes, q_labels, db_labels, ks, device=0):

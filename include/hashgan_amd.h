@@ -255,6 +255,24 @@ int hg_graded(hg_ctx* ctx, const int64_t* host_ks, int nk, const double* host_ga
 int hg_get_graded(hg_ctx* ctx, int64_t* host_gsum, int64_t* host_hits, double* host_dcg, double* host_wsum);   /* [Q][nk] each; null: skipped */
 int hg_get_grades(hg_ctx* ctx, uint8_t* host_grades);                   /* [Q][R]; HG_ERR_STATE unless the last hg_graded kept them */
 
+/* ---- tie-aware AP at the top-R cut (expected AP over the orders inside the Hamming tie groups, and its bounds) -------------
+ * A b-bit code has b + 1 distances, so nearly every rank of a Hamming ranking lies inside a tie group, and AP@R depends on how the
+ * relevant rows happen to be ordered inside each group.  hg_tie_ap computes, per query and cut-off R = Rs[j], from hg_rel_hist's two
+ * tables alone (no select, no lists; it runs that pass itself unless the tables of the loaded queries and database are there):
+ *   ap_exp   the expectation of the reference's AP@R (lib/metric.py:19-23) over uniformly random orders inside every tie group, given
+ *            that the top R hold a relevant row (the reference skips a query without one); NaN when p_hit = 0
+ *   p_hit    the probability of that condition
+ *   ap_min, ap_max   the exact minimum and maximum of AP@R over all those orders (NaN when no order has a hit)
+ *   rel_exp, rel_lo, rel_hi   expectation, minimum and maximum of the relevant rows among the top R
+ * Rs: nR (1..64) strictly ascending values in 1..N, anything else HG_ERR_ARG; copied before the call returns.  The context must hold the
+ * whole database (idx_base 0, N = n_total; HG_ERR_STATE otherwise).  float64 throughout; the order of every addition is a function of
+ * the query's two table columns and R, so equal inputs give equal bits whatever Q is.  Tables of its own: the staged pipeline's
+ * state, hg_hist's histogram, lists, match bits, APs and a step of hg_map_begin in flight are left as they were.  A database or query
+ * reload and hg_trim invalidate the results (hg_get_tie_ap then returns HG_ERR_STATE, as it does before the first pass). */
+int hg_tie_ap(hg_ctx* ctx, const int64_t* host_Rs, int nR);
+int hg_get_tie_ap(hg_ctx* ctx, double* host_ap_exp, double* host_p_hit, double* host_ap_min, double* host_ap_max,
+                  double* host_rel_exp, int64_t* host_rel_lo, int64_t* host_rel_hi);   /* [Q][nR] each; null: skipped */
+
 /* ---- collectives: RCCL over xGMI, one process per GPU (the reference has no counterpart --
  * main.py:260-263 only sets CUDA_VISIBLE_DEVICES) --------------------------------------------------------
  * librccl.so.1 is dlopen'ed by the first hg_comm_* call (HG_RCCL_LIBRARY overrides the search); a single-GPU
