@@ -34,6 +34,8 @@ _SIGNATURES = {
     "hg_set_queries": [_p, _p, _p, _i64],
     "hg_set_database_f32": [_p, _p, _p, _i64, C.c_int, C.c_int, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)],
     "hg_set_queries_f32": [_p, _p, _p, _i64, C.POINTER(_i64), C.POINTER(_i64)],
+    "hg_set_database_dev": [_p, _p, _p, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)],
+    "hg_set_queries_dev": [_p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
     "hg_get_packed": [_p, C.c_int, _p, _p],
     "hg_hist": [_p],
     "hg_hist_buffer": [_p, C.POINTER(_p), C.POINTER(_i64)],
@@ -109,6 +111,23 @@ _SIGNATURES = {
 EXPORTS = sorted(list(_SIGNATURES) + ["hg_last_error"])
 
 _lib = None
+
+# hg_dev_array.dtype (include/hashgan_amd.h)
+HG_F32, HG_F16, HG_BF16, HG_I64, HG_I32, HG_U8 = range(6)
+DEV_DTYPES = {"float32": HG_F32, "float16": HG_F16, "bfloat16": HG_BF16, "int64": HG_I64, "int32": HG_I32, "uint8": HG_U8, "bool": HG_U8}
+
+
+class DevArrayStruct(C.Structure):
+    """hg_dev_array: a 2-D array in device memory, strides in elements."""
+    _fields_ = [("ptr", _p), ("rows", _i64), ("cols", _i64), ("row_stride", _i64), ("col_stride", _i64),
+                ("dtype", C.c_int), ("stream", _p)]
+
+
+def _dev_struct(a):
+    """devarray.DeviceArray (or anything with ptr / shape / strides / dtype / stream) -> hg_dev_array.  An unknown dtype name goes
+    down as -1: the library refuses it with HG_ERR_ARG like every other bad descriptor."""
+    return DevArrayStruct(_p(int(a.ptr)), int(a.shape[0]), int(a.shape[1]), int(a.strides[0]), int(a.strides[1]),
+                          DEV_DTYPES.get(str(a.dtype), -1), _p(int(a.stream)) if a.stream else None)
 
 
 def library_path():
@@ -218,6 +237,26 @@ class Context:
         bc, bl = _i64(), _i64()
         check(self._lib.hg_set_queries_f32(self._h, _ptr(x), _ptr(lab), x.shape[0], C.byref(bc), C.byref(bl)))
         self.Q = x.shape[0]
+        return bc.value, bl.value
+
+    def set_database_dev(self, features, labels, idx_base=0, n_total=None):
+        """The same from arrays in DEVICE memory (devarray.DeviceArray: any strides; float32 / float16 / bfloat16 features, int64 /
+        int32 / uint8 / float32 labels), packed by one kernel straight out of the caller's memory; complete -- the arrays free to be
+        overwritten -- on return (hg_set_database_dev).  -> (entries outside {-1,0,+1}, label entries outside {0,1})"""
+        f, l = _dev_struct(features), _dev_struct(labels)
+        n_total = f.rows if n_total is None else int(n_total)
+        bc, bl = _i64(), _i64()
+        check(self._lib.hg_set_database_dev(self._h, C.byref(f), C.byref(l), int(idx_base), n_total, C.byref(bc), C.byref(bl)))
+        self.N, self.b, self.C = f.rows, f.cols, l.cols
+        return bc.value, bl.value
+
+    def set_queries_dev(self, features, labels):
+        """Queries from arrays in device memory, like set_database_dev (hg_set_queries_dev); same b and C as the database, their
+        floats kept iff the database's are.  -> (entries outside {-1,0,+1}, label entries outside {0,1})"""
+        f, l = _dev_struct(features), _dev_struct(labels)
+        bc, bl = _i64(), _i64()
+        check(self._lib.hg_set_queries_dev(self._h, C.byref(f), C.byref(l), C.byref(bc), C.byref(bl)))
+        self.Q = f.rows
         return bc.value, bl.value
 
     def get_packed(self, which):

@@ -2,6 +2,7 @@
 // for the map of the translation units).
 #include "hg_ctx.hpp"
 #include "hg_host_pack.hpp"
+#include "hg_dev_in.hpp"
 
 #include <exception>
 #include <map>
@@ -559,6 +560,24 @@ static int pack_on_host(hg_ctx* c, const float* x, const int64_t* lab, i64 n, De
     return HG_OK;
 }
 
+// What a successful load of the database's float32 / device arrays ends with (hg_set_database_f32, hg_set_database_dev): queries must
+// be set again, everything derived from the old tables is invalid, earlier lost bets say nothing about the new one.
+static void database_loaded(hg_ctx* c) {
+    if (!c->dbf_resident) c->bpad = 0;
+    c->stage = ST_DB;
+    c->dbx_valid = false;
+    c->dbx3_valid = false;
+    c->dbx4_valid = false;
+    c->dbx8_valid = false;
+    c->dbfx_valid = false;
+    c->dbfb_valid = false;
+    c->bet_consecutive_fail = c->shard_bet_fail = 0;
+    c->cap_boost = c->real_cap_boost = 1;
+    c->crowd_probed = false;
+    c->cfg_epoch++;
+    c->db_gen++;
+}
+
 int hg_set_database_f32(hg_ctx* c, const float* host_x, const int64_t* host_labels, int64_t N, int b, int C,
                         int64_t idx_base, int64_t n_total, int64_t* bad_codes, int64_t* bad_labels) {
     if (!c) return fail(HG_ERR_ARG, "hg_set_database_f32: null context");
@@ -579,19 +598,7 @@ int hg_set_database_f32(hg_ctx* c, const float* host_x, const int64_t* host_labe
         HG_TRY(pack_on_device(c, host_x, host_labels, N, c->db, c->dblab, c->dbf, bad_codes, bad_labels, c->census_db));
         c->dbf_resident = true;
     }
-    if (!c->dbf_resident) c->bpad = 0;
-    c->stage = ST_DB;
-    c->dbx_valid = false;
-    c->dbx3_valid = false;
-    c->dbx4_valid = false;
-    c->dbx8_valid = false;
-    c->dbfx_valid = false;
-    c->dbfb_valid = false;
-    c->bet_consecutive_fail = c->shard_bet_fail = 0;
-    c->cap_boost = c->real_cap_boost = 1;
-    c->crowd_probed = false;
-    c->cfg_epoch++;
-    c->db_gen++;
+    database_loaded(c);
     return HG_OK;
 }
 
@@ -614,6 +621,13 @@ static void queries_replaced(hg_ctx* c, i64 old_q, bool had_q) {
     if (carry) c->map_warm_cfg = c->cfg_epoch;
 }
 
+// ... and of the queries' (hg_set_queries_f32, hg_set_queries_dev)
+static void queries_loaded(hg_ctx* c, i64 old_q, bool had_q) {
+    c->stage = ST_DB | ST_Q;
+    c->qx_valid = false;
+    queries_replaced(c, old_q, had_q);
+}
+
 int hg_set_queries_f32(hg_ctx* c, const float* host_x, const int64_t* host_labels, int64_t Q, int64_t* bad_codes,
                        int64_t* bad_labels) {
     HG_TRY(need(c, ST_DB, "hg_set_queries_f32", "hg_set_database"));
@@ -632,9 +646,121 @@ int hg_set_queries_f32(hg_ctx* c, const float* host_x, const int64_t* host_label
         HG_TRY(pack_on_device(c, host_x, host_labels, Q, c->qc, c->qlab, c->qf, bad_codes, bad_labels, c->census_q));
         c->qf_resident = true;
     }
-    c->stage = ST_DB | ST_Q;
-    c->qx_valid = false;
-    queries_replaced(c, old_q, had_q);
+    queries_loaded(c, old_q, had_q);
+    return HG_OK;
+}
+
+// ---- features and labels in DEVICE memory (hg_dev_in.hpp: the kernels; hg_dev_desc.hpp: the descriptor arithmetic) ----
+// Is a.ptr device memory of the context's GPU, and does the array's extent lie inside its allocation?  Asked of the runtime
+// before anything is launched: a pointer it does not know comes back as HG_ERR_ARG, never as a fault.
+static int check_dev_pointer(hg_ctx* c, const char* who, const char* what, const hg_dev_array& a, int64_t extent) {
+    hipPointerAttribute_t at{};
+    hipError_t e = hipPointerGetAttributes(&at, a.ptr);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();                       // (not a launch failure: leave nothing for check_launch to find)
+        return fail(HG_ERR_ARG, "%s: the %s pointer %p is not known to the HIP runtime (%s)", who, what, a.ptr, hipGetErrorString(e));
+    }
+    if (at.type != hipMemoryTypeDevice || at.isManaged)
+        return fail(HG_ERR_ARG, "%s: the %s pointer %p is not plain device memory (host, managed or unregistered memory)", who, what, a.ptr);
+    if (at.device != c->device)
+        return fail(HG_ERR_ARG, "%s: the %s lie on device %d, the context runs on device %d", who, what, at.device, c->device);
+    void* base = nullptr;
+    size_t size = 0;
+    e = hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)a.ptr);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(HG_ERR_ARG, "%s: no allocation found around the %s pointer %p (%s)", who, what, a.ptr, hipGetErrorString(e));
+    }
+    if (!hg_dev::inside(a.ptr, extent, base, size))
+        return fail(HG_ERR_ARG, "%s: the %s span %lld bytes from %p, the allocation ends %lld bytes from there", who, what, (long long)extent,
+                    a.ptr, (long long)((const char*)base + size - (const char*)a.ptr));
+    return HG_OK;
+}
+
+static int check_dev_arrays(hg_ctx* c, const char* who, const hg_dev_array* f, const hg_dev_array* l, int64_t max_rows, int want_b,
+                            int want_C) {
+    char msg[256];
+    int64_t fb = 0, lb = 0;
+    if (hg_dev::check_pair(f, l, HG_MAX_BITS, max_rows, want_b, want_C, &fb, &lb, msg, sizeof msg)) return fail(HG_ERR_ARG, "%s: %s", who, msg);
+    HG_TRY(check_dev_pointer(c, who, "features", *f, fb));
+    return check_dev_pointer(c, who, "labels", *l, lb);
+}
+
+// The context's stream behind whatever the producer has enqueued so far on `s` (NULL: the null stream)
+static int wait_for_producer(hg_ctx* c, void* s) {
+    if ((hipStream_t)s == c->stream) return HG_OK;
+    hipEvent_t ev = c->get_event();
+    if (!ev) return fail(HG_ERR_HIP, "hipEventCreate failed");
+    hipError_t e = hipEventRecord(ev, (hipStream_t)s);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, ev, 0);
+    c->pool.push_back(ev);                             // (the wait is enqueued: the event may be recorded again)
+    HG_HIP(e);
+    return HG_OK;
+}
+
+// Device arrays -> packed device tables (+ the float table: floats = 0 never, 1 always, 2 iff the census finds no +-1 code),
+// c->b / C / NW / LW set.  Everything here was validated by check_dev_arrays.
+static int pack_from_device(hg_ctx* c, const hg_dev_array& f, const hg_dev_array& l, DevBuf& codes, DevBuf& labels, DevBuf& feats,
+                            int floats, bool* has_floats, int64_t* bad_codes, int64_t* bad_labels, i64 (&census)[3]) {
+    const i64 n = f.rows;
+    const int bpad = (c->b + 15) / 16 * 16;
+    const size_t fb = (size_t)n * bpad * 4;
+    HG_TRY(c->badcnt.reserve(32));
+    HG_TRY(codes.reserve((size_t)n * c->NW * 4 + 64 * 4));
+    HG_TRY(labels.reserve((size_t)n * c->LW * 8));
+    if (floats == 1) HG_TRY(feats.reserve(fb + 256));
+    HG_TRY(wait_for_producer(c, f.stream));
+    if (l.stream != f.stream) HG_TRY(wait_for_producer(c, l.stream));
+    HG_HIP(hipMemsetAsync(c->badcnt.p, 0, 32, c->stream));
+    HG_TRY(launch_pack_dev(c, f, codes.as<u32>(), floats == 1 ? feats.as<float>() : nullptr, bpad));
+    HG_TRY(launch_pack_labels_dev(c, l, labels.as<u64>()));
+    unsigned long long bad[4] = {0, 0, 0, 0};
+    HG_HIP(hipMemcpyAsync(bad, c->badcnt.p, 32, hipMemcpyDeviceToHost, c->stream));
+    HG_TRY(c->sync());
+    const bool pm1 = bad[0] == 0 && bad[2] == 0;
+    const bool up = floats == 1 || (floats == 2 && !pm1);
+    if (up && floats != 1) {                           // the census asked for the floats: a second pass over the caller's memory
+        HG_TRY(feats.reserve(fb + 256));
+        HG_TRY(launch_pack_dev(c, f, nullptr, feats.as<float>(), bpad));
+        HG_TRY(c->sync());
+    }
+    if (up) c->bpad = bpad;
+    *has_floats = up;
+    if (bad_codes) *bad_codes = (int64_t)bad[0];
+    if (bad_labels) *bad_labels = (int64_t)bad[1];
+    census[0] = (i64)bad[0]; census[1] = (i64)bad[2]; census[2] = (i64)bad[3];
+    return HG_OK;
+}
+
+int hg_set_database_dev(hg_ctx* c, const hg_dev_array* features, const hg_dev_array* labels, int64_t idx_base, int64_t n_total,
+                        int64_t* bad_codes, int64_t* bad_labels) {
+    if (!c) return fail(HG_ERR_ARG, "hg_set_database_dev: null context");
+    HG_TRY(c->use());
+    HG_TRY(check_dev_arrays(c, "hg_set_database_dev", features, labels, 0xFFFFFFFEll, 0, 0));
+    const i64 N = features->rows;
+    if (idx_base < 0 || n_total < N || idx_base + N > n_total || n_total >= 0xFFFFFFFFll)
+        return fail(HG_ERR_ARG, "hg_set_database_dev: shard [%lld, %lld) does not fit a database of %lld rows (< 2^32 - 1)",
+                    (long long)idx_base, (long long)(idx_base + N), (long long)n_total);
+    const int b = (int)features->cols, C = (int)labels->cols;
+    c->N = N; c->b = b; c->C = C; c->n_total = n_total;
+    c->NW = (b + 31) / 32; c->NB = b + 1; c->LW = (C + 63) / 64;
+    c->idx_base = (u32)idx_base;
+    HG_TRY(pack_from_device(c, *features, *labels, c->db, c->dblab, c->dbf, (int)c->opt.keep_floats, &c->dbf_resident, bad_codes,
+                            bad_labels, c->census_db));
+    database_loaded(c);
+    return HG_OK;
+}
+
+int hg_set_queries_dev(hg_ctx* c, const hg_dev_array* features, const hg_dev_array* labels, int64_t* bad_codes, int64_t* bad_labels) {
+    HG_TRY(need(c, ST_DB, "hg_set_queries_dev", "hg_set_database"));
+    HG_TRY(check_dev_arrays(c, "hg_set_queries_dev", features, labels, 0x7FFFFFC0ll, c->b, c->C));
+    const i64 old_q = c->Q;
+    const bool had_q = (c->stage & ST_Q) != 0;
+    c->Q = features->rows;
+    // the queries' floats follow the database's (the inner-product ranking needs both); without them c->bpad stays as it is
+    HG_TRY(pack_from_device(c, *features, *labels, c->qc, c->qlab, c->qf, c->dbf_resident ? 1 : 0, &c->qf_resident, bad_codes, bad_labels,
+                            c->census_q));
+    queries_loaded(c, old_q, had_q);
     return HG_OK;
 }
 

@@ -1,0 +1,123 @@
+"""Arrays that already lie in GPU memory, described without importing the framework that owns them.
+
+A training process produces its features on the GPU the metric runs on (main.py:151-164: forward_all(), then the metric).
+`as_device_array` turns what such a caller holds into a `DeviceArray` -- address, shape, strides in ELEMENTS, dtype name, producer
+stream -- which the library packs straight out of the caller's memory (hg_set_database_dev / hg_set_queries_dev); host data gives
+None and goes the NumPy way.  Nothing here touches the GPU or imports torch.
+"""
+import re
+
+# dtype name -> item size in bytes: what the library's kernels read (features: the float types; labels: the rest and float32)
+ITEMSIZE = {"float32": 4, "float16": 2, "bfloat16": 2, "int64": 8, "int32": 4, "uint8": 1, "bool": 1}
+# __cuda_array_interface__ type strings (NumPy's array-interface codes; bfloat16 has none)
+_TYPESTR = {"f4": "float32", "f2": "float16", "i8": "int64", "i4": "int32", "u1": "uint8", "b1": "bool"}
+
+
+class DeviceArray:
+    """A 2-D array in device memory: `ptr` (int address), `shape` (rows, cols), `strides` (row, col) in elements, both >= 1,
+    `dtype` (a key of ITEMSIZE), `stream` (the producer's hipStream_t as an int; 0 / None = the null stream).
+
+    The library orders its reads behind everything enqueued so far on `stream`, and has copied what it needs when the load
+    returns: the memory may be overwritten or freed afterwards."""
+    __slots__ = ("ptr", "shape", "strides", "dtype", "stream")
+
+    def __init__(self, ptr, shape, strides=None, dtype="float32", stream=None):
+        shape = tuple(int(s) for s in shape)
+        if len(shape) != 2:
+            raise ValueError("device arrays must be 2-D [n, width] (got %d-D)" % len(shape))
+        if shape[0] < 1 or shape[1] < 1:
+            raise ValueError("device arrays must have at least one row and one column (got shape %r)" % (shape,))
+        dtype = str(dtype)
+        if dtype not in ITEMSIZE:
+            raise ValueError("unsupported device dtype %r (supported: %s)" % (dtype, ", ".join(sorted(ITEMSIZE))))
+        strides = (shape[1], 1) if strides is None else tuple(int(s) for s in strides)
+        if len(strides) != 2:
+            raise ValueError("device arrays need one stride per dimension (got %r)" % (strides,))
+        if strides[0] < 1 or strides[1] < 1:
+            # (a one-row or one-column view may carry any stride: it is never applied)
+            fixed = tuple(1 if (s < 1 and n == 1) else s for s, n in zip(strides, shape))
+            if fixed[0] < 1 or fixed[1] < 1:
+                raise ValueError("negative or zero strides %r are not supported: make the array contiguous first" % (strides,))
+            strides = fixed
+        if not ptr:
+            raise ValueError("device array with a null pointer")
+        self.ptr, self.shape, self.strides, self.dtype = int(ptr), shape, strides, dtype
+        self.stream = int(stream) if stream else None
+
+    @property
+    def ndim(self):
+        return 2
+
+    @property
+    def itemsize(self):
+        return ITEMSIZE[self.dtype]
+
+    def __repr__(self):
+        return "DeviceArray(ptr=0x%x, shape=%r, strides=%r, dtype=%s, stream=%r)" % (self.ptr, self.shape, self.strides, self.dtype,
+                                                                                   self.stream)
+
+
+def _from_cuda_array_interface(obj, cai, stream):
+    version = int(cai.get("version", 0))
+    if version not in (2, 3):
+        raise ValueError("__cuda_array_interface__ version %r is not supported (2 or 3)" % cai.get("version"))
+    if cai.get("mask") is not None:
+        raise ValueError("masked device arrays are not supported")
+    typestr = str(cai["typestr"])
+    name = _TYPESTR.get(typestr[1:]) if typestr[:1] in "<|=" else None
+    if name is None:
+        raise ValueError("unsupported device dtype %r (supported: %s)" % (typestr, ", ".join(sorted(ITEMSIZE))))
+    shape = tuple(cai["shape"])
+    if len(shape) != 2:
+        raise ValueError("device arrays must be 2-D [n, width] (got %d-D)" % len(shape))
+    isz = ITEMSIZE[name]
+    strides = cai.get("strides")
+    if strides is not None:
+        if any(int(s) % isz for s in strides):
+            raise ValueError("byte strides %r are not multiples of the item size %d" % (tuple(strides), isz))
+        strides = tuple(int(s) // isz for s in strides)
+    ptr = cai["data"][0]
+    if stream is None and version >= 3:
+        # v3: None = no synchronisation needed, 1 = the legacy default stream, 2 = the per-thread default stream, else a handle
+        s = cai.get("stream")
+        stream = None if s in (None, 1) else int(s)
+    return DeviceArray(ptr, shape, strides, name, stream)
+
+
+def _from_tensor(obj, stream):
+    m = re.search(r"(\w+)$", str(obj.dtype))           # 'torch.bfloat16' -> 'bfloat16'
+    name = m.group(1) if m else str(obj.dtype)
+    name = {"float": "float32", "half": "float16", "long": "int64", "int": "int32"}.get(name, name)
+    if name not in ITEMSIZE:
+        raise ValueError("unsupported device dtype %s (supported: %s)" % (obj.dtype, ", ".join(sorted(ITEMSIZE))))
+    shape = tuple(obj.shape)
+    if len(shape) != 2:
+        raise ValueError("device arrays must be 2-D [n, width] (got %d-D)" % len(shape))
+    return DeviceArray(obj.data_ptr(), shape, tuple(obj.stride()), name, stream)
+
+
+def as_device_array(obj, stream=None):
+    """-> DeviceArray for data in GPU memory, None for host data (NumPy arrays, lists, CPU tensors).
+
+    Accepted: a DeviceArray; an object with `__cuda_array_interface__` (version 2 or 3; byte strides must be multiples of the item
+    size, `strides: None` means C-contiguous, the `stream` key of version 3 is honoured, a mask is refused); a tensor-like object
+    whose `is_cuda` is true, with `data_ptr()`, `stride()`, `shape` and `dtype` -- the dtype is read from `str(dtype)`, which is how
+    bfloat16 arrives (it has no array-interface type string).  2-D only, strides >= 1, dtypes of ITEMSIZE; anything else raises
+    ValueError naming the problem.
+
+    `stream`: the HIP stream (an int handle) on which the producer's work was enqueued; it overrides the interface's own.  The
+    default is the null stream, which is ordered after every BLOCKING stream of the process -- torch's default stream included.
+    Work queued on a NON-BLOCKING side stream (torch.cuda.Stream()) is not ordered with the null stream: pass that stream's handle
+    (torch.cuda.current_stream().cuda_stream), or synchronise it first."""
+    if isinstance(obj, DeviceArray):
+        if stream is not None and stream != obj.stream:
+            return DeviceArray(obj.ptr, obj.shape, obj.strides, obj.dtype, stream)
+        return obj
+    if getattr(obj, "is_cuda", None) is True and hasattr(obj, "data_ptr"):
+        return _from_tensor(obj, stream)
+    if getattr(obj, "is_cuda", None) is False:
+        return None                                    # a CPU tensor: np.asarray takes it
+    cai = getattr(obj, "__cuda_array_interface__", None)
+    if cai is not None:
+        return _from_cuda_array_interface(obj, cai, stream)
+    return None

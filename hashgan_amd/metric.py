@@ -17,12 +17,18 @@ product (`binarize=True` applies sign() first instead).  MAP / calc_map take bin
 {0,1} bits or +-1, and rank by Hamming distance.  Labels are {0,1} matrices.  All ranking work
 runs in the HIP kernels behind hashgan_amd._native; the host only checks arguments and takes the
 final mean (metric.py:24).
+
+Every array argument may also lie in GPU memory -- a torch tensor on the device, anything with
+__cuda_array_interface__, a devarray.DeviceArray: it is then packed on the GPU straight out of the
+caller's memory (devarray.as_device_array decides; INTEGRATION.md has the stream rule).  Database and
+queries may be on different sides; the features and labels of one table must be on the same side.
 """
 import threading
 
 import numpy as np
 
 from . import _native
+from .devarray import DeviceArray, as_device_array
 
 
 # ------------------------------------------------------------------ packing
@@ -213,6 +219,19 @@ def release_engines():
     _native.release_cache()
 
 
+def _sides(codes, labels, what):
+    """One table's (features, labels) as the loaders take them: two DeviceArray descriptors (device memory: never handed to
+    np.asarray) or two ndarrays."""
+    dc, dl = as_device_array(codes), as_device_array(labels)
+    if (dc is None) != (dl is None):
+        raise ValueError("%s features and labels must be on the same side: both in device memory or both on the host "
+                         "(features on the %s, labels on the %s)" % (what, "device" if dc is not None else "host",
+                                                                     "device" if dl is not None else "host"))
+    if dc is not None:
+        return dc, dl
+    return np.asarray(codes), np.asarray(labels)
+
+
 def _check_shapes(q_codes, db_codes, q_labels, db_labels, R):
     if db_codes.ndim != 2 or q_codes.ndim != 2 or db_codes.shape[1] != q_codes.shape[1]:
         raise ValueError("query and database codes must be [n, b] with the same b")
@@ -238,19 +257,33 @@ def _kind(ctx, which):
 
 
 def _load_database(eng, db_codes, db_labels, mode="reference", floats=None):
-    """Pack on the host, upload (hg_set_database_f32).  The float table itself goes to the GPU only when it may be ranked
+    """Host arrays: pack on the host, upload (hg_set_database_f32); DeviceArray descriptors: packed on the GPU out of the caller's
+    memory (hg_set_database_dev; 'reference' mode keeps the floats at once).  The float table itself goes to the GPU only when it may be ranked
     by inner product: never for the spellings that binarise or insist on binary codes, and in 'reference' mode only if
     the database is not a +-1 code (a +-1 database meeting real-valued queries is uploaded again with it, below)."""
     eng.b = eng.C = eng.N = eng.db_kind = eng.db_src = None      # nothing is resident until this load has succeeded
     eng.resident = None                               # whoever loads another database (extra_metrics, MAPs) ends _evaluate's shortcut
-    eng.ctx.set_option("keep_floats", floats if floats is not None else (2 if mode == "reference" else 0))
-    bad_c, bad_l = eng.ctx.set_database_f32(db_codes, db_labels)
+    on_device = isinstance(db_codes, DeviceArray)
+    if on_device:
+        # device arrays: in 'reference' mode the floats are kept at once (a copy inside the GPU's memory, no PCIe) -- the caller's
+        # memory may have changed by the time real-valued queries would ask for a second load, so there is none
+        eng.ctx.set_option("keep_floats", floats if floats is not None else (1 if mode == "reference" else 0))
+        bad_c, bad_l = eng.ctx.set_database_dev(db_codes, db_labels)
+    else:
+        eng.ctx.set_option("keep_floats", floats if floats is not None else (2 if mode == "reference" else 0))
+        bad_c, bad_l = eng.ctx.set_database_f32(db_codes, db_labels)
     if bad_l:
         raise ValueError("labels must be {0,1} indicator matrices")
     eng.b, eng.C = db_codes.shape[1], db_labels.shape[1]
     eng.db_kind = _kind(eng.ctx, 0)
     eng.N = db_codes.shape[0]
-    eng.db_src = (db_codes, db_labels)                # for that second upload
+    eng.db_src = None if on_device else (db_codes, db_labels)     # for that second upload (host arrays only)
+
+
+def _set_queries(eng, q_codes, q_labels):
+    if isinstance(q_codes, DeviceArray):
+        return eng.ctx.set_queries_dev(q_codes, q_labels)
+    return eng.ctx.set_queries_f32(q_codes, q_labels)
 
 
 def _rank(eng, q_codes, q_labels, R, mode):
@@ -261,7 +294,7 @@ def _rank(eng, q_codes, q_labels, R, mode):
        'sign'       MAPs(binarize=True): sign() first, then Hamming;
        'codes'      MAP / calc_map (north-star spelling): binary codes only, {0,1} bits or +-1, ranked by Hamming
                     distance; anything else is an error."""
-    qbad_c, qbad_l = eng.ctx.set_queries_f32(q_codes, q_labels)
+    qbad_c, qbad_l = _set_queries(eng, q_codes, q_labels)
     if qbad_l:
         raise ValueError("labels must be {0,1} indicator matrices")
     qk, dk = _kind(eng.ctx, 1), eng.db_kind
@@ -277,15 +310,18 @@ def _rank(eng, q_codes, q_labels, R, mode):
         raise ValueError("inner-product ranking supports up to 255 features (have %d)" % q_codes.shape[1])
     if not eng.ctx.census(0)[3]:             # a +-1 database whose floats stayed on the host: bring them over now
         src = eng.db_src
+        if src is None:                      # (a device database in 'reference' mode keeps its floats from the start)
+            raise ValueError("the resident database holds no float features: load it again")
         _load_database(eng, src[0], src[1], floats=1)
-        eng.ctx.set_queries_f32(q_codes, q_labels)
+        _set_queries(eng, q_codes, q_labels)
     return eng.ctx.map_real(R)
 
 
 def _evaluate(q_codes, db_codes, q_labels, db_labels, R, device, mode):
-    db_codes, q_codes = np.asarray(db_codes), np.asarray(q_codes)
-    db_labels, q_labels = np.asarray(db_labels), np.asarray(q_labels)
+    db_codes, db_labels = _sides(db_codes, db_labels, "database")
+    q_codes, q_labels = _sides(q_codes, q_labels, "query")
     _check_shapes(q_codes, db_codes, q_labels, db_labels, R)
+    db_on_device = isinstance(db_codes, DeviceArray)
     eng = _Shared.get(device)
     with eng.lock:
         # the same read-only arrays as the last call (an evaluation loop over one database): the packed copy on the GPU
@@ -293,13 +329,14 @@ def _evaluate(q_codes, db_codes, q_labels, db_labels, R, device, mode):
         # (every load goes through _load_database, which clears `resident`: another database loaded into this shared
         # engine in between -- extra_metrics -- can never be mistaken for this one)
         res = eng.resident
-        same = (res is not None and res[0] is db_codes and res[1] is db_labels and res[2] == mode
+        # (never for device arrays: nothing says their memory is unchanged -- residency comes from MAPs.set_database)
+        same = (not db_on_device and res is not None and res[0] is db_codes and res[1] is db_labels and res[2] == mode
                 and eng.db_src is not None and eng.db_src[0] is db_codes and eng.db_src[1] is db_labels
                 and not db_codes.flags.writeable and not db_labels.flags.writeable)
         if not same:
             eng.resident = None
             _load_database(eng, db_codes, db_labels, mode)
-            eng.resident = (db_codes, db_labels, mode)
+            eng.resident = None if db_on_device else (db_codes, db_labels, mode)
         try:
             ap, rel = _rank(eng, q_codes, q_labels, R, mode)
         except Exception:
@@ -353,8 +390,9 @@ class MAPs:
 
     def set_database(self, database):
         """Upload + pack `database` (.output [N, b], .label [N, C]) once; get_maps_by_feature(None, query) -- or with
-        the same object -- then ranks against the resident copy."""
-        out, lab = np.asarray(database.output), np.asarray(database.label)
+        the same object -- then ranks against the resident copy.  Arrays in device memory are copied in: the caller may
+        overwrite them afterwards."""
+        out, lab = _sides(database.output, database.label, "database")
         if out.ndim != 2 or lab.ndim != 2 or out.shape[0] != lab.shape[0]:
             raise ValueError("database.output must be [N, b] and database.label [N, C]")
         with self._lock:
@@ -378,19 +416,22 @@ class MAPs:
             return
         if self._resident is not None and self._resident[0] == "explicit" and self._resident[1] is database:
             return
-        out, lab = np.asarray(database.output), np.asarray(database.label)
-        if (self._resident is not None and self._resident[0] == "auto" and self._resident[1] is out
+        out, lab = _sides(database.output, database.label, "database")
+        # device arrays handed over here are loaded on every call (nothing says their memory is unchanged).  What the load leaves is
+        # the library's own copy, so a later get_maps_by_feature(None, query) ranks against it like after set_database.
+        on_device = isinstance(out, DeviceArray)
+        if (not on_device and self._resident is not None and self._resident[0] == "auto" and self._resident[1] is out
                 and self._resident[2] is lab and not out.flags.writeable and not lab.flags.writeable):
             return                                     # the very same immutable arrays as last time
         if out.ndim != 2 or lab.ndim != 2 or out.shape[0] != lab.shape[0]:
             raise ValueError("database.output must be [N, b] and database.label [N, C]")
         self._resident = None                          # a failed load leaves NO database
         self._guard(_load_database, self._engine(), out, lab, "sign" if self.binarize else "reference")
-        self._resident = ("auto", out, lab)
+        self._resident = ("device",) if on_device else ("auto", out, lab)
 
     def get_maps_by_feature(self, database, query):
         """database/query: objects with .output [n, b] and .label [n, C] (main.py:157); database first."""
-        q_codes, q_labels = np.asarray(query.output), np.asarray(query.label)
+        q_codes, q_labels = _sides(query.output, query.label, "query")
         with self._lock:
             self._ensure_database(database)
             eng = self._engine()

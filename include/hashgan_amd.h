@@ -81,6 +81,39 @@ int hg_set_database_f32(hg_ctx* ctx, const float* host_features, const int64_t* 
                         int64_t idx_base, int64_t n_total, int64_t* bad_codes, int64_t* bad_labels);
 int hg_set_queries_f32(hg_ctx* ctx, const float* host_features, const int64_t* host_labels, int64_t Q,
                        int64_t* bad_codes, int64_t* bad_labels);
+/* The same two calls for a caller whose features never left the GPU (forward_all() runs on the device the metric runs on):
+ * a 2-D array in DEVICE memory, described as the caller's framework laid it out -- any row / column stride (a slice, a
+ * transposed view), float32 / IEEE float16 / bfloat16 features, int64 / int32 / uint8 (bool) / float32 labels; no alignment is
+ * assumed.  One kernel (k_pack_dev, hg_dev_in.hpp) reads the caller's memory once and writes the packed code words, the census and
+ * -- where "keep_floats" asks for it -- the float32 table; 16-bit features are widened exactly first.  With "keep_floats" = 2 the
+ * census decides, so the floats of a table that is not a +-1 code are written by a second pass over the caller's memory.
+ * Afterwards the context holds exactly what hg_set_*_f32 leaves for the same values ("host_pack" plays no part).
+ *   Ordering  the context's stream waits for everything enqueued so far on features->stream and labels->stream (an event on each), so
+ *             the producer need not synchronise; stream = NULL is the null stream -- work queued on a non-blocking stream of the
+ *             caller's is only ordered if that stream's handle is passed.
+ *   Copy-in   the call is complete when it returns: the caller may overwrite or free its arrays, no pointer to them is kept.
+ *   Refused   with HG_ERR_ARG before anything is launched: a dtype outside the lists above, a stride < 1, unequal row counts, the
+ *             shape limits of hg_set_*_f32, a pointer that hipPointerGetAttributes does not report as device memory (host, managed,
+ *             unknown) of the context's device, an extent -- ptr .. ptr + ((rows-1)*row_stride + (cols-1)*col_stride + 1) * itemsize
+ *             -- that does not lie inside the allocation hipMemGetAddressRange reports.
+ * A label entry counts as bad unless it is exactly 0 or 1 (0.5 and NaN in float32 labels are bad). */
+#define HG_F32 0
+#define HG_F16 1
+#define HG_BF16 2
+#define HG_I64 3
+#define HG_I32 4
+#define HG_U8 5     /* also bool */
+typedef struct hg_dev_array {      /* a 2-D array in device memory, as the caller's framework laid it out */
+    const void* ptr;
+    int64_t rows, cols;
+    int64_t row_stride, col_stride;    /* strides in ELEMENTS, both >= 1 */
+    int dtype;                         /* HG_F32, HG_F16, HG_BF16 (features); HG_I64, HG_I32, HG_U8, HG_F32 (labels) */
+    void* stream;                      /* producer's hipStream_t; NULL = the null stream */
+} hg_dev_array;
+int hg_set_database_dev(hg_ctx* ctx, const hg_dev_array* features, const hg_dev_array* labels,
+                        int64_t idx_base, int64_t n_total, int64_t* bad_codes, int64_t* bad_labels);
+int hg_set_queries_dev(hg_ctx* ctx, const hg_dev_array* features, const hg_dev_array* labels,
+                       int64_t* bad_codes, int64_t* bad_labels);
 /* Packed device tables back to the host: which = 0 database, 1 queries; codes as dense
  * uint32 [n][ceil(b/32)], labels uint64 [n][ceil(C/64)]. */
 int hg_get_packed(hg_ctx* ctx, int which, uint32_t* host_codes, uint64_t* host_labels);
