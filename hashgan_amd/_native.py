@@ -43,6 +43,7 @@ _SIGNATURES = {
     "hg_grade_hist": [_p],
     "hg_graded": [_p, _p, C.c_int, _p, _p, C.c_int],
     "hg_tie_ap": [_p, _p, C.c_int],
+    "hg_ap_at": [_p, _p, C.c_int],
     "hg_plan": [_p, _i64, _p, C.c_int, C.c_int],
     "hg_select": [_p],
     "hg_bet_eligible": [_p, _i64, C.c_int, C.POINTER(C.c_int)],
@@ -82,6 +83,7 @@ _SIGNATURES = {
     "hg_get_graded": [_p, _p, _p, _p, _p],
     "hg_get_grades": [_p, _p],
     "hg_get_tie_ap": [_p, _p, _p, _p, _p, _p, _p, _p],
+    "hg_get_ap_at": [_p, _p, _p],
     "hg_comm_unique_id": [_p],
     "hg_comm_init": [_p, _p, C.c_int, C.c_int],
     "hg_comm_destroy": [_p],
@@ -296,6 +298,13 @@ class Context:
         check(self._lib.hg_tie_ap(self._h, _ptr(Rs), len(Rs)))
         self._tie_nR = len(Rs)
 
+    def ap_at(self, Rs):
+        """AP@R and the hits among the top R at the strictly ascending cut-offs Rs (at most 64, each within 1..R of the last ranking),
+        in one pass over the match bitmap that ranking left (topr, topr_real, map, map_real).  Results: get_ap_at()."""
+        Rs = _carray(Rs, np.int64).ravel()
+        check(self._lib.hg_ap_at(self._h, _ptr(Rs), len(Rs)))
+        self._ap_at_nR = len(Rs)
+
     def hist_buffer(self):
         p, n = _p(), _i64()
         check(self._lib.hg_hist_buffer(self._h, C.byref(p), C.byref(n)))
@@ -498,6 +507,14 @@ class Context:
         i = [np.empty(shape, dtype=np.int64) for _ in range(2)]
         check(self._lib.hg_get_tie_ap(self._h, *[_ptr(x) for x in f + i]))
         return dict(zip(("ap", "p_hit", "ap_min", "ap_max", "rel_exp", "rel_lo", "rel_hi"), f + i))
+
+    def get_ap_at(self):
+        """-> (ap float64 [Q, nR] with nan where the top R hold no hit, rel int64 [Q, nR]) (after ap_at())."""
+        shape = (self.Q or 0, getattr(self, "_ap_at_nR", 0))
+        ap = np.empty(shape, dtype=np.float64)
+        rel = np.empty(shape, dtype=np.int64)
+        check(self._lib.hg_get_ap_at(self._h, _ptr(ap), _ptr(rel)))
+        return ap, rel
 
     def get_grades(self):
         """-> uint8 [Q, R]: the grade of every rank (after graded(..., keep_grades=True))."""

@@ -25,7 +25,7 @@ int fail(int code, const char* fmt, ...) {
 const char* const kKernelNames[KI_COUNT] = {"k_hist", "k_hist_reduce", "k_plan", "k_seg_counts", "k_seg_layout", "k_guess",
                                             "k_select", "k_rank_hist", "k_order", "k_rank_fused", "k_match", "k_ap", "k_merge", "k_pack",
                                             "k_real_sample", "k_real_guess", "k_real_select", "k_radix_pass", "k_real_finish", "k_select_mx", "k_rank_cnt", "rccl_allgather", "step_gpu_span", "k_real_rescore",
-                                            "k_hist_rel", "k_hist_rel_reduce", "k_graded", "k_grade_hist", "k_grade_hist_reduce", "k_tie_ap"};
+                                            "k_hist_rel", "k_hist_rel_reduce", "k_graded", "k_grade_hist", "k_grade_hist_reduce", "k_tie_ap", "k_ap_at"};
 // Flatten NumPy's pairwise-summation tree for a chunk of n elements (n <= 8192):
 // numpy/_core/src/umath/loops_utils.h.src, pairwise_sum: n <= 128 is a leaf,
 // otherwise split at n/2 rounded down to a multiple of 8.
@@ -833,6 +833,7 @@ extern "C++" int do_match(hg_ctx* c) {
     HG_TRY(c->check_launch("k_match"));
     c->stage |= ST_MATCH;
     c->stage &= ~(unsigned)ST_AP;
+    c->aa_done = false;                                // (the bitmap hg_ap_at walked is rewritten)
     return HG_OK;
 }
 
@@ -860,6 +861,8 @@ int hg_merge_match(hg_ctx* c, const uint64_t* dev_bits_all, int G) {
     hipLaunchKernelGGL(k_or_bits, dim3(grid_for(n)), dim3(256), 0, c->stream, (const u64*)dev_bits_all, c->mbits.as<u64>(), n, G);
     c->t_end();
     HG_TRY(c->check_launch("k_or_bits"));
+    c->aa_done = false;                                // (hg_ap_at's tables were the unmerged bitmap's)
+    c->mbits_merged = true;
     return c->stage_end();
 }
 
@@ -1065,6 +1068,19 @@ int hg_get_tie_ap(hg_ctx* c, double* host_ap_exp, double* host_p_hit, double* ho
     return c->sync();
 }
 
+int hg_get_ap_at(hg_ctx* c, double* host_ap, int64_t* host_rel) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_ap_at", "hg_ap_at"));
+    if (!c->aa_done || c->aa_q_gen != c->q_gen || c->aa_db_gen != c->db_gen)
+        return fail(HG_ERR_STATE, "hg_get_ap_at called before hg_ap_at (on the match bitmap and tables held now)");
+    const size_t n = (size_t)c->aa_Q * c->aa_nR;
+    std::vector<u32> rel(host_rel ? n : 0);
+    if (host_ap) HG_HIP(hipMemcpyAsync(host_ap, c->aa_out.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (host_rel) HG_HIP(hipMemcpyAsync(rel.data(), c->aa_out.as<char>() + n * 8, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HG_TRY(c->sync());
+    for (size_t i = 0; i < rel.size(); ++i) host_rel[i] = rel[i];
+    return HG_OK;
+}
+
 // Context-owned device scratch (grows only) and a stream-ordered device-to-device copy: what an in-process
 // communicator (virtual shards of one GPU in the tests) needs to do hg_allgather's job without RCCL.
 int hg_scratch(hg_ctx* c, int slot, int64_t nbytes, void** dev_ptr) {
@@ -1249,6 +1265,7 @@ int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "select_variant")) *value = c->last_select;
     else if (!strcmp(key, "rank_variant")) *value = c->last_rank;
     else if (!strcmp(key, "rel_hist_variant")) *value = c->last_rel_hist;
+    else if (!strcmp(key, "ap_at_cutoffs")) *value = c->aa_nR;
     else if (!strcmp(key, "ap_fused")) *value = c->ap_fused ? 1 : 0;
     else if (!strcmp(key, "cap_boost")) *value = c->cap_boost;
     else if (!strcmp(key, "crowding_x100")) *value = c->crowd_x100;

@@ -210,7 +210,7 @@ struct DevBuf {
 enum KernelId { KI_HIST = 0, KI_HIST_REDUCE, KI_PLAN, KI_SEG_COUNTS, KI_SEG_LAYOUT, KI_GUESS, KI_SELECT, KI_CAND_HIST,
                 KI_ORDER, KI_RANK_FUSED, KI_MATCH, KI_AP, KI_MERGE, KI_PACK, KI_REAL_SAMPLE, KI_REAL_GUESS, KI_REAL_SELECT,
                 KI_RADIX, KI_REAL_FINISH, KI_SELECT_MX, KI_RANK_LDS, KI_COMM, KI_STEP, KI_REAL_RESCORE, KI_HIST_REL, KI_HIST_REL_REDUCE,
-                KI_GRADED, KI_GRADE_HIST, KI_GRADE_HIST_REDUCE, KI_TIE_AP, KI_COUNT };
+                KI_GRADED, KI_GRADE_HIST, KI_GRADE_HIST_REDUCE, KI_TIE_AP, KI_AP_AT, KI_COUNT };
 enum Stage { ST_NONE = 0, ST_DB = 1, ST_Q = 2, ST_HIST = 4, ST_PLAN = 8, ST_SELECT = 16, ST_MATCH = 32, ST_AP = 64 };
 extern const char* const kKernelNames[KI_COUNT];
 
@@ -406,6 +406,16 @@ struct hg_ctx : StepBufs, StepState {
     unsigned long long ta_q_gen = 0, ta_db_gen = 0;
     i64 ta_Q = 0;
     int ta_nR = 0;
+    // AP at many cut-offs (hg_ap_at.hpp): aa_out holds ap [Q][nR] float64 and rel [Q][nR] u32 of the match bitmap the last ranking left.
+    // Any later ranking (set_R, a blind hg_map_begin), a rewrite of the bitmap (hg_match, the merges), a reload (generations) and
+    // hg_trim end that.
+    bool aa_done = false;
+    unsigned long long aa_q_gen = 0, aa_db_gen = 0;
+    i64 aa_Q = 0;
+    int aa_nR = 0;             // stat "ap_at_cutoffs": cut-offs of the last pass
+    i64 aa_recip_n = -1;       // aa_recip holds RN(1 / k) for k = 1 .. this (+ AP_RECIP_SLACK)
+    bool mbits_merged = false; // G > 1: the shards' bitmaps have been merged into mbits for all queries (hg_merge_match, hg_merge_ranked)
+    bool mbits_in_ws_b = false;   // the last ranking was a blind step on stream_b: its bitmap is ws_b's, not mbits
     bool verdict_pending = false, verdict_known = false;
     int verdict_flag = 0;
     // pinned landing zone for a one-shot call's results: AP, hit counts and the lost-bet flag come back with the
@@ -483,6 +493,8 @@ struct hg_ctx : StepBufs, StepState {
     DevBuf gr_tab, gr_out, gr_grades;   // hg_graded: [ks 64 x i64][gain C + 1][disc kmax], the tables gsum / hits / dcg / wsum [Q][nk] each, grade bytes [Q][R]
     DevBuf gh_part, gh_tab;    // hg_grade_hist: per-segment counters [S][C + 1][Qpad], the table [C + 1][Qpad] (gh_done)
     DevBuf ta_tab, ta_out;     // hg_tie_ap: the cut-offs [64 x i64], the tables ap_exp / p_hit / ap_min / ap_max / rel_exp / rel_lo / rel_hi [Q][nR] each (ta_done)
+    DevBuf aa_tab, aa_out;     // hg_ap_at: [cut-offs 64 x i64][ApShape x (1 + nR)], the tables ap [Q][nR] x 8 and rel [Q][nR] x 4 (aa_done)
+    DevBuf aa_recip;           // hg_ap_at's own reciprocals (aa_recip_n) when the ranking's table (ap_recip, recip_for_R) is not there
     DevBuf dbx3;               // fp4 image for k_select_mx3 (48-row supertiles, three rows per accumulator; dbx3_valid)
     DevBuf dbx4;               // fp4 image for k_select_mx4 (32-row supertiles, two rows per accumulator; codes of 65..128 bits; dbx4_valid)
     DevBuf dbfx;               // float features of the database in MFMA A-fragment order (k_real_select_mx; dbfx_valid)
@@ -507,10 +519,10 @@ struct hg_ctx : StepBufs, StepState {
     // Every device buffer of the context, each once, with its class: hg_destroy, hg_trim and the stat "device_bytes" walk this.
     template <class F> void for_each_buf(F&& f) {
         for (DevBuf* d : {&db, &dblab, &qc, &qlab, &dbf, &qf}) f(*d, BUF_TABLE);
-        for (DevBuf* d : {&dbx, &qx, &dbx8, &dbx3, &dbx4, &dbfx, &dbfb, &xmax2, &shapes, &ap_recip}) f(*d, BUF_DERIVED);
+        for (DevBuf* d : {&dbx, &qx, &dbx8, &dbx3, &dbx4, &dbfx, &dbfb, &xmax2, &shapes, &ap_recip, &aa_recip}) f(*d, BUF_DERIVED);
         for (DevBuf* d : {&seglt, &segtie, &mbits2, &part, &obuf[0], &obuf[1], &beyond, &stage_in, &badcnt, &flist, &dbytes, &samp, &thr,
                           &sortA, &sortB, &scores, &gtab, &sampx, &cntq, &krows, &thr2, &hist2, &comm_tmp, &gath_idx, &gath_dist, &rh_part, &rh_all, &rh_rel,
-                          &gr_tab, &gr_out, &gr_grades, &gh_part, &gh_tab, &ta_tab, &ta_out})
+                          &gr_tab, &gr_out, &gr_grades, &gh_part, &gh_tab, &ta_tab, &ta_out, &aa_tab, &aa_out})
             f(*d, BUF_WORK);
         for (DevBuf& d : gathered) f(d, BUF_WORK);
         for (DevBuf& d : scratch) f(d, BUF_WORK);
@@ -521,8 +533,8 @@ struct hg_ctx : StepBufs, StepState {
     void forget_derived() {
         dbx_valid = qx_valid = dbx8_valid = dbx3_valid = dbx4_valid = dbfx_valid = dbfb_valid = false;
         rh_done = false;               // (hg_trim releases the tables with the other work buffers)
-        gr_done = gr_kept = gh_done = ta_done = false;
-        shapes_for_R = recip_for_R = -1;
+        gr_done = gr_kept = gh_done = ta_done = aa_done = false;
+        shapes_for_R = recip_for_R = aa_recip_n = -1;
         outblk_q = ws_b.outblk_q = -1;
     }
 

@@ -9,6 +9,7 @@
 #include "hg_hist_rel.hpp"
 #include "hg_graded.hpp"
 #include "hg_tie_ap.hpp"
+#include "hg_ap_at.hpp"
 #include "hg_rank_cnt.hpp"
 #include "hg_rank_lean.hpp"
 #include "hg_rank_dense.hpp"
@@ -380,6 +381,71 @@ int hg_tie_ap(hg_ctx* c, const int64_t* host_Rs, int nR) {
     return HG_OK;
 }
 
+// AP@R and the hits among the top R at the cut-offs `host_Rs` from the match bitmap the last ranking left, in one pass per query
+// (hg_ap_at.hpp).  Like hg_graded: buffers and tables of its own, the ranking's state -- stage, hg_ap's results, lists, the one-R
+// AP tables -- left as it was, the host array copied before the call returns (it synchronises whatever "stage_sync" says).
+int hg_ap_at(hg_ctx* c, const int64_t* host_Rs, int nR) {
+    HG_TRY(need(c, ST_MATCH, "hg_ap_at", "a ranking that leaves the whole match bitmap (hg_topr, hg_topr_real, hg_map, hg_match, a merge of all queries)"));
+    c->aa_done = false;
+    if (c->ranked_local) return fail(HG_ERR_STATE, "hg_ap_at: the match bitmap is in this shard's local rank order (hg_select_ranked): merge it first");
+    if (c->G > 1 && !c->mbits_merged)
+        return fail(HG_ERR_STATE, "hg_ap_at: the match bitmap holds this shard's rows only (%d shards): merge it first (hg_merge_match, hg_merge_ranked)", c->G);
+    if (c->mbits_in_ws_b) return fail(HG_ERR_STATE, "hg_ap_at: the last ranking was a step of hg_map_begin in its own workspace: rank with hg_topr / hg_map first");
+    if (!host_Rs) return fail(HG_ERR_ARG, "hg_ap_at: null pointer");
+    if (nR < 1 || nR > AA_MAX_R) return fail(HG_ERR_ARG, "hg_ap_at: %d cut-offs (1..%d)", nR, AA_MAX_R);
+    const i64 Q = c->geo.Q, R = c->geo.R;
+    for (int j = 0; j < nR; ++j)
+        if (host_Rs[j] < 1 || host_Rs[j] > R || (j > 0 && host_Rs[j] <= host_Rs[j - 1]))
+            return fail(HG_ERR_ARG, "hg_ap_at: Rs must be strictly ascending within 1..R (R=%lld of the last ranking; Rs[%d]=%lld)", (long long)R, j, (long long)host_Rs[j]);
+    const i64 Rmax = host_Rs[nR - 1];
+    // host image of the tables: the cut-offs, the full chunk's tree, one tree per cut-off for its last chunk
+    const size_t o_shapes = AA_MAX_R * 8, tab = o_shapes + sizeof(ApShape) * (size_t)(1 + nR);
+    std::vector<char> img(tab, 0);
+    memcpy(img.data(), host_Rs, (size_t)nR * 8);
+    ApShape* sh = reinterpret_cast<ApShape*>(img.data() + o_shapes);
+    build_shape(AP_CHUNK, sh[0]);
+    for (int j = 0; j < nR; ++j) build_shape((int)(host_Rs[j] % AP_CHUNK), sh[1 + j]);
+    const size_t n = (size_t)Q * nR;
+    const unsigned long long e0 = g_alloc_epoch.load();
+    HG_TRY(c->aa_tab.reserve(tab));
+    HG_TRY(c->aa_out.reserve(n * 12));
+    // reciprocals of the ranks (ensure_ap_tables' rule: lists beyond 2^20 divide): the ranking's table if it is there, else one of its own
+    const bool use_recip = c->opt.ap_recip && Rmax <= (1ll << 20);
+    const double* recip = nullptr;
+    if (use_recip && c->recip_for_R == R && c->ap_recip.p) {
+        recip = c->ap_recip.as<double>();
+    } else if (use_recip) {
+        if (c->aa_recip_n < Rmax) {
+            HG_TRY(c->aa_recip.reserve((size_t)(Rmax + 1 + AP_RECIP_SLACK) * 8));
+            hipLaunchKernelGGL(k_recip_table, dim3(grid_for(Rmax + 1 + AP_RECIP_SLACK)), dim3(256), 0, c->stream, c->aa_recip.as<double>(), Rmax + AP_RECIP_SLACK);
+            HG_TRY(c->check_launch("k_recip_table"));
+            c->aa_recip_n = Rmax;
+        }
+        recip = c->aa_recip.as<double>();
+    }
+    // (first reservations move no buffer hg_map_begin's licence to enqueue blind was given for)
+    if (c->map_warm_epoch == e0) c->map_warm_epoch = g_alloc_epoch;
+    HG_HIP(hipMemcpyAsync(c->aa_tab.p, img.data(), tab, hipMemcpyHostToDevice, c->stream));
+    ApAtArgs a;
+    a.mbits = c->mbits.as<u64>(); a.RW = c->RW;
+    a.Rs = c->aa_tab.as<i64>(); a.shapes = (const ApShape*)(c->aa_tab.as<char>() + o_shapes);
+    a.recip = recip;
+    a.ap = c->aa_out.as<double>(); a.rel = (u32*)(c->aa_out.as<char>() + n * 8);
+    a.nR = nR;
+    // few queries with long lists: four times the threads per query (do_ap_range's rule, on the longest list)
+    const bool wide = Q * 2 < (i64)c->n_cu * 8 && Rmax > 2 * AP_CHUNK && c->opt.ap_wide;
+    c->t_begin(KI_AP_AT);
+    if (Q > 0 && wide) hipLaunchKernelGGL(k_ap_at<512>, dim3((unsigned)Q), dim3(512), 0, c->stream, a);
+    else if (Q > 0) hipLaunchKernelGGL(k_ap_at<AP_THREADS>, dim3((unsigned)Q), dim3(AP_THREADS), 0, c->stream, a);
+    c->t_end();
+    HG_TRY(c->check_launch("k_ap_at"));
+    HG_TRY(c->sync());                                 // (the host image goes out of scope)
+    c->aa_done = true;
+    c->aa_q_gen = c->q_gen; c->aa_db_gen = c->db_gen;
+    c->aa_Q = Q; c->aa_nR = nR;
+    return HG_OK;
+}
+
 int hg_hist_buffer(hg_ctx* c, void** dev_ptr, int64_t* nbytes) {
     HG_TRY(need(c, ST_DB | ST_Q, "hg_hist_buffer", "hg_hist / hg_sample_hist / hg_select_candidates"));
     if (!c->hown.p) return fail(HG_ERR_STATE, "hg_hist_buffer: no histogram computed yet");
@@ -394,6 +460,8 @@ extern "C++" int set_R(hg_ctx* c, int64_t R, int G, int rank) {
         return fail(HG_ERR_ARG, "R=%lld outside 1..N (N=%lld rows in the database)", (long long)R, (long long)c->n_total);
     c->R = R; c->G = G; c->rank = rank;
     c->gr_done = c->gr_kept = false;                   // every ranking comes through here: hg_graded's tables were the previous lists'
+    c->aa_done = false;                                // ... and hg_ap_at's the previous bitmap's
+    c->mbits_merged = c->mbits_in_ws_b = false;
     c->geo.R = R;
     c->RW = (R + 63) / 64;
     return HG_OK;
@@ -969,6 +1037,8 @@ static int merge_ranked_range(hg_ctx* c, const uint32_t* dev_hist_all, const uin
     HG_TRY(c->check_launch("k_merge_ranked"));
     std::swap(c->mbits, c->mbits2);                    // the global bitmap is what hg_ap and hg_get_match see
     c->ranked_local = false;
+    c->aa_done = false;
+    c->mbits_merged = q0 == 0 && nq == g.Q;
     c->G = G;
     return HG_OK;
 }
@@ -1798,6 +1868,8 @@ int hg_map_begin(hg_ctx* c, int64_t R) {
         const bool two = c->opt.step_streams >= 2 && c->own_stream && c->timing == 0 && !c->capturing;
         bool prepped = false;
         if (two) HG_TRY(prepare_shared(c, R, &prepped));
+        c->aa_done = false;                            // (a ranking that does not come through set_R: hg_ap_at's tables were the previous bitmap's)
+        c->mbits_in_ws_b = two && slot == 1;
         if (two && slot == 1) {
             HG_TRY(enqueue_bet_on_b(c, m, R, stride, prepped));
         } else {

@@ -18,10 +18,28 @@ so AP@R depends on how the rows happen to be ordered inside each tie group.  tie
 AP@R over all those orders, the probability that the top R hold a hit, and the exact minimum and maximum, per query -- a function
 of the relevant-row histogram and R alone (Context.tie_ap), no ranking and no lists; tie_aware_precision_recall_at_k the expected
 precision and recall at k from the same call.  Shuffling the database rows leaves every one of these bits unchanged.
+
+Many cut-offs from one ranking: map_at_k gives mAP@k, precision@k and recall@k for up to 64 cut-offs -- binary codes or real-valued
+features, host or device arrays -- from ONE ranking at max(ks): the top k is a prefix of the top max(ks), and Context.ap_at walks the
+match bitmap that ranking left once per query for all of them (hg_ap_at; every AP with the bits a ranking at that k alone gives).
+What comes to the host is two [Q, len(ks)] tables and the relevant-row histogram; map_from_ap_tables is the reduction alone.
+precision_recall_at_k takes its hits from the same pass.
 """
 import numpy as np
 
 from . import metric
+
+
+def _load_sided(eng, q_codes, db_codes, q_labels, db_labels):
+    """_load for tables as metric._sides hands them over: host arrays or device descriptors."""
+    metric._load_database(eng, db_codes, db_labels, "codes")
+    qbad = metric._set_queries(eng, q_codes, q_labels)
+    if qbad[1]:
+        raise ValueError("labels must be {0,1} indicator matrices")
+    qk, dk = metric._kind(eng.ctx, 1), eng.db_kind
+    if not (qk == dk and qk in ("pm1", "bits")):
+        raise ValueError("codes must be binary: all {-1,+1} or all {0,1} (found %s queries, %s database)" % (qk, dk))
+    return eng.ctx
 
 
 def _load(eng, q_codes, db_codes, q_labels, db_labels):
@@ -77,24 +95,12 @@ def hamming_radius_curves(q_codes, db_codes, q_labels, db_labels, device=0):
 
 
 MAX_CLASSES = 255      # a grade is a byte on the GPU
-MAX_CUTOFFS = 64
+MAX_CUTOFFS = metric.MAX_CUTOFFS
 
 
 def _check_ks(ks, N):
     """-> int64 array; strictly ascending values in 1..N, at most MAX_CUTOFFS of them."""
-    ks = np.asarray(ks)
-    if ks.ndim != 1 or ks.size == 0:
-        raise ValueError("ks must be a non-empty list of cut-offs")
-    if ks.dtype.kind not in "iu":
-        raise ValueError("ks must be integers")
-    ks = ks.astype(np.int64)
-    if ks.size > MAX_CUTOFFS:
-        raise ValueError("at most %d cut-offs per call (have %d)" % (MAX_CUTOFFS, ks.size))
-    if (np.diff(ks) <= 0).any():
-        raise ValueError("ks must be strictly ascending")
-    if ks[0] < 1 or (N is not None and ks[-1] > N):
-        raise ValueError("every k must be in 1..N")
-    return ks
+    return metric._check_cutoffs(ks, N, "ks")
 
 
 def gain_table(gain, C):
@@ -268,22 +274,88 @@ def tie_aware_precision_recall_at_k(q_codes, db_codes, q_labels, db_labels, ks, 
     return precision, recall
 
 
-def precision_recall_at_k(q_codes, db_codes, q_labels, db_labels, ks, device=0):
-    """Mean precision@k and recall@k over the queries, Hamming ranking with the canonical tie order.
-    recall uses the number of relevant rows in the WHOLE database; queries without any are skipped
-    for recall.  -> (precision [len(ks)], recall [len(ks)])"""
-    ks = np.asarray(sorted(int(k) for k in ks), dtype=np.int64)
-    N = np.asarray(db_codes).shape[0]
-    if ks[0] < 1 or ks[-1] > N:
-        raise ValueError("every k must be in 1..N")
+def _ap_at_tables(q, db, q_labels, db_labels, ks, features, device):
+    """One ranking at ks[-1] (ks: strictly ascending int64, any number of them: passes of 64), every cut-off from its match
+    bitmap.  The four arrays as metric._sides hands them over.  -> (ap float64 [Q, nk], hits int64 [Q, nk], total_rel int64 [Q])"""
     eng = metric._Shared.get(device)
     with eng.lock:
-        ctx = _load(eng, q_codes, db_codes, q_labels, db_labels)
-        ctx.topr(int(ks[-1]))                                            # ranked once, for the hits at k
-        match = ctx.get_match()
-        total_rel = _tables(ctx)[1].sum(1)                               # relevant rows in the whole database, per query
-    cum = np.cumsum(match.astype(np.int64), axis=1)                      # [Q, kmax]
-    hits = cum[:, ks - 1]
+        if features:
+            metric._load_database(eng, db, db_labels, "reference", floats=1)
+            if metric._set_queries(eng, q, q_labels)[1]:
+                raise ValueError("labels must be {0,1} indicator matrices")
+            ctx = eng.ctx
+            ctx.topr_real(int(ks[-1]), download=False)                   # ranked once; the lists stay on the device
+        else:
+            ctx = _load_sided(eng, q, db, q_labels, db_labels)
+            ctx.topr(int(ks[-1]))
+        ap, hits = [], []
+        for i in range(0, len(ks), MAX_CUTOFFS):
+            ctx.ap_at(ks[i:i + MAX_CUTOFFS])
+            a, h = ctx.get_ap_at()
+            ap.append(a)
+            hits.append(h)
+        total_rel = _tables(ctx)[1].sum(1)                               # relevant rows in the whole database, per query (a device table)
+    return np.concatenate(ap, axis=1), np.concatenate(hits, axis=1), total_rel
+
+
+def map_from_ap_tables(ap, hits, total_rel, ks):
+    """mAP@k, precision@k and recall@k from the device tables (NumPy only).  ap [Q, len(ks)]: AP@k per query, NaN where the top k
+    hold no hit; hits [Q, len(ks)]: relevant rows among the top k; total_rel [Q]: relevant rows in the whole database.
+    map[j] = metric.mean_over_hits of column j -- the reference's mean over the queries with a hit (metric.py:22-24), NaN when none
+    has; precision[j] = mean over ALL queries of hits / k; recall[j] = mean of hits / total_rel over the queries that have
+    relevant rows (NaN if none has): precision_recall_at_k's conventions.
+    -> dict(map, precision, recall [len(ks)], per_query=dict(ap, hits [Q, len(ks)], total_rel [Q]))"""
+    ks = _check_ks(ks, None)
+    ap = np.asarray(ap, dtype=np.float64)
+    hits = np.asarray(hits, dtype=np.int64)
+    total_rel = np.asarray(total_rel, dtype=np.int64)
+    if ap.ndim != 2 or ap.shape != hits.shape or ap.shape[1] != ks.size or total_rel.shape != ap.shape[:1]:
+        raise ValueError("ap and hits must be [Q, len(ks)] tables and total_rel [Q]")
+    m = np.full(ks.size, np.nan)
+    for j in range(ks.size):
+        if (hits[:, j] != 0).any():
+            m[j] = metric.mean_over_hits(np.ascontiguousarray(ap[:, j]), np.ascontiguousarray(hits[:, j]))
+    precision = (hits / ks[None, :]).mean(0) if ap.shape[0] else np.full(ks.size, np.nan)
+    ok = total_rel > 0
+    recall = (hits[ok] / total_rel[ok, None]).mean(0) if ok.any() else np.full(ks.size, np.nan)
+    return {"map": m, "precision": precision, "recall": recall, "per_query": {"ap": ap, "hits": hits, "total_rel": total_rel}}
+
+
+def map_at_k(q, db, q_labels, db_labels, ks, features=False, device=0):
+    """mAP@k, precision@k and recall@k at the strictly ascending cut-offs ks (at most 64, each in 1..N) from ONE ranking at max(ks).
+    features=False: q and db are binary codes ({0,1} or +-1), ranked by Hamming distance, ties by index, like MAP;
+    features=True: real-valued features (up to 255), ranked by float32 inner product descending, ties by index, like
+    MAPs.get_maps_by_feature.  Every array may be a host array or lie in device memory (a torch tensor on the device, anything with
+    __cuda_array_interface__, a DeviceArray; the two arrays of one table on the same side).  AP@k of every query has the bits
+    MAP_per_query / Context.map_real give at R = k.  The ranking, the walk over the match bitmap (Context.ap_at) and the recall
+    denominator (Context.rel_hist) run on the GPU; two [Q, len(ks)] tables come to the host.  -> map_from_ap_tables' dict"""
+    db, db_labels = metric._sides(db, db_labels, "database")
+    q, q_labels = metric._sides(q, q_labels, "query")
+    metric._check_shapes(q, db, q_labels, db_labels, 1)
+    ks = _check_ks(ks, db.shape[0])
+    if features and db.shape[1] > 255:
+        raise ValueError("inner-product ranking supports up to 255 features (have %d)" % db.shape[1])
+    ap, hits, total_rel = _ap_at_tables(q, db, q_labels, db_labels, ks, features, device)
+    return map_from_ap_tables(ap, hits, total_rel, ks)
+
+
+def precision_recall_at_k(q_codes, db_codes, q_labels, db_labels, ks, device=0, features=False):
+    """Mean precision@k and recall@k over the queries, Hamming ranking with the canonical tie order (features=True: real-valued
+    features ranked by inner product, like map_at_k).  recall uses the number of relevant rows in the WHOLE database; queries
+    without any are skipped for recall.  ks: any number of cut-offs in any order, repeats allowed; the results are in ascending
+    order of k.  Ranked once at max(ks); the hits at every k come from one walk over the match bitmap per 64 distinct cut-offs
+    (Context.ap_at): nothing of size Q x k on the host.  -> (precision [len(ks)], recall [len(ks)])"""
+    ks = np.asarray(sorted(int(k) for k in ks), dtype=np.int64)
+    db_codes, db_labels = metric._sides(db_codes, db_labels, "database")
+    q_codes, q_labels = metric._sides(q_codes, q_labels, "query")
+    N = db_codes.shape[0]
+    if ks[0] < 1 or ks[-1] > N:
+        raise ValueError("every k must be in 1..N")
+    if features and db_codes.shape[1] > 255:
+        raise ValueError("inner-product ranking supports up to 255 features (have %d)" % db_codes.shape[1])
+    uniq, back = np.unique(ks, return_inverse=True)
+    _, hits, total_rel = _ap_at_tables(q_codes, db_codes, q_labels, db_labels, uniq, features, device)
+    hits = hits[:, back]
     precision = (hits / ks[None, :]).mean(0)
     ok = total_rel > 0
     recall = (hits[ok] / total_rel[ok, None]).mean(0) if ok.any() else np.full(len(ks), np.nan)

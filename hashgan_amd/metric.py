@@ -245,6 +245,36 @@ def _check_shapes(q_codes, db_codes, q_labels, db_labels, R):
         raise ValueError("R=%d must be in 1..N (N=%d database rows)" % (R, N))
 
 
+MAX_CUTOFFS = 64       # cut-offs one hg_ap_at pass takes
+
+
+def _check_cutoffs(Rs, N, what="Rs"):
+    """-> int64 array: 1..MAX_CUTOFFS strictly ascending integer cut-offs, each in 1..N (N None: no upper bound yet)."""
+    Rs = np.asarray(Rs)
+    if Rs.ndim != 1 or Rs.size == 0:
+        raise ValueError("%s must be a non-empty list of cut-offs" % what)
+    if Rs.dtype.kind not in "iu":
+        raise ValueError("%s must be integers" % what)
+    Rs = Rs.astype(np.int64)
+    if Rs.size > MAX_CUTOFFS:
+        raise ValueError("at most %d cut-offs per call (have %d)" % (MAX_CUTOFFS, Rs.size))
+    if (np.diff(Rs) <= 0).any():
+        raise ValueError("%s must be strictly ascending" % what)
+    if Rs[0] < 1 or (N is not None and Rs[-1] > N):
+        raise ValueError("every cut-off must be in 1..N")
+    return Rs
+
+
+def _ap_at(ctx, Rs, real):
+    """One ranking at the largest cut-off, then every cut-off from its match bitmap (hg_ap_at) -> (ap [Q, nR], rel [Q, nR])."""
+    if real:
+        ctx.topr_real(int(Rs[-1]), download=False)
+    else:
+        ctx.topr(int(Rs[-1]))
+    ctx.ap_at(Rs)
+    return ctx.get_ap_at()
+
+
 def _kind(ctx, which):
     """What hg_set_*_f32 found in a float table: 'ones' (every entry +1: reads as either spelling), 'pm1' (every
     entry +-1), 'bits' (every entry 0/1), 'ternary' (-1/0/+1 mixed) or 'real'."""
@@ -286,8 +316,9 @@ def _set_queries(eng, q_codes, q_labels):
     return eng.ctx.set_queries_f32(q_codes, q_labels)
 
 
-def _rank(eng, q_codes, q_labels, R, mode):
-    """Queries against the engine's resident database.  mode:
+def _rank(eng, q_codes, q_labels, R, mode, Rs=None):
+    """Queries against the engine's resident database -> (ap [Q], rel [Q]) at R, or with Rs (ascending cut-offs, R ignored)
+    (ap [Q, nR], rel [Q, nR]) from one ranking at Rs[-1] (_ap_at).  mode:
        'reference'  MAPs: what np.dot ranks (metric.py:13-14).  +-1 codes on both sides -> Hamming kernels (the same
                     order, ties by index); anything else -- real-valued tanh outputs, {0,1} bits (np.dot counts common
                     ones, not a Hamming distance), codes with zeros -- goes through the float32 inner-product ranking;
@@ -299,10 +330,10 @@ def _rank(eng, q_codes, q_labels, R, mode):
         raise ValueError("labels must be {0,1} indicator matrices")
     qk, dk = _kind(eng.ctx, 1), eng.db_kind
     if mode == "sign" or {qk, dk} <= {"pm1", "ones"}:
-        return eng.average_precisions(R)
+        return eng.average_precisions(R) if Rs is None else _ap_at(eng.ctx, Rs, False)
     if mode == "codes":
         if {qk, dk} <= {"bits", "ones"}:
-            return eng.average_precisions(R)
+            return eng.average_precisions(R) if Rs is None else _ap_at(eng.ctx, Rs, False)
         raise ValueError("codes must be binary -- all {0,1} or all {-1,+1}, the same spelling for queries and "
                          "database (found %s queries, %s database); binarise first (np.sign), or hand real-valued "
                          "features to MAPs.get_maps_by_feature, which ranks them by inner product like metric.py:13" % (qk, dk))
@@ -314,6 +345,8 @@ def _rank(eng, q_codes, q_labels, R, mode):
             raise ValueError("the resident database holds no float features: load it again")
         _load_database(eng, src[0], src[1], floats=1)
         _set_queries(eng, q_codes, q_labels)
+    if Rs is not None:
+        return _ap_at(eng.ctx, Rs, True)
     return eng.ctx.map_real(R)
 
 
@@ -447,6 +480,44 @@ class MAPs:
                 raise ValueError("R=%d must be in 1..N (N=%d database rows)" % (R, eng.N))
             ap, rel = self._guard(_rank, eng, q_codes, q_labels, R, "sign" if self.binarize else "reference")
         return mean_over_hits(ap, rel)
+
+
+    def get_maps_at(self, database, query, Rs):
+        """mAP@R for every R of the strictly ascending cut-offs Rs (at most 64, each in 1..N) from ONE ranking at Rs[-1]: the top R is
+        a prefix of the top Rs[-1], and each entry has the bits MAPs(R).get_maps_by_feature(database, query) returns.  Database
+        residency, `binarize` and the routing (+-1 codes by Hamming distance, anything else by inner product) are
+        get_maps_by_feature's; self.R is not used.  -> float64 [len(Rs)]"""
+        q_codes, q_labels = _sides(query.output, query.label, "query")
+        Rs = _check_cutoffs(Rs, None)
+        if q_codes.ndim != 2 or q_labels.ndim != 2 or q_labels.shape[0] != q_codes.shape[0]:
+            raise ValueError("query.output must be [Q, b] and query.label [Q, C]")
+        if database is not None:                       # (what can be refused before any GPU use is)
+            out, lab = _sides(database.output, database.label, "database")
+            if out.ndim != 2 or lab.ndim != 2 or out.shape[0] != lab.shape[0]:
+                raise ValueError("database.output must be [N, b] and database.label [N, C]")
+            if q_codes.shape[1] != out.shape[1]:
+                raise ValueError("query and database codes must be [n, b] with the same b")
+            if q_labels.shape[1] != lab.shape[1]:
+                raise ValueError("query labels must be [Q, C] with the database's C")
+            if Rs[-1] > out.shape[0]:
+                raise ValueError("R=%d must be in 1..N (N=%d database rows)" % (Rs[-1], out.shape[0]))
+        with self._lock:
+            self._ensure_database(database)
+            eng = self._engine()
+            if eng.b is None:
+                self._resident = None
+                raise ValueError("no resident database: the last load failed")
+            if q_codes.shape[1] != eng.b:
+                raise ValueError("query and database codes must be [n, b] with the same b")
+            if q_labels.shape[1] != eng.C:
+                raise ValueError("query labels must be [Q, C] with the database's C")
+            if Rs[-1] > eng.N:
+                raise ValueError("R=%d must be in 1..N (N=%d database rows)" % (Rs[-1], eng.N))
+            ap, rel = self._guard(_rank, eng, q_codes, q_labels, int(Rs[-1]), "sign" if self.binarize else "reference", Rs)
+        out = np.empty(len(Rs), dtype=np.float64)
+        for j in range(len(Rs)):
+            out[j] = mean_over_hits(np.ascontiguousarray(ap[:, j]), np.ascontiguousarray(rel[:, j]))
+        return out
 
 
 def MAP(query_codes, db_codes, query_labels, db_labels, R, device=0):

@@ -306,6 +306,22 @@ int hg_tie_ap(hg_ctx* ctx, const int64_t* host_Rs, int nR);
 int hg_get_tie_ap(hg_ctx* ctx, double* host_ap_exp, double* host_p_hit, double* host_ap_min, double* host_ap_max,
                   double* host_rel_exp, int64_t* host_rel_lo, int64_t* host_rel_hi);   /* [Q][nR] each; null: skipped */
 
+/* ---- AP, precision and recall at many cut-offs from one ranking ------------------------------------------------------------------
+ * The canonical order is total, so the top Rs[j] is a prefix of the top R: hg_ap_at walks the match bitmap the last ranking left --
+ * hg_topr, hg_topr_real, hg_map, hg_map_real, a staged sequence up to hg_match, a merge of all queries -- once per query and gives,
+ * for every cut-off, ap[q][j] with the very bits hg_ap gives after a ranking at R = Rs[j] (NaN where the top Rs[j] hold no hit) and
+ * rel[q][j], the hits among the top Rs[j] (precision@k = rel / k; recall@k = rel / hg_rel_hist's total).  One kernel launch (k_ap_at).
+ * Precondition: hg_ap's (the match stage), in global rank order for all Q queries: HG_ERR_STATE for a bitmap in a shard's local
+ * rank order (hg_select_ranked before its merge), for a shard's own part of a bitmap (G > 1 before hg_merge_match / hg_merge_ranked),
+ * after a merge of a query range only, and after a step of hg_map_begin that ran in the second stream's workspace.
+ * Rs: nR (1..64) strictly ascending values in 1..R of the last ranking, anything else HG_ERR_ARG; copied before the call returns.
+ * float64 throughout, no atomics: equal inputs give equal bits whatever Q and the other cut-offs are.  Tables and buffers of its own:
+ * stage, hg_ap's results, lists, the one-R AP tables and a step of hg_map_begin in flight are left as they were.  Results belong to the
+ * bitmap they were computed on: a later ranking, hg_match, hg_merge_match / hg_merge_ranked, a database or query reload and hg_trim
+ * invalidate them (hg_get_ap_at then returns HG_ERR_STATE, as it does before the first pass). */
+int hg_ap_at(hg_ctx* ctx, const int64_t* host_Rs, int nR);
+int hg_get_ap_at(hg_ctx* ctx, double* host_ap, int64_t* host_rel);   /* [Q][nR] each; null: skipped */
+
 /* ---- collectives: RCCL over xGMI, one process per GPU (the reference has no counterpart --
  * main.py:260-263 only sets CUDA_VISIBLE_DEVICES) --------------------------------------------------------
  * librccl.so.1 is dlopen'ed by the first hg_comm_* call (HG_RCCL_LIBRARY overrides the search); a single-GPU
@@ -387,10 +403,10 @@ int hg_set_stream(hg_ctx* ctx, void* hip_stream);
  *                 ALU), "real_sample_half" (1: the sampled cut's scores in the filter's 16-bit arithmetic -- they only place the cut; 0: exact float32 chains), "real_second_sample" (1: a second, counting sample four times as large tightens that cut), "real_sort_lds" (1: ranked by the LDS-resident kernel when the records fit), "real_groups" (1: lists beyond the LDS ordered group by group), "real_map_lists" (0; 1: hg_map_real also writes the ranked idx / score lists), "real_whole_rounds" (3: without a cut -- R = N -- the database is cut so that k_real_select_mx's blocks fill whole rounds of that many per CU; 0: the plain geometry)
  *   ("probe_select" exists only in the measurement build, python -m hashgan_amd.build --probes) */
 int hg_set_option(hg_ctx* ctx, const char* key, int64_t value);
-/* Counters and facts about the last call (24 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
+/* Counters and facts about the last call (25 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
  * "optimistic_requeried" (single queries rerun exactly after losing their bet), "optimistic_rebets" (second and widened bets), "last_optimistic",
  * "rank_leftovers" (queries the LDS-resident rank kernel left to the general one), "select_variant" (1 k_select, 2 k_select_dense, 3 k_select_mx,
- * 5 k_select_mx3, 6 k_select_mx4), "rank_variant" (1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>), "rel_hist_variant" (the kernel of the last hg_rel_hist: 1 k_hist_rel, the vector-ALU pass -- the only one so far, whatever "hist_mfma" says; 0: no pass yet), "ap_fused",
+ * 5 k_select_mx3, 6 k_select_mx4), "rank_variant" (1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>), "rel_hist_variant" (the kernel of the last hg_rel_hist: 1 k_hist_rel, the vector-ALU pass -- the only one so far, whatever "hist_mfma" says; 0: no pass yet), "ap_at_cutoffs" (cut-offs of the last hg_ap_at; 0: no pass yet), "ap_fused",
  * "cap_boost", "crowding_x100", "segments", "records_kept" (records the last bet's select left in the slices: a download, not part of a step),
  * "device_bytes" (every device buffer the context and its requery child hold, the second stream's workspace included), "graph_replays", "map_async_steps" / "map_async_redone" / "map_overlapped_steps" (hg_map_begin: steps enqueued blind / of those, run again by hg_map_end /
  * of those, run on the second stream);
