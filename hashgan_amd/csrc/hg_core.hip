@@ -1264,6 +1264,8 @@ int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "rank_leftovers")) *value = c->rank_leftovers;
     else if (!strcmp(key, "select_variant")) *value = c->last_select;
     else if (!strcmp(key, "rank_variant")) *value = c->last_rank;
+    else if (!strcmp(key, "rank_lds_recs")) *value = c->last_lds_recs;
+    else if (!strcmp(key, "slice_cap")) *value = c->cap;
     else if (!strcmp(key, "rel_hist_variant")) *value = c->last_rel_hist;
     else if (!strcmp(key, "ap_at_cutoffs")) *value = c->aa_nR;
     else if (!strcmp(key, "ap_fused")) *value = c->ap_fused ? 1 : 0;

@@ -769,6 +769,7 @@ static int launch_rank(hg_ctx* c, int mode, const StepReq& req, bool leftovers_o
             c->t_end();
             HG_TRY(c->check_launch("k_rank_lean"));
             c->last_rank = 6;
+            c->last_lds_recs = rb;
             if (fuse) {
                 c->ap_fused = true;
                 HG_TRY(rank_leftovers_inline(c, req, mode, use_recip));
@@ -819,6 +820,7 @@ static int launch_rank(hg_ctx* c, int mode, const StepReq& req, bool leftovers_o
             c->t_end();
             HG_TRY(c->check_launch("k_rank_cnt"));
             c->last_rank = 3;
+            c->last_lds_recs = r2;
             if (fuse) { c->ap_fused = true; if (c->rec8) HG_TRY(rank_leftovers_inline(c, req, mode, use_recip)); return HG_OK; }
             only = c->bigq.as<u32>();                // k_rank_fused below ranks what this path declined
             counted = true;
@@ -1753,7 +1755,11 @@ static int run_oneshot(hg_ctx* c, int64_t R, bool lists, bool with_ap) {
         c->bet_consecutive_fail++;
     }
     if (exact_mx_applies(c, R)) {
-        HG_TRY(run_attempt(c, AT_EXACT_MX, R, 0, StepReq{}, with_ap, &flag));
+        // (hg_map: the AP from the rank kernel's epilogue, as in the bet it shares the rank stage with -- and what that kernel
+        // declines is counted in "rank_leftovers" and ranked by finish_leftovers, the same way)
+        StepReq mx;
+        mx.fuse_ap = with_ap && !lists;
+        HG_TRY(run_attempt(c, AT_EXACT_MX, R, 0, mx, with_ap, &flag));
         if (!flag) return HG_OK;                   // (else a slice overflowed: the vector-ALU select with exact-sized slices)
     }
     StepReq exact;

@@ -12,7 +12,8 @@ from hashgan_amd import _native, metric, sharded
 pytestmark = pytest.mark.gpu
 
 
-def _run_virtual(c, G, gather_topr, defer=False, routed=True):
+def _run_virtual(c, G, gather_topr, defer=False, routed=True, options=None):
+    """options: engine options (hg_set_option) set on every shard's context before its tables are loaded."""
     N = c["dbbits"].shape[0]
     qw, ql = metric.pack_codes(c["qbits"]), metric.pack_labels(c["qlab"])
     comms = sharded.LocalComm.create(G)
@@ -25,6 +26,8 @@ def _run_virtual(c, G, gather_topr, defer=False, routed=True):
         try:
             base, rows = sharded.shard_bounds(N, G)[r]
             ctx = _native.Context(0)
+            for key, value in (options or {}).items():
+                ctx.set_option(key, value)
             ctx.set_database(metric.pack_codes(c["dbbits"][base:base + rows]), metric.pack_labels(c["dblab"][base:base + rows]),
                              c["b"], c["dblab"].shape[1], idx_base=base, n_total=N)
             ctx.set_queries(qw, ql)
