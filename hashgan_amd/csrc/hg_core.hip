@@ -1264,6 +1264,7 @@ int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "rank_leftovers")) *value = c->rank_leftovers;
     else if (!strcmp(key, "select_variant")) *value = c->last_select;
     else if (!strcmp(key, "rank_variant")) *value = c->last_rank;
+    else if (!strcmp(key, "hist_variant")) *value = c->last_hist;
     else if (!strcmp(key, "rank_lds_recs")) *value = c->last_lds_recs;
     else if (!strcmp(key, "slice_cap")) *value = c->cap;
     else if (!strcmp(key, "rel_hist_variant")) *value = c->last_rel_hist;

@@ -313,6 +313,7 @@ struct StepState {
     bool leftovers_inline = false;     // ... and the step ranked those leftovers itself within the stream (rank_leftovers_inline)
     int last_select = 0;       // stat "select_variant": 1 k_select, 2 k_select_dense, 3 k_select_mx, 5 k_select_mx3, 6 k_select_mx4
     int last_rank = 0;         // stat "rank_variant": 1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>
+    int last_hist = 0;         // stat "hist_variant": 1 k_hist, 2 k_hist_mx, 3 k_hist_i8; + 4: the matrix-core kernel's counters were dwords (else 16-bit halves)
     i64 last_lds_recs = 0;     // stat "rank_lds_recs": the record capacity handed to the last k_rank_lean / k_rank_cnt launch (RankLdsArgs::lds_recs)
 };
 

@@ -52,6 +52,7 @@ template <int NW> int launch_hist_mx_t(hg_ctx* c) {
     const i64 visited_per_pair = 2 * tiles_per_half * 16;
     const bool pack16 = visited_per_pair < 65536;
     const size_t lds = (size_t)WPB * (pack16 ? 1 : 2) * g.NB * 32 * 4;
+    c->last_hist = pack16 ? 2 : 6;
     c->t_begin(KI_HIST);
     if (pack16) {
         hipLaunchKernelGGL((k_hist_mx<NW, true>), dim3(padded_grid(g.nBlk)), dim3(256), lds, c->stream, c->qc.as<u32>(), c->qx.as<u8>(),
@@ -131,6 +132,7 @@ template <int NW> int launch_hist_i8_t(hg_ctx* c) {
     const i64 tiles_per_half = ((g.L + 15) / 16 + g.hist_stride - 1) / g.hist_stride;
     const bool pack16 = 2 * tiles_per_half * 16 < 65536;
     const size_t lds = (size_t)WPB * hist_i8_cols(pack16) * g.NB * 32 * 4;
+    c->last_hist = pack16 ? 3 : 7;
     c->t_begin(KI_HIST);
     if (pack16) {
         if (lds > 64 * 1024)

@@ -14,6 +14,7 @@ template <int NW> int launch_hist_t(hg_ctx* c) {
     const size_t lds = (size_t)wpb * g.NB * 256;
     if (lds > 64 * 1024)
         HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hist<NW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    c->last_hist = 1;
     c->t_begin(KI_HIST);
     hipLaunchKernelGGL(k_hist<NW>, dim3(padded_grid(g.nBlk)), dim3(64 * wpb), lds, c->stream,
                        c->qc.as<u32>(), c->db.as<u32>(), c->hist.as<u32>(), g);

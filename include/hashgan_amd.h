@@ -403,10 +403,10 @@ int hg_set_stream(hg_ctx* ctx, void* hip_stream);
  *                 ALU), "real_sample_half" (1: the sampled cut's scores in the filter's 16-bit arithmetic -- they only place the cut; 0: exact float32 chains), "real_second_sample" (1: a second, counting sample four times as large tightens that cut), "real_sort_lds" (1: ranked by the LDS-resident kernel when the records fit), "real_groups" (1: lists beyond the LDS ordered group by group), "real_map_lists" (0; 1: hg_map_real also writes the ranked idx / score lists), "real_whole_rounds" (3: without a cut -- R = N -- the database is cut so that k_real_select_mx's blocks fill whole rounds of that many per CU; 0: the plain geometry)
  *   ("probe_select" exists only in the measurement build, python -m hashgan_amd.build --probes) */
 int hg_set_option(hg_ctx* ctx, const char* key, int64_t value);
-/* Counters and facts about the last call (27 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
+/* Counters and facts about the last call (28 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
  * "optimistic_requeried" (single queries rerun exactly after losing their bet), "optimistic_rebets" (second and widened bets), "last_optimistic",
  * "rank_leftovers" (queries the LDS-resident rank kernel left to the general one), "select_variant" (1 k_select, 2 k_select_dense, 3 k_select_mx,
- * 5 k_select_mx3, 6 k_select_mx4), "rank_variant" (1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>), "rank_lds_recs" (records the last k_rank_lean / k_rank_cnt launch had LDS room for), "slice_cap" (capacity of a (segment, query) slice of the last bet), "rel_hist_variant" (the kernel of the last hg_rel_hist: 1 k_hist_rel, the vector-ALU pass -- the only one so far, whatever "hist_mfma" says; 0: no pass yet), "ap_at_cutoffs" (cut-offs of the last hg_ap_at; 0: no pass yet), "ap_fused",
+ * 5 k_select_mx3, 6 k_select_mx4), "rank_variant" (1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>), "hist_variant" (the kernel of the last histogram pass, full or sampled: 1 k_hist, 2 k_hist_mx, 3 k_hist_i8; 6 / 7: k_hist_mx / k_hist_i8 with one dword counter per query tile instead of 16-bit halves; 0: no pass yet), "rank_lds_recs" (records the last k_rank_lean / k_rank_cnt launch had LDS room for), "slice_cap" (capacity of a (segment, query) slice of the last bet), "rel_hist_variant" (the kernel of the last hg_rel_hist: 1 k_hist_rel, the vector-ALU pass -- the only one so far, whatever "hist_mfma" says; 0: no pass yet), "ap_at_cutoffs" (cut-offs of the last hg_ap_at; 0: no pass yet), "ap_fused",
  * "cap_boost", "crowding_x100", "segments", "records_kept" (records the last bet's select left in the slices: a download, not part of a step),
  * "device_bytes" (every device buffer the context and its requery child hold, the second stream's workspace included), "graph_replays", "map_async_steps" / "map_async_redone" / "map_overlapped_steps" (hg_map_begin: steps enqueued blind / of those, run again by hg_map_end /
  * of those, run on the second stream);
