@@ -833,7 +833,7 @@ extern "C++" int do_match(hg_ctx* c) {
     HG_TRY(c->check_launch("k_match"));
     c->stage |= ST_MATCH;
     c->stage &= ~(unsigned)ST_AP;
-    c->aa_done = false;                                // (the bitmap hg_ap_at walked is rewritten)
+    c->bitmap_changed();
     return HG_OK;
 }
 
@@ -861,7 +861,7 @@ int hg_merge_match(hg_ctx* c, const uint64_t* dev_bits_all, int G) {
     hipLaunchKernelGGL(k_or_bits, dim3(grid_for(n)), dim3(256), 0, c->stream, (const u64*)dev_bits_all, c->mbits.as<u64>(), n, G);
     c->t_end();
     HG_TRY(c->check_launch("k_or_bits"));
-    c->aa_done = false;                                // (hg_ap_at's tables were the unmerged bitmap's)
+    c->bitmap_changed();                               // (hg_ap_at's tables were the unmerged bitmap's)
     c->mbits_merged = true;
     return c->stage_end();
 }
@@ -942,7 +942,7 @@ int hg_merge_topr(hg_ctx* c, const uint32_t* dev_idx_all, const uint8_t* dev_dis
                        (const u8*)dev_dist_all, c->out_idx.as<u32>(), c->out_dist.as<u8>(), n, G);
     c->t_end();
     HG_TRY(c->check_launch("k_min_topr"));
-    c->gr_done = c->gr_kept = false;                   // (the lists are no longer the ones hg_graded walked)
+    c->lists_changed();
     return c->stage_end();
 }
 
@@ -980,28 +980,19 @@ int hg_get_match(hg_ctx* c, uint8_t* host_imatch) {
 int hg_get_ap(hg_ctx* c, double* host_ap, int64_t* host_rel) {
     HG_TRY(need(c, ST_AP, "hg_get_ap", "hg_ap"));
     const i64 Q = c->geo.Q;
-    if (c->ap_staged && c->pin) {                      // the one-shot call already brought them over
-        const char* pb = (const char*)c->pin;
-        if (host_ap) memcpy(host_ap, pb + 16, (size_t)Q * 8);
-        if (host_rel) {
-            const u32* r = (const u32*)(pb + 16 + (size_t)Q * 8);
-            for (i64 q = 0; q < Q; ++q) host_rel[q] = r[q];
-        }
-        return HG_OK;
+    if (!(c->ap_staged && c->pin)) {                   // (else the one-shot call already brought them over)
+        // one batch of copies into pinned memory, one synchronisation; a deferred verdict rides along
+        HG_TRY(ensure_pin(c, (size_t)Q * 12 + 16));
+        char* pb = (char*)c->pin;
+        if (c->verdict_pending) HG_HIP(hipMemcpyAsync(pb, c->err.p, 4, hipMemcpyDeviceToHost, c->stream));
+        if (host_ap) HG_HIP(hipMemcpyAsync(pb + 16, c->ap.p, (size_t)Q * 8, hipMemcpyDeviceToHost, c->stream));
+        if (host_rel) HG_HIP(hipMemcpyAsync(pb + 16 + (size_t)Q * 8, c->rel.p, (size_t)Q * 4, hipMemcpyDeviceToHost, c->stream));
+        HG_TRY(c->sync());
+        if (c->verdict_pending) { c->verdict_flag = *(const int*)pb; c->verdict_known = true; }
     }
-    // one batch of copies into pinned memory, one synchronisation; a deferred verdict rides along
-    HG_TRY(ensure_pin(c, (size_t)Q * 12 + 16));
-    char* pb = (char*)c->pin;
-    if (c->verdict_pending) HG_HIP(hipMemcpyAsync(pb, c->err.p, 4, hipMemcpyDeviceToHost, c->stream));
-    if (host_ap) HG_HIP(hipMemcpyAsync(pb + 16, c->ap.p, (size_t)Q * 8, hipMemcpyDeviceToHost, c->stream));
-    if (host_rel) HG_HIP(hipMemcpyAsync(pb + 16 + (size_t)Q * 8, c->rel.p, (size_t)Q * 4, hipMemcpyDeviceToHost, c->stream));
-    HG_TRY(c->sync());
-    if (c->verdict_pending) { c->verdict_flag = *(const int*)pb; c->verdict_known = true; }
+    const char* pb = (const char*)c->pin;
     if (host_ap) memcpy(host_ap, pb + 16, (size_t)Q * 8);
-    if (host_rel) {
-        const u32* r = (const u32*)(pb + 16 + (size_t)Q * 8);
-        for (i64 q = 0; q < Q; ++q) host_rel[q] = r[q];
-    }
+    if (host_rel) widen_u32(host_rel, pb + 16 + (size_t)Q * 8, (size_t)Q);
     return HG_OK;
 }
 
@@ -1009,76 +1000,8 @@ int hg_get_hist(hg_ctx* c, uint32_t* host_hist) {
     HG_TRY(need(c, ST_HIST, "hg_get_hist", "hg_hist"));
     if (!host_hist) return fail(HG_ERR_ARG, "hg_get_hist: null pointer");
     const Geo& g = c->geo;
-    HG_HIP(hipMemcpy2DAsync(host_hist, (size_t)g.Q * 4, c->hown.p, (size_t)g.Qpad * 4, (size_t)g.Q * 4, (size_t)g.NB,
-                            hipMemcpyDeviceToHost, c->stream));
+    HG_TRY(download_pitched(c, host_hist, c->hown, g.Q, g.Qpad, g.NB));
     return c->sync();
-}
-
-int hg_get_rel_hist(hg_ctx* c, uint32_t* host_all, uint32_t* host_rel) {
-    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_rel_hist", "hg_rel_hist"));
-    if (!c->rh_done || c->rh_q_gen != c->q_gen || c->rh_db_gen != c->db_gen)
-        return fail(HG_ERR_STATE, "hg_get_rel_hist called before hg_rel_hist (on the tables loaded now)");
-    const size_t row = (size_t)c->rh_Q * 4, pitch = (size_t)c->rh_Qpad * 4;
-    if (host_all) HG_HIP(hipMemcpy2DAsync(host_all, row, c->rh_all.p, pitch, row, (size_t)c->rh_NB, hipMemcpyDeviceToHost, c->stream));
-    if (host_rel) HG_HIP(hipMemcpy2DAsync(host_rel, row, c->rh_rel.p, pitch, row, (size_t)c->rh_NB, hipMemcpyDeviceToHost, c->stream));
-    return c->sync();
-}
-
-int hg_get_graded(hg_ctx* c, int64_t* host_gsum, int64_t* host_hits, double* host_dcg, double* host_wsum) {
-    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_graded", "hg_graded"));
-    if (!c->gr_done || c->gr_q_gen != c->q_gen || c->gr_db_gen != c->db_gen)
-        return fail(HG_ERR_STATE, "hg_get_graded called before hg_graded (on the ranked lists and tables held now)");
-    const size_t plane = (size_t)c->gr_Q * c->gr_nk * 8;
-    const char* o = c->gr_out.as<char>();
-    void* dst[4] = {host_gsum, host_hits, host_dcg, host_wsum};
-    for (int i = 0; i < 4; ++i)
-        if (dst[i]) HG_HIP(hipMemcpyAsync(dst[i], o + i * plane, plane, hipMemcpyDeviceToHost, c->stream));
-    return c->sync();
-}
-
-int hg_get_grades(hg_ctx* c, uint8_t* host_grades) {
-    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_grades", "hg_graded"));
-    if (!c->gr_done || !c->gr_kept || c->gr_q_gen != c->q_gen || c->gr_db_gen != c->db_gen)
-        return fail(HG_ERR_STATE, "hg_get_grades: the last hg_graded on these lists did not keep the grade bytes (keep_grades = 0), or there was none");
-    if (!host_grades) return fail(HG_ERR_ARG, "hg_get_grades: null pointer");
-    HG_HIP(hipMemcpyAsync(host_grades, c->gr_grades.p, (size_t)c->gr_Q * c->gr_R, hipMemcpyDeviceToHost, c->stream));
-    return c->sync();
-}
-
-int hg_get_grade_hist(hg_ctx* c, uint32_t* host_hist) {
-    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_grade_hist", "hg_grade_hist"));
-    if (!c->gh_done || c->gh_q_gen != c->q_gen || c->gh_db_gen != c->db_gen)
-        return fail(HG_ERR_STATE, "hg_get_grade_hist called before hg_grade_hist (on the tables loaded now)");
-    if (!host_hist) return fail(HG_ERR_ARG, "hg_get_grade_hist: null pointer");
-    const size_t row = (size_t)c->gh_Q * 4, pitch = (size_t)c->gh_Qpad * 4;
-    HG_HIP(hipMemcpy2DAsync(host_hist, row, c->gh_tab.p, pitch, row, (size_t)c->gh_G, hipMemcpyDeviceToHost, c->stream));
-    return c->sync();
-}
-
-int hg_get_tie_ap(hg_ctx* c, double* host_ap_exp, double* host_p_hit, double* host_ap_min, double* host_ap_max, double* host_rel_exp,
-                  int64_t* host_rel_lo, int64_t* host_rel_hi) {
-    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_tie_ap", "hg_tie_ap"));
-    if (!c->ta_done || c->ta_q_gen != c->q_gen || c->ta_db_gen != c->db_gen)
-        return fail(HG_ERR_STATE, "hg_get_tie_ap called before hg_tie_ap (on the tables loaded now)");
-    const size_t plane = (size_t)c->ta_Q * c->ta_nR * 8;
-    const char* o = c->ta_out.as<char>();
-    void* dst[7] = {host_ap_exp, host_p_hit, host_ap_min, host_ap_max, host_rel_exp, host_rel_lo, host_rel_hi};
-    for (int i = 0; i < 7; ++i)
-        if (dst[i]) HG_HIP(hipMemcpyAsync(dst[i], o + i * plane, plane, hipMemcpyDeviceToHost, c->stream));
-    return c->sync();
-}
-
-int hg_get_ap_at(hg_ctx* c, double* host_ap, int64_t* host_rel) {
-    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_ap_at", "hg_ap_at"));
-    if (!c->aa_done || c->aa_q_gen != c->q_gen || c->aa_db_gen != c->db_gen)
-        return fail(HG_ERR_STATE, "hg_get_ap_at called before hg_ap_at (on the match bitmap and tables held now)");
-    const size_t n = (size_t)c->aa_Q * c->aa_nR;
-    std::vector<u32> rel(host_rel ? n : 0);
-    if (host_ap) HG_HIP(hipMemcpyAsync(host_ap, c->aa_out.p, n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (host_rel) HG_HIP(hipMemcpyAsync(rel.data(), c->aa_out.as<char>() + n * 8, n * 4, hipMemcpyDeviceToHost, c->stream));
-    HG_TRY(c->sync());
-    for (size_t i = 0; i < rel.size(); ++i) host_rel[i] = rel[i];
-    return HG_OK;
 }
 
 // Context-owned device scratch (grows only) and a stream-ordered device-to-device copy: what an in-process
@@ -1245,7 +1168,7 @@ int hg_preload(hg_ctx* c) {
     HG_TRY(ensure_pin(c, (size_t)1 << 20));
     hipFuncAttributes a;
     HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_ap<AP_THREADS>)));
-    HG_TRY(preload_seq()); HG_TRY(preload_valu()); HG_TRY(preload_mx()); HG_TRY(preload_mx1()); HG_TRY(preload_real());
+    HG_TRY(preload_seq()); HG_TRY(preload_side()); HG_TRY(preload_valu()); HG_TRY(preload_mx()); HG_TRY(preload_mx1()); HG_TRY(preload_real());
     host_pack_warm();
     return HG_OK;
 }
@@ -1268,7 +1191,7 @@ int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "rank_lds_recs")) *value = c->last_lds_recs;
     else if (!strcmp(key, "slice_cap")) *value = c->cap;
     else if (!strcmp(key, "rel_hist_variant")) *value = c->last_rel_hist;
-    else if (!strcmp(key, "ap_at_cutoffs")) *value = c->aa_nR;
+    else if (!strcmp(key, "ap_at_cutoffs")) *value = c->aa.dim;
     else if (!strcmp(key, "ap_fused")) *value = c->ap_fused ? 1 : 0;
     else if (!strcmp(key, "cap_boost")) *value = c->cap_boost;
     else if (!strcmp(key, "crowding_x100")) *value = c->crowd_x100;

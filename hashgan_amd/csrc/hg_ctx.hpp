@@ -3,6 +3,7 @@
 //
 //   hg_core.hip        context, tables (hg_set_*), options / statistics / timing, label match, AP, downloads
 //   hg_seq.hip         the Hamming sequences: geometry, histogram -> plan -> select -> rank, staged (sharded) and one-shot forms
+//   hg_side.hip        the side metrics (hg_rel_hist, hg_graded, hg_grade_hist, hg_tie_ap, hg_ap_at) and their getters: one SideResult each
 //   hg_pairs_valu.hip  launchers of the vector-ALU pair passes (k_hist, k_select, k_select_dense)
 //   hg_pairs_mx.hip    launchers of the matrix-core pair passes (k_select_mx3 / mx4, k_hist_mx, k_hist_i8) and their images
 //   hg_pairs_mx1.hip   launcher of k_select_mx (every code length: the longest compile)
@@ -356,6 +357,19 @@ struct RealState {
     i64 attempts = 0;          // stat "real_attempts": attempts of the last call (1 = the first bet held)
 };
 
+// The results of one side metric (hg_side.hip) and what they were computed from: the generations of the two tables, the rows Q, their
+// pitch Qpad (where the table is pitched), the second dimension (NB, C + 1, nk or nR).  The entry point calls begin() first and finish()
+// last, so a refused or failed call leaves none; the getters, and hg_tie_ap for the histogram it reuses, ask current().  DESIGN.md, "Side metrics: the host side".
+struct hg_ctx;
+struct SideResult {
+    bool done = false;
+    unsigned long long q_gen = 0, db_gen = 0;
+    i64 Q = 0, Qpad = 0, dim = 0;
+    void begin() { done = false; }
+    inline void finish(const hg_ctx* c, i64 Q_, i64 Qpad_, i64 dim_);
+    inline bool current(const hg_ctx* c) const;
+};
+
 struct hg_ctx : StepBufs, StepState {
     int device = 0;
     int n_cu = 256;            // compute units of the device
@@ -389,33 +403,17 @@ struct hg_ctx : StepBufs, StepState {
     bool dbx_valid = false, qx_valid = false, dbx8_valid = false, dbx3_valid = false, dbx4_valid = false;
     bool hist_pairs = false;   // the last FULL histogram pass ran per segment pair (k_hist_mx)
     i64 bet_rebets = 0;        // stat "optimistic_rebets"
-    // the relevant-row histogram (hg_rel_hist): rh_all / rh_rel hold the tables of the queries and database of these generations
-    bool rh_done = false;
-    unsigned long long rh_q_gen = 0, rh_db_gen = 0;
-    i64 rh_Q = 0, rh_Qpad = 0, rh_NB = 0;
+    // the side metrics (hg_side.hip): one record per result set, and what is a feature's own next to it
+    SideResult rh;             // hg_rel_hist: rh_all / rh_rel [NB][Qpad]
+    SideResult gr;             // hg_graded: gr_out's four tables [Q][nk] of the ranked lists it found
+    SideResult gh;             // hg_grade_hist: gh_tab [C + 1][Qpad]
+    SideResult ta;             // hg_tie_ap: ta_out's seven tables [Q][nR]
+    SideResult aa;             // hg_ap_at: aa_out, ap [Q][nR] and rel [Q][nR] of the match bitmap the last ranking left; dim is also stat "ap_at_cutoffs"
     int last_rel_hist = 0;     // stat "rel_hist_variant": 1 k_hist_rel (0: no pass yet)
-    // graded relevance (hg_graded.hpp).  gr_out holds hg_graded's four [Q][nk] tables of the ranked lists it found: any later ranking
-    // (set_R), a merge into the lists, a reload (generations) and hg_trim end that.  gh_tab is hg_grade_hist's table, kept like rh_all.
-    bool gr_done = false, gr_kept = false;     // gr_kept: gr_grades holds the grade bytes [Q][R] of that pass
-    unsigned long long gr_q_gen = 0, gr_db_gen = 0;
-    i64 gr_Q = 0, gr_R = 0;
-    int gr_nk = 0;
-    bool gh_done = false;
-    unsigned long long gh_q_gen = 0, gh_db_gen = 0;
-    i64 gh_Q = 0, gh_Qpad = 0, gh_G = 0;
-    // tie-aware AP (hg_tie_ap.hpp): ta_out holds the seven [Q][nR] tables of the queries and database of these generations
-    bool ta_done = false;
-    unsigned long long ta_q_gen = 0, ta_db_gen = 0;
-    i64 ta_Q = 0;
-    int ta_nR = 0;
-    // AP at many cut-offs (hg_ap_at.hpp): aa_out holds ap [Q][nR] float64 and rel [Q][nR] u32 of the match bitmap the last ranking left.
-    // Any later ranking (set_R, a blind hg_map_begin), a rewrite of the bitmap (hg_match, the merges), a reload (generations) and
-    // hg_trim end that.
-    bool aa_done = false;
-    unsigned long long aa_q_gen = 0, aa_db_gen = 0;
-    i64 aa_Q = 0;
-    int aa_nR = 0;             // stat "ap_at_cutoffs": cut-offs of the last pass
+    bool gr_kept = false; i64 gr_R = 0;   // gr_grades holds the grade bytes [Q][gr_R] of gr's pass
     i64 aa_recip_n = -1;       // aa_recip holds RN(1 / k) for k = 1 .. this (+ AP_RECIP_SLACK)
+    void lists_changed() { gr.begin(); }      // the ranked lists are no longer the ones hg_graded walked (a merge into them)
+    void bitmap_changed() { aa.begin(); }     // the match bitmap is no longer the one hg_ap_at walked (hg_match, the merges, a blind step)
     bool mbits_merged = false; // G > 1: the shards' bitmaps have been merged into mbits for all queries (hg_merge_match, hg_merge_ranked)
     bool mbits_in_ws_b = false;   // the last ranking was a blind step on stream_b: its bitmap is ws_b's, not mbits
     bool verdict_pending = false, verdict_known = false;
@@ -491,11 +489,11 @@ struct hg_ctx : StepBufs, StepState {
     DevBuf dbf, qf;                             // the float tables (hg_set_*_f32 with keep_floats)
     DevBuf dbx, qx;            // fp4 images of db / qc in MFMA fragment order for k_select_mx (dbx_valid, qx_valid)
     DevBuf dbx8;               // i8 image of the database codes in A-fragment order (k_hist_i8; dbx8_valid)
-    DevBuf rh_part, rh_all, rh_rel;   // hg_rel_hist: per-segment counters [S][2 NB][Qpad], the tables all / rel [NB][Qpad] (rh_done)
+    DevBuf rh_part, rh_all, rh_rel;   // hg_rel_hist: per-segment counters [S][2 NB][Qpad], the tables all / rel [NB][Qpad] (rh)
     DevBuf gr_tab, gr_out, gr_grades;   // hg_graded: [ks 64 x i64][gain C + 1][disc kmax], the tables gsum / hits / dcg / wsum [Q][nk] each, grade bytes [Q][R]
-    DevBuf gh_part, gh_tab;    // hg_grade_hist: per-segment counters [S][C + 1][Qpad], the table [C + 1][Qpad] (gh_done)
-    DevBuf ta_tab, ta_out;     // hg_tie_ap: the cut-offs [64 x i64], the tables ap_exp / p_hit / ap_min / ap_max / rel_exp / rel_lo / rel_hi [Q][nR] each (ta_done)
-    DevBuf aa_tab, aa_out;     // hg_ap_at: [cut-offs 64 x i64][ApShape x (1 + nR)], the tables ap [Q][nR] x 8 and rel [Q][nR] x 4 (aa_done)
+    DevBuf gh_part, gh_tab;    // hg_grade_hist: per-segment counters [S][C + 1][Qpad], the table [C + 1][Qpad] (gh)
+    DevBuf ta_tab, ta_out;     // hg_tie_ap: the cut-offs [64 x i64], the tables ap_exp / p_hit / ap_min / ap_max / rel_exp / rel_lo / rel_hi [Q][nR] each (ta)
+    DevBuf aa_tab, aa_out;     // hg_ap_at: [cut-offs 64 x i64][ApShape x (1 + nR)], the tables ap [Q][nR] x 8 and rel [Q][nR] x 4 (aa)
     DevBuf aa_recip;           // hg_ap_at's own reciprocals (aa_recip_n) when the ranking's table (ap_recip, recip_for_R) is not there
     DevBuf dbx3;               // fp4 image for k_select_mx3 (48-row supertiles, three rows per accumulator; dbx3_valid)
     DevBuf dbx4;               // fp4 image for k_select_mx4 (32-row supertiles, two rows per accumulator; codes of 65..128 bits; dbx4_valid)
@@ -534,8 +532,7 @@ struct hg_ctx : StepBufs, StepState {
     // the keys of the BUF_DERIVED buffers: after this each is rebuilt on its next use
     void forget_derived() {
         dbx_valid = qx_valid = dbx8_valid = dbx3_valid = dbx4_valid = dbfx_valid = dbfb_valid = false;
-        rh_done = false;               // (hg_trim releases the tables with the other work buffers)
-        gr_done = gr_kept = gh_done = ta_done = aa_done = false;
+        for (SideResult* r : {&rh, &gr, &gh, &ta, &aa}) r->begin();   // (hg_trim releases their tables with the other work buffers)
         shapes_for_R = recip_for_R = aa_recip_n = -1;
         outblk_q = ws_b.outblk_q = -1;
     }
@@ -656,6 +653,31 @@ struct hg_ctx : StepBufs, StepState {
     }
 };
 
+inline void SideResult::finish(const hg_ctx* c, i64 Q_, i64 Qpad_, i64 dim_) { *this = SideResult{true, c->q_gen, c->db_gen, Q_, Qpad_, dim_}; }
+inline bool SideResult::current(const hg_ctx* c) const { return done && q_gen == c->q_gen && db_gen == c->db_gen; }
+
+// hg_map_begin enqueues blind only while no device buffer has moved since the hg_map that gave the licence (map_warm_epoch).  First
+// reservations of buffers a blind step never touches (a side metric's tables, the second workspace) move none of those: take one
+// of these before such a group and call keep() once all of it succeeded -- not on an early return.
+struct FirstReservations {
+    const unsigned long long e0 = g_alloc_epoch.load();
+    void keep(hg_ctx* c) const { if (c->map_warm_epoch == e0) c->map_warm_epoch = g_alloc_epoch; }
+};
+
+// downloads on the context's stream (the caller synchronises): k equal planes into optional host pointers; a [rows][Qpad] table of
+// 32-bit words without its padding.  And hit counts widened u32 -> int64.
+inline int download_planes(hg_ctx* c, const DevBuf& src, size_t plane, void* const* host, int k) {
+    for (int i = 0; i < k; ++i)
+        if (host[i]) HG_HIP(hipMemcpyAsync(host[i], src.as<char>() + i * plane, plane, hipMemcpyDeviceToHost, c->stream));
+    return HG_OK;
+}
+inline int download_pitched(hg_ctx* c, void* host, const DevBuf& src, i64 Q, i64 Qpad, i64 rows) {
+    HG_HIP(hipMemcpy2DAsync(host, (size_t)Q * 4, src.p, (size_t)Qpad * 4, (size_t)Q * 4, (size_t)rows, hipMemcpyDeviceToHost, c->stream));
+    return HG_OK;
+}
+inline void widen_u32(int64_t* dst, const void* src, size_t n) {
+    for (size_t i = 0; i < n; ++i) dst[i] = ((const u32*)src)[i];
+}
 
 inline int grid_for(i64 n, int per_block = 256) { return (int)((n + per_block - 1) / per_block); }
 inline int padded_grid(int nBlk) { return (nBlk + 7) / 8 * 8; }
@@ -676,12 +698,13 @@ hg_ctx* requery_child(hg_ctx* c, i64 nF);       // c->sub, set up to rerun nF lo
 // hg_seq.hip
 int stage_ap_download(hg_ctx* c, void* dst = nullptr);   // {verdict, AP, hit counts} into pinned host memory behind everything enqueued so far (no synchronisation)
 int wait_verdict(hg_ctx* c, bool staged, int* flag);     // waits for the stream; the verdict word from the context's pinned block (staged) or by a download of its own
-void make_geometry(hg_ctx* c);
+Geo full_geometry(const hg_ctx* c);               // the full pass's segment geometry for the tables and options held now
+inline void make_geometry(hg_ctx* c) { c->geo = full_geometry(c); }
 Geo hist_geometry(const hg_ctx* c);
 int set_R(hg_ctx* c, int64_t R, int G, int rank);
 // hg_pairs_valu.hip
 int launch_hist(hg_ctx* c);                      // k_hist<NW>
-int launch_hist_rel(hg_ctx* c, const Geo& g);    // k_hist_rel<NW, LW> into c->rh_part (g: the full pass's geometry)
+int launch_hist_rel(hg_ctx* c, const Geo& g);    // k_hist_rel<NW, LW> into c->rh_part (g: full_geometry)
 int launch_select_valu(hg_ctx* c, int lw, bool optimistic);   // k_select<NW, LW, OPT>
 int launch_select_dense(hg_ctx* c, int lw);      // k_select_dense<NW, LW>
 // hg_pairs_mx.hip (k_select_mx: hg_pairs_mx1.hip)
@@ -691,7 +714,7 @@ int launch_hist_mx(hg_ctx* c);                   // k_hist_i8 / k_hist_mx
 int launch_select_mx(hg_ctx* c, int lw, const int* cut);    // k_select_mx<NW, LW, QT, COMPACT>
 int launch_select_mx3(hg_ctx* c, int lw, const int* cut);   // k_select_mx3 (codes of <= 64 bits, one-byte records)
 int launch_select_mx4(hg_ctx* c, int lw, const int* cut);   // k_select_mx4 (codes of 65..128 bits, one-byte records)
-int preload_valu(); int preload_mx(); int preload_mx1(); int preload_real(); int preload_seq();   // one per translation unit with kernels (hg_preload)
+int preload_valu(); int preload_mx(); int preload_mx1(); int preload_real(); int preload_seq(); int preload_side();   // one per translation unit with kernels (hg_preload)
 // hg_comm.hip
 void comm_release(hg_ctx* c);                    // destroys the context's communicator, if any
 

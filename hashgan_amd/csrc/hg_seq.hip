@@ -6,10 +6,6 @@
 #include "hg_select_mx3.hpp"
 #include "hg_select_mx4.hpp"
 #include "hg_hist_mx.hpp"
-#include "hg_hist_rel.hpp"
-#include "hg_graded.hpp"
-#include "hg_tie_ap.hpp"
-#include "hg_ap_at.hpp"
 #include "hg_rank_cnt.hpp"
 #include "hg_rank_lean.hpp"
 #include "hg_rank_dense.hpp"
@@ -17,8 +13,8 @@
 // Segment geometry of the pair passes: ~target_units wavefront-sized units.
 constexpr i64 SAMPLE_RATIO = 2;      // the sampled pass works on segments this many times longer than the select pass's (= per segment pair)
 
-void make_geometry(hg_ctx* c) {
-    Geo& g = c->geo;
+Geo full_geometry(const hg_ctx* c) {
+    Geo g = c->geo;
     g.Q = (int)c->Q;
     g.nQT = (int)((c->Q + 63) / 64);
     g.Qpad = g.nQT * 64;
@@ -73,6 +69,7 @@ void make_geometry(hg_ctx* c) {
     g.hcap = 0;
     g.wpb = WPB;
     g.nBlk = (int)((g.nUnits + WPB - 1) / WPB);
+    return g;
 }
 
 // The sampled pass only needs the shard total: use 2x longer segments so the per-segment
@@ -204,248 +201,6 @@ int hg_hist(hg_ctx* c) {
     return c->stage_end();
 }
 
-// The relevant-row histogram (hg_hist_rel.hpp): one pass over the pairs leaves all[d][q] (rows at distance d) and rel[d][q] (those
-// that share a label with the query) in buffers of its own.  The geometry is the full pass's (do_hist(c, 1)), taken on a copy: the
-// step state -- stage, geometry, hist / hown, hist_pairs -- stays what the last call left, so a plan, a select or a step in flight
-// goes on as if this call had not happened.
-int hg_rel_hist(hg_ctx* c) {
-    HG_TRY(need(c, ST_DB | ST_Q, "hg_rel_hist", "hg_set_database + hg_set_queries"));
-    const Geo kept = c->geo;
-    make_geometry(c);
-    const Geo g = c->geo;
-    c->geo = kept;
-    c->rh_done = false;
-    const unsigned long long e0 = g_alloc_epoch.load();
-    const size_t plane = (size_t)g.NB * g.Qpad * 4;
-    HG_TRY(c->rh_part.reserve(2 * plane * g.S));
-    HG_TRY(c->rh_all.reserve(plane));
-    HG_TRY(c->rh_rel.reserve(plane));
-    // (first reservations move no buffer hg_map_begin's licence to enqueue blind was given for)
-    if (c->map_warm_epoch == e0) c->map_warm_epoch = g_alloc_epoch;
-    HG_TRY(launch_hist_rel(c, g));
-    c->last_rel_hist = 1;
-    c->t_begin(KI_HIST_REL_REDUCE);
-    hipLaunchKernelGGL(k_hist_rel_reduce, dim3(grid_for((i64)g.NB * g.Qpad)), dim3(256), 0, c->stream, c->rh_part.as<u32>(),
-                       c->rh_all.as<u32>(), c->rh_rel.as<u32>(), g);
-    c->t_end();
-    HG_TRY(c->check_launch("k_hist_rel_reduce"));
-    c->rh_done = true;
-    c->rh_q_gen = c->q_gen; c->rh_db_gen = c->db_gen;
-    c->rh_Q = g.Q; c->rh_Qpad = g.Qpad; c->rh_NB = g.NB;
-    return c->stage_end();
-}
-
-// Graded relevance along the ranked lists (hg_graded.hpp): per query and cut-off k of `host_ks`, the sum of the grades, the ranks with a
-// grade, the discounted gain and the sum WAP averages, from the idx lists the last ranking left in out_idx -- hg_topr, a staged
-// select with lists, hg_topr_real.  Reads the lists and the label tables, writes buffers of its own: stage, geometry and match bits
-// stay the ranking's.  The host tables are copied before the call returns (it synchronises whatever "stage_sync" says).
-int hg_graded(hg_ctx* c, const int64_t* host_ks, int nk, const double* host_gain, const double* host_disc, int keep_grades) {
-    HG_TRY(need(c, ST_DB | ST_Q, "hg_graded", "hg_set_database + hg_set_queries"));
-    c->gr_done = c->gr_kept = false;
-    if (c->idx_base != 0 || c->N != c->n_total)
-        return fail(HG_ERR_STATE, "hg_graded: the context holds rows [%lld, %lld) of %lld: graded sums need the whole database in one context (lists of a shard are partial)",
-                    (long long)c->idx_base, (long long)(c->idx_base + c->N), (long long)c->n_total);
-    if (!(c->stage & ST_SELECT) || !(c->lists_valid || c->real_lists))
-        return fail(HG_ERR_STATE, "hg_graded: no ranked lists on the device (hg_map and hg_map_real write none): call hg_topr / hg_topr_real first");
-    if (c->C > GR_MAX_C) return fail(HG_ERR_ARG, "hg_graded: C=%d classes (a grade is a byte: at most %d)", c->C, GR_MAX_C);
-    if (!host_ks || !host_gain || !host_disc) return fail(HG_ERR_ARG, "hg_graded: null pointer");
-    if (nk < 1 || nk > GR_MAX_K) return fail(HG_ERR_ARG, "hg_graded: %d cut-offs (1..%d)", nk, GR_MAX_K);
-    const i64 Q = c->geo.Q, R = c->geo.R;
-    for (int j = 0; j < nk; ++j)
-        if (host_ks[j] < 1 || host_ks[j] > R || (j > 0 && host_ks[j] <= host_ks[j - 1]))
-            return fail(HG_ERR_ARG, "hg_graded: ks must be strictly ascending within 1..R (R=%lld; ks[%d]=%lld)", (long long)R, j, (long long)host_ks[j]);
-    const i64 kmax = host_ks[nk - 1];
-    const size_t o_gain = GR_MAX_K * 8, o_disc = o_gain + (size_t)(c->C + 1) * 8, tab = o_disc + (size_t)kmax * 8;
-    const size_t plane = (size_t)Q * nk * 8;
-    const unsigned long long e0 = g_alloc_epoch.load();
-    HG_TRY(c->gr_tab.reserve(tab));
-    HG_TRY(c->gr_out.reserve(4 * plane));
-    if (keep_grades) HG_TRY(c->gr_grades.reserve((size_t)Q * R));
-    // (first reservations move no buffer hg_map_begin's licence to enqueue blind was given for)
-    if (c->map_warm_epoch == e0) c->map_warm_epoch = g_alloc_epoch;
-    char* t = c->gr_tab.as<char>();
-    HG_HIP(hipMemcpyAsync(t, host_ks, (size_t)nk * 8, hipMemcpyHostToDevice, c->stream));
-    HG_HIP(hipMemcpyAsync(t + o_gain, host_gain, (size_t)(c->C + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HG_HIP(hipMemcpyAsync(t + o_disc, host_disc, (size_t)kmax * 8, hipMemcpyHostToDevice, c->stream));
-    char* o = c->gr_out.as<char>();
-    GradedArgs a;
-    a.idx = c->out_idx.as<u32>(); a.dblab = c->dblab.as<u64>(); a.qlab = c->qlab.as<u64>();
-    a.ks = (const i64*)t; a.gain = (const double*)(t + o_gain); a.disc = (const double*)(t + o_disc);
-    a.gsum = (i64*)o; a.hits = (i64*)(o + plane); a.dcg = (double*)(o + 2 * plane); a.wsum = (double*)(o + 3 * plane);
-    a.grades = keep_grades ? c->gr_grades.as<u8>() : nullptr;
-    a.R = R; a.N = c->N; a.nk = nk; a.LW = c->LW;
-    a.lastmask = c->C % 64 ? (1ull << (c->C % 64)) - 1ull : ~0ull;
-    c->t_begin(KI_GRADED);
-    hipLaunchKernelGGL(k_graded, dim3((unsigned)Q), dim3(GR_THREADS), 0, c->stream, a);
-    c->t_end();
-    HG_TRY(c->check_launch("k_graded"));
-    HG_TRY(c->sync());                                 // (the host tables are the caller's)
-    c->gr_done = true; c->gr_kept = keep_grades != 0;
-    c->gr_q_gen = c->q_gen; c->gr_db_gen = c->db_gen;
-    c->gr_Q = Q; c->gr_R = R; c->gr_nk = nk;
-    return HG_OK;
-}
-
-// The grade histogram of this shard (hg_graded.hpp): rows per (grade, query) in one pass over the label pairs.  Like hg_rel_hist: the
-// full pass's geometry on a copy, buffers of its own, the step state left as it was.
-extern "C++" {
-template <int LWT> static int launch_grade_hist_t(hg_ctx* c, Geo g, int G, u64 lastmask) {
-    // LDS: wpb * G * 64 * 4 bytes (C = 255: two wavefronts, 128 KiB)
-    int wpb = WPB;
-    while (wpb > 1 && (size_t)wpb * G * 256 > 160u * 1024u) wpb >>= 1;
-    g.wpb = wpb;
-    g.nBlk = (int)((g.nUnits + wpb - 1) / wpb);
-    const size_t lds = (size_t)wpb * G * 256;
-    static std::atomic<unsigned long long> lds_allowed{0};
-    if (lds > 64 * 1024 && !(lds_allowed.load() >> (c->device & 63) & 1ull)) {
-        HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grade_hist<LWT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        lds_allowed.fetch_or(1ull << (c->device & 63));
-    }
-    c->t_begin(KI_GRADE_HIST);
-    hipLaunchKernelGGL((k_grade_hist<LWT>), dim3(padded_grid(g.nBlk)), dim3(64 * wpb), lds, c->stream, c->qlab.as<u64>(),
-                       c->dblab.as<u64>(), c->gh_part.as<u32>(), g, G, lastmask);
-    c->t_end();
-    return c->check_launch("k_grade_hist");
-}
-}  // extern "C++"
-
-int hg_grade_hist(hg_ctx* c) {
-    HG_TRY(need(c, ST_DB | ST_Q, "hg_grade_hist", "hg_set_database + hg_set_queries"));
-    if (c->C > GR_MAX_C) return fail(HG_ERR_ARG, "hg_grade_hist: C=%d classes (a grade is a byte: at most %d)", c->C, GR_MAX_C);
-    const Geo kept = c->geo;
-    make_geometry(c);
-    const Geo g = c->geo;
-    c->geo = kept;
-    c->gh_done = false;
-    const int G = c->C + 1;
-    const unsigned long long e0 = g_alloc_epoch.load();
-    const i64 plane = (i64)G * g.Qpad;
-    HG_TRY(c->gh_part.reserve((size_t)plane * 4 * g.S));
-    HG_TRY(c->gh_tab.reserve((size_t)plane * 4));
-    if (c->map_warm_epoch == e0) c->map_warm_epoch = g_alloc_epoch;
-    const u64 lastmask = c->C % 64 ? (1ull << (c->C % 64)) - 1ull : ~0ull;
-    switch (c->LW) {
-        case 1: HG_TRY(launch_grade_hist_t<1>(c, g, G, lastmask)); break;
-        case 2: HG_TRY(launch_grade_hist_t<2>(c, g, G, lastmask)); break;
-        default: HG_TRY(launch_grade_hist_t<0>(c, g, G, lastmask)); break;
-    }
-    c->t_begin(KI_GRADE_HIST_REDUCE);
-    hipLaunchKernelGGL(k_grade_hist_reduce, dim3(grid_for(plane)), dim3(256), 0, c->stream, c->gh_part.as<u32>(), c->gh_tab.as<u32>(), plane, g.S);
-    c->t_end();
-    HG_TRY(c->check_launch("k_grade_hist_reduce"));
-    c->gh_done = true;
-    c->gh_q_gen = c->q_gen; c->gh_db_gen = c->db_gen;
-    c->gh_Q = g.Q; c->gh_Qpad = g.Qpad; c->gh_G = G;
-    return c->stage_end();
-}
-
-// Tie-aware AP at the cut-offs `host_Rs` (hg_tie_ap.hpp): expectation, hit probability, minimum and maximum of AP@R over the orders
-// inside the tie groups, from hg_rel_hist's two tables alone.  Runs that pass when the tables of the current generations are not
-// there and reuses them otherwise.  Like hg_graded: buffers of its own, the step state left as it was, the host array copied
-// before the call returns (it synchronises whatever "stage_sync" says).
-int hg_tie_ap(hg_ctx* c, const int64_t* host_Rs, int nR) {
-    HG_TRY(need(c, ST_DB | ST_Q, "hg_tie_ap", "hg_set_database + hg_set_queries"));
-    c->ta_done = false;
-    if (c->idx_base != 0 || c->N != c->n_total)
-        return fail(HG_ERR_STATE, "hg_tie_ap: the context holds rows [%lld, %lld) of %lld: the cut at R needs the tables of the whole database in one context",
-                    (long long)c->idx_base, (long long)(c->idx_base + c->N), (long long)c->n_total);
-    if (!host_Rs) return fail(HG_ERR_ARG, "hg_tie_ap: null pointer");
-    if (nR < 1 || nR > TA_MAX_R) return fail(HG_ERR_ARG, "hg_tie_ap: %d cut-offs (1..%d)", nR, TA_MAX_R);
-    for (int j = 0; j < nR; ++j)
-        if (host_Rs[j] < 1 || host_Rs[j] > c->N || (j > 0 && host_Rs[j] <= host_Rs[j - 1]))
-            return fail(HG_ERR_ARG, "hg_tie_ap: Rs must be strictly ascending within 1..N (N=%lld; Rs[%d]=%lld)", (long long)c->N, j, (long long)host_Rs[j]);
-    if (c->NB > TA_THREADS) return fail(HG_ERR_ARG, "hg_tie_ap: b=%d bits (at most %d)", c->b, TA_THREADS - 1);
-    if (!c->rh_done || c->rh_q_gen != c->q_gen || c->rh_db_gen != c->db_gen) HG_TRY(hg_rel_hist(c));
-    const i64 Q = c->rh_Q;
-    const size_t plane = (size_t)Q * nR * 8;
-    const unsigned long long e0 = g_alloc_epoch.load();
-    HG_TRY(c->ta_tab.reserve(TA_MAX_R * 8));
-    HG_TRY(c->ta_out.reserve(7 * plane));
-    // (first reservations move no buffer hg_map_begin's licence to enqueue blind was given for)
-    if (c->map_warm_epoch == e0) c->map_warm_epoch = g_alloc_epoch;
-    HG_HIP(hipMemcpyAsync(c->ta_tab.p, host_Rs, (size_t)nR * 8, hipMemcpyHostToDevice, c->stream));
-    char* o = c->ta_out.as<char>();
-    TieApArgs a;
-    a.all = c->rh_all.as<u32>(); a.rel = c->rh_rel.as<u32>(); a.Rs = c->ta_tab.as<i64>();
-    a.ap_exp = (double*)o; a.p_hit = (double*)(o + plane); a.ap_min = (double*)(o + 2 * plane); a.ap_max = (double*)(o + 3 * plane);
-    a.rel_exp = (double*)(o + 4 * plane); a.rel_lo = (i64*)(o + 5 * plane); a.rel_hi = (i64*)(o + 6 * plane);
-    a.Qpad = c->rh_Qpad; a.NB = (int)c->rh_NB; a.nR = nR;
-    c->t_begin(KI_TIE_AP);
-    hipLaunchKernelGGL(k_tie_ap, dim3((unsigned)Q, (unsigned)nR), dim3(TA_THREADS), 0, c->stream, a);
-    c->t_end();
-    HG_TRY(c->check_launch("k_tie_ap"));
-    HG_TRY(c->sync());                                 // (the host array is the caller's)
-    c->ta_done = true;
-    c->ta_q_gen = c->q_gen; c->ta_db_gen = c->db_gen;
-    c->ta_Q = Q; c->ta_nR = nR;
-    return HG_OK;
-}
-
-// AP@R and the hits among the top R at the cut-offs `host_Rs` from the match bitmap the last ranking left, in one pass per query
-// (hg_ap_at.hpp).  Like hg_graded: buffers and tables of its own, the ranking's state -- stage, hg_ap's results, lists, the one-R
-// AP tables -- left as it was, the host array copied before the call returns (it synchronises whatever "stage_sync" says).
-int hg_ap_at(hg_ctx* c, const int64_t* host_Rs, int nR) {
-    HG_TRY(need(c, ST_MATCH, "hg_ap_at", "a ranking that leaves the whole match bitmap (hg_topr, hg_topr_real, hg_map, hg_match, a merge of all queries)"));
-    c->aa_done = false;
-    if (c->ranked_local) return fail(HG_ERR_STATE, "hg_ap_at: the match bitmap is in this shard's local rank order (hg_select_ranked): merge it first");
-    if (c->G > 1 && !c->mbits_merged)
-        return fail(HG_ERR_STATE, "hg_ap_at: the match bitmap holds this shard's rows only (%d shards): merge it first (hg_merge_match, hg_merge_ranked)", c->G);
-    if (c->mbits_in_ws_b) return fail(HG_ERR_STATE, "hg_ap_at: the last ranking was a step of hg_map_begin in its own workspace: rank with hg_topr / hg_map first");
-    if (!host_Rs) return fail(HG_ERR_ARG, "hg_ap_at: null pointer");
-    if (nR < 1 || nR > AA_MAX_R) return fail(HG_ERR_ARG, "hg_ap_at: %d cut-offs (1..%d)", nR, AA_MAX_R);
-    const i64 Q = c->geo.Q, R = c->geo.R;
-    for (int j = 0; j < nR; ++j)
-        if (host_Rs[j] < 1 || host_Rs[j] > R || (j > 0 && host_Rs[j] <= host_Rs[j - 1]))
-            return fail(HG_ERR_ARG, "hg_ap_at: Rs must be strictly ascending within 1..R (R=%lld of the last ranking; Rs[%d]=%lld)", (long long)R, j, (long long)host_Rs[j]);
-    const i64 Rmax = host_Rs[nR - 1];
-    // host image of the tables: the cut-offs, the full chunk's tree, one tree per cut-off for its last chunk
-    const size_t o_shapes = AA_MAX_R * 8, tab = o_shapes + sizeof(ApShape) * (size_t)(1 + nR);
-    std::vector<char> img(tab, 0);
-    memcpy(img.data(), host_Rs, (size_t)nR * 8);
-    ApShape* sh = reinterpret_cast<ApShape*>(img.data() + o_shapes);
-    build_shape(AP_CHUNK, sh[0]);
-    for (int j = 0; j < nR; ++j) build_shape((int)(host_Rs[j] % AP_CHUNK), sh[1 + j]);
-    const size_t n = (size_t)Q * nR;
-    const unsigned long long e0 = g_alloc_epoch.load();
-    HG_TRY(c->aa_tab.reserve(tab));
-    HG_TRY(c->aa_out.reserve(n * 12));
-    // reciprocals of the ranks (ensure_ap_tables' rule: lists beyond 2^20 divide): the ranking's table if it is there, else one of its own
-    const bool use_recip = c->opt.ap_recip && Rmax <= (1ll << 20);
-    const double* recip = nullptr;
-    if (use_recip && c->recip_for_R == R && c->ap_recip.p) {
-        recip = c->ap_recip.as<double>();
-    } else if (use_recip) {
-        if (c->aa_recip_n < Rmax) {
-            HG_TRY(c->aa_recip.reserve((size_t)(Rmax + 1 + AP_RECIP_SLACK) * 8));
-            hipLaunchKernelGGL(k_recip_table, dim3(grid_for(Rmax + 1 + AP_RECIP_SLACK)), dim3(256), 0, c->stream, c->aa_recip.as<double>(), Rmax + AP_RECIP_SLACK);
-            HG_TRY(c->check_launch("k_recip_table"));
-            c->aa_recip_n = Rmax;
-        }
-        recip = c->aa_recip.as<double>();
-    }
-    // (first reservations move no buffer hg_map_begin's licence to enqueue blind was given for)
-    if (c->map_warm_epoch == e0) c->map_warm_epoch = g_alloc_epoch;
-    HG_HIP(hipMemcpyAsync(c->aa_tab.p, img.data(), tab, hipMemcpyHostToDevice, c->stream));
-    ApAtArgs a;
-    a.mbits = c->mbits.as<u64>(); a.RW = c->RW;
-    a.Rs = c->aa_tab.as<i64>(); a.shapes = (const ApShape*)(c->aa_tab.as<char>() + o_shapes);
-    a.recip = recip;
-    a.ap = c->aa_out.as<double>(); a.rel = (u32*)(c->aa_out.as<char>() + n * 8);
-    a.nR = nR;
-    // few queries with long lists: four times the threads per query (do_ap_range's rule, on the longest list)
-    const bool wide = Q * 2 < (i64)c->n_cu * 8 && Rmax > 2 * AP_CHUNK && c->opt.ap_wide;
-    c->t_begin(KI_AP_AT);
-    if (Q > 0 && wide) hipLaunchKernelGGL(k_ap_at<512>, dim3((unsigned)Q), dim3(512), 0, c->stream, a);
-    else if (Q > 0) hipLaunchKernelGGL(k_ap_at<AP_THREADS>, dim3((unsigned)Q), dim3(AP_THREADS), 0, c->stream, a);
-    c->t_end();
-    HG_TRY(c->check_launch("k_ap_at"));
-    HG_TRY(c->sync());                                 // (the host image goes out of scope)
-    c->aa_done = true;
-    c->aa_q_gen = c->q_gen; c->aa_db_gen = c->db_gen;
-    c->aa_Q = Q; c->aa_nR = nR;
-    return HG_OK;
-}
-
 int hg_hist_buffer(hg_ctx* c, void** dev_ptr, int64_t* nbytes) {
     HG_TRY(need(c, ST_DB | ST_Q, "hg_hist_buffer", "hg_hist / hg_sample_hist / hg_select_candidates"));
     if (!c->hown.p) return fail(HG_ERR_STATE, "hg_hist_buffer: no histogram computed yet");
@@ -459,8 +214,8 @@ extern "C++" int set_R(hg_ctx* c, int64_t R, int G, int rank) {
     if (R < 1 || R > c->n_total)
         return fail(HG_ERR_ARG, "R=%lld outside 1..N (N=%lld rows in the database)", (long long)R, (long long)c->n_total);
     c->R = R; c->G = G; c->rank = rank;
-    c->gr_done = c->gr_kept = false;                   // every ranking comes through here: hg_graded's tables were the previous lists'
-    c->aa_done = false;                                // ... and hg_ap_at's the previous bitmap's
+    c->lists_changed();                                // every ranking comes through here: hg_graded's tables were the previous lists'
+    c->bitmap_changed();                               // ... and hg_ap_at's the previous bitmap's
     c->mbits_merged = c->mbits_in_ws_b = false;
     c->geo.R = R;
     c->RW = (R + 63) / 64;
@@ -1039,7 +794,7 @@ static int merge_ranked_range(hg_ctx* c, const uint32_t* dev_hist_all, const uin
     HG_TRY(c->check_launch("k_merge_ranked"));
     std::swap(c->mbits, c->mbits2);                    // the global bitmap is what hg_ap and hg_get_match see
     c->ranked_local = false;
-    c->aa_done = false;
+    c->bitmap_changed();
     c->mbits_merged = q0 == 0 && nq == g.Q;
     c->G = G;
     return HG_OK;
@@ -1829,7 +1584,7 @@ static int enqueue_bet_on_b(hg_ctx* c, hg_ctx::MapSlot& m, int64_t R, int stride
         HG_HIP(hipStreamWaitEvent(c->stream_b, c->ev_pre, 0));
     }
     c->b_open = false;
-    const unsigned long long e0 = g_alloc_epoch.load();
+    const FirstReservations first;                     // (ws_b's: the context's own workspace is untouched)
     c->swap_step();
     int rc = ensure_out_block(c);                      // (ws_b's own err / ap / rel views; on first use)
     if (rc == HG_OK) rc = enqueue_attempt(c, AT_BET, R, stride, bet_request(c, true, m.pin), true);
@@ -1838,8 +1593,7 @@ static int enqueue_bet_on_b(hg_ctx* c, hg_ctx::MapSlot& m, int64_t R, int stride
     if (rc != HG_OK) { (void)hipStreamSynchronize(c->stream_b); return rc; }
     c->b_ev = m.ev;
     c->b_open = true;
-    // ws_b's first reservations move no buffer the licence was given for (the context's own workspace is untouched)
-    if (c->map_warm_epoch == e0) c->map_warm_epoch = g_alloc_epoch;
+    first.keep(c);
     c->map_overlapped++;
     return HG_OK;
 }
@@ -1874,7 +1628,7 @@ int hg_map_begin(hg_ctx* c, int64_t R) {
         const bool two = c->opt.step_streams >= 2 && c->own_stream && c->timing == 0 && !c->capturing;
         bool prepped = false;
         if (two) HG_TRY(prepare_shared(c, R, &prepped));
-        c->aa_done = false;                            // (a ranking that does not come through set_R: hg_ap_at's tables were the previous bitmap's)
+        c->bitmap_changed();                           // (a ranking that does not come through set_R)
         c->mbits_in_ws_b = two && slot == 1;
         if (two && slot == 1) {
             HG_TRY(enqueue_bet_on_b(c, m, R, stride, prepped));

@@ -1,0 +1,292 @@
+// libhashgan_amd.so -- the side metrics: passes next to the ranking that read the tables, the ranked lists or the match bitmap and write
+// buffers of their own.  None touches the step state -- stage, geometry, hist / hown, lists, match bits, hg_ap's results -- so a plan, a
+// select or a step in flight goes on as if the call had not happened.  Each keeps one SideResult (hg_ctx.hpp; DESIGN.md, "Side metrics: the host side").
+#include "hg_ctx.hpp"
+#include "hg_hist_rel.hpp"
+#include "hg_graded.hpp"
+#include "hg_tie_ap.hpp"
+#include "hg_ap_at.hpp"
+
+// the classes of the last label word
+static u64 lastmask(int C) { return C % 64 ? (1ull << (C % 64)) - 1ull : ~0ull; }
+
+// Cut-offs handed over by the caller: `n` of them (1..max_n), strictly ascending within 1..bound.
+static int check_cutoffs(const char* who, const char* name, const int64_t* host, int n, int max_n, i64 bound, const char* bound_name) {
+    if (!host) return fail(HG_ERR_ARG, "%s: null pointer (%s)", who, name);
+    if (n < 1 || n > max_n) return fail(HG_ERR_ARG, "%s: %d cut-offs in %s (1..%d)", who, n, name, max_n);
+    for (int j = 0; j < n; ++j)
+        if (host[j] < 1 || host[j] > bound || (j > 0 && host[j] <= host[j - 1]))
+            return fail(HG_ERR_ARG, "%s: %s must be strictly ascending within 1..%lld (%s); %s[%d]=%lld", who, name, (long long)bound, bound_name, name, j, (long long)host[j]);
+    return HG_OK;
+}
+
+static int whole_database(const hg_ctx* c, const char* who, const char* why) {
+    if (c->idx_base == 0 && c->N == c->n_total) return HG_OK;
+    return fail(HG_ERR_STATE, "%s: the context holds rows [%lld, %lld) of %lld: %s", who, (long long)c->idx_base, (long long)(c->idx_base + c->N), (long long)c->n_total, why);
+}
+
+template <int LWT> static int launch_grade_hist_t(hg_ctx* c, Geo g, int G) {
+    // LDS: wpb * G * 64 * 4 bytes (C = 255: two wavefronts, 128 KiB)
+    int wpb = WPB;
+    while (wpb > 1 && (size_t)wpb * G * 256 > 160u * 1024u) wpb >>= 1;
+    g.wpb = wpb;
+    g.nBlk = (int)((g.nUnits + wpb - 1) / wpb);
+    const size_t lds = (size_t)wpb * G * 256;
+    static std::atomic<unsigned long long> lds_allowed{0};
+    if (lds > 64 * 1024 && !(lds_allowed.load() >> (c->device & 63) & 1ull)) {
+        HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_grade_hist<LWT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        lds_allowed.fetch_or(1ull << (c->device & 63));
+    }
+    c->t_begin(KI_GRADE_HIST);
+    hipLaunchKernelGGL((k_grade_hist<LWT>), dim3(padded_grid(g.nBlk)), dim3(64 * wpb), lds, c->stream, c->qlab.as<u64>(),
+                       c->dblab.as<u64>(), c->gh_part.as<u32>(), g, G, lastmask(c->C));
+    c->t_end();
+    return c->check_launch("k_grade_hist");
+}
+
+extern "C" {
+
+// The relevant-row histogram (hg_hist_rel.hpp): one pass over the pairs leaves all[d][q] (rows at distance d) and rel[d][q] (those
+// that share a label with the query), in the full pass's geometry (do_hist(c, 1)).
+int hg_rel_hist(hg_ctx* c) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_rel_hist", "hg_set_database + hg_set_queries"));
+    const Geo g = full_geometry(c);
+    c->rh.begin();
+    const FirstReservations first;
+    const size_t plane = (size_t)g.NB * g.Qpad * 4;
+    HG_TRY(c->rh_part.reserve(2 * plane * g.S));
+    HG_TRY(c->rh_all.reserve(plane));
+    HG_TRY(c->rh_rel.reserve(plane));
+    first.keep(c);
+    HG_TRY(launch_hist_rel(c, g));
+    c->last_rel_hist = 1;
+    c->t_begin(KI_HIST_REL_REDUCE);
+    hipLaunchKernelGGL(k_hist_rel_reduce, dim3(grid_for((i64)g.NB * g.Qpad)), dim3(256), 0, c->stream, c->rh_part.as<u32>(),
+                       c->rh_all.as<u32>(), c->rh_rel.as<u32>(), g);
+    c->t_end();
+    HG_TRY(c->check_launch("k_hist_rel_reduce"));
+    c->rh.finish(c, g.Q, g.Qpad, g.NB);
+    return c->stage_end();
+}
+
+// Graded relevance along the ranked lists (hg_graded.hpp): per query and cut-off k of `host_ks`, the sum of the grades, the ranks with a
+// grade, the discounted gain and the sum WAP averages, from the idx lists the last ranking left in out_idx -- hg_topr, a staged
+// select with lists, hg_topr_real.  The host tables are copied before the call returns (it synchronises whatever "stage_sync" says).
+int hg_graded(hg_ctx* c, const int64_t* host_ks, int nk, const double* host_gain, const double* host_disc, int keep_grades) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_graded", "hg_set_database + hg_set_queries"));
+    c->gr.begin();
+    HG_TRY(whole_database(c, "hg_graded", "graded sums need the whole database in one context (lists of a shard are partial)"));
+    if (!(c->stage & ST_SELECT) || !(c->lists_valid || c->real_lists))
+        return fail(HG_ERR_STATE, "hg_graded: no ranked lists on the device (hg_map and hg_map_real write none): call hg_topr / hg_topr_real first");
+    if (c->C > GR_MAX_C) return fail(HG_ERR_ARG, "hg_graded: C=%d classes (a grade is a byte: at most %d)", c->C, GR_MAX_C);
+    if (!host_gain || !host_disc) return fail(HG_ERR_ARG, "hg_graded: null pointer");
+    const i64 Q = c->geo.Q, R = c->geo.R;
+    HG_TRY(check_cutoffs("hg_graded", "ks", host_ks, nk, GR_MAX_K, R, "R"));
+    const i64 kmax = host_ks[nk - 1];
+    const size_t o_gain = GR_MAX_K * 8, o_disc = o_gain + (size_t)(c->C + 1) * 8, tab = o_disc + (size_t)kmax * 8;
+    const size_t plane = (size_t)Q * nk * 8;
+    const FirstReservations first;
+    HG_TRY(c->gr_tab.reserve(tab));
+    HG_TRY(c->gr_out.reserve(4 * plane));
+    if (keep_grades) HG_TRY(c->gr_grades.reserve((size_t)Q * R));
+    first.keep(c);
+    char* t = c->gr_tab.as<char>();
+    HG_HIP(hipMemcpyAsync(t, host_ks, (size_t)nk * 8, hipMemcpyHostToDevice, c->stream));
+    HG_HIP(hipMemcpyAsync(t + o_gain, host_gain, (size_t)(c->C + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HG_HIP(hipMemcpyAsync(t + o_disc, host_disc, (size_t)kmax * 8, hipMemcpyHostToDevice, c->stream));
+    char* o = c->gr_out.as<char>();
+    GradedArgs a;
+    a.idx = c->out_idx.as<u32>(); a.dblab = c->dblab.as<u64>(); a.qlab = c->qlab.as<u64>();
+    a.ks = (const i64*)t; a.gain = (const double*)(t + o_gain); a.disc = (const double*)(t + o_disc);
+    a.gsum = (i64*)o; a.hits = (i64*)(o + plane); a.dcg = (double*)(o + 2 * plane); a.wsum = (double*)(o + 3 * plane);
+    a.grades = keep_grades ? c->gr_grades.as<u8>() : nullptr;
+    a.R = R; a.N = c->N; a.nk = nk; a.LW = c->LW;
+    a.lastmask = lastmask(c->C);
+    c->t_begin(KI_GRADED);
+    hipLaunchKernelGGL(k_graded, dim3((unsigned)Q), dim3(GR_THREADS), 0, c->stream, a);
+    c->t_end();
+    HG_TRY(c->check_launch("k_graded"));
+    HG_TRY(c->sync());                                 // (the host tables are the caller's)
+    c->gr_kept = keep_grades != 0; c->gr_R = R;
+    c->gr.finish(c, Q, Q, nk);
+    return HG_OK;
+}
+
+// The grade histogram of this shard (hg_graded.hpp): rows per (grade, query) in one pass over the label pairs, in the full pass's
+// geometry like hg_rel_hist.
+int hg_grade_hist(hg_ctx* c) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_grade_hist", "hg_set_database + hg_set_queries"));
+    if (c->C > GR_MAX_C) return fail(HG_ERR_ARG, "hg_grade_hist: C=%d classes (a grade is a byte: at most %d)", c->C, GR_MAX_C);
+    const Geo g = full_geometry(c);
+    c->gh.begin();
+    const int G = c->C + 1;
+    const FirstReservations first;
+    const i64 plane = (i64)G * g.Qpad;
+    HG_TRY(c->gh_part.reserve((size_t)plane * 4 * g.S));
+    HG_TRY(c->gh_tab.reserve((size_t)plane * 4));
+    first.keep(c);
+    switch (c->LW) {
+        case 1: HG_TRY(launch_grade_hist_t<1>(c, g, G)); break;
+        case 2: HG_TRY(launch_grade_hist_t<2>(c, g, G)); break;
+        default: HG_TRY(launch_grade_hist_t<0>(c, g, G)); break;
+    }
+    c->t_begin(KI_GRADE_HIST_REDUCE);
+    hipLaunchKernelGGL(k_grade_hist_reduce, dim3(grid_for(plane)), dim3(256), 0, c->stream, c->gh_part.as<u32>(), c->gh_tab.as<u32>(), plane, g.S);
+    c->t_end();
+    HG_TRY(c->check_launch("k_grade_hist_reduce"));
+    c->gh.finish(c, g.Q, g.Qpad, G);
+    return c->stage_end();
+}
+
+// Tie-aware AP at the cut-offs `host_Rs` (hg_tie_ap.hpp): expectation, hit probability, minimum and maximum of AP@R over the orders
+// inside the tie groups, from hg_rel_hist's two tables alone.  Runs that pass when the tables of the current generations are not
+// there and reuses them otherwise.  The host array is copied before the call returns (it synchronises whatever "stage_sync" says).
+int hg_tie_ap(hg_ctx* c, const int64_t* host_Rs, int nR) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_tie_ap", "hg_set_database + hg_set_queries"));
+    c->ta.begin();
+    HG_TRY(whole_database(c, "hg_tie_ap", "the cut at R needs the tables of the whole database in one context"));
+    HG_TRY(check_cutoffs("hg_tie_ap", "Rs", host_Rs, nR, TA_MAX_R, c->N, "N"));
+    if (c->NB > TA_THREADS) return fail(HG_ERR_ARG, "hg_tie_ap: b=%d bits (at most %d)", c->b, TA_THREADS - 1);
+    if (!c->rh.current(c)) HG_TRY(hg_rel_hist(c));
+    const i64 Q = c->rh.Q;
+    const size_t plane = (size_t)Q * nR * 8;
+    const FirstReservations first;
+    HG_TRY(c->ta_tab.reserve(TA_MAX_R * 8));
+    HG_TRY(c->ta_out.reserve(7 * plane));
+    first.keep(c);
+    HG_HIP(hipMemcpyAsync(c->ta_tab.p, host_Rs, (size_t)nR * 8, hipMemcpyHostToDevice, c->stream));
+    char* o = c->ta_out.as<char>();
+    TieApArgs a;
+    a.all = c->rh_all.as<u32>(); a.rel = c->rh_rel.as<u32>(); a.Rs = c->ta_tab.as<i64>();
+    a.ap_exp = (double*)o; a.p_hit = (double*)(o + plane); a.ap_min = (double*)(o + 2 * plane); a.ap_max = (double*)(o + 3 * plane);
+    a.rel_exp = (double*)(o + 4 * plane); a.rel_lo = (i64*)(o + 5 * plane); a.rel_hi = (i64*)(o + 6 * plane);
+    a.Qpad = c->rh.Qpad; a.NB = (int)c->rh.dim; a.nR = nR;
+    c->t_begin(KI_TIE_AP);
+    hipLaunchKernelGGL(k_tie_ap, dim3((unsigned)Q, (unsigned)nR), dim3(TA_THREADS), 0, c->stream, a);
+    c->t_end();
+    HG_TRY(c->check_launch("k_tie_ap"));
+    HG_TRY(c->sync());                                 // (the host array is the caller's)
+    c->ta.finish(c, Q, Q, nR);
+    return HG_OK;
+}
+
+// AP@R and the hits among the top R at the cut-offs `host_Rs` from the match bitmap the last ranking left, in one pass per query
+// (hg_ap_at.hpp).  Tables of its own -- the one-R AP tables stay the ranking's; the host array is copied before the call returns
+// (it synchronises whatever "stage_sync" says).
+int hg_ap_at(hg_ctx* c, const int64_t* host_Rs, int nR) {
+    HG_TRY(need(c, ST_MATCH, "hg_ap_at", "a ranking that leaves the whole match bitmap (hg_topr, hg_topr_real, hg_map, hg_match, a merge of all queries)"));
+    c->aa.begin();
+    if (c->ranked_local) return fail(HG_ERR_STATE, "hg_ap_at: the match bitmap is in this shard's local rank order (hg_select_ranked): merge it first");
+    if (c->G > 1 && !c->mbits_merged)
+        return fail(HG_ERR_STATE, "hg_ap_at: the match bitmap holds this shard's rows only (%d shards): merge it first (hg_merge_match, hg_merge_ranked)", c->G);
+    if (c->mbits_in_ws_b) return fail(HG_ERR_STATE, "hg_ap_at: the last ranking was a step of hg_map_begin in its own workspace: rank with hg_topr / hg_map first");
+    const i64 Q = c->geo.Q, R = c->geo.R;
+    HG_TRY(check_cutoffs("hg_ap_at", "Rs", host_Rs, nR, AA_MAX_R, R, "R of the last ranking"));
+    const i64 Rmax = host_Rs[nR - 1];
+    // host image of the tables: the cut-offs, the full chunk's tree, one tree per cut-off for its last chunk
+    const size_t o_shapes = AA_MAX_R * 8, tab = o_shapes + sizeof(ApShape) * (size_t)(1 + nR);
+    std::vector<char> img(tab, 0);
+    memcpy(img.data(), host_Rs, (size_t)nR * 8);
+    ApShape* sh = reinterpret_cast<ApShape*>(img.data() + o_shapes);
+    build_shape(AP_CHUNK, sh[0]);
+    for (int j = 0; j < nR; ++j) build_shape((int)(host_Rs[j] % AP_CHUNK), sh[1 + j]);
+    const size_t n = (size_t)Q * nR;
+    const FirstReservations first;
+    HG_TRY(c->aa_tab.reserve(tab));
+    HG_TRY(c->aa_out.reserve(n * 12));
+    // reciprocals of the ranks (ensure_ap_tables' rule: lists beyond 2^20 divide): the ranking's table if it is there, else one of its own
+    const bool use_recip = c->opt.ap_recip && Rmax <= (1ll << 20);
+    const double* recip = nullptr;
+    if (use_recip && c->recip_for_R == R && c->ap_recip.p) {
+        recip = c->ap_recip.as<double>();
+    } else if (use_recip) {
+        if (c->aa_recip_n < Rmax) {
+            HG_TRY(c->aa_recip.reserve((size_t)(Rmax + 1 + AP_RECIP_SLACK) * 8));
+            hipLaunchKernelGGL(k_recip_table, dim3(grid_for(Rmax + 1 + AP_RECIP_SLACK)), dim3(256), 0, c->stream, c->aa_recip.as<double>(), Rmax + AP_RECIP_SLACK);
+            HG_TRY(c->check_launch("k_recip_table"));
+            c->aa_recip_n = Rmax;
+        }
+        recip = c->aa_recip.as<double>();
+    }
+    first.keep(c);
+    HG_HIP(hipMemcpyAsync(c->aa_tab.p, img.data(), tab, hipMemcpyHostToDevice, c->stream));
+    ApAtArgs a;
+    a.mbits = c->mbits.as<u64>(); a.RW = c->RW;
+    a.Rs = c->aa_tab.as<i64>(); a.shapes = (const ApShape*)(c->aa_tab.as<char>() + o_shapes);
+    a.recip = recip;
+    a.ap = c->aa_out.as<double>(); a.rel = (u32*)(c->aa_out.as<char>() + n * 8);
+    a.nR = nR;
+    // few queries with long lists: four times the threads per query (do_ap_range's rule, on the longest list)
+    const bool wide = Q * 2 < (i64)c->n_cu * 8 && Rmax > 2 * AP_CHUNK && c->opt.ap_wide;
+    c->t_begin(KI_AP_AT);
+    if (Q > 0 && wide) hipLaunchKernelGGL(k_ap_at<512>, dim3((unsigned)Q), dim3(512), 0, c->stream, a);
+    else if (Q > 0) hipLaunchKernelGGL(k_ap_at<AP_THREADS>, dim3((unsigned)Q), dim3(AP_THREADS), 0, c->stream, a);
+    c->t_end();
+    HG_TRY(c->check_launch("k_ap_at"));
+    HG_TRY(c->sync());                                 // (the host image goes out of scope)
+    c->aa.finish(c, Q, Q, nR);
+    return HG_OK;
+}
+
+// ---- getters: the copies on the context's stream, one synchronisation
+int hg_get_rel_hist(hg_ctx* c, uint32_t* host_all, uint32_t* host_rel) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_rel_hist", "hg_rel_hist"));
+    if (!c->rh.current(c)) return fail(HG_ERR_STATE, "hg_get_rel_hist called before hg_rel_hist (on the tables loaded now)");
+    if (host_all) HG_TRY(download_pitched(c, host_all, c->rh_all, c->rh.Q, c->rh.Qpad, c->rh.dim));
+    if (host_rel) HG_TRY(download_pitched(c, host_rel, c->rh_rel, c->rh.Q, c->rh.Qpad, c->rh.dim));
+    return c->sync();
+}
+
+int hg_get_graded(hg_ctx* c, int64_t* host_gsum, int64_t* host_hits, double* host_dcg, double* host_wsum) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_graded", "hg_graded"));
+    if (!c->gr.current(c)) return fail(HG_ERR_STATE, "hg_get_graded called before hg_graded (on the ranked lists and tables held now)");
+    void* const dst[4] = {host_gsum, host_hits, host_dcg, host_wsum};
+    HG_TRY(download_planes(c, c->gr_out, (size_t)c->gr.Q * c->gr.dim * 8, dst, 4));
+    return c->sync();
+}
+
+int hg_get_grades(hg_ctx* c, uint8_t* host_grades) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_grades", "hg_graded"));
+    if (!c->gr.current(c) || !c->gr_kept)
+        return fail(HG_ERR_STATE, "hg_get_grades: the last hg_graded on these lists did not keep the grade bytes (keep_grades = 0), or there was none");
+    if (!host_grades) return fail(HG_ERR_ARG, "hg_get_grades: null pointer");
+    HG_HIP(hipMemcpyAsync(host_grades, c->gr_grades.p, (size_t)c->gr.Q * c->gr_R, hipMemcpyDeviceToHost, c->stream));
+    return c->sync();
+}
+
+int hg_get_grade_hist(hg_ctx* c, uint32_t* host_hist) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_grade_hist", "hg_grade_hist"));
+    if (!c->gh.current(c)) return fail(HG_ERR_STATE, "hg_get_grade_hist called before hg_grade_hist (on the tables loaded now)");
+    if (!host_hist) return fail(HG_ERR_ARG, "hg_get_grade_hist: null pointer");
+    HG_TRY(download_pitched(c, host_hist, c->gh_tab, c->gh.Q, c->gh.Qpad, c->gh.dim));
+    return c->sync();
+}
+
+int hg_get_tie_ap(hg_ctx* c, double* host_ap_exp, double* host_p_hit, double* host_ap_min, double* host_ap_max, double* host_rel_exp,
+                  int64_t* host_rel_lo, int64_t* host_rel_hi) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_tie_ap", "hg_tie_ap"));
+    if (!c->ta.current(c)) return fail(HG_ERR_STATE, "hg_get_tie_ap called before hg_tie_ap (on the tables loaded now)");
+    void* const dst[7] = {host_ap_exp, host_p_hit, host_ap_min, host_ap_max, host_rel_exp, host_rel_lo, host_rel_hi};
+    HG_TRY(download_planes(c, c->ta_out, (size_t)c->ta.Q * c->ta.dim * 8, dst, 7));
+    return c->sync();
+}
+
+int hg_get_ap_at(hg_ctx* c, double* host_ap, int64_t* host_rel) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_ap_at", "hg_ap_at"));
+    if (!c->aa.current(c)) return fail(HG_ERR_STATE, "hg_get_ap_at called before hg_ap_at (on the match bitmap and tables held now)");
+    const size_t n = (size_t)c->aa.Q * c->aa.dim;
+    std::vector<u32> rel(host_rel ? n : 0);
+    if (host_ap) HG_HIP(hipMemcpyAsync(host_ap, c->aa_out.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (host_rel) HG_HIP(hipMemcpyAsync(rel.data(), c->aa_out.as<char>() + n * 8, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HG_TRY(c->sync());
+    widen_u32(host_rel, rel.data(), rel.size());
+    return HG_OK;
+}
+
+}  // extern "C"
+
+int preload_side() {   // (hg_preload: see preload_seq)
+    hipFuncAttributes a;
+    HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_tie_ap)));
+    return HG_OK;
+}
