@@ -41,6 +41,7 @@ _SIGNATURES = {
     "hg_hist_buffer": [_p, C.POINTER(_p), C.POINTER(_i64)],
     "hg_rel_hist": [_p],
     "hg_grade_hist": [_p],
+    "hg_joint_hist": [_p],
     "hg_graded": [_p, _p, C.c_int, _p, _p, C.c_int],
     "hg_tie_ap": [_p, _p, C.c_int],
     "hg_ap_at": [_p, _p, C.c_int],
@@ -80,6 +81,7 @@ _SIGNATURES = {
     "hg_get_hist": [_p, _p],
     "hg_get_rel_hist": [_p, _p, _p],
     "hg_get_grade_hist": [_p, _p],
+    "hg_get_joint_hist": [_p, _p],
     "hg_get_graded": [_p, _p, _p, _p, _p],
     "hg_get_grades": [_p, _p],
     "hg_get_tie_ap": [_p, _p, _p, _p, _p, _p, _p, _p],
@@ -279,6 +281,10 @@ class Context:
     def grade_hist(self):
         """One pass over the label pairs: rows per (grade, query), grade = labels shared with the query."""
         check(self._lib.hg_grade_hist(self._h))
+
+    def joint_hist(self):
+        """One pass over the pairs: rows per (distance, grade, query), grade = labels shared with the query."""
+        check(self._lib.hg_joint_hist(self._h))
 
     def graded(self, ks, gain, disc, keep_grades=False):
         """Graded sums along the ranked lists of the last topr() / topr_real() at the ascending cut-offs ks; gain [C+1] and
@@ -528,6 +534,12 @@ class Context:
         check(self._lib.hg_get_grade_hist(self._h, _ptr(h)))
         return h
 
+    def get_joint_hist(self):
+        """-> uint32 [b+1, G, Q] of this shard, G = stat "joint_hist_grades" (after joint_hist())."""
+        h = np.empty(((self.b or 0) + 1, self.get_stat("joint_hist_grades"), self.Q or 0), dtype=np.uint32)
+        check(self._lib.hg_get_joint_hist(self._h, _ptr(h)))
+        return h
+
     # -- collectives (RCCL) -------------------------------------------------------
     def comm_init(self, unique_id, rank, world):
         buf = (C.c_uint8 * COMM_ID_BYTES).from_buffer_copy(bytes(unique_id))
@@ -629,7 +641,7 @@ class Context:
         check(self._lib.hg_timing_reset(self._h))
 
     def timing_read(self):
-        cap = 32
+        cap = 64
         names = (C.c_char_p * cap)()
         ms = (C.c_double * cap)()
         cnt = (_i64 * cap)()

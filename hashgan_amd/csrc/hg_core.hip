@@ -25,7 +25,8 @@ int fail(int code, const char* fmt, ...) {
 const char* const kKernelNames[KI_COUNT] = {"k_hist", "k_hist_reduce", "k_plan", "k_seg_counts", "k_seg_layout", "k_guess",
                                             "k_select", "k_rank_hist", "k_order", "k_rank_fused", "k_match", "k_ap", "k_merge", "k_pack",
                                             "k_real_sample", "k_real_guess", "k_real_select", "k_radix_pass", "k_real_finish", "k_select_mx", "k_rank_cnt", "rccl_allgather", "step_gpu_span", "k_real_rescore",
-                                            "k_hist_rel", "k_hist_rel_reduce", "k_graded", "k_grade_hist", "k_grade_hist_reduce", "k_tie_ap", "k_ap_at"};
+                                            "k_hist_rel", "k_hist_rel_reduce", "k_graded", "k_grade_hist", "k_grade_hist_reduce", "k_tie_ap", "k_ap_at",
+                                            "k_label_max", "k_hist_joint", "k_hist_joint_reduce"};
 // Flatten NumPy's pairwise-summation tree for a chunk of n elements (n <= 8192):
 // numpy/_core/src/umath/loops_utils.h.src, pairwise_sum: n <= 128 is a leaf,
 // otherwise split at n/2 rounded down to a multiple of 8.
@@ -1192,6 +1193,8 @@ int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "slice_cap")) *value = c->cap;
     else if (!strcmp(key, "rel_hist_variant")) *value = c->last_rel_hist;
     else if (!strcmp(key, "ap_at_cutoffs")) *value = c->aa.dim;
+    else if (!strcmp(key, "joint_hist_grades")) *value = c->jh_G;
+    else if (!strcmp(key, "joint_hist_bands")) *value = c->jh_bands;
     else if (!strcmp(key, "ap_fused")) *value = c->ap_fused ? 1 : 0;
     else if (!strcmp(key, "cap_boost")) *value = c->cap_boost;
     else if (!strcmp(key, "crowding_x100")) *value = c->crowd_x100;

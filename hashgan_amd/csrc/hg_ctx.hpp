@@ -3,7 +3,7 @@
 //
 //   hg_core.hip        context, tables (hg_set_*), options / statistics / timing, label match, AP, downloads
 //   hg_seq.hip         the Hamming sequences: geometry, histogram -> plan -> select -> rank, staged (sharded) and one-shot forms
-//   hg_side.hip        the side metrics (hg_rel_hist, hg_graded, hg_grade_hist, hg_tie_ap, hg_ap_at) and their getters: one SideResult each
+//   hg_side.hip        the side metrics (hg_rel_hist, hg_graded, hg_grade_hist, hg_tie_ap, hg_ap_at, hg_joint_hist) and their getters: one SideResult each
 //   hg_pairs_valu.hip  launchers of the vector-ALU pair passes (k_hist, k_select, k_select_dense)
 //   hg_pairs_mx.hip    launchers of the matrix-core pair passes (k_select_mx3 / mx4, k_hist_mx, k_hist_i8) and their images
 //   hg_pairs_mx1.hip   launcher of k_select_mx (every code length: the longest compile)
@@ -211,7 +211,7 @@ struct DevBuf {
 enum KernelId { KI_HIST = 0, KI_HIST_REDUCE, KI_PLAN, KI_SEG_COUNTS, KI_SEG_LAYOUT, KI_GUESS, KI_SELECT, KI_CAND_HIST,
                 KI_ORDER, KI_RANK_FUSED, KI_MATCH, KI_AP, KI_MERGE, KI_PACK, KI_REAL_SAMPLE, KI_REAL_GUESS, KI_REAL_SELECT,
                 KI_RADIX, KI_REAL_FINISH, KI_SELECT_MX, KI_RANK_LDS, KI_COMM, KI_STEP, KI_REAL_RESCORE, KI_HIST_REL, KI_HIST_REL_REDUCE,
-                KI_GRADED, KI_GRADE_HIST, KI_GRADE_HIST_REDUCE, KI_TIE_AP, KI_AP_AT, KI_COUNT };
+                KI_GRADED, KI_GRADE_HIST, KI_GRADE_HIST_REDUCE, KI_TIE_AP, KI_AP_AT, KI_LABEL_MAX, KI_HIST_JOINT, KI_HIST_JOINT_REDUCE, KI_COUNT };
 enum Stage { ST_NONE = 0, ST_DB = 1, ST_Q = 2, ST_HIST = 4, ST_PLAN = 8, ST_SELECT = 16, ST_MATCH = 32, ST_AP = 64 };
 extern const char* const kKernelNames[KI_COUNT];
 
@@ -358,7 +358,7 @@ struct RealState {
 };
 
 // The results of one side metric (hg_side.hip) and what they were computed from: the generations of the two tables, the rows Q, their
-// pitch Qpad (where the table is pitched), the second dimension (NB, C + 1, nk or nR).  The entry point calls begin() first and finish()
+// pitch Qpad (where the table is pitched), the second dimension (NB, C + 1, nk, nR or NB * G).  The entry point calls begin() first and finish()
 // last, so a refused or failed call leaves none; the getters, and hg_tie_ap for the histogram it reuses, ask current().  DESIGN.md, "Side metrics: the host side".
 struct hg_ctx;
 struct SideResult {
@@ -409,6 +409,8 @@ struct hg_ctx : StepBufs, StepState {
     SideResult gh;             // hg_grade_hist: gh_tab [C + 1][Qpad]
     SideResult ta;             // hg_tie_ap: ta_out's seven tables [Q][nR]
     SideResult aa;             // hg_ap_at: aa_out, ap [Q][nR] and rel [Q][nR] of the match bitmap the last ranking left; dim is also stat "ap_at_cutoffs"
+    SideResult jh;             // hg_joint_hist: jh_tab [NB * G][Qpad]; dim = NB * G
+    int jh_G = 0, jh_bands = 0;   // stats "joint_hist_grades" / "joint_hist_bands": grades and distance bands of the last hg_joint_hist (0: no pass yet)
     int last_rel_hist = 0;     // stat "rel_hist_variant": 1 k_hist_rel (0: no pass yet)
     bool gr_kept = false; i64 gr_R = 0;   // gr_grades holds the grade bytes [Q][gr_R] of gr's pass
     i64 aa_recip_n = -1;       // aa_recip holds RN(1 / k) for k = 1 .. this (+ AP_RECIP_SLACK)
@@ -492,6 +494,7 @@ struct hg_ctx : StepBufs, StepState {
     DevBuf rh_part, rh_all, rh_rel;   // hg_rel_hist: per-segment counters [S][2 NB][Qpad], the tables all / rel [NB][Qpad] (rh)
     DevBuf gr_tab, gr_out, gr_grades;   // hg_graded: [ks 64 x i64][gain C + 1][disc kmax], the tables gsum / hits / dcg / wsum [Q][nk] each, grade bytes [Q][R]
     DevBuf gh_part, gh_tab;    // hg_grade_hist: per-segment counters [S][C + 1][Qpad], the table [C + 1][Qpad] (gh)
+    DevBuf jh_max, jh_part, jh_tab;   // hg_joint_hist: {most labels on a query, on a database row}, per-segment counters [S][NB * G][Qpad], the table [NB * G][Qpad] (jh)
     DevBuf ta_tab, ta_out;     // hg_tie_ap: the cut-offs [64 x i64], the tables ap_exp / p_hit / ap_min / ap_max / rel_exp / rel_lo / rel_hi [Q][nR] each (ta)
     DevBuf aa_tab, aa_out;     // hg_ap_at: [cut-offs 64 x i64][ApShape x (1 + nR)], the tables ap [Q][nR] x 8 and rel [Q][nR] x 4 (aa)
     DevBuf aa_recip;           // hg_ap_at's own reciprocals (aa_recip_n) when the ranking's table (ap_recip, recip_for_R) is not there
@@ -522,7 +525,7 @@ struct hg_ctx : StepBufs, StepState {
         for (DevBuf* d : {&dbx, &qx, &dbx8, &dbx3, &dbx4, &dbfx, &dbfb, &xmax2, &shapes, &ap_recip, &aa_recip}) f(*d, BUF_DERIVED);
         for (DevBuf* d : {&seglt, &segtie, &mbits2, &part, &obuf[0], &obuf[1], &beyond, &stage_in, &badcnt, &flist, &dbytes, &samp, &thr,
                           &sortA, &sortB, &scores, &gtab, &sampx, &cntq, &krows, &thr2, &hist2, &comm_tmp, &gath_idx, &gath_dist, &rh_part, &rh_all, &rh_rel,
-                          &gr_tab, &gr_out, &gr_grades, &gh_part, &gh_tab, &ta_tab, &ta_out, &aa_tab, &aa_out})
+                          &gr_tab, &gr_out, &gr_grades, &gh_part, &gh_tab, &ta_tab, &ta_out, &aa_tab, &aa_out, &jh_max, &jh_part, &jh_tab})
             f(*d, BUF_WORK);
         for (DevBuf& d : gathered) f(d, BUF_WORK);
         for (DevBuf& d : scratch) f(d, BUF_WORK);
@@ -532,7 +535,7 @@ struct hg_ctx : StepBufs, StepState {
     // the keys of the BUF_DERIVED buffers: after this each is rebuilt on its next use
     void forget_derived() {
         dbx_valid = qx_valid = dbx8_valid = dbx3_valid = dbx4_valid = dbfx_valid = dbfb_valid = false;
-        for (SideResult* r : {&rh, &gr, &gh, &ta, &aa}) r->begin();   // (hg_trim releases their tables with the other work buffers)
+        for (SideResult* r : {&rh, &gr, &gh, &ta, &aa, &jh}) r->begin();   // (hg_trim releases their tables with the other work buffers)
         shapes_for_R = recip_for_R = aa_recip_n = -1;
         outblk_q = ws_b.outblk_q = -1;
     }

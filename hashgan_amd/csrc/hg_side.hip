@@ -6,6 +6,7 @@
 #include "hg_graded.hpp"
 #include "hg_tie_ap.hpp"
 #include "hg_ap_at.hpp"
+#include "hg_hist_joint.hpp"
 
 // the classes of the last label word
 static u64 lastmask(int C) { return C % 64 ? (1ull << (C % 64)) - 1ull : ~0ull; }
@@ -43,6 +44,35 @@ template <int LWT> static int launch_grade_hist_t(hg_ctx* c, Geo g, int G) {
     c->t_end();
     return c->check_launch("k_grade_hist");
 }
+
+// the distance-by-grade histogram: G counters per distance of the band in the lane's column
+template <int NW, int LWT> static int launch_hist_joint_t(hg_ctx* c, Geo g, const JointArgs& ja) {
+    // LDS: wpb * bw * G * 64 * 4 bytes; a band holds at most HJ_LDS_CELLS cells, so one wavefront always fits 160 KiB
+    const size_t column = (size_t)ja.bw * ja.G * 256;
+    int wpb = WPB;
+    while (wpb > 1 && (size_t)wpb * column > 160u * 1024u) wpb >>= 1;
+    g.wpb = wpb;
+    g.nBlk = (int)((g.nUnits + wpb - 1) / wpb) * ja.bands;
+    const size_t lds = (size_t)wpb * column;
+    static std::atomic<unsigned long long> lds_allowed{0};
+    if (lds > 64 * 1024 && !(lds_allowed.load() >> (c->device & 63) & 1ull)) {
+        HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hist_joint<NW, LWT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        lds_allowed.fetch_or(1ull << (c->device & 63));
+    }
+    c->t_begin(KI_HIST_JOINT);
+    hipLaunchKernelGGL((k_hist_joint<NW, LWT>), dim3(padded_grid(g.nBlk)), dim3(64 * wpb), lds, c->stream, c->qc.as<u32>(),
+                       c->qlab.as<u64>(), c->db.as<u32>(), c->dblab.as<u64>(), c->jh_part.as<u32>(), g, ja);
+    c->t_end();
+    return c->check_launch("k_hist_joint");
+}
+template <int NW> static int hist_joint_nw(hg_ctx* c, const Geo& g, const JointArgs& ja) {
+    switch (c->LW) {
+        case 1: return launch_hist_joint_t<NW, 1>(c, g, ja);
+        case 2: return launch_hist_joint_t<NW, 2>(c, g, ja);
+        default: return launch_hist_joint_t<NW, 0>(c, g, ja);
+    }
+}
+static int launch_hist_joint(hg_ctx* c, const Geo& g, const JointArgs& ja) { HG_DISPATCH_NW(hist_joint_nw, c, g, ja) }
 
 extern "C" {
 
@@ -135,6 +165,52 @@ int hg_grade_hist(hg_ctx* c) {
     c->t_end();
     HG_TRY(c->check_launch("k_grade_hist_reduce"));
     c->gh.finish(c, g.Q, g.Qpad, G);
+    return c->stage_end();
+}
+
+// The distance-by-grade histogram of this shard (hg_hist_joint.hpp): rows per (distance, grade, query) in one pass over the pairs.
+// G = 1 + min(most labels on a query, most labels on a database row) comes from a max-reduce over the two label tables (one
+// synchronisation: the host sizes the buffers and the LDS column by it).  A geometry of its own, cut from the full pass's: the bands
+// multiply the grid, so the segments are divided by them -- c->geo is not touched.
+int hg_joint_hist(hg_ctx* c) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_joint_hist", "hg_set_database + hg_set_queries"));
+    if (c->C > GR_MAX_C) return fail(HG_ERR_ARG, "hg_joint_hist: C=%d classes (a grade is a byte: at most %d)", c->C, GR_MAX_C);
+    Geo g = full_geometry(c);
+    c->jh.begin();
+    const FirstReservations first;
+    HG_TRY(c->jh_max.reserve(8));
+    HG_HIP(hipMemsetAsync(c->jh_max.p, 0, 8, c->stream));
+    c->t_begin(KI_LABEL_MAX);
+    hipLaunchKernelGGL(k_label_max, dim3(grid_for((i64)g.Qpad + c->N)), dim3(256), 0, c->stream, c->qlab.as<u64>(), c->dblab.as<u64>(),
+                       c->Q, (i64)g.Qpad, c->N, c->LW, lastmask(c->C), c->jh_max.as<u32>());
+    c->t_end();
+    HG_TRY(c->check_launch("k_label_max"));
+    u32 most[2] = {0, 0};
+    HG_HIP(hipMemcpyAsync(most, c->jh_max.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HG_TRY(c->sync());
+    JointArgs ja;
+    ja.G = 1 + (int)(most[0] < most[1] ? most[0] : most[1]);
+    if (ja.G > c->C + 1) return fail(HG_ERR_HIP, "hg_joint_hist: %d grades from %d classes", ja.G, c->C);   // (the popcounts are masked: cannot happen)
+    ja.bw = g.NB * ja.G <= HJ_LDS_CELLS ? g.NB : HJ_LDS_CELLS / ja.G;      // (G <= 256: a band has at least two distances)
+    ja.bands = (g.NB + ja.bw - 1) / ja.bw;
+    ja.lastmask = lastmask(c->C);
+    if (ja.bands > 1) {                                // S x bands ~ the full pass's S
+        const i64 S = (g.S + ja.bands / 2) / ja.bands > 1 ? (g.S + ja.bands / 2) / ja.bands : 1;
+        g.L = ((c->N + S - 1) / S + 31) / 32 * 32;
+        g.S = (int)((c->N + g.L - 1) / g.L);
+        g.nUnits = (i64)g.S * g.nQT;
+    }
+    const i64 plane = (i64)g.NB * ja.G * g.Qpad;
+    HG_TRY(c->jh_part.reserve((size_t)plane * 4 * g.S));
+    HG_TRY(c->jh_tab.reserve((size_t)plane * 4));
+    first.keep(c);
+    HG_TRY(launch_hist_joint(c, g, ja));
+    c->jh_G = ja.G; c->jh_bands = ja.bands;
+    c->t_begin(KI_HIST_JOINT_REDUCE);
+    hipLaunchKernelGGL(k_hist_joint_reduce, dim3(grid_for(plane)), dim3(256), 0, c->stream, c->jh_part.as<u32>(), c->jh_tab.as<u32>(), plane, g.S);
+    c->t_end();
+    HG_TRY(c->check_launch("k_hist_joint_reduce"));
+    c->jh.finish(c, g.Q, g.Qpad, (i64)g.NB * ja.G);
     return c->stage_end();
 }
 
@@ -259,6 +335,14 @@ int hg_get_grade_hist(hg_ctx* c, uint32_t* host_hist) {
     if (!c->gh.current(c)) return fail(HG_ERR_STATE, "hg_get_grade_hist called before hg_grade_hist (on the tables loaded now)");
     if (!host_hist) return fail(HG_ERR_ARG, "hg_get_grade_hist: null pointer");
     HG_TRY(download_pitched(c, host_hist, c->gh_tab, c->gh.Q, c->gh.Qpad, c->gh.dim));
+    return c->sync();
+}
+
+int hg_get_joint_hist(hg_ctx* c, uint32_t* host_hist) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_joint_hist", "hg_joint_hist"));
+    if (!c->jh.current(c)) return fail(HG_ERR_STATE, "hg_get_joint_hist called before hg_joint_hist (on the tables loaded now)");
+    if (!host_hist) return fail(HG_ERR_ARG, "hg_get_joint_hist: null pointer");
+    HG_TRY(download_pitched(c, host_hist, c->jh_tab, c->jh.Q, c->jh.Qpad, c->jh.dim));
     return c->sync();
 }
 

@@ -19,6 +19,12 @@ AP@R over all those orders, the probability that the top R hold a hit, and the e
 of the relevant-row histogram and R alone (Context.tie_ap), no ranking and no lists; tie_aware_precision_recall_at_k the expected
 precision and recall at k from the same call.  Shuffling the database rows leaves every one of these bits unchanged.
 
+Tie-aware graded relevance (the same paper defines tie-aware DCG / NDCG next to tie-aware AP): along the canonical list NDCG@k and ACG@k
+depend on how the rows happen to be ordered inside each tie group.  tie_aware_graded_at_k gives their expectation over uniformly random
+orders inside every group and the exact minimum and maximum, per query -- functions of one table, the rows per (distance, grade)
+(Context.joint_hist, one pass over the pairs; distance_grade_histograms for the table, tie_graded_from_tables for the reduction alone).
+Shuffling the database rows leaves every one of these bits unchanged.
+
 Many cut-offs from one ranking: map_at_k gives mAP@k, precision@k and recall@k for up to 64 cut-offs -- binary codes or real-valued
 features, host or device arrays -- from ONE ranking at max(ks): the top k is a prefix of the top max(ks), and Context.ap_at walks the
 match bitmap that ranking left once per query for all of them (hg_ap_at; every AP with the bits a ranking at that k alone gives).
@@ -129,6 +135,19 @@ def discount_table(kmax):
     return 1.0 / np.log2(np.arange(2, int(kmax) + 2, dtype=np.float64))
 
 
+def _idcg(grade_hist, ks, gain, cum):
+    """IDCG@k [Q, len(ks)]: the DCG of the database sorted by grade descending (graded_from_tables)."""
+    Q, G = grade_hist.shape
+    above = np.zeros(Q, dtype=np.int64)                                  # rows with a higher grade than the one being placed
+    idcg = np.zeros((Q, ks.size), dtype=np.float64)
+    for g in range(G - 1, -1, -1):
+        start = np.minimum(above[:, None], ks[None, :])
+        above = above + grade_hist[:, g]
+        end = np.minimum(above[:, None], ks[None, :])
+        idcg += gain[g] * (cum[end] - cum[start])
+    return idcg
+
+
 def graded_from_tables(gsum, hits, dcg, wsum, grade_hist, ks, gain, disc):
     """ACG@k, NDCG@k and WAP@k from the device tables (NumPy only).  gsum, hits, dcg, wsum: [Q, len(ks)] (Context.get_graded);
     grade_hist: [Q, C + 1] rows of the whole database per grade; gain [C + 1], disc [>= max(ks)] the tables the GPU was given.
@@ -152,13 +171,7 @@ def graded_from_tables(gsum, hits, dcg, wsum, grade_hist, ks, gain, disc):
         if a.shape != (Q, ks.size):
             raise ValueError("gsum, hits, dcg and wsum must be [Q, len(ks)] tables")
     cum = np.concatenate([[0.0], np.cumsum(disc[:ks[-1]])])             # cum[n] = discounts of the ranks 1..n
-    above = np.zeros(Q, dtype=np.int64)                                  # rows with a higher grade than the one being placed
-    idcg = np.zeros((Q, ks.size), dtype=np.float64)
-    for g in range(G - 1, -1, -1):
-        start = np.minimum(above[:, None], ks[None, :])
-        above = above + grade_hist[:, g]
-        end = np.minimum(above[:, None], ks[None, :])
-        idcg += gain[g] * (cum[end] - cum[start])
+    idcg = _idcg(grade_hist, ks, gain, cum)
     has = idcg > 0
     with np.errstate(divide="ignore", invalid="ignore"):
         ndcg = np.where(has, dcg / idcg, np.nan)
@@ -220,6 +233,128 @@ def graded_relevance_at_k(q, db, q_labels, db_labels, ks, gain="exp", features=F
         ctx.grade_hist()
         hist = ctx.get_grade_hist().T
     return graded_from_tables(gsum, hits, dcg, wsum, hist, ks, tab, disc)
+
+
+def _joint_table(q_codes, db_codes, q_labels, db_labels, device):
+    """The four arrays as metric._sides hands them over -> int64 [Q, b + 1, G]."""
+    eng = metric._Shared.get(device)
+    with eng.lock:
+        ctx = _load_sided(eng, q_codes, db_codes, q_labels, db_labels)
+        ctx.joint_hist()
+        return np.ascontiguousarray(ctx.get_joint_hist().transpose(2, 0, 1)).astype(np.int64)
+
+
+def _sided_graded_inputs(q_codes, db_codes, q_labels, db_labels):
+    db_codes, db_labels = metric._sides(db_codes, db_labels, "database")
+    q_codes, q_labels = metric._sides(q_codes, q_labels, "query")
+    metric._check_shapes(q_codes, db_codes, q_labels, db_labels, 1)
+    if db_labels.shape[1] > MAX_CLASSES:
+        raise ValueError("graded relevance takes up to %d classes (have %d)" % (MAX_CLASSES, db_labels.shape[1]))
+    return q_codes, db_codes, q_labels, db_labels
+
+
+def distance_grade_histograms(q_codes, db_codes, q_labels, db_labels, device=0):
+    """Per query, Hamming distance d = 0..b and grade g = 0..G-1: the database rows at distance d that share exactly g labels with
+    the query.  G = 1 + min(most labels on a query, most labels on a database row): no pair has a higher grade.  Binary codes
+    ({0,1} or +-1); every array may be a host array or lie in device memory, like map_at_k's.  One pass over the pairs on the GPU
+    (Context.joint_hist); no ranking, no lists.  -> int64 [Q, b + 1, G]"""
+    return _joint_table(*_sided_graded_inputs(q_codes, db_codes, q_labels, db_labels), device)
+
+
+def tie_graded_from_tables(joint, ks, gain, disc):
+    """Tie-aware DCG@k, NDCG@k and ACG@k from the distance-by-grade table (NumPy only).  joint: [Q, b + 1, G] rows per (distance,
+    grade) of the whole database; ks: strictly ascending cut-offs; gain: "exp", "linear" or G non-decreasing values; disc [>= max(ks)]:
+    non-increasing, non-negative discounts (disc[i - 1] for rank i) -- both envelope arguments need the monotonicity.
+    Per query, with n_d = sum_g J[d][g] the size of tie group d, a_d the rows closer than d, m_d(k) = clamp(k - a_d, 0, n_d) the group's
+    positions within k and cum[n] the discounts of the ranks 1..n, over uniformly random, independent orders inside every group:
+      gsum_exp = sum_d m_d (sum_g g J[d][g]) / n_d,   acg = gsum_exp / k,   hits_exp = sum_d m_d (n_d - J[d][0]) / n_d,
+      dcg      = sum_d (sum_g gain[g] J[d][g]) / n_d (cum[a_d + m_d] - cum[a_d])           (the expectations)
+      dcg_max, gsum_hi   the group's m_d highest grades fill its positions within k in descending order,
+      dcg_min, gsum_lo   its m_d lowest grades in ascending order; the groups are independent, so these are the exact extremes.
+    idcg as graded_from_tables computes it, from the table summed over d; ndcg, ndcg_min, ndcg_max = dcg, dcg_min, dcg_max / idcg
+    (NaN where idcg is 0).  Means: acg over all queries, ndcg over those with idcg > 0.  The order of every float addition is fixed by the
+    query's table and ks (d ascending; inside a group g ascending, descending for the maximum): a query's results do not depend on Q.
+    -> dict(acg, ndcg [len(ks)], per_query=dict(acg, acg_min, acg_max, dcg, dcg_min, dcg_max, idcg, ndcg, ndcg_min, ndcg_max,
+    gsum_exp, gsum_lo, gsum_hi, hits_exp [Q, len(ks)], total_rel [Q]))"""
+    joint = np.asarray(joint)
+    if joint.ndim != 3 or joint.shape[2] < 1:
+        raise ValueError("joint must be a [Q, b + 1, G] table")
+    joint = joint.astype(np.int64)
+    Q, NB, G = joint.shape
+    gain = gain_table(gain, G - 1)
+    ks = _check_ks(ks, None)
+    disc = np.asarray(disc, dtype=np.float64)
+    if disc.ndim != 1 or disc.size < ks[-1]:
+        raise ValueError("disc must hold a discount for every rank up to max(ks)")
+    disc = disc[:ks[-1]]
+    if not np.isfinite(disc).all() or (disc < 0).any() or (np.diff(disc) > 0).any():
+        raise ValueError("disc must be finite, non-negative and non-increasing in the rank")
+    nk = ks.size
+    cum = np.concatenate([[0.0], np.cumsum(disc)])                       # cum[n] = discounts of the ranks 1..n
+    grades = np.arange(G, dtype=np.int64)
+    f = {k: np.zeros((Q, nk), dtype=np.float64) for k in ("gsum_exp", "hits_exp", "dcg", "dcg_min", "dcg_max")}
+    gsum_lo, gsum_hi = np.zeros((Q, nk), dtype=np.int64), np.zeros((Q, nk), dtype=np.int64)
+    a = np.zeros(Q, dtype=np.int64)                                      # rows closer than d
+
+    def expected(m, n, s):
+        """m s / n: what m of the group's n rows, drawn uniformly, are expected to add up to when all n add up to s (s when m = n)."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            part = m.astype(np.float64) * s[:, None].astype(np.float64) / n[:, None].astype(np.float64)
+        return np.where(m == n[:, None], s[:, None].astype(np.float64), np.where(m > 0, part, 0.0))
+
+    for d in range(NB):
+        J = joint[:, d, :]
+        n = J.sum(1)
+        start = np.minimum(a[:, None], ks[None, :])
+        m = np.minimum((a + n)[:, None], ks[None, :]) - start            # the group's positions within k
+        a = a + n
+        if not m.any():
+            continue
+        f["gsum_exp"] += expected(m, n, (J * grades[None, :]).sum(1))
+        f["hits_exp"] += expected(m, n, n - J[:, 0])
+        w = np.zeros(Q, dtype=np.float64)
+        for g in range(G):
+            w = w + gain[g] * J[:, g]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            w = np.where(n > 0, w / n, 0.0)
+        f["dcg"] += w[:, None] * (cum[start + m] - cum[start])
+        for name, gs, order in (("dcg_min", gsum_lo, range(G)), ("dcg_max", gsum_hi, range(G - 1, -1, -1))):
+            left, pos = m.copy(), start.copy()
+            for g in order:
+                take = np.minimum(J[:, g][:, None], left)
+                f[name] += gain[g] * (cum[pos + take] - cum[pos])
+                gs += g * take
+                pos += take
+                left -= take
+    hist = joint.sum(1)
+    idcg = _idcg(hist, ks, gain, cum)
+    has = idcg > 0
+    pq = {"acg": f["gsum_exp"] / ks[None, :], "acg_min": gsum_lo / ks[None, :], "acg_max": gsum_hi / ks[None, :],
+          "dcg": f["dcg"], "dcg_min": f["dcg_min"], "dcg_max": f["dcg_max"], "idcg": idcg}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for name in ("ndcg", "ndcg_min", "ndcg_max"):
+            pq[name] = np.where(has, pq[name[1:]] / idcg, np.nan)
+    pq.update(gsum_exp=f["gsum_exp"], gsum_lo=gsum_lo, gsum_hi=gsum_hi, hits_exp=f["hits_exp"], total_rel=hist[:, 1:].sum(1))
+    ndcg = np.array([pq["ndcg"][has[:, j], j].mean() if has[:, j].any() else np.nan for j in range(nk)])
+    return {"acg": pq["acg"].mean(0) if Q else np.full(nk, np.nan), "ndcg": ndcg, "per_query": pq}
+
+
+def tie_aware_graded_at_k(q_codes, db_codes, q_labels, db_labels, ks, gain="exp", device=0):
+    """Tie-aware ACG@k and NDCG@k of a Hamming ranking with grade = number of labels a row shares with the query, at the strictly
+    ascending cut-offs ks (at most 64, each in 1..N): per query the expectation over uniformly random orders inside every group of
+    rows at equal distance, and the exact minimum and maximum over all those orders -- where graded_relevance_at_k reports the one
+    order "by database index".  gain: "exp" (2^g - 1), "linear" (g) or C + 1 non-decreasing values; the discount is 1 / log2(1 + rank).
+    Binary codes ({0,1} or +-1); every array may be a host array or lie in device memory, like map_at_k's.  One pass over the pairs
+    on the GPU (Context.joint_hist) and a NumPy reduction of its [Q, b + 1, G] table: no ranking, no lists, nothing of size Q x N or
+    Q x k on the host.  Out of scope: tie-aware WAP (its expectation is AP-shaped and needs tie_aware_map's machinery on the device);
+    real-valued features (an inner-product ranking has no tie groups to average over); a matrix-core form of the pass (LDS atomics
+    bound every histogram here).  -> tie_graded_from_tables' dict"""
+    q_codes, db_codes, q_labels, db_labels = _sided_graded_inputs(q_codes, db_codes, q_labels, db_labels)
+    ks = _check_ks(ks, db_codes.shape[0])
+    tab = gain_table(gain, db_labels.shape[1])
+    disc = discount_table(ks[-1])
+    joint = _joint_table(q_codes, db_codes, q_labels, db_labels, device)
+    return tie_graded_from_tables(joint, ks, tab[:joint.shape[2]], disc)
 
 
 def _tie_tables(q_codes, db_codes, q_labels, db_labels, Rs, device):

@@ -152,6 +152,17 @@ int hg_rel_hist(hg_ctx* ctx);                                            /* need
  * (HG_ERR_ARG beyond).  Same rules as hg_rel_hist: a table of its own, the staged pipeline's state and a step of hg_map_begin in
  * flight are left as they were; additive over shards; a database or query reload invalidates it; hg_trim frees it. */
 int hg_grade_hist(hg_ctx* ctx);                                          /* needs database + queries */
+/* The distance-by-grade histogram of this shard, for tie-aware graded metrics (expected DCG / NDCG / ACG at k over the orders inside
+ * the Hamming tie groups, and their exact extremes): one pass over the pairs counts, per query, distance d = 0..b and grade g = 0..G-1,
+ * the rows at distance d that share exactly g labels with the query -- no ranking, no lists.  hg_rel_hist's tables are this one collapsed
+ * to g = 0 / g > 0, hg_grade_hist's is this one summed over d.  G = 1 + min(most labels on a loaded query, most labels on a loaded
+ * database row), an upper bound on any pair's grade, found on the device first (stat "joint_hist_grades"; the call synchronises once
+ * for it whatever "stage_sync" says).  When (b+1) * G > 640 a wavefront's counters outgrow the LDS and the distances are served in
+ * bands of 640 / G (stat "joint_hist_bands"); the table is the same for any band count.  C <= 255 (HG_ERR_ARG beyond), b up to
+ * HG_MAX_BITS.  Same rules as hg_rel_hist: tables of its own, the staged pipeline's state, the other side metrics' results and a step
+ * of hg_map_begin in flight are left as they were; additive over shards (zero-pad to a common G; idx_base plays no part); a database
+ * or query reload invalidates it; hg_trim frees it. */
+int hg_joint_hist(hg_ctx* ctx);                                          /* needs database + queries */
 int hg_plan(hg_ctx* ctx, int64_t R, const uint32_t* dev_hist_all, int G, int rank);
 int hg_select(hg_ctx* ctx);
 int hg_match(hg_ctx* ctx);
@@ -271,6 +282,7 @@ int hg_get_ap(hg_ctx* ctx, double* host_ap, int64_t* host_rel);         /* [Q]; 
 int hg_get_hist(hg_ctx* ctx, uint32_t* host_hist);                      /* [b+1][Q] of this shard */
 int hg_get_rel_hist(hg_ctx* ctx, uint32_t* host_all, uint32_t* host_rel); /* [b+1][Q] each, this shard (after hg_rel_hist) */
 int hg_get_grade_hist(hg_ctx* ctx, uint32_t* host_hist);                /* [C+1][Q] of this shard (after hg_grade_hist) */
+int hg_get_joint_hist(hg_ctx* ctx, uint32_t* host_hist);                /* [b+1][G][Q] of this shard, G = stat "joint_hist_grades" (after hg_joint_hist) */
 
 /* ---- graded relevance along the ranked lists (ACG, NDCG, WAP at k) -------------
  * hg_graded walks the ranked index lists the last ranking left on the device -- hg_topr, a staged hg_select with lists, hg_topr_real;
@@ -403,10 +415,10 @@ int hg_set_stream(hg_ctx* ctx, void* hip_stream);
  *                 ALU), "real_sample_half" (1: the sampled cut's scores in the filter's 16-bit arithmetic -- they only place the cut; 0: exact float32 chains), "real_second_sample" (1: a second, counting sample four times as large tightens that cut), "real_sort_lds" (1: ranked by the LDS-resident kernel when the records fit), "real_groups" (1: lists beyond the LDS ordered group by group), "real_map_lists" (0; 1: hg_map_real also writes the ranked idx / score lists), "real_whole_rounds" (3: without a cut -- R = N -- the database is cut so that k_real_select_mx's blocks fill whole rounds of that many per CU; 0: the plain geometry)
  *   ("probe_select" exists only in the measurement build, python -m hashgan_amd.build --probes) */
 int hg_set_option(hg_ctx* ctx, const char* key, int64_t value);
-/* Counters and facts about the last call (28 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
+/* Counters and facts about the last call (30 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
  * "optimistic_requeried" (single queries rerun exactly after losing their bet), "optimistic_rebets" (second and widened bets), "last_optimistic",
  * "rank_leftovers" (queries the LDS-resident rank kernel left to the general one), "select_variant" (1 k_select, 2 k_select_dense, 3 k_select_mx,
- * 5 k_select_mx3, 6 k_select_mx4), "rank_variant" (1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>), "hist_variant" (the kernel of the last histogram pass, full or sampled: 1 k_hist, 2 k_hist_mx, 3 k_hist_i8; 6 / 7: k_hist_mx / k_hist_i8 with one dword counter per query tile instead of 16-bit halves; 0: no pass yet), "rank_lds_recs" (records the last k_rank_lean / k_rank_cnt launch had LDS room for), "slice_cap" (capacity of a (segment, query) slice of the last bet), "rel_hist_variant" (the kernel of the last hg_rel_hist: 1 k_hist_rel, the vector-ALU pass -- the only one so far, whatever "hist_mfma" says; 0: no pass yet), "ap_at_cutoffs" (cut-offs of the last hg_ap_at; 0: no pass yet), "ap_fused",
+ * 5 k_select_mx3, 6 k_select_mx4), "rank_variant" (1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>), "hist_variant" (the kernel of the last histogram pass, full or sampled: 1 k_hist, 2 k_hist_mx, 3 k_hist_i8; 6 / 7: k_hist_mx / k_hist_i8 with one dword counter per query tile instead of 16-bit halves; 0: no pass yet), "rank_lds_recs" (records the last k_rank_lean / k_rank_cnt launch had LDS room for), "slice_cap" (capacity of a (segment, query) slice of the last bet), "rel_hist_variant" (the kernel of the last hg_rel_hist: 1 k_hist_rel, the vector-ALU pass -- the only one so far, whatever "hist_mfma" says; 0: no pass yet), "ap_at_cutoffs" (cut-offs of the last hg_ap_at; 0: no pass yet), "joint_hist_grades" / "joint_hist_bands" (grades G and distance bands of the last hg_joint_hist; 0: no pass yet), "ap_fused",
  * "cap_boost", "crowding_x100", "segments", "records_kept" (records the last bet's select left in the slices: a download, not part of a step),
  * "device_bytes" (every device buffer the context and its requery child hold, the second stream's workspace included), "graph_replays", "map_async_steps" / "map_async_redone" / "map_overlapped_steps" (hg_map_begin: steps enqueued blind / of those, run again by hg_map_end /
  * of those, run on the second stream);
