@@ -75,6 +75,9 @@ _SIGNATURES = {
     "hg_map_real": [_p, _i64, _p, _p],
     "hg_topr_real": [_p, _i64],
     "hg_get_topr_real": [_p, _p, _p],
+    "hg_topr_rerank": [_p, _i64],
+    "hg_map_rerank": [_p, _i64, _p, _p],
+    "hg_get_rerank_scores": [_p, _p],
     "hg_get_topr": [_p, _p, _p],
     "hg_get_match": [_p, _p],
     "hg_get_ap": [_p, _p, _p],
@@ -466,6 +469,28 @@ class Context:
         score = np.empty((self.Q, self.R), dtype=np.float32)
         check(self._lib.hg_get_topr_real(self._h, _ptr(idx), _ptr(score)))
         return idx, score
+
+    # -- Hamming ranking, ties re-ranked by the float inner product ---------------
+    def topr_rerank(self, R, download=True):
+        """Rank by (Hamming distance, inner product descending, index) -> (idx, dist, scores); download=False: the lists stay on the device."""
+        check(self._lib.hg_topr_rerank(self._h, int(R)))
+        self.R = int(R)
+        if not download:
+            return None
+        idx, dist = self.get_topr()
+        return idx, dist, self.get_rerank_scores()
+
+    def map_rerank(self, R):
+        ap = np.empty(self.Q, dtype=np.float64)
+        rel = np.empty(self.Q, dtype=np.int64)
+        check(self._lib.hg_map_rerank(self._h, int(R), _ptr(ap), _ptr(rel)))
+        self.R = int(R)
+        return ap, rel
+
+    def get_rerank_scores(self):
+        s = np.empty((self.Q or 0, self.R or 0), dtype=np.float32)      # (before any ranking the call is refused: nothing is written)
+        check(self._lib.hg_get_rerank_scores(self._h, _ptr(s)))
+        return s
 
     # -- results ----------------------------------------------------------------
     def get_topr(self):

@@ -26,7 +26,8 @@ const char* const kKernelNames[KI_COUNT] = {"k_hist", "k_hist_reduce", "k_plan",
                                             "k_select", "k_rank_hist", "k_order", "k_rank_fused", "k_match", "k_ap", "k_merge", "k_pack",
                                             "k_real_sample", "k_real_guess", "k_real_select", "k_radix_pass", "k_real_finish", "k_select_mx", "k_rank_cnt", "rccl_allgather", "step_gpu_span", "k_real_rescore",
                                             "k_hist_rel", "k_hist_rel_reduce", "k_graded", "k_grade_hist", "k_grade_hist_reduce", "k_tie_ap", "k_ap_at",
-                                            "k_label_max", "k_hist_joint", "k_hist_joint_reduce"};
+                                            "k_label_max", "k_hist_joint", "k_hist_joint_reduce",
+                                            "k_rr_scan", "k_rr_collect", "k_rr_score", "k_rr_order"};
 // Flatten NumPy's pairwise-summation tree for a chunk of n elements (n <= 8192):
 // numpy/_core/src/umath/loops_utils.h.src, pairwise_sum: n <= 128 is a leaf,
 // otherwise split at n/2 rounded down to a multiple of 8.
@@ -1169,7 +1170,7 @@ int hg_preload(hg_ctx* c) {
     HG_TRY(ensure_pin(c, (size_t)1 << 20));
     hipFuncAttributes a;
     HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_ap<AP_THREADS>)));
-    HG_TRY(preload_seq()); HG_TRY(preload_side()); HG_TRY(preload_valu()); HG_TRY(preload_mx()); HG_TRY(preload_mx1()); HG_TRY(preload_real());
+    HG_TRY(preload_seq()); HG_TRY(preload_side()); HG_TRY(preload_valu()); HG_TRY(preload_mx()); HG_TRY(preload_mx1()); HG_TRY(preload_real()); HG_TRY(preload_rerank());
     host_pack_warm();
     return HG_OK;
 }
@@ -1195,6 +1196,10 @@ int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "ap_at_cutoffs")) *value = c->aa.dim;
     else if (!strcmp(key, "joint_hist_grades")) *value = c->jh_G;
     else if (!strcmp(key, "joint_hist_bands")) *value = c->jh_bands;
+    else if (!strcmp(key, "rerank_records")) *value = c->rr_records;
+    else if (!strcmp(key, "rerank_chunks")) *value = c->rr_chunks;
+    else if (!strcmp(key, "rerank_groups_lds")) *value = c->rr_groups_lds;
+    else if (!strcmp(key, "rerank_groups_global")) *value = c->rr_groups_global;
     else if (!strcmp(key, "ap_fused")) *value = c->ap_fused ? 1 : 0;
     else if (!strcmp(key, "cap_boost")) *value = c->cap_boost;
     else if (!strcmp(key, "crowding_x100")) *value = c->crowd_x100;

@@ -4,6 +4,7 @@
 //   hg_core.hip        context, tables (hg_set_*), options / statistics / timing, label match, AP, downloads
 //   hg_seq.hip         the Hamming sequences: geometry, histogram -> plan -> select -> rank, staged (sharded) and one-shot forms
 //   hg_side.hip        the side metrics (hg_rel_hist, hg_graded, hg_grade_hist, hg_tie_ap, hg_ap_at, hg_joint_hist) and their getters: one SideResult each
+//   hg_rerank.hip      the re-ranked Hamming ranking (hg_topr_rerank, hg_map_rerank): distance, then float32 inner product inside equal distances
 //   hg_pairs_valu.hip  launchers of the vector-ALU pair passes (k_hist, k_select, k_select_dense)
 //   hg_pairs_mx.hip    launchers of the matrix-core pair passes (k_select_mx3 / mx4, k_hist_mx, k_hist_i8) and their images
 //   hg_pairs_mx1.hip   launcher of k_select_mx (every code length: the longest compile)
@@ -211,7 +212,8 @@ struct DevBuf {
 enum KernelId { KI_HIST = 0, KI_HIST_REDUCE, KI_PLAN, KI_SEG_COUNTS, KI_SEG_LAYOUT, KI_GUESS, KI_SELECT, KI_CAND_HIST,
                 KI_ORDER, KI_RANK_FUSED, KI_MATCH, KI_AP, KI_MERGE, KI_PACK, KI_REAL_SAMPLE, KI_REAL_GUESS, KI_REAL_SELECT,
                 KI_RADIX, KI_REAL_FINISH, KI_SELECT_MX, KI_RANK_LDS, KI_COMM, KI_STEP, KI_REAL_RESCORE, KI_HIST_REL, KI_HIST_REL_REDUCE,
-                KI_GRADED, KI_GRADE_HIST, KI_GRADE_HIST_REDUCE, KI_TIE_AP, KI_AP_AT, KI_LABEL_MAX, KI_HIST_JOINT, KI_HIST_JOINT_REDUCE, KI_COUNT };
+                KI_GRADED, KI_GRADE_HIST, KI_GRADE_HIST_REDUCE, KI_TIE_AP, KI_AP_AT, KI_LABEL_MAX, KI_HIST_JOINT, KI_HIST_JOINT_REDUCE,
+                KI_RR_SCAN, KI_RR_COLLECT, KI_RR_SCORE, KI_RR_ORDER, KI_COUNT };
 enum Stage { ST_NONE = 0, ST_DB = 1, ST_Q = 2, ST_HIST = 4, ST_PLAN = 8, ST_SELECT = 16, ST_MATCH = 32, ST_AP = 64 };
 extern const char* const kKernelNames[KI_COUNT];
 
@@ -410,6 +412,8 @@ struct hg_ctx : StepBufs, StepState {
     SideResult ta;             // hg_tie_ap: ta_out's seven tables [Q][nR]
     SideResult aa;             // hg_ap_at: aa_out, ap [Q][nR] and rel [Q][nR] of the match bitmap the last ranking left; dim is also stat "ap_at_cutoffs"
     SideResult jh;             // hg_joint_hist: jh_tab [NB * G][Qpad]; dim = NB * G
+    SideResult rr;             // the last ranking was a re-rank (hg_rerank.hip) of these tables: rr_scores [Q][R]; dim = R.  Not a side metric -- set_R ends it
+    i64 rr_records = 0, rr_chunks = 0, rr_groups_lds = 0, rr_groups_global = 0;   // stats "rerank_records" / "rerank_chunks" / "rerank_groups_lds" / "rerank_groups_global" of the last re-rank
     int jh_G = 0, jh_bands = 0;   // stats "joint_hist_grades" / "joint_hist_bands": grades and distance bands of the last hg_joint_hist (0: no pass yet)
     int last_rel_hist = 0;     // stat "rel_hist_variant": 1 k_hist_rel (0: no pass yet)
     bool gr_kept = false; i64 gr_R = 0;   // gr_grades holds the grade bytes [Q][gr_R] of gr's pass
@@ -498,6 +502,8 @@ struct hg_ctx : StepBufs, StepState {
     DevBuf ta_tab, ta_out;     // hg_tie_ap: the cut-offs [64 x i64], the tables ap_exp / p_hit / ap_min / ap_max / rel_exp / rel_lo / rel_hi [Q][nR] each (ta)
     DevBuf aa_tab, aa_out;     // hg_ap_at: [cut-offs 64 x i64][ApShape x (1 + nR)], the tables ap [Q][nR] x 8 and rel [Q][nR] x 4 (aa)
     DevBuf aa_recip;           // hg_ap_at's own reciprocals (aa_recip_n) when the ranking's table (ap_recip, recip_for_R) is not there
+    DevBuf rr_recs, rr_tmp;    // re-rank: a chunk's records (row index, then the sort key), the radix passes' second buffer (groups beyond the LDS only)
+    DevBuf rr_base, rr_msz, rr_cnt, rr_scores;   // re-rank: a query's first record in its chunk [Q] x 8, records per query [Q] x 4, {groups in LDS, groups by radix}, the score lists [Q][R]
     DevBuf dbx3;               // fp4 image for k_select_mx3 (48-row supertiles, three rows per accumulator; dbx3_valid)
     DevBuf dbx4;               // fp4 image for k_select_mx4 (32-row supertiles, two rows per accumulator; codes of 65..128 bits; dbx4_valid)
     DevBuf dbfx;               // float features of the database in MFMA A-fragment order (k_real_select_mx; dbfx_valid)
@@ -525,7 +531,8 @@ struct hg_ctx : StepBufs, StepState {
         for (DevBuf* d : {&dbx, &qx, &dbx8, &dbx3, &dbx4, &dbfx, &dbfb, &xmax2, &shapes, &ap_recip, &aa_recip}) f(*d, BUF_DERIVED);
         for (DevBuf* d : {&seglt, &segtie, &mbits2, &part, &obuf[0], &obuf[1], &beyond, &stage_in, &badcnt, &flist, &dbytes, &samp, &thr,
                           &sortA, &sortB, &scores, &gtab, &sampx, &cntq, &krows, &thr2, &hist2, &comm_tmp, &gath_idx, &gath_dist, &rh_part, &rh_all, &rh_rel,
-                          &gr_tab, &gr_out, &gr_grades, &gh_part, &gh_tab, &ta_tab, &ta_out, &aa_tab, &aa_out, &jh_max, &jh_part, &jh_tab})
+                          &gr_tab, &gr_out, &gr_grades, &gh_part, &gh_tab, &ta_tab, &ta_out, &aa_tab, &aa_out, &jh_max, &jh_part, &jh_tab,
+                          &rr_recs, &rr_tmp, &rr_base, &rr_msz, &rr_cnt, &rr_scores})
             f(*d, BUF_WORK);
         for (DevBuf& d : gathered) f(d, BUF_WORK);
         for (DevBuf& d : scratch) f(d, BUF_WORK);
@@ -535,7 +542,7 @@ struct hg_ctx : StepBufs, StepState {
     // the keys of the BUF_DERIVED buffers: after this each is rebuilt on its next use
     void forget_derived() {
         dbx_valid = qx_valid = dbx8_valid = dbx3_valid = dbx4_valid = dbfx_valid = dbfb_valid = false;
-        for (SideResult* r : {&rh, &gr, &gh, &ta, &aa, &jh}) r->begin();   // (hg_trim releases their tables with the other work buffers)
+        for (SideResult* r : {&rh, &gr, &gh, &ta, &aa, &jh, &rr}) r->begin();   // (hg_trim releases their tables with the other work buffers)
         shapes_for_R = recip_for_R = aa_recip_n = -1;
         outblk_q = ws_b.outblk_q = -1;
     }
@@ -705,6 +712,7 @@ Geo full_geometry(const hg_ctx* c);               // the full pass's segment geo
 inline void make_geometry(hg_ctx* c) { c->geo = full_geometry(c); }
 Geo hist_geometry(const hg_ctx* c);
 int set_R(hg_ctx* c, int64_t R, int G, int rank);
+int rerank_hist_plan(hg_ctx* c, int64_t R);       // full per-segment histogram (k_hist) + k_plan on one shard: c->hist, c->hown, c->t, c->cnt_lt, c->posbase
 // hg_pairs_valu.hip
 int launch_hist(hg_ctx* c);                      // k_hist<NW>
 int launch_hist_rel(hg_ctx* c, const Geo& g);    // k_hist_rel<NW, LW> into c->rh_part (g: full_geometry)
@@ -717,7 +725,7 @@ int launch_hist_mx(hg_ctx* c);                   // k_hist_i8 / k_hist_mx
 int launch_select_mx(hg_ctx* c, int lw, const int* cut);    // k_select_mx<NW, LW, QT, COMPACT>
 int launch_select_mx3(hg_ctx* c, int lw, const int* cut);   // k_select_mx3 (codes of <= 64 bits, one-byte records)
 int launch_select_mx4(hg_ctx* c, int lw, const int* cut);   // k_select_mx4 (codes of 65..128 bits, one-byte records)
-int preload_valu(); int preload_mx(); int preload_mx1(); int preload_real(); int preload_seq(); int preload_side();   // one per translation unit with kernels (hg_preload)
+int preload_valu(); int preload_mx(); int preload_mx1(); int preload_real(); int preload_seq(); int preload_side(); int preload_rerank();   // one per translation unit with kernels (hg_preload)
 // hg_comm.hip
 void comm_release(hg_ctx* c);                    // destroys the context's communicator, if any
 

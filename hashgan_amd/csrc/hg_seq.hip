@@ -217,6 +217,7 @@ extern "C++" int set_R(hg_ctx* c, int64_t R, int G, int rank) {
     c->lists_changed();                                // every ranking comes through here: hg_graded's tables were the previous lists'
     c->bitmap_changed();                               // ... and hg_ap_at's the previous bitmap's
     c->mbits_merged = c->mbits_in_ws_b = false;
+    c->rr.begin();                                     // ... and a re-rank's score list goes with its lists
     c->geo.R = R;
     c->RW = (R + 63) / 64;
     return HG_OK;
@@ -268,6 +269,13 @@ static int do_plan(hg_ctx* c, int64_t R, const uint32_t* dev_hist_all, int G, in
     c->cap = 0;
     c->stage = ST_DB | ST_Q | ST_HIST | ST_PLAN;
     return HG_OK;
+}
+
+// the re-rank's first two steps (hg_rerank.hip): the exact histogram per segment on the vector ALU, then threshold and group starts
+extern "C++" int rerank_hist_plan(hg_ctx* c, int64_t R) {
+    HG_TRY(do_hist(c, 1));
+    HG_TRY(set_R(c, R, 1, 0));
+    return launch_plan(c, nullptr);
 }
 
 static int plan_overrun(hg_ctx* c) {                  // k_plan's verdict on an exact sequence

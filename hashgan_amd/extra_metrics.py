@@ -30,6 +30,9 @@ features, host or device arrays -- from ONE ranking at max(ks): the top k is a p
 match bitmap that ranking left once per query for all of them (hg_ap_at; every AP with the bits a ranking at that k alone gives).
 What comes to the host is two [Q, len(ks)] tables and the relevant-row histogram; map_from_ap_tables is the reduction alone.
 precision_recall_at_k takes its hits from the same pass.
+
+Ties resolved instead of described: rerank_topr ranks by Hamming distance and, inside equal distances, by the float32 inner product of
+the features the codes were taken from (Context.topr_rerank) -- the lists, distances, scores and match bits of that order.
 """
 import numpy as np
 
@@ -510,3 +513,22 @@ def precision_within_radius(q_codes, db_codes, q_labels, db_labels, radius=2, de
     hits = rel_hist[:, :radius + 1].sum(1)
     prec = np.where(ball > 0, hits / np.maximum(ball, 1), 0.0)
     return float(prec.mean()), ball
+
+
+def rerank_topr(q, db, q_labels, db_labels, R, device=0):
+    """The Hamming ranking with its tie groups resolved by the features (hg_topr_rerank): sign() gives the codes, rows are ranked by
+    (Hamming distance ascending, float32 inner product of the features descending, database index ascending) and the top R kept -- of
+    the threshold distance's rows the ones with the highest inner product.  q / db: real-valued features [n, b] (b <= 255, at most
+    2^24 database rows), host or device arrays.
+    -> (idx uint32 [Q, R], dist uint8 [Q, R], scores float32 [Q, R], match uint8 [Q, R])"""
+    db, db_labels = metric._sides(db, db_labels, "database")
+    q, q_labels = metric._sides(q, q_labels, "query")
+    metric._check_shapes(q, db, q_labels, db_labels, int(R))
+    eng = metric._Shared.get(device)
+    with eng.lock:
+        metric._load_database(eng, db, db_labels, "rerank")
+        if metric._set_queries(eng, q, q_labels)[1]:
+            raise ValueError("labels must be {0,1} indicator matrices")
+        idx, dist, scores = eng.ctx.topr_rerank(int(R))
+        match = eng.ctx.get_match()
+    return idx, dist, scores, match

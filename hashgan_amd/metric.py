@@ -265,9 +265,11 @@ def _check_cutoffs(Rs, N, what="Rs"):
     return Rs
 
 
-def _ap_at(ctx, Rs, real):
+def _ap_at(ctx, Rs, real, rerank=False):
     """One ranking at the largest cut-off, then every cut-off from its match bitmap (hg_ap_at) -> (ap [Q, nR], rel [Q, nR])."""
-    if real:
+    if rerank:
+        ctx.topr_rerank(int(Rs[-1]), download=False)
+    elif real:
         ctx.topr_real(int(Rs[-1]), download=False)
     else:
         ctx.topr(int(Rs[-1]))
@@ -290,17 +292,18 @@ def _load_database(eng, db_codes, db_labels, mode="reference", floats=None):
     """Host arrays: pack on the host, upload (hg_set_database_f32); DeviceArray descriptors: packed on the GPU out of the caller's
     memory (hg_set_database_dev; 'reference' mode keeps the floats at once).  The float table itself goes to the GPU only when it may be ranked
     by inner product: never for the spellings that binarise or insist on binary codes, and in 'reference' mode only if
-    the database is not a +-1 code (a +-1 database meeting real-valued queries is uploaded again with it, below)."""
+    the database is not a +-1 code (a +-1 database meeting real-valued queries is uploaded again with it, below); 'rerank' mode always
+    keeps it (keep_floats = 1): the floats order the rows inside equal Hamming distances."""
     eng.b = eng.C = eng.N = eng.db_kind = eng.db_src = None      # nothing is resident until this load has succeeded
     eng.resident = None                               # whoever loads another database (extra_metrics, MAPs) ends _evaluate's shortcut
     on_device = isinstance(db_codes, DeviceArray)
     if on_device:
         # device arrays: in 'reference' mode the floats are kept at once (a copy inside the GPU's memory, no PCIe) -- the caller's
         # memory may have changed by the time real-valued queries would ask for a second load, so there is none
-        eng.ctx.set_option("keep_floats", floats if floats is not None else (1 if mode == "reference" else 0))
+        eng.ctx.set_option("keep_floats", floats if floats is not None else (1 if mode in ("reference", "rerank") else 0))
         bad_c, bad_l = eng.ctx.set_database_dev(db_codes, db_labels)
     else:
-        eng.ctx.set_option("keep_floats", floats if floats is not None else (2 if mode == "reference" else 0))
+        eng.ctx.set_option("keep_floats", floats if floats is not None else (1 if mode == "rerank" else 2 if mode == "reference" else 0))
         bad_c, bad_l = eng.ctx.set_database_f32(db_codes, db_labels)
     if bad_l:
         raise ValueError("labels must be {0,1} indicator matrices")
@@ -324,10 +327,16 @@ def _rank(eng, q_codes, q_labels, R, mode, Rs=None):
                     ones, not a Hamming distance), codes with zeros -- goes through the float32 inner-product ranking;
        'sign'       MAPs(binarize=True): sign() first, then Hamming;
        'codes'      MAP / calc_map (north-star spelling): binary codes only, {0,1} bits or +-1, ranked by Hamming
-                    distance; anything else is an error."""
+                    distance; anything else is an error;
+       'rerank'     MAPs(rerank=True): sign() first, Hamming distance, then the float32 inner product of the features inside
+                    equal distances, then the index (hg_topr_rerank): both float tables are on the GPU (_load_database)."""
     qbad_c, qbad_l = _set_queries(eng, q_codes, q_labels)
     if qbad_l:
         raise ValueError("labels must be {0,1} indicator matrices")
+    if mode == "rerank":
+        if q_codes.shape[1] > 255:
+            raise ValueError("inner-product ranking supports up to 255 features (have %d)" % q_codes.shape[1])
+        return eng.ctx.map_rerank(R) if Rs is None else _ap_at(eng.ctx, Rs, False, rerank=True)
     qk, dk = _kind(eng.ctx, 1), eng.db_kind
     if mode == "sign" or {qk, dk} <= {"pm1", "ones"}:
         return eng.average_precisions(R) if Rs is None else _ap_at(eng.ctx, Rs, False)
@@ -390,10 +399,14 @@ class MAPs:
     calls (explicit), and a database whose arrays are the SAME read-only objects as last time is reused
     automatically (a writable array may have changed in place, so it is uploaded again)."""
 
-    def __init__(self, r, device=0, binarize=False):
+    def __init__(self, r, device=0, binarize=False, rerank=False):
+        """rerank=True: sign() first (it implies binarize), rank by Hamming distance, and inside equal distances by the float32 inner
+        product of the features (descending), then by database index -- the ties of the Hamming ranking resolved by the
+        magnitudes sign() throws away; the threshold group's rows with the highest inner product make the cut at R."""
         self.R = r
         self.device = device
-        self.binarize = binarize
+        self.binarize = binarize or rerank
+        self.rerank = rerank
         self._eng = None
         self._lock = threading.RLock()
         self._resident = None          # (output array, label array) the engine holds, or ("explicit",)
@@ -407,6 +420,9 @@ class MAPs:
         if self._eng is None:
             self._eng = _Pool.acquire(self.device)
         return self._eng
+
+    def _mode(self):
+        return "rerank" if self.rerank else "sign" if self.binarize else "reference"
 
     def close(self):
         with self._lock:
@@ -430,7 +446,7 @@ class MAPs:
             raise ValueError("database.output must be [N, b] and database.label [N, C]")
         with self._lock:
             self._resident = None                      # a failed load leaves NO database (never the previous one half replaced)
-            self._guard(_load_database, self._engine(), out, lab, "sign" if self.binarize else "reference")
+            self._guard(_load_database, self._engine(), out, lab, self._mode())
             self._resident = ("explicit", database)
 
     def _guard(self, fn, *args):
@@ -459,7 +475,7 @@ class MAPs:
         if out.ndim != 2 or lab.ndim != 2 or out.shape[0] != lab.shape[0]:
             raise ValueError("database.output must be [N, b] and database.label [N, C]")
         self._resident = None                          # a failed load leaves NO database
-        self._guard(_load_database, self._engine(), out, lab, "sign" if self.binarize else "reference")
+        self._guard(_load_database, self._engine(), out, lab, self._mode())
         self._resident = ("device",) if on_device else ("auto", out, lab)
 
     def get_maps_by_feature(self, database, query):
@@ -478,7 +494,7 @@ class MAPs:
             R = int(self.R)
             if not 1 <= R <= eng.N:
                 raise ValueError("R=%d must be in 1..N (N=%d database rows)" % (R, eng.N))
-            ap, rel = self._guard(_rank, eng, q_codes, q_labels, R, "sign" if self.binarize else "reference")
+            ap, rel = self._guard(_rank, eng, q_codes, q_labels, R, self._mode())
         return mean_over_hits(ap, rel)
 
 
@@ -513,7 +529,7 @@ class MAPs:
                 raise ValueError("query labels must be [Q, C] with the database's C")
             if Rs[-1] > eng.N:
                 raise ValueError("R=%d must be in 1..N (N=%d database rows)" % (Rs[-1], eng.N))
-            ap, rel = self._guard(_rank, eng, q_codes, q_labels, int(Rs[-1]), "sign" if self.binarize else "reference", Rs)
+            ap, rel = self._guard(_rank, eng, q_codes, q_labels, int(Rs[-1]), self._mode(), Rs)
         out = np.empty(len(Rs), dtype=np.float64)
         for j in range(len(Rs)):
             out[j] = mean_over_hits(np.ascontiguousarray(ap[:, j]), np.ascontiguousarray(rel[:, j]))

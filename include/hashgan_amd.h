@@ -275,6 +275,33 @@ int hg_map_real(hg_ctx* ctx, int64_t R, double* host_ap, int64_t* host_rel);
 int hg_topr_real(hg_ctx* ctx, int64_t R);
 int hg_get_topr_real(hg_ctx* ctx, uint32_t* host_idx, float* host_scores);   /* [Q][R] each */
 
+/* ---- Hamming ranking with the tie groups re-ranked by the features ("sign, rank by Hamming distance, re-rank inside equal
+ * distances by the real-valued inner product") ----
+ * Row n against query q has d = popcount(code_q xor code_n) on the codes the loaders make (bit = feature > 0) and s = the float32
+ * inner product of the FLOAT features in the fixed summation order of the real-valued ranking above (one fma chain from +0.0 in
+ * feature order, then + 0.0: never -0.0; oracle/real_map.py::inner_products restates it).  Rows are ranked by (d ascending, s descending,
+ * database index ascending) and the top R kept: of the threshold group the rows with the highest s get in, not the ones with the lowest
+ * index, so membership differs from hg_topr's as well as the order.  The order is total and does not depend on R: the top k of a
+ * ranking at R is the ranking at k (hg_ap_at stays valid on it).  Among NaN scores the order is unspecified (the keys are their bits).
+ * Needs both float tables on the device (hg_set_*_f32 / hg_set_*_dev with option "keep_floats" = 1 when the features are a +-1 code;
+ * HG_ERR_STATE otherwise) and the whole database in one context (a shard: HG_ERR_STATE).  R within 1..N, up to 255 features, and at most
+ * 2^24 = 16 777 216 rows -- a record's 64-bit sort key is {distance: 8, score: 32, index: 24 bits} -- HG_ERR_ARG beyond.
+ * hg_topr_rerank is a ranking like hg_topr: it owns the step state and leaves the idx / dist lists (hg_get_topr), the match bitmap
+ * (hg_get_match; gathered through the idx lists, any class count), stage select + match, plus a float32 score list [Q][R]
+ * (hg_get_rerank_scores: HG_ERR_STATE unless the last ranking on the tables loaded now was a re-rank).  hg_ap, hg_ap_at and hg_graded
+ * work on it unchanged; like every ranking it ends the results hg_graded and hg_ap_at computed from the previous one, leaves the histogram
+ * side tables (hg_rel_hist ...) alone, and is ended by a later ranking, a reload of either table or hg_trim.  hg_map_rerank = the same,
+ * then hg_ap's float64 AP and the download.  Pipeline: exact histogram and plan (no bet, no capacity guess), one pass over the pairs
+ * that collects the rows with d <= t into exact per-(query, distance) ranges, the exact score per record, one sort per query -- in LDS
+ * up to 16384 records or group by group, a group beyond the LDS by radix passes in global memory.  Queries are processed in contiguous
+ * chunks whose records (16 bytes each) fit option "dense_budget_mb"; a query beyond it is a chunk of one.  The call synchronises once
+ * in the middle (the record counts come home) and once at the end whatever "stage_sync" says; results do not depend on the chunks or
+ * the segment geometry.  Stats "rerank_records" (records kept, all queries), "rerank_chunks", "rerank_groups_lds" / "rerank_groups_global"
+ * (distance groups ordered in LDS / by the radix passes). */
+int hg_topr_rerank(hg_ctx* ctx, int64_t R);
+int hg_map_rerank(hg_ctx* ctx, int64_t R, double* host_ap, int64_t* host_rel);
+int hg_get_rerank_scores(hg_ctx* ctx, float* host_scores);                   /* [Q][R] */
+
 /* ---- results to the host ----------------------------------------------------- */
 int hg_get_topr(hg_ctx* ctx, uint32_t* host_idx, uint8_t* host_dist);   /* [Q][R] each */
 int hg_get_match(hg_ctx* ctx, uint8_t* host_imatch);                    /* [Q][R] of 0/1 */
@@ -415,7 +442,7 @@ int hg_set_stream(hg_ctx* ctx, void* hip_stream);
  *                 ALU), "real_sample_half" (1: the sampled cut's scores in the filter's 16-bit arithmetic -- they only place the cut; 0: exact float32 chains), "real_second_sample" (1: a second, counting sample four times as large tightens that cut), "real_sort_lds" (1: ranked by the LDS-resident kernel when the records fit), "real_groups" (1: lists beyond the LDS ordered group by group), "real_map_lists" (0; 1: hg_map_real also writes the ranked idx / score lists), "real_whole_rounds" (3: without a cut -- R = N -- the database is cut so that k_real_select_mx's blocks fill whole rounds of that many per CU; 0: the plain geometry)
  *   ("probe_select" exists only in the measurement build, python -m hashgan_amd.build --probes) */
 int hg_set_option(hg_ctx* ctx, const char* key, int64_t value);
-/* Counters and facts about the last call (30 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
+/* Counters and facts about the last call (34 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
  * "optimistic_requeried" (single queries rerun exactly after losing their bet), "optimistic_rebets" (second and widened bets), "last_optimistic",
  * "rank_leftovers" (queries the LDS-resident rank kernel left to the general one), "select_variant" (1 k_select, 2 k_select_dense, 3 k_select_mx,
  * 5 k_select_mx3, 6 k_select_mx4), "rank_variant" (1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>), "hist_variant" (the kernel of the last histogram pass, full or sampled: 1 k_hist, 2 k_hist_mx, 3 k_hist_i8; 6 / 7: k_hist_mx / k_hist_i8 with one dword counter per query tile instead of 16-bit halves; 0: no pass yet), "rank_lds_recs" (records the last k_rank_lean / k_rank_cnt launch had LDS room for), "slice_cap" (capacity of a (segment, query) slice of the last bet), "rel_hist_variant" (the kernel of the last hg_rel_hist: 1 k_hist_rel, the vector-ALU pass -- the only one so far, whatever "hist_mfma" says; 0: no pass yet), "ap_at_cutoffs" (cut-offs of the last hg_ap_at; 0: no pass yet), "joint_hist_grades" / "joint_hist_bands" (grades G and distance bands of the last hg_joint_hist; 0: no pass yet), "ap_fused",
@@ -424,7 +451,7 @@ int hg_set_option(hg_ctx* ctx, const char* key, int64_t value);
  * of those, run on the second stream);
  * "cut_beyond_planes" (1: the last hg_guess_finish met a query whose cut lies beyond the b/2 + 2 planes the owner-routed exchange carries -- its bet
  * cannot be won by wider slices; a download); real-valued path: "real_attempts", "real_requeried" (queries that lost the first cut and were ranked again on their own, cumulative), "real_cap_boost", "real_path" (bit 0 filter + rescoring, bit 1 ranked in LDS,
- * bit 2 lists ordered group by group). */
+ * bit 2 lists ordered group by group); re-rank: "rerank_records", "rerank_chunks", "rerank_groups_lds", "rerank_groups_global" (see hg_topr_rerank). */
 int hg_get_stat(hg_ctx* ctx, const char* key, int64_t* value);
 /* What hg_set_database_f32 (queries = 0) / hg_set_queries_f32 (queries = 1) found in the float table: out[0] entries outside
  * {-1, 0, +1}, out[1] zeros, out[2] minus ones, out[3] = 1 if the float table is resident on the device -- from which the caller
