@@ -36,6 +36,7 @@ _SIGNATURES = {
     "hg_set_queries_f32": [_p, _p, _p, _i64, C.POINTER(_i64), C.POINTER(_i64)],
     "hg_set_database_dev": [_p, _p, _p, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)],
     "hg_set_queries_dev": [_p, _p, _p, C.POINTER(_i64), C.POINTER(_i64)],
+    "hg_export": [_p, _p, C.c_int],
     "hg_get_packed": [_p, C.c_int, _p, _p],
     "hg_hist": [_p],
     "hg_hist_buffer": [_p, C.POINTER(_p), C.POINTER(_i64)],
@@ -120,14 +121,24 @@ EXPORTS = sorted(list(_SIGNATURES) + ["hg_last_error"])
 _lib = None
 
 # hg_dev_array.dtype (include/hashgan_amd.h)
-HG_F32, HG_F16, HG_BF16, HG_I64, HG_I32, HG_U8 = range(6)
-DEV_DTYPES = {"float32": HG_F32, "float16": HG_F16, "bfloat16": HG_BF16, "int64": HG_I64, "int32": HG_I32, "uint8": HG_U8, "bool": HG_U8}
+HG_F32, HG_F16, HG_BF16, HG_I64, HG_I32, HG_U8, HG_F64 = range(7)      # (HG_F64: destinations of hg_export only; the loaders refuse it)
+DEV_DTYPES = {"float32": HG_F32, "float16": HG_F16, "bfloat16": HG_BF16, "int64": HG_I64, "int32": HG_I32, "uint8": HG_U8, "bool": HG_U8,
+              "float64": HG_F64}
+# hg_export_item.what
+HG_OUT_IDX, HG_OUT_DIST, HG_OUT_SCORE, HG_OUT_MATCH, HG_OUT_AP, HG_OUT_HITS, HG_OUT_GRADES = range(7)
+OUT_ITEMS = {"idx": HG_OUT_IDX, "dist": HG_OUT_DIST, "score": HG_OUT_SCORE, "match": HG_OUT_MATCH, "ap": HG_OUT_AP, "hits": HG_OUT_HITS,
+             "grades": HG_OUT_GRADES}
 
 
 class DevArrayStruct(C.Structure):
     """hg_dev_array: a 2-D array in device memory, strides in elements."""
     _fields_ = [("ptr", _p), ("rows", _i64), ("cols", _i64), ("row_stride", _i64), ("col_stride", _i64),
                 ("dtype", C.c_int), ("stream", _p)]
+
+
+class ExportItemStruct(C.Structure):
+    """hg_export_item: what to write, and where."""
+    _fields_ = [("what", C.c_int), ("dst", DevArrayStruct)]
 
 
 def _dev_struct(a):
@@ -265,6 +276,18 @@ class Context:
         check(self._lib.hg_set_queries_dev(self._h, C.byref(f), C.byref(l), C.byref(bc), C.byref(bl)))
         self.Q = f.rows
         return bc.value, bl.value
+
+    def export(self, items):
+        """Results into the caller's device memory (hg_export): items = [(what, destination), ...], what an HG_OUT_* value or a key of
+        OUT_ITEMS ("idx", "dist", "score", "match", "ap", "hits", "grades"), destination a devarray.DeviceOut (or anything with ptr /
+        shape / strides / dtype / stream) of shape [Q, k], k <= R -- [Q, 1] for "ap" and "hits" --, its stream the consumer's.  Every
+        item is checked before anything is written; ordering and refusals: include/hashgan_amd.h."""
+        items = list(items)
+        arr = (ExportItemStruct * max(len(items), 1))()
+        for i, (what, dst) in enumerate(items):
+            arr[i].what = OUT_ITEMS[what] if isinstance(what, str) else int(what)
+            arr[i].dst = _dev_struct(dst)
+        check(self._lib.hg_export(self._h, arr, len(items)))
 
     def get_packed(self, which):
         n = self.Q if which else self.N

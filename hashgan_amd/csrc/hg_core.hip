@@ -3,6 +3,7 @@
 #include "hg_ctx.hpp"
 #include "hg_host_pack.hpp"
 #include "hg_dev_in.hpp"
+#include "hg_dev_out.hpp"
 
 #include <exception>
 #include <map>
@@ -27,7 +28,7 @@ const char* const kKernelNames[KI_COUNT] = {"k_hist", "k_hist_reduce", "k_plan",
                                             "k_real_sample", "k_real_guess", "k_real_select", "k_radix_pass", "k_real_finish", "k_select_mx", "k_rank_cnt", "rccl_allgather", "step_gpu_span", "k_real_rescore",
                                             "k_hist_rel", "k_hist_rel_reduce", "k_graded", "k_grade_hist", "k_grade_hist_reduce", "k_tie_ap", "k_ap_at",
                                             "k_label_max", "k_hist_joint", "k_hist_joint_reduce",
-                                            "k_rr_scan", "k_rr_collect", "k_rr_score", "k_rr_order"};
+                                            "k_rr_scan", "k_rr_collect", "k_rr_score", "k_rr_order", "k_export"};
 // Flatten NumPy's pairwise-summation tree for a chunk of n elements (n <= 8192):
 // numpy/_core/src/umath/loops_utils.h.src, pairwise_sum: n <= 128 is a leaf,
 // otherwise split at n/2 rounded down to a multiple of 8.
@@ -766,6 +767,106 @@ int hg_set_queries_dev(hg_ctx* c, const hg_dev_array* features, const hg_dev_arr
     return HG_OK;
 }
 
+// ---- results into DEVICE memory (hg_dev_out.hpp: the kernel; hg_dev_desc.hpp: the descriptor arithmetic) ----
+namespace {
+struct ExportPlan { int cls; const void* src; i64 pitch, Q, R; int64_t bytes; };
+}
+// Where an item's values lie, by its host getter's rules: class, base, row pitch (in source elements), queries and list length.
+// HG_ERR_STATE, naming the call that would provide them, when the context does not hold them.
+static int export_source(hg_ctx* c, int what, ExportPlan* p) {
+    const bool ranked = (c->stage & ST_SELECT) != 0;
+    p->Q = c->geo.Q; p->R = c->geo.R; p->pitch = c->geo.R;
+    switch (what) {
+        case HG_OUT_IDX:
+            if (!ranked || !(c->lists_valid || c->real_lists))
+                return fail(HG_ERR_STATE, "hg_export: IDX needs ranked lists, and the last call materialised none (hg_map skips them): call hg_topr, hg_topr_real or hg_topr_rerank");
+            p->cls = XC_U32; p->src = c->out_idx.p;
+            return HG_OK;
+        case HG_OUT_DIST:
+            // (real_lists: out_idx is a real-valued ranking's, which writes no distances -- out_dist would be an earlier ranking's)
+            if (!ranked || !c->lists_valid || c->real_lists)
+                return fail(HG_ERR_STATE, "hg_export: DIST needs the lists of a Hamming ranking: call hg_topr or hg_topr_rerank (hg_map and the real-valued rankings leave no distances)");
+            p->cls = XC_U8; p->src = c->out_dist.p;
+            return HG_OK;
+        case HG_OUT_SCORE:
+            p->cls = XC_U32;
+            if (ranked && c->rr.current(c)) { p->src = c->rr_scores.p; p->Q = c->rr.Q; p->R = p->pitch = c->rr.dim; return HG_OK; }
+            if (ranked && c->real_lists) { p->src = c->scores.p; return HG_OK; }
+            return fail(HG_ERR_STATE, "hg_export: SCORE needs the score list of a real-valued ranking or a re-rank: call hg_topr_real or hg_topr_rerank");
+        case HG_OUT_MATCH:
+            if (!(c->stage & ST_MATCH)) return fail(HG_ERR_STATE, "hg_export: MATCH called before hg_match (or a ranking that leaves the match bitmap)");
+            if (c->ranked_local) return fail(HG_ERR_STATE, "hg_export: the match bitmap is in this shard's local rank order (hg_select_ranked): merge it first");
+            if (c->G > 1 && !c->mbits_merged)
+                return fail(HG_ERR_STATE, "hg_export: the match bitmap holds this shard's rows only (%d shards): merge it first (hg_merge_match, hg_merge_ranked)", c->G);
+            if (c->mbits_in_ws_b) return fail(HG_ERR_STATE, "hg_export: the last ranking was a step of hg_map_begin in its own workspace: rank with hg_topr / hg_map first");
+            p->cls = XC_BIT; p->src = c->mbits.p; p->pitch = c->RW;
+            return HG_OK;
+        case HG_OUT_AP: case HG_OUT_HITS:
+            if (!(c->stage & ST_AP)) return fail(HG_ERR_STATE, "hg_export: %s called before hg_ap", hg_dev::out_name(what));
+            p->cls = what == HG_OUT_AP ? XC_F64 : XC_U32;
+            p->src = what == HG_OUT_AP ? c->ap.p : c->rel.p;
+            p->R = p->pitch = 1;
+            return HG_OK;
+        case HG_OUT_GRADES:
+            if ((c->stage & (ST_DB | ST_Q)) != (ST_DB | ST_Q) || !c->gr.current(c) || !c->gr_kept)
+                return fail(HG_ERR_STATE, "hg_export: GRADES needs the grade bytes of these lists: call hg_graded with keep_grades = 1");
+            p->cls = XC_U8; p->src = c->gr_grades.p; p->Q = c->gr.Q; p->R = p->pitch = c->gr_R;
+            return HG_OK;
+        default: return fail(HG_ERR_ARG, "hg_export: unknown item %d", what);
+    }
+}
+
+int hg_export(hg_ctx* c, const hg_export_item* items, int n) {
+    if (!c) return fail(HG_ERR_ARG, "hg_export: null context");
+    if (!items || n < 1 || n > 8) return fail(HG_ERR_ARG, "hg_export: 1..8 items (have %d)", n);
+    // results that may still be withdrawn are not handed to another stream
+    if (c->ms_n) return fail(HG_ERR_STATE, "hg_export: a step of hg_map_begin is in flight: take it with hg_map_end first");
+    if (c->verdict_pending) return fail(HG_ERR_STATE, "hg_export: the bet's verdict is pending (defer_verdict): ask hg_bet_verdict first");
+    // every item is judged before anything is enqueued
+    ExportPlan plan[8];
+    for (int i = 0; i < n; ++i) HG_TRY(export_source(c, items[i].what, &plan[i]));
+    HG_TRY(c->use());
+    for (int i = 0; i < n; ++i) {
+        const hg_dev_array& d = items[i].dst;
+        char msg[256];
+        if (hg_dev::check_out_item(items[i], plan[i].Q, plan[i].R, c->n_total, &plan[i].bytes, msg, sizeof msg))
+            return fail(HG_ERR_ARG, "hg_export: item %d: %s", i, msg);
+        HG_TRY(check_dev_pointer(c, "hg_export", hg_dev::out_name(items[i].what), d, plan[i].bytes));
+        for (const DevBuf* s : {&c->out_idx, &c->out_dist, &c->scores, &c->rr_scores, &c->mbits, &c->ap, &c->rel, &c->gr_grades})
+            if (s->p && hg_dev::ranges_intersect(d.ptr, plan[i].bytes, s->p, (int64_t)s->cap))
+                return fail(HG_ERR_ARG, "hg_export: item %d: the destination lies inside a result buffer of this context", i);
+        for (int j = 0; j < i; ++j)
+            if (hg_dev::ranges_intersect(d.ptr, plan[i].bytes, items[j].dst.ptr, plan[j].bytes))
+                return fail(HG_ERR_ARG, "hg_export: the destinations of items %d and %d intersect", j, i);
+    }
+    // the consumers' streams, each once
+    void* consumers[8];
+    int nc = 0;
+    for (int i = 0; i < n; ++i) {
+        void* s = items[i].dst.stream;
+        bool seen = (hipStream_t)s == c->stream;
+        for (int j = 0; j < nc; ++j) seen = seen || consumers[j] == s;
+        if (!seen) consumers[nc++] = s;
+    }
+    for (int j = 0; j < nc; ++j) HG_TRY(wait_for_producer(c, consumers[j]));       // earlier readers and writers of the destinations finish first
+    c->export_bytes = 0; c->export_variant = 0;
+    for (int i = 0; i < n; ++i) {
+        bool vec = false;
+        HG_TRY(launch_export(c, plan[i].cls, plan[i].src, plan[i].pitch, items[i].dst, &vec));
+        c->export_variant |= vec ? 1 : 2;
+        c->export_bytes += items[i].dst.rows * items[i].dst.cols * hg_dev::itemsize(items[i].dst.dtype);
+    }
+    if (nc) {                                          // whatever the consumers enqueue from here on sees the data
+        hipEvent_t ev = c->get_event();
+        if (!ev) return fail(HG_ERR_HIP, "hipEventCreate failed");
+        hipError_t e = hipEventRecord(ev, c->stream);
+        for (int j = 0; j < nc && e == hipSuccess; ++j) e = hipStreamWaitEvent((hipStream_t)consumers[j], ev, 0);
+        c->pool.push_back(ev);                         // (the waits are enqueued: the event may be recorded again)
+        HG_HIP(e);
+    }
+    return c->stage_end();
+}
+
 // packed tables back to the host (tests; also lets a caller keep the packed form)
 int hg_get_packed(hg_ctx* c, int which, uint32_t* host_codes, uint64_t* host_labels) {
     HG_TRY(need(c, which ? (ST_DB | ST_Q) : ST_DB, "hg_get_packed", "hg_set_database / hg_set_queries"));
@@ -1200,6 +1301,8 @@ int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "rerank_chunks")) *value = c->rr_chunks;
     else if (!strcmp(key, "rerank_groups_lds")) *value = c->rr_groups_lds;
     else if (!strcmp(key, "rerank_groups_global")) *value = c->rr_groups_global;
+    else if (!strcmp(key, "export_bytes")) *value = c->export_bytes;
+    else if (!strcmp(key, "export_variant")) *value = c->export_variant;
     else if (!strcmp(key, "ap_fused")) *value = c->ap_fused ? 1 : 0;
     else if (!strcmp(key, "cap_boost")) *value = c->cap_boost;
     else if (!strcmp(key, "crowding_x100")) *value = c->crowd_x100;

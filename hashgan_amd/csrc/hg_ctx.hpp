@@ -1,7 +1,7 @@
 // Host side of libhashgan_amd.so, shared by its translation units: error plumbing, device buffers, the context
 // (struct hg_ctx, opaque in include/hashgan_amd.h) and the handful of host functions one unit calls in another.
 //
-//   hg_core.hip        context, tables (hg_set_*), options / statistics / timing, label match, AP, downloads
+//   hg_core.hip        context, tables (hg_set_*), options / statistics / timing, label match, AP, downloads, results into device arrays (hg_export)
 //   hg_seq.hip         the Hamming sequences: geometry, histogram -> plan -> select -> rank, staged (sharded) and one-shot forms
 //   hg_side.hip        the side metrics (hg_rel_hist, hg_graded, hg_grade_hist, hg_tie_ap, hg_ap_at, hg_joint_hist) and their getters: one SideResult each
 //   hg_rerank.hip      the re-ranked Hamming ranking (hg_topr_rerank, hg_map_rerank): distance, then float32 inner product inside equal distances
@@ -213,7 +213,7 @@ enum KernelId { KI_HIST = 0, KI_HIST_REDUCE, KI_PLAN, KI_SEG_COUNTS, KI_SEG_LAYO
                 KI_ORDER, KI_RANK_FUSED, KI_MATCH, KI_AP, KI_MERGE, KI_PACK, KI_REAL_SAMPLE, KI_REAL_GUESS, KI_REAL_SELECT,
                 KI_RADIX, KI_REAL_FINISH, KI_SELECT_MX, KI_RANK_LDS, KI_COMM, KI_STEP, KI_REAL_RESCORE, KI_HIST_REL, KI_HIST_REL_REDUCE,
                 KI_GRADED, KI_GRADE_HIST, KI_GRADE_HIST_REDUCE, KI_TIE_AP, KI_AP_AT, KI_LABEL_MAX, KI_HIST_JOINT, KI_HIST_JOINT_REDUCE,
-                KI_RR_SCAN, KI_RR_COLLECT, KI_RR_SCORE, KI_RR_ORDER, KI_COUNT };
+                KI_RR_SCAN, KI_RR_COLLECT, KI_RR_SCORE, KI_RR_ORDER, KI_EXPORT, KI_COUNT };
 enum Stage { ST_NONE = 0, ST_DB = 1, ST_Q = 2, ST_HIST = 4, ST_PLAN = 8, ST_SELECT = 16, ST_MATCH = 32, ST_AP = 64 };
 extern const char* const kKernelNames[KI_COUNT];
 
@@ -418,6 +418,7 @@ struct hg_ctx : StepBufs, StepState {
     int last_rel_hist = 0;     // stat "rel_hist_variant": 1 k_hist_rel (0: no pass yet)
     bool gr_kept = false; i64 gr_R = 0;   // gr_grades holds the grade bytes [Q][gr_R] of gr's pass
     i64 aa_recip_n = -1;       // aa_recip holds RN(1 / k) for k = 1 .. this (+ AP_RECIP_SLACK)
+    i64 export_bytes = 0; int export_variant = 0;   // stats "export_bytes" / "export_variant" of the last hg_export: bytes written; bit 0 a 16-byte-store kernel ran, bit 1 an element-wise one
     void lists_changed() { gr.begin(); }      // the ranked lists are no longer the ones hg_graded walked (a merge into them)
     void bitmap_changed() { aa.begin(); }     // the match bitmap is no longer the one hg_ap_at walked (hg_match, the merges, a blind step)
     bool mbits_merged = false; // G > 1: the shards' bitmaps have been merged into mbits for all queries (hg_merge_match, hg_merge_ranked)

@@ -57,21 +57,53 @@ class DeviceArray:
                                                                                    self.stream)
 
 
-def _from_cuda_array_interface(obj, cai, stream):
+class DeviceOut(DeviceArray):
+    """A 2-D array in device memory that the library WRITES (Context.export, MAPs.rank_into): DeviceArray's fields and rules, with
+    float64 among the dtypes (per-query AP).  `stream` is the CONSUMER's: the library's writes wait for everything enqueued so far
+    on it, and whatever is enqueued on it after the call sees the data.  The memory must stay allocated until then."""
+    __slots__ = ()
+    ITEMSIZE = dict(ITEMSIZE, float64=8)
+
+    def __init__(self, ptr, shape, strides=None, dtype="float32", stream=None):
+        dtype = str(dtype)
+        if dtype not in self.ITEMSIZE:
+            raise ValueError("unsupported device dtype %r (supported: %s)" % (dtype, ", ".join(sorted(self.ITEMSIZE))))
+        # (float64 is laid out like int64: the base class checks shape, strides and pointer)
+        DeviceArray.__init__(self, ptr, shape, strides, "int64" if dtype == "float64" else dtype, stream)
+        self.dtype = dtype
+
+    @property
+    def itemsize(self):
+        return self.ITEMSIZE[self.dtype]
+
+    def __repr__(self):
+        return "DeviceOut" + DeviceArray.__repr__(self)[len("DeviceArray"):]
+
+
+def _from_cuda_array_interface(obj, cai, stream, out=False):
+    """out: a destination -- float64 and 1-D [n] (taken as [n, 1]) are accepted, a read-only array is refused."""
     version = int(cai.get("version", 0))
     if version not in (2, 3):
         raise ValueError("__cuda_array_interface__ version %r is not supported (2 or 3)" % cai.get("version"))
     if cai.get("mask") is not None:
         raise ValueError("masked device arrays are not supported")
+    sizes = DeviceOut.ITEMSIZE if out else ITEMSIZE
     typestr = str(cai["typestr"])
     name = _TYPESTR.get(typestr[1:]) if typestr[:1] in "<|=" else None
+    if name is None and out and typestr[:1] in "<|=" and typestr[1:] == "f8":
+        name = "float64"
     if name is None:
-        raise ValueError("unsupported device dtype %r (supported: %s)" % (typestr, ", ".join(sorted(ITEMSIZE))))
+        raise ValueError("unsupported device dtype %r (supported: %s)" % (typestr, ", ".join(sorted(sizes))))
+    if out and cai["data"][1]:
+        raise ValueError("the device array is read-only: it cannot be written")
     shape = tuple(cai["shape"])
+    strides = cai.get("strides")
+    if out and len(shape) == 1:
+        shape = (shape[0], 1)
+        strides = None if strides is None else (strides[0], sizes[name])
     if len(shape) != 2:
         raise ValueError("device arrays must be 2-D [n, width] (got %d-D)" % len(shape))
-    isz = ITEMSIZE[name]
-    strides = cai.get("strides")
+    isz = sizes[name]
     if strides is not None:
         if any(int(s) % isz for s in strides):
             raise ValueError("byte strides %r are not multiples of the item size %d" % (tuple(strides), isz))
@@ -81,19 +113,22 @@ def _from_cuda_array_interface(obj, cai, stream):
         # v3: None = no synchronisation needed, 1 = the legacy default stream, 2 = the per-thread default stream, else a handle
         s = cai.get("stream")
         stream = None if s in (None, 1) else int(s)
-    return DeviceArray(ptr, shape, strides, name, stream)
+    return (DeviceOut if out else DeviceArray)(ptr, shape, strides, name, stream)
 
 
-def _from_tensor(obj, stream):
+def _from_tensor(obj, stream, out=False):
+    sizes = DeviceOut.ITEMSIZE if out else ITEMSIZE
     m = re.search(r"(\w+)$", str(obj.dtype))           # 'torch.bfloat16' -> 'bfloat16'
     name = m.group(1) if m else str(obj.dtype)
-    name = {"float": "float32", "half": "float16", "long": "int64", "int": "int32"}.get(name, name)
-    if name not in ITEMSIZE:
-        raise ValueError("unsupported device dtype %s (supported: %s)" % (obj.dtype, ", ".join(sorted(ITEMSIZE))))
-    shape = tuple(obj.shape)
+    name = {"float": "float32", "half": "float16", "long": "int64", "int": "int32", "double": "float64"}.get(name, name)
+    if name not in sizes:
+        raise ValueError("unsupported device dtype %s (supported: %s)" % (obj.dtype, ", ".join(sorted(sizes))))
+    shape, strides = tuple(obj.shape), tuple(obj.stride())
+    if out and len(shape) == 1:
+        shape, strides = (shape[0], 1), (strides[0], 1)
     if len(shape) != 2:
         raise ValueError("device arrays must be 2-D [n, width] (got %d-D)" % len(shape))
-    return DeviceArray(obj.data_ptr(), shape, tuple(obj.stride()), name, stream)
+    return (DeviceOut if out else DeviceArray)(obj.data_ptr(), shape, strides, name, stream)
 
 
 def as_device_array(obj, stream=None):
@@ -121,3 +156,27 @@ def as_device_array(obj, stream=None):
     if cai is not None:
         return _from_cuda_array_interface(obj, cai, stream)
     return None
+
+
+def as_device_output(obj, stream=None):
+    """-> DeviceOut for an array in GPU memory that the library is to write.  The spellings of as_device_array: a DeviceOut; an object
+    with `__cuda_array_interface__` (refused when its `data` says read-only); a tensor-like object whose `is_cuda` is true.  float64 is
+    accepted (per-query AP), and a 1-D array of length n is taken as [n, 1] (torch users hold AP as [Q]).  There is no host route:
+    host data raises ValueError, like everything as_device_array refuses.
+
+    `stream`: the CONSUMER's HIP stream (an int handle); it overrides the interface's own.  The library's writes are ordered behind
+    what is enqueued on it so far, and what is enqueued on it afterwards sees the data.  The default is the null stream; work on a
+    NON-BLOCKING stream (torch.cuda.Stream()) is only ordered if its handle is passed (torch.cuda.current_stream().cuda_stream)."""
+    if isinstance(obj, DeviceOut):
+        if stream is not None and stream != obj.stream:
+            return DeviceOut(obj.ptr, obj.shape, obj.strides, obj.dtype, stream)
+        return obj
+    if isinstance(obj, DeviceArray):
+        return DeviceOut(obj.ptr, obj.shape, obj.strides, obj.dtype, obj.stream if stream is None else stream)
+    if getattr(obj, "is_cuda", None) is True and hasattr(obj, "data_ptr"):
+        return _from_tensor(obj, stream, out=True)
+    cai = None if getattr(obj, "is_cuda", None) is False else getattr(obj, "__cuda_array_interface__", None)
+    if cai is not None:
+        return _from_cuda_array_interface(obj, cai, stream, out=True)
+    raise ValueError("results are written into device memory only: %s is host data (a DeviceOut, a device tensor or an object with "
+                     "__cuda_array_interface__ is needed)" % type(obj).__name__)

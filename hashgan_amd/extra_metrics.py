@@ -532,3 +532,25 @@ def rerank_topr(q, db, q_labels, db_labels, R, device=0):
         idx, dist, scores = eng.ctx.topr_rerank(int(R))
         match = eng.ctx.get_match()
     return idx, dist, scores, match
+
+
+def rank_into(q, db, q_labels, db_labels, R, features=False, rerank=False, device=0, stream=None, **outs):
+    """Rank and write the results into arrays of the caller's in GPU memory (MAPs.rank_into, query first): outs are idx, dist, score,
+    match [Q, k <= R] and ap, hits [Q] or [Q, 1] -- torch tensors on the device, anything with __cuda_array_interface__ or
+    devarray.DeviceOut; `stream` is the consumer's HIP stream.  features=False: q and db are binary codes ({0,1} or +-1) ranked by
+    Hamming distance like MAP; features=True: what MAPs(R) ranks (real-valued features by float32 inner product); rerank=True: what
+    MAPs(R, rerank=True) ranks (sign(), Hamming distance, then the inner product inside equal distances).  Inputs may be host or device
+    arrays.  -> {"by": "hamming" | "inner_product" | "rerank", "R": R}"""
+    unknown = set(outs) - set(metric.OUT_NAMES)
+    if unknown:
+        raise TypeError("rank_into: unknown destination %s (known: %s)" % (", ".join(sorted(unknown)), ", ".join(metric.OUT_NAMES)))
+    db, db_labels = metric._sides(db, db_labels, "database")
+    q, q_labels = metric._sides(q, q_labels, "query")
+    R = int(R)
+    metric._check_shapes(q, db, q_labels, db_labels, R)
+    dsts = metric._check_outs(outs, q.shape[0], db.shape[0], R, stream)
+    mode = "rerank" if rerank else "reference" if features else "codes"
+    eng = metric._Shared.get(device)
+    with eng.lock:
+        metric._load_database(eng, db, db_labels, mode)
+        return metric._rank_into(eng, q, q_labels, R, mode, dsts)

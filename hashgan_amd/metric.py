@@ -28,7 +28,7 @@ import threading
 import numpy as np
 
 from . import _native
-from .devarray import DeviceArray, as_device_array
+from .devarray import DeviceArray, as_device_array, as_device_output
 
 
 # ------------------------------------------------------------------ packing
@@ -319,9 +319,10 @@ def _set_queries(eng, q_codes, q_labels):
     return eng.ctx.set_queries_f32(q_codes, q_labels)
 
 
-def _rank(eng, q_codes, q_labels, R, mode, Rs=None):
+def _rank(eng, q_codes, q_labels, R, mode, Rs=None, lists=False):
     """Queries against the engine's resident database -> (ap [Q], rel [Q]) at R, or with Rs (ascending cut-offs, R ignored)
-    (ap [Q, nR], rel [Q, nR]) from one ranking at Rs[-1] (_ap_at).  mode:
+    (ap [Q, nR], rel [Q, nR]) from one ranking at Rs[-1] (_ap_at); lists=True: the ranking at R with its lists left on the device
+    (topr, topr_real or topr_rerank: what rank_into exports) -> "hamming" | "inner_product" | "rerank".  mode:
        'reference'  MAPs: what np.dot ranks (metric.py:13-14).  +-1 codes on both sides -> Hamming kernels (the same
                     order, ties by index); anything else -- real-valued tanh outputs, {0,1} bits (np.dot counts common
                     ones, not a Hamming distance), codes with zeros -- goes through the float32 inner-product ranking;
@@ -336,13 +337,23 @@ def _rank(eng, q_codes, q_labels, R, mode, Rs=None):
     if mode == "rerank":
         if q_codes.shape[1] > 255:
             raise ValueError("inner-product ranking supports up to 255 features (have %d)" % q_codes.shape[1])
+        if lists:
+            eng.ctx.topr_rerank(R, download=False)
+            return "rerank"
         return eng.ctx.map_rerank(R) if Rs is None else _ap_at(eng.ctx, Rs, False, rerank=True)
     qk, dk = _kind(eng.ctx, 1), eng.db_kind
-    if mode == "sign" or {qk, dk} <= {"pm1", "ones"}:
+
+    def hamming():
+        if lists:
+            eng.ctx.topr(R)
+            return "hamming"
         return eng.average_precisions(R) if Rs is None else _ap_at(eng.ctx, Rs, False)
+
+    if mode == "sign" or {qk, dk} <= {"pm1", "ones"}:
+        return hamming()
     if mode == "codes":
         if {qk, dk} <= {"bits", "ones"}:
-            return eng.average_precisions(R) if Rs is None else _ap_at(eng.ctx, Rs, False)
+            return hamming()
         raise ValueError("codes must be binary -- all {0,1} or all {-1,+1}, the same spelling for queries and "
                          "database (found %s queries, %s database); binarise first (np.sign), or hand real-valued "
                          "features to MAPs.get_maps_by_feature, which ranks them by inner product like metric.py:13" % (qk, dk))
@@ -354,9 +365,50 @@ def _rank(eng, q_codes, q_labels, R, mode, Rs=None):
             raise ValueError("the resident database holds no float features: load it again")
         _load_database(eng, src[0], src[1], floats=1)
         _set_queries(eng, q_codes, q_labels)
+    if lists:
+        eng.ctx.topr_real(R, download=False)
+        return "inner_product"
     if Rs is not None:
         return _ap_at(eng.ctx, Rs, True)
     return eng.ctx.map_real(R)
+
+
+OUT_NAMES = ("idx", "dist", "score", "match", "ap", "hits")      # the results rank_into writes (keys of _native.OUT_ITEMS)
+
+
+def _check_outs(outs, Q, N, R, stream):
+    """rank_into's destinations, before any GPU use: {name: DeviceOut} of the ones given, each [Q, k] with 1 <= k <= R ([Q, 1] for
+    "ap" and "hits"; a 1-D [Q] array counts as that)."""
+    if not 1 <= R <= N:
+        raise ValueError("R=%d must be in 1..N (N=%d database rows)" % (R, N))
+    got = {}
+    for name in OUT_NAMES:
+        if outs.get(name) is None:
+            continue
+        d = as_device_output(outs[name], stream)
+        per_query = name in ("ap", "hits")
+        if d.shape[0] != Q or (d.shape[1] != 1 if per_query else not 1 <= d.shape[1] <= R):
+            raise ValueError("%s must be [Q, %s] with Q=%d%s (got %r)" % (name, "1" if per_query else "k", Q, "" if per_query else
+                                                                          ", 1 <= k <= R=%d" % R, d.shape))
+        got[name] = d
+    if not got:
+        raise ValueError("rank_into needs at least one destination (%s)" % ", ".join(OUT_NAMES))
+    return got
+
+
+def _rank_into(eng, q_codes, q_labels, R, mode, outs):
+    """One ranking with lists at R, the match and AP stages the destinations need, one export -> {"by": ..., "R": R}."""
+    by = _rank(eng, q_codes, q_labels, R, mode, lists=True)
+    if by == "inner_product" and "dist" in outs:
+        raise ValueError("dist: an inner-product ranking has no Hamming distances (score has the inner products)")
+    if by == "hamming" and "score" in outs:
+        raise ValueError("score: a plain Hamming ranking has no scores (dist has the distances; MAPs(R, rerank=True) ranks with both)")
+    if {"match", "ap", "hits"} & set(outs):
+        eng.ctx.match()
+    if {"ap", "hits"} & set(outs):
+        eng.ctx.ap()
+    eng.ctx.export([(name, d) for name, d in outs.items()])
+    return {"by": by, "R": R}
 
 
 def _evaluate(q_codes, db_codes, q_labels, db_labels, R, device, mode):
@@ -534,6 +586,38 @@ class MAPs:
         for j in range(len(Rs)):
             out[j] = mean_over_hits(np.ascontiguousarray(ap[:, j]), np.ascontiguousarray(rel[:, j]))
         return out
+
+
+    def rank_into(self, database, query, idx=None, dist=None, score=None, match=None, ap=None, hits=None, stream=None):
+        """Rank `query` against `database` at self.R and write the results into arrays of the caller's in GPU memory -- no host pass:
+        idx [Q, k] int64 | int32 ranked database indices, dist [Q, k] uint8 | int32 Hamming distances, score [Q, k] float32 inner
+        products, match [Q, k] uint8 / bool label match per rank, ap [Q] or [Q, 1] float64 | float32 (nan: no hit in the top R), hits
+        [Q] or [Q, 1] int64 | int32; k <= R gives the first k ranks.  Destinations: torch tensors on the device, anything with
+        __cuda_array_interface__, devarray.DeviceOut (devarray.as_device_output); `stream` is the consumer's HIP stream (an int
+        handle, e.g. torch.cuda.current_stream().cuda_stream): what it holds so far is waited for, what is enqueued on it afterwards
+        sees the data.  Database residency, `binarize`, `rerank` and the routing are get_maps_by_feature's.  dist on an inner-product
+        ranking and score on a plain Hamming ranking raise ValueError.  -> {"by": "hamming" | "inner_product" | "rerank", "R": R}"""
+        q_codes, q_labels = _sides(query.output, query.label, "query")
+        if q_codes.ndim != 2 or q_labels.ndim != 2 or q_labels.shape[0] != q_codes.shape[0]:
+            raise ValueError("query.output must be [Q, b] and query.label [Q, C]")
+        R = int(self.R)
+        given = dict(idx=idx, dist=dist, score=score, match=match, ap=ap, hits=hits)
+        if database is not None:                       # (what can be refused before any GPU use is)
+            out, lab = _sides(database.output, database.label, "database")
+            _check_shapes(q_codes, out, q_labels, lab, R)
+            outs = _check_outs(given, q_codes.shape[0], out.shape[0], R, stream)
+        with self._lock:
+            self._ensure_database(database)
+            eng = self._engine()
+            if eng.b is None:
+                self._resident = None
+                raise ValueError("no resident database: the last load failed")
+            if q_codes.shape[1] != eng.b:
+                raise ValueError("query and database codes must be [n, b] with the same b")
+            if q_labels.shape[1] != eng.C:
+                raise ValueError("query labels must be [Q, C] with the database's C")
+            outs = _check_outs(given, q_codes.shape[0], eng.N, R, stream)
+            return self._guard(_rank_into, eng, q_codes, q_labels, R, self._mode(), outs)
 
 
 def MAP(query_codes, db_codes, query_labels, db_labels, R, device=0):

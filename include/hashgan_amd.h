@@ -96,19 +96,21 @@ int hg_set_queries_f32(hg_ctx* ctx, const float* host_features, const int64_t* h
  *             shape limits of hg_set_*_f32, a pointer that hipPointerGetAttributes does not report as device memory (host, managed,
  *             unknown) of the context's device, an extent -- ptr .. ptr + ((rows-1)*row_stride + (cols-1)*col_stride + 1) * itemsize
  *             -- that does not lie inside the allocation hipMemGetAddressRange reports.
- * A label entry counts as bad unless it is exactly 0 or 1 (0.5 and NaN in float32 labels are bad). */
+ * A label entry counts as bad unless it is exactly 0 or 1 (0.5 and NaN in float32 labels are bad).  HG_F64 is a dtype of
+ * hg_export's destinations only: both loaders refuse it like any dtype outside their lists. */
 #define HG_F32 0
 #define HG_F16 1
 #define HG_BF16 2
 #define HG_I64 3
 #define HG_I32 4
 #define HG_U8 5     /* also bool */
+#define HG_F64 6                       /* accepted by hg_export only */
 typedef struct hg_dev_array {      /* a 2-D array in device memory, as the caller's framework laid it out */
     const void* ptr;
     int64_t rows, cols;
     int64_t row_stride, col_stride;    /* strides in ELEMENTS, both >= 1 */
-    int dtype;                         /* HG_F32, HG_F16, HG_BF16 (features); HG_I64, HG_I32, HG_U8, HG_F32 (labels) */
-    void* stream;                      /* producer's hipStream_t; NULL = the null stream */
+    int dtype;                         /* HG_F32, HG_F16, HG_BF16 (features); HG_I64, HG_I32, HG_U8, HG_F32 (labels); hg_export: see HG_OUT_* */
+    void* stream;                      /* producer's hipStream_t (hg_export: the consumer's); NULL = the null stream */
 } hg_dev_array;
 int hg_set_database_dev(hg_ctx* ctx, const hg_dev_array* features, const hg_dev_array* labels,
                         int64_t idx_base, int64_t n_total, int64_t* bad_codes, int64_t* bad_labels);
@@ -311,6 +313,44 @@ int hg_get_rel_hist(hg_ctx* ctx, uint32_t* host_all, uint32_t* host_rel); /* [b+
 int hg_get_grade_hist(hg_ctx* ctx, uint32_t* host_hist);                /* [C+1][Q] of this shard (after hg_grade_hist) */
 int hg_get_joint_hist(hg_ctx* ctx, uint32_t* host_hist);                /* [b+1][G][Q] of this shard, G = stat "joint_hist_grades" (after hg_joint_hist) */
 
+/* ---- results into the caller's DEVICE memory -------------------------------------------------------------------------------------
+ * hg_export writes what the host getters above return into arrays of the caller's on the context's GPU -- a torch tensor, anything a
+ * hg_dev_array can describe: any row / column stride (a slice, a transposed view), no alignment assumed -- without a host pass: one
+ * copy-convert kernel per item (k_export, hg_dev_out.hpp).  dst.ptr is written through; dst.rows must be Q; dst.cols = k with
+ * 1 <= k <= R of the last ranking: the first k ranks of every list are written (the top k of a ranking at R is the ranking at k);
+ * HG_OUT_AP and HG_OUT_HITS take cols = 1.  Every value is the one the matching getter returns, converted: an index zero-extended to
+ * int64 (or its 32 bits as int32: refused when n_total > 2^31 - 1), a distance or grade byte widened, a score's or an AP's bits as they
+ * are (AP as float32: the correctly rounded conversion; NaN where the query has no hit), a match bit as 0 / 1, a hit count widened.
+ *   State     each item follows its getter: IDX needs ranked lists (hg_topr, hg_topr_real, hg_topr_rerank, a staged select with lists),
+ *             DIST Hamming lists, SCORE a real-valued ranking with lists or a re-rank, MATCH the match stage with the global bitmap of
+ *             all Q queries (hg_ap_at's rule), AP and HITS hg_ap, GRADES the last hg_graded with keep_grades on these lists; otherwise
+ *             HG_ERR_STATE naming the call that would provide it.  HG_ERR_STATE also while a step of hg_map_begin is in flight or a
+ *             verdict is pending ("defer_verdict"): results that may still be withdrawn are not handed to another stream.
+ *   Refused   with HG_ERR_ARG: everything hg_set_*_dev refuses (null pointers, strides < 1, an extent that overflows, a pointer that is
+ *             not plain device memory of the context's device, an extent outside its allocation), a dtype outside the item's list, a
+ *             wrong shape, strides under which two elements share an address (accepted: one row or one column, row_stride >
+ *             (cols-1)*col_stride, or col_stride > (rows-1)*row_stride -- every slice or transpose of a contiguous array), a
+ *             destination that intersects a result buffer of the context, two items of one call whose extents intersect.
+ *   All or nothing   every item is checked before anything is enqueued: a refused call writes no byte.
+ *   Ordering  dst.stream is the CONSUMER's stream (NULL = the null stream).  The context's stream first waits for everything enqueued
+ *             so far on each distinct dst.stream (an event on each: earlier readers and writers of the destination finish first), the
+ *             kernels run on the context's stream, then every distinct dst.stream waits for an event recorded behind them: whatever
+ *             the consumer enqueues on its stream after the call sees the data, with no host synchronisation.  With "stage_sync" = 1
+ *             (default) the call is also complete on return; with 0 it only enqueues, and the destination must stay allocated until
+ *             its stream has passed the wait.  Work on a non-blocking stream of the caller's is only ordered if that stream's handle
+ *             is passed.
+ *   No pointer is kept.  Timing name "k_export"; stats "export_bytes" (bytes the last call wrote) and "export_variant" (bit 0: a kernel
+ *   of the last call took the 16-byte store path, bit 1: one took the element-wise path; 0: no call yet). */
+#define HG_OUT_IDX    0   /* ranked database indices      [Q][k]  int64 | int32 */
+#define HG_OUT_DIST   1   /* their Hamming distances      [Q][k]  uint8 | int32 */
+#define HG_OUT_SCORE  2   /* float32 inner products       [Q][k]  float32 */
+#define HG_OUT_MATCH  3   /* label match per rank, 0/1    [Q][k]  uint8 (bool) */
+#define HG_OUT_AP     4   /* AP per query, NaN = no hit   [Q][1]  float64 | float32 */
+#define HG_OUT_HITS   5   /* hits among the top R         [Q][1]  int64 | int32 */
+#define HG_OUT_GRADES 6   /* grade per rank (hg_graded, keep_grades) [Q][k] uint8 | int32 */
+typedef struct hg_export_item { int what; hg_dev_array dst; } hg_export_item;
+int hg_export(hg_ctx* ctx, const hg_export_item* items, int n);     /* 1 <= n <= 8 */
+
 /* ---- graded relevance along the ranked lists (ACG, NDCG, WAP at k) -------------
  * hg_graded walks the ranked index lists the last ranking left on the device -- hg_topr, a staged hg_select with lists, hg_topr_real;
  * HG_ERR_STATE after anything that writes none (hg_map, hg_map_real): call hg_topr / hg_topr_real first -- and leaves, per query and
@@ -442,13 +482,14 @@ int hg_set_stream(hg_ctx* ctx, void* hip_stream);
  *                 ALU), "real_sample_half" (1: the sampled cut's scores in the filter's 16-bit arithmetic -- they only place the cut; 0: exact float32 chains), "real_second_sample" (1: a second, counting sample four times as large tightens that cut), "real_sort_lds" (1: ranked by the LDS-resident kernel when the records fit), "real_groups" (1: lists beyond the LDS ordered group by group), "real_map_lists" (0; 1: hg_map_real also writes the ranked idx / score lists), "real_whole_rounds" (3: without a cut -- R = N -- the database is cut so that k_real_select_mx's blocks fill whole rounds of that many per CU; 0: the plain geometry)
  *   ("probe_select" exists only in the measurement build, python -m hashgan_amd.build --probes) */
 int hg_set_option(hg_ctx* ctx, const char* key, int64_t value);
-/* Counters and facts about the last call (34 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
+/* Counters and facts about the last call (36 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
  * "optimistic_requeried" (single queries rerun exactly after losing their bet), "optimistic_rebets" (second and widened bets), "last_optimistic",
  * "rank_leftovers" (queries the LDS-resident rank kernel left to the general one), "select_variant" (1 k_select, 2 k_select_dense, 3 k_select_mx,
  * 5 k_select_mx3, 6 k_select_mx4), "rank_variant" (1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>), "hist_variant" (the kernel of the last histogram pass, full or sampled: 1 k_hist, 2 k_hist_mx, 3 k_hist_i8; 6 / 7: k_hist_mx / k_hist_i8 with one dword counter per query tile instead of 16-bit halves; 0: no pass yet), "rank_lds_recs" (records the last k_rank_lean / k_rank_cnt launch had LDS room for), "slice_cap" (capacity of a (segment, query) slice of the last bet), "rel_hist_variant" (the kernel of the last hg_rel_hist: 1 k_hist_rel, the vector-ALU pass -- the only one so far, whatever "hist_mfma" says; 0: no pass yet), "ap_at_cutoffs" (cut-offs of the last hg_ap_at; 0: no pass yet), "joint_hist_grades" / "joint_hist_bands" (grades G and distance bands of the last hg_joint_hist; 0: no pass yet), "ap_fused",
  * "cap_boost", "crowding_x100", "segments", "records_kept" (records the last bet's select left in the slices: a download, not part of a step),
  * "device_bytes" (every device buffer the context and its requery child hold, the second stream's workspace included), "graph_replays", "map_async_steps" / "map_async_redone" / "map_overlapped_steps" (hg_map_begin: steps enqueued blind / of those, run again by hg_map_end /
  * of those, run on the second stream);
+ * "export_bytes" / "export_variant" (see hg_export);
  * "cut_beyond_planes" (1: the last hg_guess_finish met a query whose cut lies beyond the b/2 + 2 planes the owner-routed exchange carries -- its bet
  * cannot be won by wider slices; a download); real-valued path: "real_attempts", "real_requeried" (queries that lost the first cut and were ranked again on their own, cumulative), "real_cap_boost", "real_path" (bit 0 filter + rescoring, bit 1 ranked in LDS,
  * bit 2 lists ordered group by group); re-rank: "rerank_records", "rerank_chunks", "rerank_groups_lds", "rerank_groups_global" (see hg_topr_rerank). */
