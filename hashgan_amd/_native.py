@@ -46,6 +46,7 @@ _SIGNATURES = {
     "hg_graded": [_p, _p, C.c_int, _p, _p, C.c_int],
     "hg_tie_ap": [_p, _p, C.c_int],
     "hg_ap_at": [_p, _p, C.c_int],
+    "hg_votes": [_p, _p, C.c_int],
     "hg_plan": [_p, _i64, _p, C.c_int, C.c_int],
     "hg_select": [_p],
     "hg_bet_eligible": [_p, _i64, C.c_int, C.POINTER(C.c_int)],
@@ -90,6 +91,9 @@ _SIGNATURES = {
     "hg_get_grades": [_p, _p],
     "hg_get_tie_ap": [_p, _p, _p, _p, _p, _p, _p, _p],
     "hg_get_ap_at": [_p, _p, _p],
+    "hg_get_vote_pred": [_p, _p, _p],
+    "hg_get_vote_confusion": [_p, _p],
+    "hg_get_votes": [_p, _p],
     "hg_comm_unique_id": [_p],
     "hg_comm_init": [_p, _p, C.c_int, C.c_int],
     "hg_comm_destroy": [_p],
@@ -337,6 +341,14 @@ class Context:
         check(self._lib.hg_ap_at(self._h, _ptr(Rs), len(Rs)))
         self._ap_at_nR = len(Rs)
 
+    def votes(self, ks):
+        """Class votes along the ranked lists of the last topr() / topr_real() / topr_rerank() at the strictly ascending cut-offs ks (at
+        most 64, each within 1..R of that ranking): how many of the first k ranks carry each class, the majority class, and the
+        confusion matrix over the queries' own labels.  Results: get_vote_pred(), get_vote_confusion(), get_votes()."""
+        ks = _carray(ks, np.int64).ravel()
+        check(self._lib.hg_votes(self._h, _ptr(ks), len(ks)))
+        self._votes_nk = len(ks)
+
     def hist_buffer(self):
         p, n = _p(), _i64()
         check(self._lib.hg_hist_buffer(self._h, C.byref(p), C.byref(n)))
@@ -569,6 +581,27 @@ class Context:
         rel = np.empty(shape, dtype=np.int64)
         check(self._lib.hg_get_ap_at(self._h, _ptr(ap), _ptr(rel)))
         return ap, rel
+
+    def get_vote_pred(self):
+        """-> (pred int32 [Q, nk]: the smallest class with the most votes among the top k, -1 where no retrieved row has a label;
+        top int64 [Q, nk]: that class's votes) (after votes())."""
+        shape = (self.Q or 0, getattr(self, "_votes_nk", 0))
+        pred = np.empty(shape, dtype=np.int32)
+        top = np.empty(shape, dtype=np.int64)
+        check(self._lib.hg_get_vote_pred(self._h, _ptr(pred), _ptr(top)))
+        return pred, top
+
+    def get_vote_confusion(self):
+        """-> int64 [nk, C, C]: conf[j, a, b] = rows of class b among the top ks[j] of the queries that carry class a (after votes())."""
+        conf = np.empty((getattr(self, "_votes_nk", 0), self.C or 0, self.C or 0), dtype=np.int64)
+        check(self._lib.hg_get_vote_confusion(self._h, _ptr(conf)))
+        return conf
+
+    def get_votes(self):
+        """-> uint32 [Q, nk, C]: the rows of class c among the top ks[j] of query q (after votes())."""
+        v = np.empty((self.Q or 0, getattr(self, "_votes_nk", 0), self.C or 0), dtype=np.uint32)
+        check(self._lib.hg_get_votes(self._h, _ptr(v)))
+        return v
 
     def get_grades(self):
         """-> uint8 [Q, R]: the grade of every rank (after graded(..., keep_grades=True))."""

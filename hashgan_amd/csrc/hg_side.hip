@@ -7,6 +7,7 @@
 #include "hg_tie_ap.hpp"
 #include "hg_ap_at.hpp"
 #include "hg_hist_joint.hpp"
+#include "hg_votes.hpp"
 
 // the classes of the last label word
 static u64 lastmask(int C) { return C % 64 ? (1ull << (C % 64)) - 1ull : ~0ull; }
@@ -304,6 +305,53 @@ int hg_ap_at(hg_ctx* c, const int64_t* host_Rs, int nR) {
     return HG_OK;
 }
 
+// Class votes along the ranked lists (hg_votes.hpp): per query and cut-off k of `host_ks`, how many of the first k ranks carry each class,
+// the largest count and the smallest class that reaches it; and per cut-off the confusion matrix over the queries' own labels.  The lists
+// are hg_graded's: whatever the last ranking left in out_idx.  The host array is copied before the call returns (it synchronises
+// whatever "stage_sync" says).
+int hg_votes(hg_ctx* c, const int64_t* host_ks, int nk) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_votes", "hg_set_database + hg_set_queries"));
+    c->vt.begin();
+    HG_TRY(whole_database(c, "hg_votes", "class votes need the whole database in one context (lists of a shard are partial)"));
+    if (!(c->stage & ST_SELECT) || !(c->lists_valid || c->real_lists))
+        return fail(HG_ERR_STATE, "hg_votes: no ranked lists on the device (hg_map and hg_map_real write none): call hg_topr / hg_topr_real first");
+    if (c->C > VT_MAX_C) return fail(HG_ERR_ARG, "hg_votes: C=%d classes (at most %d)", c->C, VT_MAX_C);
+    const i64 Q = c->geo.Q, R = c->geo.R;
+    HG_TRY(check_cutoffs("hg_votes", "ks", host_ks, nk, VT_MAX_K, R, "R"));
+    const size_t n = (size_t)Q * nk, conf_bytes = (size_t)nk * c->C * c->C * 8;
+    const FirstReservations first;
+    HG_TRY(c->vt_tab.reserve(VT_MAX_K * 8));
+    HG_TRY(c->vt_votes.reserve(n * c->C * 4));
+    HG_TRY(c->vt_pred.reserve(n * 8));
+    HG_TRY(c->vt_conf.reserve(conf_bytes));
+    first.keep(c);
+    HG_HIP(hipMemcpyAsync(c->vt_tab.p, host_ks, (size_t)nk * 8, hipMemcpyHostToDevice, c->stream));
+    HG_HIP(hipMemsetAsync(c->vt_conf.p, 0, conf_bytes, c->stream));
+    VotesArgs a;
+    a.idx = c->out_idx.as<u32>(); a.dblab = c->dblab.as<u64>(); a.ks = c->vt_tab.as<i64>();
+    a.votes = c->vt_votes.as<u32>(); a.pred = c->vt_pred.as<int>(); a.top = c->vt_pred.as<u32>() + n;
+    a.R = R; a.N = c->N; a.nk = nk; a.LW = c->LW; a.C = c->C;
+    a.lastmask = lastmask(c->C);
+    c->t_begin(KI_VOTES);
+#if HG_PROBES
+    if (c->opt.probe_votes) hipLaunchKernelGGL(k_votes<true>, dim3((unsigned)Q), dim3(VT_THREADS), 0, c->stream, a);
+    else
+#endif
+    hipLaunchKernelGGL(k_votes<false>, dim3((unsigned)Q), dim3(VT_THREADS), 0, c->stream, a);
+    c->t_end();
+    HG_TRY(c->check_launch("k_votes"));
+    ConfArgs f;
+    f.votes = a.votes; f.qlab = c->qlab.as<u64>(); f.conf = c->vt_conf.as<unsigned long long>();
+    f.Q = Q; f.nk = nk; f.LW = c->LW; f.C = c->C;
+    c->t_begin(KI_VOTE_CONFUSION);
+    hipLaunchKernelGGL(k_vote_confusion, dim3((unsigned)c->C, (unsigned)nk, (unsigned)((Q + VC_SEG - 1) / VC_SEG)), dim3(256), 0, c->stream, f);
+    c->t_end();
+    HG_TRY(c->check_launch("k_vote_confusion"));
+    HG_TRY(c->sync());                                 // (the host array is the caller's)
+    c->vt.finish(c, Q, Q, nk);
+    return HG_OK;
+}
+
 // ---- getters: the copies on the context's stream, one synchronisation
 int hg_get_rel_hist(hg_ctx* c, uint32_t* host_all, uint32_t* host_rel) {
     HG_TRY(need(c, ST_DB | ST_Q, "hg_get_rel_hist", "hg_rel_hist"));
@@ -365,6 +413,34 @@ int hg_get_ap_at(hg_ctx* c, double* host_ap, int64_t* host_rel) {
     HG_TRY(c->sync());
     widen_u32(host_rel, rel.data(), rel.size());
     return HG_OK;
+}
+
+int hg_get_vote_pred(hg_ctx* c, int32_t* host_pred, int64_t* host_top) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_vote_pred", "hg_votes"));
+    if (!c->vt.current(c)) return fail(HG_ERR_STATE, "hg_get_vote_pred called before hg_votes (on the ranked lists and tables held now)");
+    const size_t n = (size_t)c->vt.Q * c->vt.dim;
+    std::vector<u32> top(host_top ? n : 0);
+    if (host_pred) HG_HIP(hipMemcpyAsync(host_pred, c->vt_pred.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (host_top) HG_HIP(hipMemcpyAsync(top.data(), c->vt_pred.as<char>() + n * 4, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HG_TRY(c->sync());
+    widen_u32(host_top, top.data(), top.size());
+    return HG_OK;
+}
+
+int hg_get_vote_confusion(hg_ctx* c, int64_t* host_conf) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_vote_confusion", "hg_votes"));
+    if (!c->vt.current(c)) return fail(HG_ERR_STATE, "hg_get_vote_confusion called before hg_votes (on the ranked lists and tables held now)");
+    if (!host_conf) return fail(HG_ERR_ARG, "hg_get_vote_confusion: null pointer");
+    HG_HIP(hipMemcpyAsync(host_conf, c->vt_conf.p, (size_t)c->vt.dim * c->C * c->C * 8, hipMemcpyDeviceToHost, c->stream));
+    return c->sync();
+}
+
+int hg_get_votes(hg_ctx* c, uint32_t* host_votes) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_votes", "hg_votes"));
+    if (!c->vt.current(c)) return fail(HG_ERR_STATE, "hg_get_votes called before hg_votes (on the ranked lists and tables held now)");
+    if (!host_votes) return fail(HG_ERR_ARG, "hg_get_votes: null pointer");
+    HG_HIP(hipMemcpyAsync(host_votes, c->vt_votes.p, (size_t)c->vt.Q * c->vt.dim * c->C * 4, hipMemcpyDeviceToHost, c->stream));
+    return c->sync();
 }
 
 }  // extern "C"

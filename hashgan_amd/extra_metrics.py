@@ -33,6 +33,11 @@ precision_recall_at_k takes its hits from the same pass.
 
 Ties resolved instead of described: rerank_topr ranks by Hamming distance and, inside equal distances, by the float32 inner product of
 the features the codes were taken from (Context.topr_rerank) -- the lists, distances, scores and match bits of that order.
+
+Which classes a query retrieved: knn_vote_at_k gives k-nearest-neighbour accuracy by majority vote of the retrieved labels, the
+retrieval confusion matrix and precision@k by query class for up to 64 cut-offs from ONE ranking at max(ks) -- binary codes, real-valued
+features or the re-ranked order.  Context.votes counts the label bits per class along the ranked lists on the GPU; a [Q, len(ks)] and a
+[len(ks), C, C] table come to the host.  knn_from_tables is the reduction alone.
 """
 import numpy as np
 
@@ -532,6 +537,95 @@ def rerank_topr(q, db, q_labels, db_labels, R, device=0):
         idx, dist, scores = eng.ctx.topr_rerank(int(R))
         match = eng.ctx.get_match()
     return idx, dist, scores, match
+
+
+def knn_from_tables(pred, conf, q_labels, ks):
+    """k-nearest-neighbour accuracy and the retrieval confusion matrix from the device tables (NumPy only).  pred [Q, len(ks)]: the
+    majority class among the top k per query, -1 where no retrieved row has a label (Context.get_vote_pred); conf [len(ks), C, C]:
+    conf[j, a, b] = rows of class b among the top ks[j] of the queries that carry class a (Context.get_vote_confusion); q_labels
+    [Q, C]: the queries' {0,1} labels.  A prediction is right when it is one of the query's labels; -1 is wrong.
+      accuracy [len(ks)]               share of right predictions over the queries with at least one label (NaN if there is none),
+      per_class_accuracy [len(ks), C]  the same over the queries that carry class a (NaN where no query does),
+      confusion [len(ks), C, C]        conf as int64,
+      class_precision [len(ks), C]     conf[j, a, a] / (ks[j] n_a), n_a the queries that carry a: on single-label data the mean
+                                       precision@k of the queries of class a (NaN where n_a = 0),
+      ks                               the cut-offs as int64.
+    -> dict(accuracy, per_class_accuracy, confusion, class_precision, ks)"""
+    ks = _check_ks(ks, None)
+    pred = np.asarray(pred)
+    conf = np.asarray(conf)
+    lab = np.asarray(q_labels) != 0
+    if lab.ndim != 2 or pred.ndim != 2 or pred.shape != (lab.shape[0], ks.size) or pred.dtype.kind not in "iu":
+        raise ValueError("pred must be an integer [Q, len(ks)] table and q_labels [Q, C]")
+    Q, C = lab.shape
+    if conf.shape != (ks.size, C, C) or conf.dtype.kind not in "iu":
+        raise ValueError("conf must be an integer [len(ks), C, C] table")
+    pred = pred.astype(np.int64)
+    if pred.size and (pred.min() < -1 or pred.max() >= C):
+        raise ValueError("pred must hold classes 0..C-1 or -1")
+    conf = conf.astype(np.int64)
+    right = np.zeros((Q, ks.size), dtype=bool)
+    if pred.size:
+        right = (pred >= 0) & lab[np.arange(Q)[:, None], np.maximum(pred, 0)]
+    labelled = lab.any(1)
+    n_lab = int(labelled.sum())
+    n_a = lab.sum(0).astype(np.int64)                                    # queries that carry class a
+    hits_a = right.astype(np.int64).T @ lab.astype(np.int64)             # [nk, C]: right predictions among them
+    with np.errstate(divide="ignore", invalid="ignore"):
+        accuracy = right[labelled].sum(0) / n_lab if n_lab else np.full(ks.size, np.nan)
+        per_class = np.where(n_a[None, :] > 0, hits_a / n_a[None, :], np.nan)
+        diag = conf[:, np.arange(C), np.arange(C)]
+        precision = np.where(n_a[None, :] > 0, diag / (ks[:, None] * n_a[None, :]), np.nan)
+    return {"accuracy": accuracy, "per_class_accuracy": per_class, "confusion": conf, "class_precision": precision, "ks": ks}
+
+
+def _check_vote_inputs(q, db, q_labels, db_labels, ks, features):
+    """knn_vote_at_k's argument checks (graded_relevance_at_k's), before any GPU use -> the four arrays and ks as int64."""
+    q, db, q_labels, db_labels = np.asarray(q), np.asarray(db), np.asarray(q_labels), np.asarray(db_labels)
+    metric._check_shapes(q, db, q_labels, db_labels, 1)
+    if db_labels.shape[1] > MAX_CLASSES:
+        raise ValueError("class votes take up to %d classes (have %d)" % (MAX_CLASSES, db_labels.shape[1]))
+    ks = _check_ks(ks, db.shape[0])
+    if features and db.shape[1] > 255:
+        raise ValueError("inner-product ranking supports up to 255 features (have %d)" % db.shape[1])
+    return q, db, q_labels, db_labels, ks
+
+
+def _vote_tables(ctx, ks):
+    """votes() on the lists the context holds and the two small getters -> (pred int32 [Q, nk], conf int64 [nk, C, C])."""
+    ctx.votes(ks)
+    return ctx.get_vote_pred()[0], ctx.get_vote_confusion()
+
+
+def knn_vote_at_k(q, db, q_labels, db_labels, ks, features=False, rerank=False, device=0):
+    """k-nearest-neighbour classification by majority vote of the retrieved labels, and the retrieval confusion matrix, at the
+    strictly ascending cut-offs ks (at most 64, each in 1..N; up to 255 classes) from ONE ranking at max(ks).  features=False: q and
+    db are binary codes ({0,1} or +-1) ranked by Hamming distance, ties by index; features=True: real-valued features (up to 255)
+    ranked by float32 inner product descending, as MAPs.get_maps_by_feature ranks them; rerank=True: real-valued features, sign()
+    gives the codes and the inner product orders the rows inside equal Hamming distances, as rerank_topr ranks them.  A query's
+    prediction at k is the class most of its top k rows carry (the smallest such class; none when no retrieved row has a label).
+    The ranking, the votes (Context.votes) and the confusion matrix run on the GPU; what comes to the host is a [Q, len(ks)] and a
+    [len(ks), C, C] table, nothing of size Q x k.  -> knn_from_tables' dict"""
+    q, db, q_labels, db_labels, ks = _check_vote_inputs(q, db, q_labels, db_labels, ks, features or rerank)
+    eng = metric._Shared.get(device)
+    with eng.lock:
+        if rerank:
+            metric._load_database(eng, db, db_labels, "rerank")
+            if metric._set_queries(eng, q, q_labels)[1]:
+                raise ValueError("labels must be {0,1} indicator matrices")
+            ctx = eng.ctx
+            ctx.topr_rerank(int(ks[-1]), download=False)
+        elif features:
+            metric._load_database(eng, db, db_labels, "reference", floats=1)
+            if eng.ctx.set_queries_f32(q, q_labels)[1]:
+                raise ValueError("labels must be {0,1} indicator matrices")
+            ctx = eng.ctx
+            ctx.topr_real(int(ks[-1]), download=False)
+        else:
+            ctx = _load(eng, q, db, q_labels, db_labels)
+            ctx.topr(int(ks[-1]))
+        pred, conf = _vote_tables(ctx, ks)
+    return knn_from_tables(pred, conf, q_labels, ks)
 
 
 def rank_into(q, db, q_labels, db_labels, R, features=False, rerank=False, device=0, stream=None, **outs):

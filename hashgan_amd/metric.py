@@ -587,6 +587,45 @@ class MAPs:
             out[j] = mean_over_hits(np.ascontiguousarray(ap[:, j]), np.ascontiguousarray(rel[:, j]))
         return out
 
+    def get_knn_at(self, database, query, ks):
+        """k-nearest-neighbour accuracy by majority vote of the retrieved labels and the retrieval confusion matrix at the strictly
+        ascending cut-offs ks (at most 64, each in 1..N; up to 255 classes) from ONE ranking with lists at ks[-1] (hg_votes walks the
+        lists; the list-free ranking get_maps_by_feature uses leaves nothing to vote on).  Database residency, `binarize`, `rerank` and
+        the routing are get_maps_at's; self.R is not used.  -> extra_metrics.knn_from_tables' dict"""
+        from . import extra_metrics as X               # (extra_metrics imports this module)
+        q_codes, q_labels = _sides(query.output, query.label, "query")
+        ks = _check_cutoffs(ks, None, "ks")
+        if q_codes.ndim != 2 or q_labels.ndim != 2 or q_labels.shape[0] != q_codes.shape[0]:
+            raise ValueError("query.output must be [Q, b] and query.label [Q, C]")
+        if q_labels.shape[1] > X.MAX_CLASSES:
+            raise ValueError("class votes take up to %d classes (have %d)" % (X.MAX_CLASSES, q_labels.shape[1]))
+        if database is not None:                       # (what can be refused before any GPU use is)
+            out, lab = _sides(database.output, database.label, "database")
+            if out.ndim != 2 or lab.ndim != 2 or out.shape[0] != lab.shape[0]:
+                raise ValueError("database.output must be [N, b] and database.label [N, C]")
+            if q_codes.shape[1] != out.shape[1]:
+                raise ValueError("query and database codes must be [n, b] with the same b")
+            if q_labels.shape[1] != lab.shape[1]:
+                raise ValueError("query labels must be [Q, C] with the database's C")
+            if ks[-1] > out.shape[0]:
+                raise ValueError("k=%d must be in 1..N (N=%d database rows)" % (ks[-1], out.shape[0]))
+        with self._lock:
+            self._ensure_database(database)
+            eng = self._engine()
+            if eng.b is None:
+                self._resident = None
+                raise ValueError("no resident database: the last load failed")
+            if q_codes.shape[1] != eng.b:
+                raise ValueError("query and database codes must be [n, b] with the same b")
+            if q_labels.shape[1] != eng.C:
+                raise ValueError("query labels must be [Q, C] with the database's C")
+            if ks[-1] > eng.N:
+                raise ValueError("k=%d must be in 1..N (N=%d database rows)" % (ks[-1], eng.N))
+            self._guard(_rank, eng, q_codes, q_labels, int(ks[-1]), self._mode(), None, True)
+            pred, conf = self._guard(X._vote_tables, eng.ctx, ks)
+            words = eng.ctx.get_packed(1)[1]           # the queries' labels as the GPU holds them (device arrays never come to the host otherwise)
+        lab = (words[:, np.arange(eng.C) // 64] >> (np.arange(eng.C) % 64).astype(np.uint64)) & np.uint64(1)
+        return X.knn_from_tables(pred, conf, lab, ks)
 
     def rank_into(self, database, query, idx=None, dist=None, score=None, match=None, ap=None, hits=None, stream=None):
         """Rank `query` against `database` at self.R and write the results into arrays of the caller's in GPU memory -- no host pass:

@@ -401,6 +401,26 @@ int hg_get_tie_ap(hg_ctx* ctx, double* host_ap_exp, double* host_p_hit, double* 
 int hg_ap_at(hg_ctx* ctx, const int64_t* host_Rs, int nR);
 int hg_get_ap_at(hg_ctx* ctx, double* host_ap, int64_t* host_rel);   /* [Q][nR] each; null: skipped */
 
+/* ---- class votes along the ranked lists (kNN accuracy, retrieval confusion matrix) ------------------------------------------------
+ * "Which classes did the query retrieve?"  hg_votes walks the ranked index lists the last ranking left on the device -- hg_graded's
+ * precondition: hg_topr, a staged hg_select with lists, hg_topr_real, hg_topr_rerank; HG_ERR_STATE after anything that writes none
+ * (hg_map, hg_map_real) and on a context that holds a shard (idx_base != 0 or N != n_total) -- and leaves, per query q, cut-off
+ * k = ks[j] and class c:
+ *   votes[q][j][c] = #{ranks i < k whose row idx[q][i] carries label c}                   uint32 [Q][nk][C]
+ *   top[q][j]      = max_c votes[q][j][c];   pred[q][j] = the smallest c that reaches it, -1 when top is 0   [Q][nk]
+ *   conf[j][a][b]  = sum over the queries q that carry label a of votes[q][j][b]          int64 [nk][C][C]
+ * An index >= N (a slot of another shard included) votes for nothing; bits past class C - 1 of a label word are never counted; a query
+ * without labels adds nothing to conf.  ks: nk (1..64) strictly ascending values in 1..R of the lists; C <= 255; anything else
+ * HG_ERR_ARG.  ks is copied before the call returns.  Integers throughout -- every value is exact and independent of any order.  Two
+ * kernel launches (k_votes, k_vote_confusion), tables and buffers of its own: stage, lists, match bits, APs, the other side metrics'
+ * results and a step of hg_map_begin in flight are left as they were.  The results belong to the lists they were computed on: any later
+ * ranking, hg_merge_topr, a database or query reload and hg_trim invalidate them, and so does a refused hg_votes call (the getters then
+ * return HG_ERR_STATE, as they do before the first pass). */
+int hg_votes(hg_ctx* ctx, const int64_t* host_ks, int nk);
+int hg_get_vote_pred(hg_ctx* ctx, int32_t* host_pred, int64_t* host_top);   /* [Q][nk] each; null: skipped */
+int hg_get_vote_confusion(hg_ctx* ctx, int64_t* host_conf);             /* [nk][C][C] */
+int hg_get_votes(hg_ctx* ctx, uint32_t* host_votes);                    /* [Q][nk][C] */
+
 /* ---- collectives: RCCL over xGMI, one process per GPU (the reference has no counterpart --
  * main.py:260-263 only sets CUDA_VISIBLE_DEVICES) --------------------------------------------------------
  * librccl.so.1 is dlopen'ed by the first hg_comm_* call (HG_RCCL_LIBRARY overrides the search); a single-GPU
@@ -480,12 +500,12 @@ int hg_set_stream(hg_ctx* ctx, void* hip_stream);
  *                 if not a +-1 code: keep the float table on the device)
  *   real-valued   "real_mfma" (2: bf16 matrix-core filter + exact float32 rescoring; 1: every pair on the float32 matrix-core instruction; 0: vector
  *                 ALU), "real_sample_half" (1: the sampled cut's scores in the filter's 16-bit arithmetic -- they only place the cut; 0: exact float32 chains), "real_second_sample" (1: a second, counting sample four times as large tightens that cut), "real_sort_lds" (1: ranked by the LDS-resident kernel when the records fit), "real_groups" (1: lists beyond the LDS ordered group by group), "real_map_lists" (0; 1: hg_map_real also writes the ranked idx / score lists), "real_whole_rounds" (3: without a cut -- R = N -- the database is cut so that k_real_select_mx's blocks fill whole rounds of that many per CU; 0: the plain geometry)
- *   ("probe_select" exists only in the measurement build, python -m hashgan_amd.build --probes) */
+ *   ("probe_select" and "probe_votes" exist only in the measurement build, python -m hashgan_amd.build --probes) */
 int hg_set_option(hg_ctx* ctx, const char* key, int64_t value);
-/* Counters and facts about the last call (36 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
+/* Counters and facts about the last call (37 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
  * "optimistic_requeried" (single queries rerun exactly after losing their bet), "optimistic_rebets" (second and widened bets), "last_optimistic",
  * "rank_leftovers" (queries the LDS-resident rank kernel left to the general one), "select_variant" (1 k_select, 2 k_select_dense, 3 k_select_mx,
- * 5 k_select_mx3, 6 k_select_mx4), "rank_variant" (1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>), "hist_variant" (the kernel of the last histogram pass, full or sampled: 1 k_hist, 2 k_hist_mx, 3 k_hist_i8; 6 / 7: k_hist_mx / k_hist_i8 with one dword counter per query tile instead of 16-bit halves; 0: no pass yet), "rank_lds_recs" (records the last k_rank_lean / k_rank_cnt launch had LDS room for), "slice_cap" (capacity of a (segment, query) slice of the last bet), "rel_hist_variant" (the kernel of the last hg_rel_hist: 1 k_hist_rel, the vector-ALU pass -- the only one so far, whatever "hist_mfma" says; 0: no pass yet), "ap_at_cutoffs" (cut-offs of the last hg_ap_at; 0: no pass yet), "joint_hist_grades" / "joint_hist_bands" (grades G and distance bands of the last hg_joint_hist; 0: no pass yet), "ap_fused",
+ * 5 k_select_mx3, 6 k_select_mx4), "rank_variant" (1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>), "hist_variant" (the kernel of the last histogram pass, full or sampled: 1 k_hist, 2 k_hist_mx, 3 k_hist_i8; 6 / 7: k_hist_mx / k_hist_i8 with one dword counter per query tile instead of 16-bit halves; 0: no pass yet), "rank_lds_recs" (records the last k_rank_lean / k_rank_cnt launch had LDS room for), "slice_cap" (capacity of a (segment, query) slice of the last bet), "rel_hist_variant" (the kernel of the last hg_rel_hist: 1 k_hist_rel, the vector-ALU pass -- the only one so far, whatever "hist_mfma" says; 0: no pass yet), "ap_at_cutoffs" (cut-offs of the last hg_ap_at; 0: no pass yet), "votes_cutoffs" (cut-offs of the last hg_votes; 0: no pass yet), "joint_hist_grades" / "joint_hist_bands" (grades G and distance bands of the last hg_joint_hist; 0: no pass yet), "ap_fused",
  * "cap_boost", "crowding_x100", "segments", "records_kept" (records the last bet's select left in the slices: a download, not part of a step),
  * "device_bytes" (every device buffer the context and its requery child hold, the second stream's workspace included), "graph_replays", "map_async_steps" / "map_async_redone" / "map_overlapped_steps" (hg_map_begin: steps enqueued blind / of those, run again by hg_map_end /
  * of those, run on the second stream);
