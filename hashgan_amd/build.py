@@ -3,7 +3,8 @@
     python -m hashgan_amd.build          # rebuild what is older than its sources
     python -m hashgan_amd.build --force
 
-The library is several translation units (csrc/*.hip, mapped in csrc/hg_ctx.hpp) compiled in parallel to objects under
+The library is several translation units (UNITS: csrc/<unit>.hip, each described in the map at the top of csrc/hg_ctx.hpp -- a
+new unit, like hg_rank, the rank stage taken out of hg_seq, is added in both places) compiled in parallel to objects under
 _lib/obj/ and linked into _lib/libhashgan_amd.so; an object is rebuilt when any file it included last time (its .d
 file) is newer.  hipcc cross-compiles without a GPU; objects and the .so are git-ignored but travel to the GPU box with
 the working tree.
@@ -20,7 +21,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB_DIR = os.path.join(PKG, "_lib")
 LIB_PATH = os.path.join(LIB_DIR, "libhashgan_amd.so")
 PROBE_LIB_PATH = os.path.join(LIB_DIR, "libhashgan_amd_probe.so")   # measurement probes compiled in (-DHG_PROBES=1)
-UNITS = ["hg_core", "hg_seq", "hg_side", "hg_rerank", "hg_pairs_valu", "hg_pairs_mx", "hg_pairs_mx1", "hg_real", "hg_comm"]
+UNITS = ["hg_core", "hg_seq", "hg_rank", "hg_side", "hg_rerank", "hg_pairs_valu", "hg_pairs_mx", "hg_pairs_mx1", "hg_real", "hg_comm"]
 SOURCES = [os.path.join(CSRC, u + ".hip") for u in UNITS]
 DEPS = SOURCES + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hpp")] + [
     os.path.join(ROOT, "include", "hashgan_amd.h")]

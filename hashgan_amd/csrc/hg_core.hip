@@ -1272,7 +1272,7 @@ int hg_preload(hg_ctx* c) {
     HG_TRY(ensure_pin(c, (size_t)1 << 20));
     hipFuncAttributes a;
     HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_ap<AP_THREADS>)));
-    HG_TRY(preload_seq()); HG_TRY(preload_side()); HG_TRY(preload_valu()); HG_TRY(preload_mx()); HG_TRY(preload_mx1()); HG_TRY(preload_real()); HG_TRY(preload_rerank());
+    HG_TRY(preload_seq()); HG_TRY(preload_rank()); HG_TRY(preload_side()); HG_TRY(preload_valu()); HG_TRY(preload_mx()); HG_TRY(preload_mx1()); HG_TRY(preload_real()); HG_TRY(preload_rerank());
     host_pack_warm();
     return HG_OK;
 }

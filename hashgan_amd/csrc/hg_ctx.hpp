@@ -3,6 +3,7 @@
 //
 //   hg_core.hip        context, tables (hg_set_*), options / statistics / timing, label match, AP, downloads, results into device arrays (hg_export)
 //   hg_seq.hip         the Hamming sequences: geometry, histogram -> plan -> select -> rank, staged (sharded) and one-shot forms
+//   hg_rank.hip        their rank stage: the choice of the kernel (RankChoice), one launcher per kernel, the leftovers of a fused step, k_order
 //   hg_side.hip        the side metrics (hg_rel_hist, hg_graded, hg_grade_hist, hg_tie_ap, hg_ap_at, hg_joint_hist, hg_votes) and their getters: one SideResult each
 //   hg_rerank.hip      the re-ranked Hamming ranking (hg_topr_rerank, hg_map_rerank): distance, then float32 inner product inside equal distances
 //   hg_pairs_valu.hip  launchers of the vector-ALU pair passes (k_hist, k_select, k_select_dense)
@@ -216,6 +217,11 @@ enum KernelId { KI_HIST = 0, KI_HIST_REDUCE, KI_PLAN, KI_SEG_COUNTS, KI_SEG_LAYO
                 KI_RR_SCAN, KI_RR_COLLECT, KI_RR_SCORE, KI_RR_ORDER, KI_EXPORT, KI_VOTES, KI_VOTE_CONFUSION, KI_COUNT };
 enum Stage { ST_NONE = 0, ST_DB = 1, ST_Q = 2, ST_HIST = 4, ST_PLAN = 8, ST_SELECT = 16, ST_MATCH = 32, ST_AP = 64 };
 extern const char* const kKernelNames[KI_COUNT];
+// the kernel that took the last record pass / the last rank stage (stats "select_variant", "rank_variant"), and what the rank stage is asked for
+enum SelectKernel { SEL_NONE = 0, SEL_VALU = 1, SEL_DENSE = 2, SEL_MX = 3, SEL_MX3 = 5, SEL_MX4 = 6 };   // none, k_select, k_select_dense, k_select_mx, k_select_mx3, k_select_mx4
+enum RankKernel { RK_NONE = 0, RK_FUSED = 1, RK_CNT = 3, RK_LEAN = 6, RK_DENSE = 7, RK_SLICES = 8 };    // none, k_rank_fused, k_rank_cnt, k_rank_lean, k_rank_dense, k_rank_dense<slices>
+enum RankMode : int { RANK_WHOLE = 0, RANK_COUNT = 1, RANK_PLACE = 2, RANK_LOCAL = 3 };   // RankArgs::mode, RankLdsArgs::mode: the whole ranking (one shard); on several
+                           // shards the records' histograms before the exchange, then the placement with the shared plan; this shard's records ranked locally (hg_select_ranked)
 
 void build_shape(int n, ApShape& sh);           // NumPy's pairwise-summation tree of an n-element chunk, flattened (hg_core.hip)
 
@@ -314,9 +320,9 @@ struct StepState {
     // AP from the rank kernel's epilogue (k_rank_cnt: the bitmap is still in LDS) -- one launch less per step, and the general
     // rank kernel for the queries k_rank_cnt declines is launched only when the step's download says there are any
     bool ap_fused = false;     // the last launch_rank left the AP of every query it ranked in c->ap / c->rel, leftovers counted in err[1]
-    bool leftovers_inline = false;     // ... and the step ranked those leftovers itself within the stream (rank_leftovers_inline)
-    int last_select = 0;       // stat "select_variant": 1 k_select, 2 k_select_dense, 3 k_select_mx, 5 k_select_mx3, 6 k_select_mx4
-    int last_rank = 0;         // stat "rank_variant": 1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>
+    bool leftovers_inline = false;     // ... and the step ranked those leftovers itself within the stream (rank_lds_done)
+    int last_select = SEL_NONE;   // stat "select_variant": a SelectKernel
+    int last_rank = RK_NONE;   // stat "rank_variant": a RankKernel
     int last_hist = 0;         // stat "hist_variant": 1 k_hist, 2 k_hist_mx, 3 k_hist_i8; + 4: the matrix-core kernel's counters were dwords (else 16-bit halves)
     i64 last_lds_recs = 0;     // stat "rank_lds_recs": the record capacity handed to the last k_rank_lean / k_rank_cnt launch (RankLdsArgs::lds_recs)
 };
@@ -717,6 +723,13 @@ inline void make_geometry(hg_ctx* c) { c->geo = full_geometry(c); }
 Geo hist_geometry(const hg_ctx* c);
 int set_R(hg_ctx* c, int64_t R, int G, int rank);
 int rerank_hist_plan(hg_ctx* c, int64_t R);       // full per-segment histogram (k_hist) + k_plan on one shard: c->hist, c->hown, c->t, c->cnt_lt, c->posbase
+// hg_rank.hip
+int launch_rank(hg_ctx* c, RankMode mode, const StepReq& req);   // the rank stage on the rows the step left: chooses the kernel, runs it, sets last_rank / ap_fused
+int launch_rank_leftovers(hg_ctx* c);            // k_rank_fused on the queries a fused step's rank kernel flagged in bigq (finish_leftovers)
+int launch_order(hg_ctx* c);                     // k_order: placement of an exact sequence on several shards
+bool rank_dense_fits(const hg_ctx* c);           // the byte matrix (k_dense_bytes + k_rank_dense) takes these tables
+inline bool lists_needed(const hg_ctx* c) { return c->want_lists || c->LW > 2; }   // the ranked idx / dist lists are written: somebody asked for them, or k_match gathers the labels through them (> 128 classes)
+inline const int* cut_of(const hg_ctx* c, const StepReq& req) { return req.exact_cut ? c->t.as<int>() : c->tguess.as<int>(); }
 // hg_pairs_valu.hip
 int launch_hist(hg_ctx* c);                      // k_hist<NW>
 int launch_hist_rel(hg_ctx* c, const Geo& g);    // k_hist_rel<NW, LW> into c->rh_part (g: full_geometry)
@@ -729,7 +742,7 @@ int launch_hist_mx(hg_ctx* c);                   // k_hist_i8 / k_hist_mx
 int launch_select_mx(hg_ctx* c, int lw, const int* cut);    // k_select_mx<NW, LW, QT, COMPACT>
 int launch_select_mx3(hg_ctx* c, int lw, const int* cut);   // k_select_mx3 (codes of <= 64 bits, one-byte records)
 int launch_select_mx4(hg_ctx* c, int lw, const int* cut);   // k_select_mx4 (codes of 65..128 bits, one-byte records)
-int preload_valu(); int preload_mx(); int preload_mx1(); int preload_real(); int preload_seq(); int preload_side(); int preload_rerank();   // one per translation unit with kernels (hg_preload)
+int preload_valu(); int preload_mx(); int preload_mx1(); int preload_real(); int preload_seq(); int preload_rank(); int preload_side(); int preload_rerank();   // one per translation unit with kernels (hg_preload)
 // hg_comm.hip
 void comm_release(hg_ctx* c);                    // destroys the context's communicator, if any
 

@@ -120,8 +120,8 @@ int run_rerank(hg_ctx* c, int64_t R, bool with_ap) {
     c->rec8 = false;
     c->ap_fused = false;
     c->ranked_local = false;
-    c->last_select = 0;
-    c->last_rank = 0;
+    c->last_select = SEL_NONE;
+    c->last_rank = RK_NONE;
     c->lists_valid = true;
     c->stage = ST_DB | ST_Q | ST_SELECT;
     HG_TRY(do_match(c));                               // label gather through the ranked idx list (any class count)

@@ -1,14 +1,10 @@
 // libhashgan_amd.so -- the Hamming sequences: segment geometry, histogram -> plan -> select -> rank, in their staged
 // (sharded) and one-shot forms (lib/metric.py:13-19 as a counting selection).
 #include "hg_ctx.hpp"
-#include <chrono>
 #include "hg_select_mx.hpp"
 #include "hg_select_mx3.hpp"
 #include "hg_select_mx4.hpp"
 #include "hg_hist_mx.hpp"
-#include "hg_rank_cnt.hpp"
-#include "hg_rank_lean.hpp"
-#include "hg_rank_dense.hpp"
 
 // Segment geometry of the pair passes: ~target_units wavefront-sized units.
 constexpr i64 SAMPLE_RATIO = 2;      // the sampled pass works on segments this many times longer than the select pass's (= per segment pair)
@@ -104,8 +100,6 @@ static bool select_takes_mx(const hg_ctx* c) { return c->optimistic && c->opt.se
 static bool records_are_bytes(const hg_ctx* c) {
     return select_takes_mx(c) && c->opt.compact_records && !c->want_lists && c->LW <= 2 && c->cap % 16 == 0 && c->crow * 64 < (1ll << 31);
 }
-// the ranked idx / dist lists are written: somebody asked for them, or k_match gathers the labels through the idx list (> 128 classes)
-static bool lists_needed(const hg_ctx* c) { return c->want_lists || c->LW > 2; }
 // the record rows of the coming select: Q x crow slots of one byte or eight.  (Until round 6 eight bytes were reserved either way:
 // 2 GB at C2 for 0.25 GB of records -- and 14.9 GB once a class-sorted database had widened the slices, a hipMalloc that took
 // between 0.4 ms and 3.5 s.)
@@ -113,22 +107,20 @@ static int reserve_records(hg_ctx* c) {
     return c->cand.reserve((size_t)c->geo.Q * (size_t)c->crow * (records_are_bytes(c) ? 1 : 8) + 64);
 }
 
-static const int* cut_of(const hg_ctx* c, const StepReq& req) { return req.exact_cut ? c->t.as<int>() : c->tguess.as<int>(); }
-
 static int launch_select(hg_ctx* c, const StepReq& req) {
     const int NW = c->NW;
     const int* cut = cut_of(c, req);
     const int lw = c->LW <= 2 ? c->LW : 0;           // > 128 classes: match bits come from k_match
     const bool mx = select_takes_mx(c);
     c->rec8 = records_are_bytes(c);
-    if (!c->optimistic && c->R * 4 >= c->n_total) { c->last_select = 2; return launch_select_dense(c, lw); }   // dense regime: most pairs are selected
+    if (!c->optimistic && c->R * 4 >= c->n_total) { c->last_select = SEL_DENSE; return launch_select_dense(c, lw); }   // dense regime: most pairs are selected
     // three rows per accumulator + batched drain: codes of <= 64 bits, one-byte records (<= 128 classes).  (For <= 32 bits the
     // second k-half of every MFMA is empty, and it still beat round 2's two-rows-per-accumulator kernel: 0.69 vs 0.85 ms at b = 32.)
-    if (NW <= 2 && c->opt.select_packed == 3 && c->rec8 && c->geo.L % M3_ROWS == 0 && (lw == 1 || lw == 2)) { c->last_select = 5; return launch_select_mx3(c, lw, cut); }
+    if (NW <= 2 && c->opt.select_packed == 3 && c->rec8 && c->geo.L % M3_ROWS == 0 && (lw == 1 || lw == 2)) { c->last_select = SEL_MX3; return launch_select_mx3(c, lw, cut); }
     // codes of 65..128 bits: two rows per accumulator (8-bit fields) and the same drain
-    if ((NW == 3 || NW == 4) && c->opt.select_packed == 3 && c->rec8 && c->geo.L % M4_ROWS == 0 && (lw == 1 || lw == 2)) { c->last_select = 6; return launch_select_mx4(c, lw, cut); }
-    if (mx) { c->last_select = 3; return launch_select_mx(c, lw, cut); }
-    c->last_select = 1;
+    if ((NW == 3 || NW == 4) && c->opt.select_packed == 3 && c->rec8 && c->geo.L % M4_ROWS == 0 && (lw == 1 || lw == 2)) { c->last_select = SEL_MX4; return launch_select_mx4(c, lw, cut); }
+    if (mx) { c->last_select = SEL_MX; return launch_select_mx(c, lw, cut); }
+    c->last_select = SEL_VALU;
     return launch_select_valu(c, lw, c->optimistic);
 }
 
@@ -299,344 +291,28 @@ int hg_plan(hg_ctx* c, int64_t R, const uint32_t* dev_hist_all, int G, int rank)
     return c->opt.stage_sync ? check_plan_flag(c) : HG_OK;
 }
 
-// k_rank_fused in one of its modes: 0 = histogram + plan + placement in one launch (single shard),
-// 1 = histogram phase (several shards, before the exchange), 2 = placement phase (after k_plan).
-// the dense regime through the byte matrix (hg_rank_dense.hpp): the counter columns always fit a block's LDS for codes of <= 126 bits
-static bool rank_dense_fits(const hg_ctx* c) {
-    return c->opt.rank_dense && c->LW <= 2 && c->NW <= 4 && c->b <= 126 && c->N == c->n_total && !c->is_sub;
-}
-
-static void launch_dense_bytes(hg_ctx* c, u8* D, i64 Npad, int q0, int nq) {
-    const int qper = 64;
-    const dim3 grid((unsigned)(Npad / 1024), (unsigned)((nq + qper - 1) / qper));
-    const u32 padbyte = (u32)c->b;                     // the distance of the rows past N (k_rank_dense: padrow)
-#define HG_DENSE_BYTES(NW_, LW_)                                                                                                      \
-    hipLaunchKernelGGL((k_dense_bytes<NW_, LW_>), grid, dim3(256), 0, c->stream, c->qc.as<u32>(), c->qlab.as<u64>(), c->db.as<u32>(), \
-                       c->dblab.as<u64>(), D, c->N, Npad, q0, nq, qper, padbyte)
-    const int key = c->NW * 2 + (c->LW <= 1 ? 0 : 1);
-    switch (key) {
-        case 2: HG_DENSE_BYTES(1, 1); break;
-        case 3: HG_DENSE_BYTES(1, 2); break;
-        case 4: HG_DENSE_BYTES(2, 1); break;
-        case 5: HG_DENSE_BYTES(2, 2); break;
-        case 6: HG_DENSE_BYTES(3, 1); break;
-        case 7: HG_DENSE_BYTES(3, 2); break;
-        case 8: HG_DENSE_BYTES(4, 1); break;
-        default: HG_DENSE_BYTES(4, 2); break;
-    }
-#undef HG_DENSE_BYTES
-}
-
-static int launch_rank_dense(hg_ctx* c, const StepReq& req) {
+// The buffers a ranking writes: the match bitmap, and the idx / dist lists where they are written (a token 16 bytes where not).
+// fill: the lists' slots start as IDX_NONE / 0xFF -- the ones that are another shard's, or past this shard's own records.
+enum ListFill { FILL_NONE, FILL_IDX, FILL_BOTH };
+static int reserve_lists(hg_ctx* c, bool lists, ListFill fill) {
     const Geo& g = c->geo;
-    HG_TRY(c->err.reserve(16));
-    HG_TRY(c->qbad.reserve((size_t)g.Qpad * 4));
-    // Where the R-bit bitmap lives.  LDS while two blocks still share a CU, and the AP then leaves from the epilogue (C1: 0.12 ms
-    // for ranking + AP).  A bitmap that leaves room for one block only: in global memory while the members are few (R < N/4:
-    // the atomic ORs of the matching members cost ~3.6 ms per 10^9; two to four blocks per CU), else in LDS with one block per CU --
-    // and k_ap afterwards either way (an epilogue on four wavefronts per CU is a latency chain: 62 chunks at R = 500k, 0.3 ms per query).
-    // Q = 10k, N = 1M, b = 64, ranking + AP: R = 130k 7.4 ms global / 11.5 LDS; 200k 9.7 / 12.0; 500k 22.7 / 13.7.
-    const int lds_cu = 160 * 1024;
-    const int tot_lds = rank_dense_layout(g.NB, c->RW, false).total, tot_gbm = rank_dense_layout(g.NB, c->RW, true).total;
-    const int blocks_lds = (c->RW * 8 + 4096 < lds_cu && tot_lds <= lds_cu) ? lds_cu / tot_lds : 0;
-    // A bitmap beyond one block's LDS with R >= N/4: K blocks per query, each ranks everything and keeps its K-th of the ranks in LDS
-    // (R = N = 1M: two blocks per query, 2 x 10 ms, against 37 ms of atomic ORs on a bitmap in global memory)
-    i64 rw_part = 0;
-    int kparts = 1;
-    if (blocks_lds == 0 && g.R * 4 >= c->N && c->opt.rank_dense_gbm != 1) {
-        const i64 room = lds_cu - tot_gbm - 4096;
-        kparts = (int)((c->RW * 8 + room - 1) / room);
-        if (kparts >= 2 && kparts <= 8) rw_part = (c->RW + kparts - 1) / kparts; else kparts = 1;
-    }
-    const bool gbm = rw_part ? false
-                   : c->opt.rank_dense_gbm >= 0 ? c->opt.rank_dense_gbm != 0 || blocks_lds == 0 : (blocks_lds == 0 || (blocks_lds < 2 && g.R * 4 < c->N));
-    const int total = gbm ? tot_gbm : rw_part ? rank_dense_layout(g.NB, rw_part, false).total : tot_lds;
-    const i64 Npad = rank_dense_pieces(c->N) * RD_THREADS * 16;
-    i64 qchunk = (c->opt.dense_budget_mb << 20) / Npad;
-    if (qchunk < 1) qchunk = 1;
-    if (qchunk > g.Q) qchunk = g.Q;
-    // (the byte matrix is a budget, not a need: when the device cannot give that much, fewer queries per chunk do)
-    for (;;) {
-        const int rc = c->dbytes.reserve((size_t)qchunk * Npad);
-        if (rc == HG_OK) break;
-        if (qchunk == 1) return rc;
-        (void)hipGetLastError();
-        qchunk = (qchunk + 1) / 2;
-    }
-    bool use_recip = false;
-    const bool fuse = !gbm && !rw_part && blocks_lds >= 2 && req.fuse_ap && c->opt.fuse_ap && !c->want_lists;
-    if (fuse) HG_TRY(ensure_ap_tables(c, &use_recip));
-    const bool fused = fuse && use_recip;
-    if (gbm) HG_HIP(hipMemsetAsync(c->mbits.p, 0, (size_t)g.Q * c->RW * 8, c->stream));
-    for (i64 q0 = 0; q0 < g.Q; q0 += qchunk) {
-        const int nq = (int)(q0 + qchunk < g.Q ? qchunk : g.Q - q0);
-        c->t_begin(KI_SELECT);
-        launch_dense_bytes(c, c->dbytes.as<u8>(), Npad, (int)q0, nq);
-        c->t_end();
-        HG_TRY(c->check_launch("k_dense_bytes"));
-        RankDenseArgs da{c->dbytes.as<u8>(), Npad, (int)q0, c->err.as<int>(), c->qbad.as<u32>(), c->RW,
-                         fused ? c->shapes.as<ApShape>() : nullptr, fused ? c->ap_recip.as<double>() : nullptr, c->ap.as<double>(), c->rel.as<u32>(),
-                         nullptr, nullptr, nullptr, 0u, 0, rw_part, nullptr, g.NB};
-        c->t_begin(KI_RANK_FUSED);
-#define HG_RANK_DENSE(LISTS_, GBM_)                                                                                                              \
-    do {                                                                                                                                         \
-        if (q0 == 0) HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rank_dense<LISTS_, GBM_, false>), hipFuncAttributeMaxDynamicSharedMemorySize, total)); \
-        hipLaunchKernelGGL((k_rank_dense<LISTS_, GBM_, false>), dim3(nq, kparts), dim3(RD_THREADS), (size_t)total, c->stream, da, c->out_idx.as<u32>(),  \
-                           c->out_dist.as<u8>(), c->mbits.as<u32>(), g);                                                                         \
-    } while (0)
-        if (c->want_lists) { if (gbm) HG_RANK_DENSE(true, true); else HG_RANK_DENSE(true, false); }
-        else { if (gbm) HG_RANK_DENSE(false, true); else HG_RANK_DENSE(false, false); }
-#undef HG_RANK_DENSE
-        c->t_end();
-        HG_TRY(c->check_launch("k_rank_dense"));
-    }
-    c->last_rank = 7;
-    c->ap_fused = fused;
+    const size_t slots = (size_t)g.Q * g.R;
+    HG_TRY(c->mbits.reserve((size_t)g.Q * c->RW * 8));
+    HG_TRY(c->out_idx.reserve(lists ? slots * 4 : 16));
+    HG_TRY(c->out_dist.reserve(lists ? slots : 16));
+    if (lists && fill != FILL_NONE) HG_HIP(hipMemsetAsync(c->out_idx.p, 0xFF, slots * 4, c->stream));
+    if (lists && fill == FILL_BOTH) HG_HIP(hipMemsetAsync(c->out_dist.p, 0xFF, slots, c->stream));
     return HG_OK;
-}
-
-// k_rank_dense<slices> (hg_rank_dense.hpp) over the bet's one-byte records: the whole launch (long lists), or only the queries
-// flagged in `only` (what k_rank_lean declined -- then always with the AP from the epilogue: a handful of blocks)
-static int slices_rows(const hg_ctx* c, const StepReq& req) {
-    // the bet's cut never exceeds b/2 + 1 -- enqueue_optimistic's sampled pass stops there --, so b/2 + 2 counter rows cover its records
-    return (!req.exact_cut && c->geo.NB / 2 + 2 < c->geo.NB) ? c->geo.NB / 2 + 2 : c->geo.NB;
-}
-static bool rank_slices_fits(const hg_ctx* c, const StepReq& req) {
-    return c->optimistic && c->rec8 && !c->want_lists && c->geo.S <= RD_THREADS && slices_rows(c, req) <= 126 &&
-           rank_dense_layout(slices_rows(c, req) + 1, c->RW, false).total <= 160 * 1024;
-}
-static int launch_rank_slices(hg_ctx* c, const StepReq& req, const u32* only) {
-    const Geo& g = c->geo;
-    const int sl_rows = slices_rows(c, req);
-    const int total = rank_dense_layout(sl_rows + 1, c->RW, false).total;
-    const bool fuse = req.fuse_ap && c->opt.fuse_ap && (only || 160 * 1024 / total >= 2);
-    bool use_recip = false;
-    if (fuse) HG_TRY(ensure_ap_tables(c, &use_recip));
-    const bool fused = fuse && use_recip;
-    if (only && !fused) return fail(HG_ERR_STATE, "launch_rank_slices: the leftover form needs the AP tables");
-    RankDenseArgs da{nullptr, 0, 0, c->err.as<int>(), c->qbad.as<u32>(), c->RW,
-                     fused ? c->shapes.as<ApShape>() : nullptr, fused ? c->ap_recip.as<double>() : nullptr, c->ap.as<double>(), c->rel.as<u32>(),
-                     c->cand.as<u8>(), c->sl_cnt.as<u32>(), c->failq.as<u32>(), c->cap, c->crow, 0, only, sl_rows};
-    HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rank_dense<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, total));
-    c->t_begin(only ? KI_RANK_FUSED : KI_RANK_LDS);
-    hipLaunchKernelGGL((k_rank_dense<false, false, true>), dim3(g.Q), dim3(RD_THREADS), (size_t)total, c->stream, da, c->out_idx.as<u32>(),
-                       c->out_dist.as<u8>(), c->mbits.as<u32>(), g);
-    c->t_end();
-    HG_TRY(c->check_launch("k_rank_dense<slices>"));
-    if (!only) { c->last_rank = 8; c->ap_fused = fused; }
-    return HG_OK;
-}
-
-// The last fused step on this context had queries its rank kernel declined (one of C5's 10 000 spans more distances than
-// k_rank_lean places): rank the flagged ones right behind it, in the same stream -- a launch of mostly returning blocks --
-// instead of a second host round trip (k_rank_fused + k_ap + three downloads: 0.08 ms of C5's 1.27).
-static int rank_leftovers_inline(hg_ctx* c, const StepReq& req, int mode, bool use_recip) {
-    c->leftovers_inline = false;
-    if (c->leftovers_expected && mode == 0 && c->opt.inline_leftovers && use_recip && rank_slices_fits(c, req)) {
-        HG_TRY(launch_rank_slices(c, req, c->bigq.as<u32>()));
-        c->leftovers_inline = true;
-    }
-    return HG_OK;
-}
-
-// Every record of a bet lies within its query's cut (the guess; the exact threshold of enqueue_exact_mx), and a list
-// reaching further down than the 16 (32) distances the LDS rank kernels place leaves them anyway: byte counters for the 18 (34)
-// distances up to the cut are all they need (round 3: b/2 + 2 of them -- 8.7 KB of LDS at b = 64, 16.9 KB at b = 128); a
-// query with a record below them goes to k_rank_fused.  0: a counter for every distance (short codes), and no cut to read.
-static int cut_counters(const Geo& g) { return rank_cnt_maxb(g.NB) + 2 < g.NB ? rank_cnt_maxb(g.NB) + 2 : 0; }
-
-// Which LDS-resident rank kernel a bet's one-byte records will meet -- decided from what is known BEFORE the select runs (R, the
-// slices' capacity, the segment count, options), because the select writes the interleaved record layout (SelArgs::il) only for
-// the kernel that reads it, k_rank_lean (k_rank_fused, the general kernel behind every path, reads both layouts).
-struct LeanPlan { bool ok; int psp; i64 rb; };
-static LeanPlan rank_lean_plan(const hg_ctx* c, int mode) {
-    const Geo& g = c->geo;
-    LeanPlan l{false, 1, 0};
-    if (!(c->optimistic && c->opt.rank_lds >= 2 && (mode == 0 || mode == 3) && c->rec8 && !c->want_lists &&
-          g.S <= 256 && (c->cap & 15u) == 0 && c->cap <= 1024 && g.R <= 60000)) return l;
-    const int nbc = cut_counters(g);
-    const int nbc_eff = nbc ? nbc : (g.NB < 128 ? g.NB : 128);
-    // room for every piece of the row when that fits HG_RANK_WAVES blocks per CU; else for the usual list (2.2 R + padding)
-    const double share = (double)c->N / (double)(c->n_total > 0 ? c->n_total : 1);
-    const i64 all = (i64)g.S * c->cap;
-    // pieces of a slice fetched up front: what it holds but for a 4-sigma exception, when the select keeps ~0.7 of the budgeted
-    // mean (cap = mean + 6 sqrt(mean) + 16, inverted); at most what four loads per thread cover
-    const double mb = std::pow(std::sqrt((double)c->cap > 7.0 ? (double)c->cap - 7.0 : 0.0) - 3.0, 2.0), est = 0.7 * mb;
-    int psp = (int)std::ceil((est + 4.0 * std::sqrt(est) + 1.0) / 16.0);
-    if (psp > (int)(c->cap >> 4)) psp = (int)(c->cap >> 4);
-    if (psp > RL_MAX_PIECES / g.S) psp = RL_MAX_PIECES / g.S;
-    if (psp < 1) psp = 1;
-    const i64 room = ((160 * 1024 / HG_RANK_WAVES) & ~511ll) - rank_lean_layout(g.NB, c->RW, g.S, 0, nbc).total;
-    i64 rb = all <= room ? all : room & ~15ll;
-    const i64 least = ((i64)(2.2 * (double)c->R * share) + 256 + 16 * (i64)g.S + 15) & ~15ll;
-    if (rb < least && least <= all) rb = least;
-    if (rb > all) rb = all;
-    if (rb > 16 * RL_MAX_PIECES) rb = 16 * RL_MAX_PIECES;      // a thread keeps at most four pieces of its query's list
-    const RankLeanLds L = rank_lean_layout(g.NB, c->RW, g.S, (int)rb, nbc);
-    l.psp = psp; l.rb = rb;
-    l.ok = nbc_eff <= 63 && L.total <= 64 * 1024 && rb >= 16 && (rb >= least || rb == all);
-    return l;
-}
-static int nbits_for(int NB) {
-    int nbits = 1;
-    while ((1 << nbits) < NB) ++nbits;
-    return nbits;
-}
-// leftovers_only: the second half of a fused step -- k_rank_cnt has run (with its AP epilogue) and flagged in bigq the queries
-// it declined; rank just those with the general kernel
-static int launch_rank(hg_ctx* c, int mode, const StepReq& req, bool leftovers_only = false) {
-    const Geo& g = c->geo;
-    if (req.rows == StepReq::BYTES && mode == 0) return launch_rank_dense(c, req);
-    const int nbits = nbits_for(g.NB);
-    const bool lists = lists_needed(c);
-    int nwav = (c->optimistic ? 3 * c->R : c->R) >= 16384 ? 16 : 4;   // k_rank_fused's wavefronts per query, by the records per query (~ 3R / R)
-    if (leftovers_only && c->R >= 1024) nwav = 16;   // a handful of blocks (mode 0: no hwq): what counts is one block's latency
-    const size_t fixed_words = (size_t)(nwav + 1) * g.NB + 8;
-    const int bits_lds = (fixed_words + 2 * (size_t)c->RW) * 4 <= 64 * 1024;
-    if (mode != 1 && !bits_lds && !leftovers_only) HG_HIP(hipMemsetAsync(c->mbits.p, 0, (size_t)g.Q * c->RW * 8, c->stream));
-    HG_TRY(c->err.reserve(16));
-    HG_TRY(c->qbad.reserve((size_t)g.Qpad * 4));
-    if (mode != 0) HG_TRY(c->hwq.reserve((size_t)g.Q * nwav * g.NB * 4));
-#ifdef HG_RANK_PROFILE
-    HG_TRY(c->hwq.reserve((size_t)4096 * 16 * 4 + (size_t)g.Q * nwav * g.NB * 4));
-#endif
-    if (mode == 0 && !leftovers_only) {
-        if (c->optimistic) { if (!req.err_zeroed) HG_HIP(hipMemsetAsync(c->err.p, 0, 8, c->stream)); }
-        else HG_HIP(hipMemsetAsync(c->failq.p, 0, (size_t)g.Qpad * 4, c->stream));
-    }
-    const u32* only = nullptr;
-    bool counted = false;
-    c->ap_fused = false;
-    if (!leftovers_only) c->last_rank = 1;                // k_rank_fused unless one of the LDS-resident kernels takes the lists
-    if (leftovers_only) { only = c->bigq.as<u32>(); counted = true; }
-    const LeanPlan lp = rank_lean_plan(c, mode);
-    const int nbc = cut_counters(g);
-    const int* cut = nbc ? cut_of(c, req) : nullptr;
-    if (!counted) {
-        // the lean counting sort (k_rank_lean): the whole record row in one coalesced read, piecewise compaction, chunks in registers
-        const int psp = lp.psp;
-        const i64 rb = lp.rb;
-        if (lp.ok) {
-            const RankLeanLds L = rank_lean_layout(g.NB, c->RW, g.S, (int)rb, nbc);
-            HG_TRY(c->bigq.reserve((size_t)g.Qpad * 4));
-            const bool fuse = req.fuse_ap && c->opt.fuse_ap && mode == 0 && c->LW <= 2;
-            bool use_recip = false;
-            if (fuse) HG_TRY(ensure_ap_tables(c, &use_recip));
-            RankLdsArgs la{c->sl_cnt.as<u32>(), c->failq.as<u32>(), c->err.as<int>(), c->qbad.as<u32>(), c->bigq.as<u32>(),
-                           c->cap, c->crow, 0, 1, c->RW, (int)rb, mode, c->hwq.as<u32>(), c->hown.as<u32>(),
-                           c->t.as<int>(), c->cnt_lt.as<u32>(), c->quota.as<u32>(), c->tie_before.as<u32>(), c->posbase.as<u32>(), nbc,
-                           fuse ? c->shapes.as<ApShape>() : nullptr, fuse && use_recip ? c->ap_recip.as<double>() : nullptr,
-                           c->ap.as<double>(), c->rel.as<u32>(), fuse ? c->err.as<u32>() + 1 : nullptr, cut, psp};
-            c->t_begin(KI_RANK_LDS);
-            hipLaunchKernelGGL(k_rank_lean, dim3(padded_grid(g.Q)), dim3(256), (size_t)L.total, c->stream, c->cand.as<u8>(), la, c->mbits.as<u32>(), g);
-            c->t_end();
-            HG_TRY(c->check_launch("k_rank_lean"));
-            c->last_rank = 6;
-            c->last_lds_recs = rb;
-            if (fuse) {
-                c->ap_fused = true;
-                HG_TRY(rank_leftovers_inline(c, req, mode, use_recip));
-                return HG_OK;
-            }
-            only = c->bigq.as<u32>();                // k_rank_fused below ranks what this path declined
-            counted = true;
-        }
-    }
-    if (!counted && mode == 0 && g.R >= c->opt.rank_slices && c->opt.rank_slices > 0 && rank_slices_fits(c, req)) {
-        // long lists of a bet (beyond k_rank_lean's LDS): k_rank_dense's two passes over the query's record slices, thread = part of a slice
-        return launch_rank_slices(c, req, nullptr);
-    }
-    if (!counted && c->optimistic && c->opt.rank_lds >= 1 && (mode == 0 || mode == 3)) {
-        // per-thread counting sort (k_rank_cnt): byte counters for every distance + a tile of the records, <= 64 KiB per
-        // block; lists longer than a tile are ranked tile by tile
-        const double share = (double)c->N / (double)(c->n_total > 0 ? c->n_total : 1);
-        i64 r2 = (i64)(2.5 * (double)c->R * share) + 256;         // a tile of the records: the usual list (1.3 - 2 R) in one
-        if (r2 < 4096) r2 = 4096;                                  // (small R: the guess's margin is relatively larger)
-        r2 = r2 / 64 * 64;
-        RankCntLds L = rank_cnt_layout(g.NB, c->RW, g.S, (int)r2, lists ? 1 : 0, nbc);
-        {   // one block more per CU when trimming the record tile by a few percent (never below 2.2 R) makes it fit
-            const int per_cu = (int)(160 * 1024 / ((L.total + 511) & ~511));
-            const i64 want = (160 * 1024 / (per_cu + 1)) & ~511ll;
-            const i64 r3 = (r2 - (L.total - want)) / 64 * 64;
-            // (the kernel is compiled for HG_RANK_WAVES wavefronts per SIMD = blocks per CU: more LDS room than that buys nothing)
-            if (per_cu + 1 <= HG_RANK_WAVES && L.total > want && r3 >= (i64)(2.2 * (double)c->R * share) + 256 && r3 >= 4096 && !lists) {
-                r2 = r3;
-                L = rank_cnt_layout(g.NB, c->RW, g.S, (int)r2, 0, nbc);
-            }
-        }
-        while (L.total > 64 * 1024 && r2 > 64) { r2 -= 64; L = rank_cnt_layout(g.NB, c->RW, g.S, (int)r2, lists ? 1 : 0, nbc); }
-        if (L.total <= 64 * 1024 && r2 >= 4096) {
-            HG_TRY(c->bigq.reserve((size_t)g.Qpad * 4));
-            // hg_map's bet: the AP leaves with the ranking (the bitmap is in LDS), and the general kernel below is NOT launched --
-            // the step's download carries the number of queries this kernel declined (err[1]); the host launches it only then
-            const bool fuse = req.fuse_ap && c->opt.fuse_ap && mode == 0 && !lists && c->LW <= 2;
-            bool use_recip = false;
-            if (fuse) HG_TRY(ensure_ap_tables(c, &use_recip));
-            RankLdsArgs la{c->sl_cnt.as<u32>(), c->failq.as<u32>(), c->err.as<int>(), c->qbad.as<u32>(), c->bigq.as<u32>(),
-                           c->cap, c->crow, lists ? 1 : 0, c->rec8 ? 1 : 0, c->RW, (int)r2, mode, c->hwq.as<u32>(), c->hown.as<u32>(),
-                           c->t.as<int>(), c->cnt_lt.as<u32>(), c->quota.as<u32>(), c->tie_before.as<u32>(), c->posbase.as<u32>(), nbc,
-                           fuse ? c->shapes.as<ApShape>() : nullptr, fuse && use_recip ? c->ap_recip.as<double>() : nullptr,
-                           c->ap.as<double>(), c->rel.as<u32>(), fuse ? c->err.as<u32>() + 1 : nullptr, cut};
-            c->t_begin(KI_RANK_LDS);
-            hipLaunchKernelGGL(k_rank_cnt, dim3(g.Q), dim3(256), (size_t)L.total, c->stream, c->cand.as<u64>(), la, c->out_idx.as<u32>(),
-                               c->out_dist.as<u8>(), c->mbits.as<u32>(), g);
-            c->t_end();
-            HG_TRY(c->check_launch("k_rank_cnt"));
-            c->last_rank = 3;
-            c->last_lds_recs = r2;
-            if (fuse) { c->ap_fused = true; if (c->rec8) HG_TRY(rank_leftovers_inline(c, req, mode, use_recip)); return HG_OK; }
-            only = c->bigq.as<u32>();                // k_rank_fused below ranks what this path declined
-            counted = true;
-        }
-    }
-    RankArgs ra{c->sl_cnt.as<u32>(), c->tot.as<u32>(), c->failq.as<u32>(), c->err.as<int>(), c->qbad.as<u32>(),
-                mode, c->hwq.as<u32>(), c->hown.as<u32>(), c->t.as<int>(), c->cnt_lt.as<u32>(), c->quota.as<u32>(),
-                c->tie_before.as<u32>(), c->posbase.as<u32>(),
-                c->optimistic ? c->cap : 256u, c->crow, c->optimistic ? 0 : 1, lists ? 1 : 0, bits_lds, c->RW, only,
-                req.rows == StepReq::DIRECT ? 1 : 0, c->rec8 ? 1 : 0, c->db.as<u32>(), c->dblab.as<u64>(), c->qc.as<u32>(), c->qlab.as<u64>()};
-    const size_t lds_bytes = (fixed_words + (bits_lds ? 2 * (size_t)c->RW : 0)) * 4;
-    c->t_begin(mode == 1 ? KI_CAND_HIST : KI_RANK_FUSED);
-    if (nwav == 16)
-        hipLaunchKernelGGL(k_rank_fused<16>, dim3(g.Q), dim3(1024), lds_bytes, c->stream, c->cand.as<u64>(), ra,
-                           c->out_idx.as<u32>(), c->out_dist.as<u8>(), c->mbits.as<u32>(), nbits, g);
-    else
-        hipLaunchKernelGGL(k_rank_fused<4>, dim3(g.Q), dim3(256), lds_bytes, c->stream, c->cand.as<u64>(), ra,
-                           c->out_idx.as<u32>(), c->out_dist.as<u8>(), c->mbits.as<u32>(), nbits, g);
-    c->t_end();
-    return c->check_launch("k_rank_fused");
 }
 
 // record pass + ordering (+ gather-based label match when labels are too wide for the record pass)
 static int do_select(hg_ctx* c, const StepReq& req) {
-    const Geo& g = c->geo;
-    const size_t slots = (size_t)g.Q * g.R;
     const bool lists = lists_needed(c);
     HG_TRY(reserve_records(c));
-    HG_TRY(c->mbits.reserve((size_t)g.Q * c->RW * 8));
-    HG_TRY(c->out_idx.reserve(lists ? slots * 4 : 16));
-    HG_TRY(c->out_dist.reserve(lists ? slots : 16));
-    if (lists && c->G > 1) {  // slots of other shards stay IDX_NONE / 0xFF
-        HG_HIP(hipMemsetAsync(c->out_idx.p, 0xFF, slots * 4, c->stream));
-        HG_HIP(hipMemsetAsync(c->out_dist.p, 0xFF, slots, c->stream));
-    }
+    HG_TRY(reserve_lists(c, lists, c->G > 1 ? FILL_BOTH : FILL_NONE));
     HG_TRY(launch_select(c, req));
-    if (c->optimistic || c->G == 1) {
-        // one block per query: verify (optimistic) + plan + order.  Exact single-shard rows hold
-        // precisely the top R, so the same counting plan reproduces t and the bucket starts.
-        HG_TRY(launch_rank(c, 0, req));
-    } else {
-        const size_t lds_words = (size_t)g.NB + 2 * (size_t)c->RW;
-        const int bits_lds = WPB * lds_words * 4 <= 64 * 1024;
-        if (!bits_lds) HG_HIP(hipMemsetAsync(c->mbits.p, 0, (size_t)g.Q * c->RW * 8, c->stream));
-        OrdArgs oa{c->t.as<int>(), c->cnt_lt.as<u32>(), c->quota.as<u32>(), c->tie_before.as<u32>(), c->posbase.as<u32>(),
-                   c->tot.as<u32>(), c->crow, lists ? 1 : 0, bits_lds, c->RW};
-        c->t_begin(KI_ORDER);
-        hipLaunchKernelGGL(k_order, dim3(grid_for(g.Q, WPB)), dim3(256),
-                           (size_t)WPB * (g.NB + (bits_lds ? 2 * (size_t)c->RW : 0)) * 4, c->stream, c->cand.as<u64>(), oa,
-                           c->out_idx.as<u32>(), c->out_dist.as<u8>(), c->mbits.as<u32>(), nbits_for(g.NB), g);
-        c->t_end();
-        HG_TRY(c->check_launch("k_order"));
-    }
+    // one block per query: verify (optimistic) + plan + order.  Exact single-shard rows hold precisely the top R, so the same counting plan reproduces t and the bucket starts.
+    HG_TRY(c->optimistic || c->G == 1 ? launch_rank(c, RANK_WHOLE, req) : launch_order(c));
     c->lists_valid = lists;
     c->stage = (c->stage & (ST_DB | ST_Q | ST_HIST | ST_PLAN)) | ST_PLAN | ST_SELECT;
     if (c->LW <= 2) c->stage |= ST_MATCH;                 // match bits came with the records
@@ -669,6 +345,27 @@ static u32 slice_capacity(const hg_ctx* c, double mean) {
     while (cap > 64u && (double)g.Q * (double)g.S * (double)cap * 8.0 > 64e9) cap = (cap / 2u + 15u) & ~15u;
     return cap;
 }
+// what every guess writes: the cut, the slices' bookkeeping, the queries whose slices overflowed
+static int reserve_guess(hg_ctx* c) {
+    const Geo& g = c->geo;
+    const size_t qb = (size_t)g.Qpad * 4;
+    HG_TRY(c->tguess.reserve(qb)); HG_TRY(c->sl_start.reserve((size_t)g.S * qb)); HG_TRY(c->sl_tie.reserve((size_t)g.S * qb));
+    HG_TRY(c->sl_cnt.reserve((size_t)g.S * qb)); HG_TRY(c->tot.reserve(qb)); HG_TRY(c->failq.reserve(qb));
+    return c->sstar.reserve(qb);
+}
+// the guess is in force: slices budgeted for `mean` records each
+static void adopt_guess(hg_ctx* c, double mean) {
+    c->optimistic = true;
+    c->cap = slice_capacity(c, mean);
+    c->crow = (i64)c->geo.S * c->cap;
+    c->stage = ST_DB | ST_Q | ST_PLAN;
+}
+// a guessed cut keeps at most ~2.6 R rows over ALL shards; a shard's share is proportional to its size,
+// with the same 6-sigma headroom per slice as the one-shot bet
+static double staged_mean(const hg_ctx* c, int64_t R) {
+    const double share = (double)c->N / (double)c->n_total;
+    return 0.1 * (double)c->opt.cand_budget_x10 * (double)c->cap_boost * (double)R * share / (double)c->geo.S;
+}
 
 static int auto_stride(hg_ctx* c, int64_t R) {
     (void)R;
@@ -700,28 +397,16 @@ int hg_guess(hg_ctx* c, int64_t R, const uint32_t* dev_hist_all, int G, int rank
     if (G > 1 && !dev_hist_all) return fail(HG_ERR_ARG, "hg_guess: G > 1 needs the gathered sample histograms");
     HG_TRY(set_R(c, R, G, rank));
     const Geo& g = c->geo;
-    const size_t qb = (size_t)g.Qpad * 4;
-    HG_TRY(c->tguess.reserve(qb));
-    HG_TRY(c->sl_start.reserve((size_t)g.S * qb)); HG_TRY(c->sl_tie.reserve((size_t)g.S * qb));
-    HG_TRY(c->sl_cnt.reserve((size_t)g.S * qb)); HG_TRY(c->tot.reserve(qb)); HG_TRY(c->failq.reserve(qb));
-    HG_HIP(hipMemsetAsync(c->failq.p, 0, qb, c->stream));
+    HG_TRY(reserve_guess(c));
+    HG_HIP(hipMemsetAsync(c->failq.p, 0, (size_t)g.Qpad * 4, c->stream));
     c->t_begin(KI_GUESS);
     const Geo gh = hist_geometry(c);                   // the sampled pass ran on coarser segments
-    HG_TRY(c->sstar.reserve(qb));
     hipLaunchKernelGGL(k_guess, dim3(grid_for(g.Q)), dim3(256), 0, c->stream, c->hown.as<u32>(), (const u32*)dev_hist_all, G,
                        rank, c->hist.as<u32>(), gh.S, (int)(gh.L / g.L), (double)c->opt.guess_sigma, (i64)c->n_total,
                        c->tguess.as<int>(), c->sstar.as<int>(), g);
     c->t_end();
     HG_TRY(c->check_launch("k_guess"));
-    // a guessed cut keeps at most ~2.6 R rows over ALL shards; a shard's share is proportional to its size,
-    // with the same 6-sigma headroom per slice as the one-shot bet
-    const double share = (double)c->N / (double)c->n_total;
-    const double mean = 0.1 * (double)c->opt.cand_budget_x10 * (double)c->cap_boost * (double)R * share / (double)g.S;
-    u32 cap = slice_capacity(c, mean);
-    c->optimistic = true;
-    c->cap = cap;
-    c->crow = (i64)g.S * cap;
-    c->stage = ST_DB | ST_Q | ST_PLAN;
+    adopt_guess(c, staged_mean(c, R));
     return c->stage_end();
 }
 
@@ -734,7 +419,7 @@ int hg_select_candidates(hg_ctx* c) {
     HG_TRY(launch_select(c, StepReq{}));
     const size_t plane = (size_t)g.NB * g.Qpad * 4;
     HG_HIP(hipMemsetAsync(c->hown.as<char>() + plane, 0, TAIL_WORDS * 4, c->stream));
-    HG_TRY(launch_rank(c, 1, StepReq{}));                // per-wave and shard histograms of the records
+    HG_TRY(launch_rank(c, RANK_COUNT, StepReq{}));                // per-wave and shard histograms of the records
     return c->stage_end();
 }
 
@@ -750,17 +435,14 @@ int hg_select_ranked(hg_ctx* c) {
     // then comes from k_match gathering the labels through the LOCAL ranked index list, so that list is kept
     const bool wide = c->LW > 2;
     c->want_lists = wide;
-    const size_t slots = (size_t)g.Q * g.R;
     HG_TRY(reserve_records(c));
-    HG_TRY(c->mbits.reserve((size_t)g.Q * c->RW * 8));
-    HG_TRY(c->out_idx.reserve(wide ? slots * 4 : 16)); HG_TRY(c->out_dist.reserve(wide ? slots : 16));
-    if (wide) HG_HIP(hipMemsetAsync(c->out_idx.p, 0xFF, slots * 4, c->stream));    // slots past the shard's own records: IDX_NONE
+    HG_TRY(reserve_lists(c, wide, FILL_IDX));          // slots past the shard's own records: IDX_NONE
     HG_TRY(c->err.reserve(16));
     HG_HIP(hipMemsetAsync(c->err.p, 0, 4, c->stream));
     HG_TRY(launch_select(c, StepReq{}));
     const size_t plane = (size_t)g.NB * g.Qpad * 4;
     HG_HIP(hipMemsetAsync(c->hown.as<char>() + plane, 0, TAIL_WORDS * 4, c->stream));
-    HG_TRY(launch_rank(c, 3, StepReq{}));
+    HG_TRY(launch_rank(c, RANK_LOCAL, StepReq{}));
     c->lists_valid = false;
     c->ranked_local = true;
     c->stage = ST_DB | ST_Q | ST_PLAN | ST_SELECT;
@@ -808,81 +490,58 @@ static int merge_ranked_range(hg_ctx* c, const uint32_t* dev_hist_all, const uin
     return HG_OK;
 }
 
+// The verdict of a sharded bet is known (computed from gathered data: the same on every rank): count it.  A lost bet sends the
+// caller back to the tables.  Returns `lost`; what else a win or a loss means is the entry point's.
+static bool count_verdict(hg_ctx* c, int lost) {
+    c->bet_runs++;
+    if (lost) { c->bet_fallbacks++; c->shard_bet_fail++; c->stage = ST_DB | ST_Q; }
+    else c->shard_bet_fail = 0;
+    return lost != 0;
+}
+// option "defer_verdict": the caller goes on as if the bet held (match bits, exchange, AP) and asks hg_bet_verdict at the end,
+// together with its final download: no host round trip in the middle of the step
+static void defer_verdict(hg_ctx* c, int* bet_lost) { *bet_lost = -1; c->verdict_pending = true; c->verdict_known = false; }
+
 int hg_merge_ranked(hg_ctx* c, const uint32_t* dev_hist_all, const uint64_t* dev_bits_all, int G, int* bet_lost) {
     if (!bet_lost) return fail(HG_ERR_ARG, "hg_merge_ranked: null argument");
     HG_TRY(merge_ranked_range(c, dev_hist_all, dev_bits_all, G, 0, c ? c->geo.Q : 0, "hg_merge_ranked"));
     if (c->opt.defer_verdict) {
-        *bet_lost = -1;
-        c->verdict_pending = true;
-        c->verdict_known = false;
+        defer_verdict(c, bet_lost);
         c->stage = ST_DB | ST_Q | ST_PLAN | ST_SELECT | ST_MATCH;
         return c->stage_end();
     }
-    int flag = 0;
-    HG_TRY(read_plan_flag(c, &flag));
-    *bet_lost = flag;
-    c->bet_runs++;
-    if (flag) {
-        c->bet_fallbacks++;
-        c->shard_bet_fail++;
-        c->stage = ST_DB | ST_Q;
-        return HG_OK;
-    }
-    c->shard_bet_fail = 0;
-    c->stage = ST_DB | ST_Q | ST_PLAN | ST_SELECT | ST_MATCH;
+    HG_TRY(read_plan_flag(c, bet_lost));
+    if (!count_verdict(c, *bet_lost)) c->stage = ST_DB | ST_Q | ST_PLAN | ST_SELECT | ST_MATCH;
     return HG_OK;
 }
 
-// bookkeeping after the verdict of a staged bet is known
-static int settle_bet(hg_ctx* c, int flag) {
-    c->bet_runs++;
-    if (flag) {
-        c->bet_fallbacks++;
-        c->shard_bet_fail++;
-        c->stage = ST_DB | ST_Q;
-        return HG_OK;
-    }
-    c->shard_bet_fail = 0;
+// hg_rank's placement stands (the bet held, or its verdict is deferred): the lists and match bits are the context's
+static int adopt_ranking(hg_ctx* c) {
     c->lists_valid = c->want_lists;
     c->stage = ST_DB | ST_Q | ST_PLAN | ST_SELECT;
     if (c->LW <= 2) c->stage |= ST_MATCH;
     else HG_TRY(do_match(c));
-    return c->sync();
+    return HG_OK;
 }
 
 int hg_rank(hg_ctx* c, const uint32_t* dev_hist_all, int G, int rank, int* bet_lost) {
     HG_TRY(need(c, ST_PLAN, "hg_rank", "hg_select_candidates"));
     if (!c->optimistic) return fail(HG_ERR_STATE, "hg_rank: no guess in force");
     if (!bet_lost || G < 1 || (G > 1 && !dev_hist_all)) return fail(HG_ERR_ARG, "hg_rank: bad argument");
-    const Geo& g = c->geo;
     c->G = G; c->rank = rank;
     c->want_lists = c->opt.staged_lists != 0 || c->LW > 2;
-    const size_t slots = (size_t)g.Q * g.R;
-    HG_TRY(c->mbits.reserve((size_t)g.Q * c->RW * 8));
-    HG_TRY(c->out_idx.reserve(c->want_lists ? slots * 4 : 16));
-    HG_TRY(c->out_dist.reserve(c->want_lists ? slots : 16));
-    if (c->want_lists && G > 1) {
-        HG_HIP(hipMemsetAsync(c->out_idx.p, 0xFF, slots * 4, c->stream));
-        HG_HIP(hipMemsetAsync(c->out_dist.p, 0xFF, slots, c->stream));
-    }
+    HG_TRY(reserve_lists(c, c->want_lists, G > 1 ? FILL_BOTH : FILL_NONE));
     HG_TRY(launch_plan(c, dev_hist_all));
-    HG_TRY(launch_rank(c, 2, StepReq{}));                // placement with the shared plan
+    HG_TRY(launch_rank(c, RANK_PLACE, StepReq{}));                // placement with the shared plan
     if (c->opt.defer_verdict) {
-        // the caller goes on as if the bet held (match bits, exchange, AP) and asks hg_bet_verdict at the end,
-        // together with its final download: no host round trip in the middle of the step
-        *bet_lost = -1;
-        c->verdict_pending = true;
-        c->verdict_known = false;
-        c->lists_valid = c->want_lists;
-        c->stage = ST_DB | ST_Q | ST_PLAN | ST_SELECT;
-        if (c->LW <= 2) c->stage |= ST_MATCH;
-        else HG_TRY(do_match(c));
+        defer_verdict(c, bet_lost);
+        HG_TRY(adopt_ranking(c));
         return c->stage_end();
     }
-    int flag = 0;
-    HG_TRY(read_plan_flag(c, &flag));
-    *bet_lost = flag;
-    return settle_bet(c, flag);
+    HG_TRY(read_plan_flag(c, bet_lost));
+    if (count_verdict(c, *bet_lost)) return HG_OK;
+    HG_TRY(adopt_ranking(c));
+    return c->sync();
 }
 
 int hg_bet_verdict(hg_ctx* c, int* bet_lost) {
@@ -894,13 +553,26 @@ int hg_bet_verdict(hg_ctx* c, int* bet_lost) {
     else HG_TRY(read_plan_flag(c, &flag));
     c->verdict_known = false;
     *bet_lost = flag;
-    if (!flag) { c->bet_runs++; c->shard_bet_fail = 0; return HG_OK; }
-    c->bet_runs++;
-    c->bet_fallbacks++;
-    c->shard_bet_fail++;
-    c->lists_valid = false;
-    c->stage = ST_DB | ST_Q;
+    if (count_verdict(c, flag)) c->lists_valid = false;
     return HG_OK;
+}
+
+// What follows the merge of this rank's queries [q0, q0 + nq): their AP (k_ap's block index is the query), then {AP, hits} and the
+// verdict packed into `part`, `width` queries wide.
+static int ap_pack_part(hg_ctx* c, i64 q0, i64 nq, i64 width, void** dev_part, int64_t* nbytes) {
+    const Geo& g = c->geo;
+    c->stage = ST_DB | ST_Q | ST_PLAN | ST_SELECT | ST_MATCH;
+    HG_TRY(c->ap.reserve((size_t)g.Q * 8));
+    HG_TRY(c->rel.reserve((size_t)g.Q * 4));
+    HG_TRY(do_ap_range(c, q0, nq));
+    if (!(q0 == 0 && nq == g.Q)) c->stage &= ~(unsigned)ST_MATCH;   // the merged bitmap holds rows [q0, q0 + nq) only: hg_get_match has nothing whole to hand out
+    const size_t pb = (size_t)(width + 1) * 16;
+    HG_TRY(c->part.reserve(pb));
+    hipLaunchKernelGGL(k_pack_part, dim3(grid_for(width + 1)), dim3(256), 0, c->stream, c->ap.as<double>(), c->rel.as<u32>(),
+                       c->err.as<int>(), q0, nq, width, c->part.as<double>());
+    HG_TRY(c->check_launch("k_pack_part"));
+    *dev_part = c->part.p; *nbytes = (int64_t)pb;
+    return c->stage_end();
 }
 
 // The sharded bet with the per-query stages SPLIT over the ranks: after the all-gather of record counts and local bitmaps
@@ -910,25 +582,7 @@ int hg_merge_ap_part(hg_ctx* c, const uint32_t* dev_hist_all, const uint64_t* de
                      int64_t width, void** dev_part, int64_t* nbytes) {
     if (!c || !dev_part || !nbytes || width < nq || width < 1) return fail(HG_ERR_ARG, "hg_merge_ap_part: bad argument");
     HG_TRY(merge_ranked_range(c, dev_hist_all, dev_bits_all, G, q0, nq, "hg_merge_ap_part"));
-    const Geo& g = c->geo;
-    c->stage = ST_DB | ST_Q | ST_PLAN | ST_SELECT | ST_MATCH;
-    // AP of the merged rows only: k_ap's block index is the query
-    {
-        const i64 Qsave = c->geo.Q;
-        HG_TRY(c->ap.reserve((size_t)Qsave * 8));
-        HG_TRY(c->rel.reserve((size_t)Qsave * 4));
-        HG_TRY(do_ap_range(c, q0, nq));
-    }
-    if (!(q0 == 0 && nq == g.Q)) c->stage &= ~(unsigned)ST_MATCH;   // the merged bitmap holds rows [q0, q0 + nq) only: hg_get_match has nothing whole to hand out
-    const size_t pb = (size_t)(width + 1) * 16;
-    HG_TRY(c->part.reserve(pb));
-    hipLaunchKernelGGL(k_pack_part, dim3(grid_for(width + 1)), dim3(256), 0, c->stream, c->ap.as<double>(), c->rel.as<u32>(),
-                       c->err.as<int>(), (i64)q0, (i64)nq, (i64)width, c->part.as<double>());
-    HG_TRY(c->check_launch("k_pack_part"));
-    (void)g;
-    *dev_part = c->part.p;
-    *nbytes = (int64_t)pb;
-    return c->stage_end();
+    return ap_pack_part(c, q0, nq, width, dev_part, nbytes);
 }
 
 int hg_unpack_parts(hg_ctx* c, const void* dev_parts_all, int G, int64_t width, double* host_ap, int64_t* host_rel, int* bet_lost) {
@@ -954,15 +608,7 @@ int hg_unpack_parts(hg_ctx* c, const void* dev_parts_all, int G, int64_t width, 
     *bet_lost = flag;
     c->verdict_pending = false;
     c->verdict_known = false;
-    c->bet_runs++;                                     // the verdict comes from gathered data: the same on every rank
-    if (flag) {
-        c->bet_fallbacks++;
-        c->shard_bet_fail++;
-        c->lists_valid = false;
-        c->stage = ST_DB | ST_Q;
-    } else {
-        c->shard_bet_fail = 0;
-    }
+    if (count_verdict(c, flag)) c->lists_valid = false;
     return HG_OK;
 }
 
@@ -1016,12 +662,8 @@ int hg_guess_finish(hg_ctx* c, int64_t R, const void* dev_answers, int G, int ra
     HG_TRY(owners_for(c, G, &w, "hg_guess_finish"));
     HG_TRY(set_R(c, R, G, rank));
     const Geo& g = c->geo;
-    const size_t qb = (size_t)g.Qpad * 4;
-    HG_TRY(c->tguess.reserve(qb));
-    HG_TRY(c->sl_start.reserve((size_t)g.S * qb)); HG_TRY(c->sl_tie.reserve((size_t)g.S * qb));
-    HG_TRY(c->sl_cnt.reserve((size_t)g.S * qb)); HG_TRY(c->tot.reserve(qb)); HG_TRY(c->failq.reserve(qb));
-    HG_TRY(c->sstar.reserve(qb));
-    HG_HIP(hipMemsetAsync(c->failq.p, 0, qb, c->stream));
+    HG_TRY(reserve_guess(c));
+    HG_HIP(hipMemsetAsync(c->failq.p, 0, (size_t)g.Qpad * 4, c->stream));
     HG_TRY(c->beyond.reserve(4));
     HG_HIP(hipMemsetAsync(c->beyond.p, 0, 4, c->stream));
     const Geo gh = hist_geometry(c);                   // the sampled pass ran on coarser segments
@@ -1030,13 +672,7 @@ int hg_guess_finish(hg_ctx* c, int64_t R, const void* dev_answers, int G, int ra
                        (int)(gh.L / g.L), c->tguess.as<int>(), c->sstar.as<int>(), c->beyond.as<u32>(), g);
     c->t_end();
     HG_TRY(c->check_launch("k_guess_finish"));
-    // (the slices' budget: as hg_guess)
-    const double share = (double)c->N / (double)c->n_total;
-    const double mean = 0.1 * (double)c->opt.cand_budget_x10 * (double)c->cap_boost * (double)R * share / (double)g.S;
-    c->optimistic = true;
-    c->cap = slice_capacity(c, mean);
-    c->crow = (i64)g.S * c->cap;
-    c->stage = ST_DB | ST_Q | ST_PLAN;
+    adopt_guess(c, staged_mean(c, R));
     return c->stage_end();
 }
 
@@ -1072,20 +708,7 @@ int hg_merge_ap_owned(hg_ctx* c, const void* dev_recv, int G, int rank, void** d
     const u32* hall = (const u32*)dev_recv;
     const u64* ball = (const u64*)(hall + cw + TAIL_WORDS);
     HG_TRY(merge_ranked_range(c, hall, ball, G, q0, nq, "hg_merge_ap_owned", &ms));
-    c->stage = ST_DB | ST_Q | ST_PLAN | ST_SELECT | ST_MATCH;
-    HG_TRY(c->ap.reserve((size_t)g.Q * 8));
-    HG_TRY(c->rel.reserve((size_t)g.Q * 4));
-    HG_TRY(do_ap_range(c, q0, nq));
-    if (!(q0 == 0 && nq == g.Q)) c->stage &= ~(unsigned)ST_MATCH;
-    const i64 width = w.width;
-    const size_t pb = (size_t)(width + 1) * 16;
-    HG_TRY(c->part.reserve(pb));
-    hipLaunchKernelGGL(k_pack_part, dim3(grid_for(width + 1)), dim3(256), 0, c->stream, c->ap.as<double>(), c->rel.as<u32>(),
-                       c->err.as<int>(), (i64)q0, (i64)nq, (i64)width, c->part.as<double>());
-    HG_TRY(c->check_launch("k_pack_part"));
-    *dev_part = c->part.p;
-    *nbytes = (int64_t)pb;
-    return c->stage_end();
+    return ap_pack_part(c, q0, nq, w.width, dev_part, nbytes);
 }
 
 // ---- one-shot forms: every stage enqueued back to back, one synchronisation ----
@@ -1112,21 +735,18 @@ static int enqueue_all_rows(hg_ctx* c, int64_t R, const StepReq& req, StepReq::R
     HG_TRY(set_R(c, R, 1, 0));
     const Geo& g = c->geo;
     const size_t qb = (size_t)g.Qpad * 4;
-    const size_t slots = (size_t)g.Q * g.R;
     HG_TRY(c->err.reserve(16)); HG_TRY(c->failq.reserve(qb)); HG_TRY(c->tot.reserve(qb)); HG_TRY(c->sl_cnt.reserve(qb));
     HG_TRY(c->cand.reserve(64));
-    HG_TRY(c->mbits.reserve((size_t)g.Q * c->RW * 8));
-    HG_TRY(c->out_idx.reserve(c->want_lists ? slots * 4 : 16));
-    HG_TRY(c->out_dist.reserve(c->want_lists ? slots : 16));
+    HG_TRY(reserve_lists(c, c->want_lists, FILL_NONE));
     HG_HIP(hipMemsetAsync(c->err.p, 0, 4, c->stream));
     c->optimistic = false;
     c->crow = R;
     c->cap = 0;
     c->rec8 = false;
-    c->last_select = 0;                                // no record pass at all
+    c->last_select = SEL_NONE;                         // no record pass at all
     StepReq walk = req;
     walk.rows = rows;
-    HG_TRY(launch_rank(c, 0, walk));
+    HG_TRY(launch_rank(c, RANK_WHOLE, walk));
     c->lists_valid = c->want_lists;
     c->stage = ST_DB | ST_Q | ST_PLAN | ST_SELECT | ST_MATCH;
     return HG_OK;
@@ -1155,6 +775,8 @@ static int enqueue_exact_mx(hg_ctx* c, int64_t R, const StepReq& req) {
     const Geo& g = c->geo;
     // in all the slices hold R records + the ties of one segment beyond the quota, but unevenly: segments up to sstar carry
     // ALL their rows at distance t (the cut bucket is typically the fullest), later ones none -- budget like the bet does
+    // (not adopt_guess: this capacity has never had slice_capacity's two clamps -- to the segment's rows, to 64 GB of record rows --
+    // and keeps its own arithmetic: no cap_boost, the stage stays do_plan's)
     const double mean = 0.1 * (double)c->opt.cand_budget_x10 * (double)R / (double)g.S;
     u32 cap = (u32)std::ceil(mean + 6.0 * std::sqrt(mean) + 16.0);
     cap = (cap + 15u) & ~15u;
@@ -1174,12 +796,8 @@ static int enqueue_optimistic(hg_ctx* c, int64_t R, int stride, const StepReq& r
     HG_TRY(do_hist(c, stride, false, false, c->NB / 2 + 2));
     HG_TRY(set_R(c, R, 1, 0));
     const Geo& g = c->geo;
-    const size_t qb = (size_t)g.Qpad * 4;
-    HG_TRY(c->tguess.reserve(qb));
-    HG_TRY(c->sl_start.reserve((size_t)g.S * qb)); HG_TRY(c->sl_tie.reserve((size_t)g.S * qb));
-    HG_TRY(c->sl_cnt.reserve((size_t)g.S * qb)); HG_TRY(c->tot.reserve(qb)); HG_TRY(c->failq.reserve(qb));
+    HG_TRY(reserve_guess(c));
     HG_TRY(c->err.reserve(16));
-    HG_TRY(c->sstar.reserve(qb));
     // first bet on this database: the guess kernel also measures how the near rows crowd (err[2], err[3]) -- see below
     const bool probe = c->opt.crowd_probe && !c->crowd_probed && c->cap_boost == 1 && !c->capturing && !c->is_sub;
     u32* crowd = probe ? c->err.as<u32>() + 2 : nullptr;
@@ -1226,12 +844,7 @@ static int enqueue_optimistic(hg_ctx* c, int64_t R, int stride, const StepReq& r
     // distance bucket, and cumulative counts grow ~2x per bucket in the tail where the cut lies; clustered
     // codes grow faster) -- budget 4 R per query over the S segments plus 6 sigma per slice.  HBM is
     // plentiful (2.5 GB at C2); an overflow only costs the exact rerun.
-    const double mean = 0.1 * (double)req.cand_budget_x10 * (double)c->cap_boost * (double)R / (double)g.S;
-    u32 cap = slice_capacity(c, mean);
-    c->optimistic = true;
-    c->cap = cap;
-    c->crow = (i64)g.S * cap;
-    c->stage = ST_DB | ST_Q | ST_PLAN;
+    adopt_guess(c, 0.1 * (double)req.cand_budget_x10 * (double)c->cap_boost * (double)R / (double)g.S);
     StepReq guessed = req;
     guessed.err_zeroed = true;                         // k_guess_direct cleared the lost-bet flag: launch_rank need not
     return do_select(c, guessed);
@@ -1403,7 +1016,7 @@ static int finish_leftovers(hg_ctx* c, int* flag) {
     c->rank_leftovers += nleft;
     c->last_leftovers_inline = c->leftovers_inline;
     if (c->leftovers_inline) { c->leftovers_inline = false; return HG_OK; }     // k_rank_dense<slices> ranked them within the step
-    HG_TRY(launch_rank(c, 0, StepReq{}, true));
+    HG_TRY(launch_rank_leftovers(c));
     HG_TRY(do_ap_range(c, 0, c->geo.Q, c->bigq.as<u32>()));
     HG_TRY(download_results(c, (char*)c->pin));
     return wait_verdict(c, true, flag);

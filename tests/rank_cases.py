@@ -1,4 +1,4 @@
-"""Deterministic workloads aimed at the rank stage of the sampled-threshold bet (launch_rank in hashgan_amd/csrc/hg_seq.hip):
+"""Deterministic workloads aimed at the rank stage of the sampled-threshold bet (launch_rank in hashgan_amd/csrc/hg_rank.hip):
 which kernel takes a query's records, and every reason k_rank_lean / k_rank_cnt have to hand a query to the general kernel.
 
 Pure NumPy, one fixed seed per case.  Every builder returns a dict with qbits, dbbits, qlab, dblab ({0,1} matrices), b, R and
@@ -195,10 +195,10 @@ LONG_SLICE_BLOCKS = (100, 333, 601)      # the 96-row blocks that hold a run
 
 @functools.lru_cache(maxsize=None)
 def crowded(R):
-    """The record-count branches of k_rank_lean, b = 64.  How the densities follow from hg_seq.hip:
+    """The record-count branches of k_rank_lean, b = 64.  How the densities follow from hg_seq.hip and hg_rank.hip:
 
     crowded(1500), the long slice.  enqueue_optimistic budgets mean = 4 R / S records per (segment, query) slice and
-    slice_capacity gives it cap = mean + 6 sqrt(mean) + 16, rounded up to 16.  rank_lean_plan fetches PSP 16-byte pieces of every
+    slice_capacity gives it cap = mean + 6 sqrt(mean) + 16, rounded up to 16.  choose_rank has k_rank_lean fetch PSP 16-byte pieces of every
     slice up front, PSP = ceil((est + 4 sqrt(est) + 1) / 16) with est = 0.7 (sqrt(cap - 7) - 3)^2, and a slice with more than
     16 PSP records is finished by its own thread (`pc > PSP`).  N = 66064 rows in segments of 288 give S = 230: mean 26,
     cap 80, est 21.6, PSP 3 -- the tail starts at 49 records, the slice overflows at 81.  A slice of the exact cut holds
@@ -207,7 +207,7 @@ def crowded(R):
     straddles two: those slices hold 50 + 6..20 records, several times their neighbours', and stay below the capacity.
 
     crowded(6000), too many records, N = 131072.  k_rank_lean keeps lds_recs = min(S cap, its LDS room, 16 * 1024) records in
-    whole 16-byte pieces, at most RL_MAX_PIECES = 1024 of them; rank_lean_plan takes the shape only if that is at least
+    whole 16-byte pieces, at most RL_MAX_PIECES = 1024 of them; choose_rank takes the shape only if that is at least
     2.2 R + 256 + 16 S = 13456 + 16 S, i.e. with S <= 183 segments (the test asks for at most 128: max_segments), and then
     lds_recs = 16384.  Queries 5, 50 and 90 (90 has the code of 5, other labels) have 0.3 R = 1800 rows at distances 1..7 and
     a plateau of 3.3 R = 19800 rows at distance 8, both spread evenly over the database (every 6.6th row); their next row is

@@ -17,7 +17,7 @@ def test_ordinary_cases_are_ordinary(b):
     assert c["dblab"].sum(1).max() > 1                                       # multi-hot
     assert np.isnan(ap[5]) and rel[5] == 0 and np.isfinite(ap).sum() > Q // 2
     assert rc.span_of(dist).max() <= rc.maxb(b)                              # nothing for a rank kernel to decline
-    # the three layouts of the counters (cut_counters in hg_seq.hip): RC_MAXB + 2 of them where that is fewer than b + 1
+    # the three layouts of the counters (cut_counters in hg_rank.hip): RC_MAXB + 2 of them where that is fewer than b + 1
     assert {16: 17, 64: 18, 100: 34}[b] == min(rc.maxb(b) + 2, b + 1)
 
 

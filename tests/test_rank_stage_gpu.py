@@ -1,4 +1,4 @@
-"""The rank stage of the sampled-threshold bet (launch_rank in hashgan_amd/csrc/hg_seq.hip), kernel by kernel and branch by
+"""The rank stage of the sampled-threshold bet (launch_rank in hashgan_amd/csrc/hg_rank.hip), kernel by kernel and branch by
 branch, bit-exact against oracle.hamming_map.map_from_codes: per-query AP (nan included), hit counts and -- where the lists
 are asked for -- idx, dist and match bits.  No tolerances.
 
@@ -83,7 +83,7 @@ def test_every_rank_kernel_on_an_ordinary_bet(b):
     8-byte records and for rank_lds = 1, k_rank_fused (1) for rank_lds = 0; with lists wanted 3 for rank_lds >= 1, else 1.
 
     b = 100 runs with `max_segments` = 200: at the default a database of 66 100 rows of four-word codes is cut into 258 segments
-    of 256 rows, k_rank_lean takes at most 256 slices per query (rank_lean_plan), and rank_lds = 2 would mean k_rank_cnt -- the
+    of 256 rows, k_rank_lean takes at most 256 slices per query (choose_rank), and rank_lds = 2 would mean k_rank_cnt -- the
     table above would then hold 3 where it says 6, and the lean kernel's 34-counter layout would not run at all."""
     c = rc.ordinary(b)
     ref = rc.reference("ordinary", b)
@@ -221,7 +221,7 @@ def _segment_rows(N, S, b):
 
 
 def _spec_pieces(cap, S):
-    """rank_lean_plan's PSP: the 16-byte pieces of a slice k_rank_lean fetches before it knows the slice's count."""
+    """choose_rank's PSP: the 16-byte pieces of a slice k_rank_lean fetches before it knows the slice's count."""
     est = 0.7 * (math.sqrt(max(cap - 7.0, 0.0)) - 3.0) ** 2
     return max(1, min(math.ceil((est + 4.0 * math.sqrt(est) + 1.0) / 16.0), cap >> 4, 1024 // S))
 
@@ -269,7 +269,7 @@ def test_more_records_than_the_lean_kernel_holds():
     k_rank_lean's record capacity (stat "rank_lds_recs"; 16 * 1024 = RL_MAX_PIECES pieces at most), inside the bet's budget of 4 R
     and every slice's capacity (stats "records_kept", "segments", "slice_cap"): the bet holds, the lean kernel declines the queries
     (`n16 * 16 > lds_recs`, `n16 > RL_MAX_PIECES`) and the general kernel -- after the step, then within the next step's stream --
-    ranks them.  k_rank_cnt takes such a list in two tiles.  `max_segments` = 128: rank_lean_plan takes R = 6000 only with <= 183
+    ranks them.  k_rank_cnt takes such a list in two tiles.  `max_segments` = 128: choose_rank takes R = 6000 only with <= 183
     segments (rank_cases.crowded says why)."""
     R = rc.TOO_MANY_R
     c = rc.crowded(R)

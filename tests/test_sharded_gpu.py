@@ -119,6 +119,19 @@ def test_virtual_shards_lost_bet_is_consistent():
         assert st[0] == st[1] == (2, 1), st                  # both ranks bet twice and lost the first, alike
         bo = _run_virtual.last_boosts
         assert bo == [8, 8], bo                              # the escalation ran in lockstep and its second bet held
+    # The other places a lost verdict is counted (the runs above learn theirs from hg_unpack_parts, the tables routed by owner):
+    # all-gathered tables (hg_merge_ap_part in front of hg_unpack_parts); one shard, where hg_merge_ranked reads the verdict
+    # itself or defers it to hg_bet_verdict; the gather-lists route, hg_select_candidates + hg_rank, whose verdict hg_rank
+    # reads or hg_bet_verdict after it -- that route bets once and answers a lost bet with the exact sequence.
+    for G, gather_topr, defer, routed, stats, boost in ((2, False, False, False, (2, 1), 8), (1, False, False, True, (2, 1), 8),
+                                                        (1, False, True, True, (2, 1), 8), (2, True, False, True, (1, 1), 1),
+                                                        (2, True, True, True, (1, 1), 1)):
+        res = _run_virtual(c, G, gather_topr=gather_topr, defer=defer, routed=routed)
+        st, bo = _run_virtual.last_stats, _run_virtual.last_boosts
+        print("lost bet: G", G, "gather_topr", gather_topr, "defer", defer, "routed", routed, "-> (runs, fallbacks)", st, "cap_boost", bo)
+        for r in range(G):
+            assert np.array_equal(res[r][0][:24], ap_ref, equal_nan=True), (G, gather_topr, defer, routed, r)
+        assert st == [stats] * G and bo == [boost] * G, (G, gather_topr, defer, routed, st, bo)
 
 
 def test_virtual_shards_cut_beyond_the_exchanged_planes_goes_exact_at_once():
