@@ -89,6 +89,11 @@ _SIGNATURES = {
     "hg_get_joint_hist": [_p, _p],
     "hg_get_graded": [_p, _p, _p, _p, _p],
     "hg_get_grades": [_p, _p],
+    "hg_pack_side_table": [_p, C.c_int, C.c_int, C.POINTER(_p), C.POINTER(_i64)],
+    "hg_merge_side_table": [_p, C.c_int, _p, C.c_int, C.c_int],
+    "hg_get_merged_rel_hist": [_p, _p, _p],
+    "hg_get_merged_grade_hist": [_p, _p],
+    "hg_get_merged_joint_hist": [_p, _p],
     "hg_get_tie_ap": [_p, _p, _p, _p, _p, _p, _p, _p],
     "hg_get_ap_at": [_p, _p, _p],
     "hg_get_vote_pred": [_p, _p, _p],
@@ -132,6 +137,9 @@ DEV_DTYPES = {"float32": HG_F32, "float16": HG_F16, "bfloat16": HG_BF16, "int64"
 HG_OUT_IDX, HG_OUT_DIST, HG_OUT_SCORE, HG_OUT_MATCH, HG_OUT_AP, HG_OUT_HITS, HG_OUT_GRADES = range(7)
 OUT_ITEMS = {"idx": HG_OUT_IDX, "dist": HG_OUT_DIST, "score": HG_OUT_SCORE, "match": HG_OUT_MATCH, "ap": HG_OUT_AP, "hits": HG_OUT_HITS,
              "grades": HG_OUT_GRADES}
+# hg_pack_side_table / hg_merge_side_table: which
+HG_SIDE_REL, HG_SIDE_GRADE, HG_SIDE_JOINT = range(3)
+SIDE_TABLES = {"rel": HG_SIDE_REL, "grade": HG_SIDE_GRADE, "joint": HG_SIDE_JOINT}
 
 
 class DevArrayStruct(C.Structure):
@@ -212,6 +220,7 @@ class Context:
         self._h = h
         self.device = int(device)
         self.Q = self.N = self.R = self.b = self.C = None
+        self.n_total = None                # rows of the whole database the loaded one is a shard of (N unless set_database* said otherwise)
         self.options_touched = set()       # keys set through set_option (metric's engine pool only recycles contexts on their defaults)
 
     def close(self):
@@ -232,7 +241,7 @@ class Context:
         N = codes.shape[0]
         n_total = N if n_total is None else int(n_total)
         check(self._lib.hg_set_database(self._h, _ptr(codes), _ptr(labels), N, int(b), int(C_), int(idx_base), n_total))
-        self.N, self.b, self.C = N, int(b), int(C_)
+        self.N, self.b, self.C, self.n_total = N, int(b), int(C_), n_total
 
     def set_queries(self, codes_u64, labels_u64):
         codes = _carray(codes_u64, np.uint64)
@@ -250,7 +259,7 @@ class Context:
         bc, bl = _i64(), _i64()
         check(self._lib.hg_set_database_f32(self._h, _ptr(x), _ptr(lab), N, b, lab.shape[1], int(idx_base), n_total,
                                             C.byref(bc), C.byref(bl)))
-        self.N, self.b, self.C = N, b, lab.shape[1]
+        self.N, self.b, self.C, self.n_total = N, b, lab.shape[1], n_total
         return bc.value, bl.value
 
     def set_queries_f32(self, features, labels):
@@ -269,7 +278,7 @@ class Context:
         n_total = f.rows if n_total is None else int(n_total)
         bc, bl = _i64(), _i64()
         check(self._lib.hg_set_database_dev(self._h, C.byref(f), C.byref(l), int(idx_base), n_total, C.byref(bc), C.byref(bl)))
-        self.N, self.b, self.C = f.rows, f.cols, l.cols
+        self.N, self.b, self.C, self.n_total = f.rows, f.cols, l.cols, n_total
         return bc.value, bl.value
 
     def set_queries_dev(self, features, labels):
@@ -619,6 +628,39 @@ class Context:
         """-> uint32 [b+1, G, Q] of this shard, G = stat "joint_hist_grades" (after joint_hist())."""
         h = np.empty(((self.b or 0) + 1, self.get_stat("joint_hist_grades"), self.Q or 0), dtype=np.uint32)
         check(self._lib.hg_get_joint_hist(self._h, _ptr(h)))
+        return h
+
+    # -- a shard's histogram tables: pack, (all-gather,) merge ------------------------
+    def pack_side_table(self, which, Gc=0):
+        """This shard's current table `which` ("rel", "grade", "joint" or an HG_SIDE_* value) as one block in the exchange layout
+        (hg_pack_side_table; Gc: the grade count the ranks agreed on, joint only) -> (device address, bytes)."""
+        p, n = _p(), _i64()
+        check(self._lib.hg_pack_side_table(self._h, SIDE_TABLES.get(which, which), int(Gc), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def merge_side_table(self, which, dev_tabs_all, Gsh, Gc=0):
+        """The Gsh gathered blocks summed into the whole database's table, column totals checked against n_total (hg_merge_side_table).
+        Results: get_merged_rel_hist() / get_merged_grade_hist() / get_merged_joint_hist(); tie_ap() on a shard reads the rel one."""
+        check(self._lib.hg_merge_side_table(self._h, SIDE_TABLES.get(which, which), _p(dev_tabs_all) if dev_tabs_all else None, int(Gsh), int(Gc)))
+
+    def get_merged_rel_hist(self):
+        """-> (all, rel), uint32 [b+1, Q] each, of the whole database (after merge_side_table("rel", ...))."""
+        shape = ((self.b or 0) + 1, self.Q or 0)
+        a = np.empty(shape, dtype=np.uint32)
+        r = np.empty(shape, dtype=np.uint32)
+        check(self._lib.hg_get_merged_rel_hist(self._h, _ptr(a), _ptr(r)))
+        return a, r
+
+    def get_merged_grade_hist(self):
+        """-> uint32 [C+1, Q] of the whole database (after merge_side_table("grade", ...))."""
+        h = np.empty(((self.C or 0) + 1, self.Q or 0), dtype=np.uint32)
+        check(self._lib.hg_get_merged_grade_hist(self._h, _ptr(h)))
+        return h
+
+    def get_merged_joint_hist(self):
+        """-> uint32 [b+1, Gc, Q] of the whole database, Gc = stat "merged_joint_grades" (after merge_side_table("joint", ...))."""
+        h = np.empty(((self.b or 0) + 1, self.get_stat("merged_joint_grades"), self.Q or 0), dtype=np.uint32)
+        check(self._lib.hg_get_merged_joint_hist(self._h, _ptr(h)))
         return h
 
     # -- collectives (RCCL) -------------------------------------------------------

@@ -28,7 +28,7 @@ const char* const kKernelNames[KI_COUNT] = {"k_hist", "k_hist_reduce", "k_plan",
                                             "k_real_sample", "k_real_guess", "k_real_select", "k_radix_pass", "k_real_finish", "k_select_mx", "k_rank_cnt", "rccl_allgather", "step_gpu_span", "k_real_rescore",
                                             "k_hist_rel", "k_hist_rel_reduce", "k_graded", "k_grade_hist", "k_grade_hist_reduce", "k_tie_ap", "k_ap_at",
                                             "k_label_max", "k_hist_joint", "k_hist_joint_reduce",
-                                            "k_rr_scan", "k_rr_collect", "k_rr_score", "k_rr_order", "k_export", "k_votes", "k_vote_confusion"};
+                                            "k_rr_scan", "k_rr_collect", "k_rr_score", "k_rr_order", "k_export", "k_votes", "k_vote_confusion", "k_side_pack", "k_side_merge"};
 // Flatten NumPy's pairwise-summation tree for a chunk of n elements (n <= 8192):
 // numpy/_core/src/umath/loops_utils.h.src, pairwise_sum: n <= 128 is a leaf,
 // otherwise split at n/2 rounded down to a multiple of 8.
@@ -1299,6 +1299,10 @@ int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "votes_cutoffs")) *value = c->vt.dim;
     else if (!strcmp(key, "joint_hist_grades")) *value = c->jh_G;
     else if (!strcmp(key, "joint_hist_bands")) *value = c->jh_bands;
+    else if (!strcmp(key, "merged_joint_grades")) *value = c->mjh_G;
+    else if (!strcmp(key, "rel_hist_current")) *value = c->rh.current(c) ? 1 : 0;       // the shard's table of the loaded queries and database is there
+    else if (!strcmp(key, "grade_hist_current")) *value = c->gh.current(c) ? 1 : 0;
+    else if (!strcmp(key, "joint_hist_current")) *value = c->jh.current(c) ? 1 : 0;
     else if (!strcmp(key, "rerank_records")) *value = c->rr_records;
     else if (!strcmp(key, "rerank_chunks")) *value = c->rr_chunks;
     else if (!strcmp(key, "rerank_groups_lds")) *value = c->rr_groups_lds;

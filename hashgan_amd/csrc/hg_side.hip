@@ -8,6 +8,7 @@
 #include "hg_ap_at.hpp"
 #include "hg_hist_joint.hpp"
 #include "hg_votes.hpp"
+#include "hg_side_merge.hpp"
 
 // the classes of the last label word
 static u64 lastmask(int C) { return C % 64 ? (1ull << (C % 64)) - 1ull : ~0ull; }
@@ -74,6 +75,36 @@ template <int NW> static int hist_joint_nw(hg_ctx* c, const Geo& g, const JointA
     }
 }
 static int launch_hist_joint(hg_ctx* c, const Geo& g, const JointArgs& ja) { HG_DISPATCH_NW(hist_joint_nw, c, g, ja) }
+
+// One of the three additive tables (hg_side_merge.hpp), seen from hg_pack_side_table and hg_merge_side_table: the shard's own result and
+// buffers, the merged ones, the planes of a block and how many of them add up to a query's column total.
+struct SideTable {
+    const char* name; const char* pass;
+    SideResult* own; SideResult* merged;
+    DevBuf* src0; DevBuf* src1; DevBuf* dst;
+    i64 planes, split, check_planes, dim;
+    int Gs, Gc;
+};
+static int side_table(hg_ctx* c, const char* who, int which, int Gc, bool packing, SideTable* t) {
+    const i64 NB = c->NB;
+    switch (which) {
+        case HG_SIDE_REL:
+            *t = SideTable{"rel", "hg_rel_hist", &c->rh, &c->mrh, &c->rh_all, &c->rh_rel, &c->mg_rel, 2 * NB, NB, NB, NB, 1, 1};
+            return HG_OK;
+        case HG_SIDE_GRADE:
+            if (c->C > GR_MAX_C) return fail(HG_ERR_ARG, "%s: C=%d classes (a grade is a byte: at most %d)", who, c->C, GR_MAX_C);
+            *t = SideTable{"grade", "hg_grade_hist", &c->gh, &c->mgh, &c->gh_tab, nullptr, &c->mg_grade, c->C + 1, c->C + 1, c->C + 1, c->C + 1, 1, 1};
+            return HG_OK;
+        case HG_SIDE_JOINT: {
+            if (c->C > GR_MAX_C) return fail(HG_ERR_ARG, "%s: C=%d classes (a grade is a byte: at most %d)", who, c->C, GR_MAX_C);
+            if (Gc < 1 || Gc > c->C + 1) return fail(HG_ERR_ARG, "%s: Gc=%d grades (1..C + 1 = %d)", who, Gc, c->C + 1);
+            const int Gs = packing && c->jh.current(c) ? (int)(c->jh.dim / NB) : Gc;
+            *t = SideTable{"joint", "hg_joint_hist", &c->jh, &c->mjh, &c->jh_tab, nullptr, &c->mg_joint, NB * Gc, NB * Gc, NB * Gc, NB * Gc, Gs, Gc};
+            return HG_OK;
+        }
+        default: return fail(HG_ERR_ARG, "%s: which=%d (HG_SIDE_REL, HG_SIDE_GRADE or HG_SIDE_JOINT)", who, which);
+    }
+}
 
 extern "C" {
 
@@ -221,11 +252,15 @@ int hg_joint_hist(hg_ctx* c) {
 int hg_tie_ap(hg_ctx* c, const int64_t* host_Rs, int nR) {
     HG_TRY(need(c, ST_DB | ST_Q, "hg_tie_ap", "hg_set_database + hg_set_queries"));
     c->ta.begin();
-    HG_TRY(whole_database(c, "hg_tie_ap", "the cut at R needs the tables of the whole database in one context"));
-    HG_TRY(check_cutoffs("hg_tie_ap", "Rs", host_Rs, nR, TA_MAX_R, c->N, "N"));
+    // a shard: the merged table of the whole database (hg_merge_side_table) stands in for the shard's own, the cut-offs reach n_total
+    const bool shard = !(c->idx_base == 0 && c->N == c->n_total);
+    if (shard && !c->mrh.current(c))
+        HG_TRY(whole_database(c, "hg_tie_ap", "the cut at R needs the tables of the whole database: merge the shards' (hg_pack_side_table, hg_merge_side_table) first"));
+    HG_TRY(check_cutoffs("hg_tie_ap", "Rs", host_Rs, nR, TA_MAX_R, shard ? c->n_total : c->N, shard ? "n_total" : "N"));
     if (c->NB > TA_THREADS) return fail(HG_ERR_ARG, "hg_tie_ap: b=%d bits (at most %d)", c->b, TA_THREADS - 1);
-    if (!c->rh.current(c)) HG_TRY(hg_rel_hist(c));
-    const i64 Q = c->rh.Q;
+    if (!shard && !c->rh.current(c)) HG_TRY(hg_rel_hist(c));
+    const SideResult& tab = shard ? c->mrh : c->rh;
+    const i64 Q = tab.Q;
     const size_t plane = (size_t)Q * nR * 8;
     const FirstReservations first;
     HG_TRY(c->ta_tab.reserve(TA_MAX_R * 8));
@@ -234,10 +269,12 @@ int hg_tie_ap(hg_ctx* c, const int64_t* host_Rs, int nR) {
     HG_HIP(hipMemcpyAsync(c->ta_tab.p, host_Rs, (size_t)nR * 8, hipMemcpyHostToDevice, c->stream));
     char* o = c->ta_out.as<char>();
     TieApArgs a;
-    a.all = c->rh_all.as<u32>(); a.rel = c->rh_rel.as<u32>(); a.Rs = c->ta_tab.as<i64>();
+    a.all = shard ? c->mg_rel.as<u32>() : c->rh_all.as<u32>();
+    a.rel = shard ? c->mg_rel.as<u32>() + tab.dim * tab.Qpad : c->rh_rel.as<u32>();
+    a.Rs = c->ta_tab.as<i64>();
     a.ap_exp = (double*)o; a.p_hit = (double*)(o + plane); a.ap_min = (double*)(o + 2 * plane); a.ap_max = (double*)(o + 3 * plane);
     a.rel_exp = (double*)(o + 4 * plane); a.rel_lo = (i64*)(o + 5 * plane); a.rel_hi = (i64*)(o + 6 * plane);
-    a.Qpad = c->rh.Qpad; a.NB = (int)c->rh.dim; a.nR = nR;
+    a.Qpad = tab.Qpad; a.NB = (int)tab.dim; a.nR = nR;
     c->t_begin(KI_TIE_AP);
     hipLaunchKernelGGL(k_tie_ap, dim3((unsigned)Q, (unsigned)nR), dim3(TA_THREADS), 0, c->stream, a);
     c->t_end();
@@ -352,6 +389,76 @@ int hg_votes(hg_ctx* c, const int64_t* host_ks, int nk) {
     return HG_OK;
 }
 
+// A shard's current table `which` as one block in the exchange layout (hg_side_merge.hpp): u32 [planes][Qpad], for the joint table
+// zero-padded in g to the common grade count Gc.  The block is the context's (mg_pack) and holds until the next pack.
+int hg_pack_side_table(hg_ctx* c, int which, int Gc, void** dev_ptr, int64_t* nbytes) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_pack_side_table", "hg_set_database + hg_set_queries"));
+    if (!dev_ptr || !nbytes) return fail(HG_ERR_ARG, "hg_pack_side_table: null pointer");
+    if (which == HG_SIDE_JOINT && c->C <= GR_MAX_C && !c->jh.current(c))        // (before Gc is looked at: without the pass there is no Gs)
+        return fail(HG_ERR_STATE, "hg_pack_side_table: no joint table of the tables loaded now: call hg_joint_hist first");
+    SideTable t;
+    HG_TRY(side_table(c, "hg_pack_side_table", which, which == HG_SIDE_JOINT ? Gc : 1, true, &t));
+    if (!t.own->current(c)) return fail(HG_ERR_STATE, "hg_pack_side_table: no %s table of the tables loaded now: call %s first", t.name, t.pass);
+    if (t.Gc < t.Gs) return fail(HG_ERR_ARG, "hg_pack_side_table: Gc=%d is less than this shard's %d grades (stat joint_hist_grades)", t.Gc, t.Gs);
+    const i64 Qpad = t.own->Qpad, cells = t.planes * Qpad;
+    const FirstReservations first;
+    HG_TRY(c->mg_pack.reserve((size_t)(cells > 0 ? cells : 1) * 4));
+    first.keep(c);
+    if (cells > 0) {
+        SidePackArgs a;
+        a.src0 = t.src0->as<u32>(); a.src1 = t.src1 ? t.src1->as<u32>() : nullptr; a.dst = c->mg_pack.as<u32>();
+        a.Qpad = Qpad; a.planes = t.planes; a.split = t.split; a.Gs = t.Gs; a.Gc = t.Gc;
+        c->t_begin(KI_SIDE_PACK);
+        hipLaunchKernelGGL(k_side_pack, dim3(grid_for(cells / 4)), dim3(256), 0, c->stream, a);
+        c->t_end();
+        HG_TRY(c->check_launch("k_side_pack"));
+    }
+    *dev_ptr = c->mg_pack.p;
+    *nbytes = cells * 4;
+    return c->stage_end();
+}
+
+// The Gsh gathered blocks of table `which` summed into the merged table of the whole database, with the two checks of
+// hg_side_merge.hpp; the flag words are read before the call returns (it synchronises whatever "stage_sync" says).
+int hg_merge_side_table(hg_ctx* c, int which, const void* dev_tabs_all, int Gsh, int Gc) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_merge_side_table", "hg_set_database + hg_set_queries"));
+    if (which == HG_SIDE_REL) c->mrh.begin();
+    else if (which == HG_SIDE_GRADE) c->mgh.begin();
+    else if (which == HG_SIDE_JOINT) c->mjh.begin();
+    SideTable t;
+    HG_TRY(side_table(c, "hg_merge_side_table", which, which == HG_SIDE_JOINT ? Gc : 1, false, &t));
+    if (!dev_tabs_all || ((uintptr_t)dev_tabs_all & 15)) return fail(HG_ERR_ARG, "hg_merge_side_table: dev_tabs_all must be a 16-byte aligned device address");
+    if (Gsh < 1 || Gsh > 4096) return fail(HG_ERR_ARG, "hg_merge_side_table: %d shards (1..4096)", Gsh);
+    const Geo g = full_geometry(c);
+    const i64 cells = t.planes * g.Qpad;
+    const FirstReservations first;
+    HG_TRY(c->mg_flag.reserve(8));
+    HG_TRY(t.dst->reserve((size_t)(cells > 0 ? cells : 1) * 4));
+    first.keep(c);
+    u32 flag[2] = {0u, 0xFFFFFFFFu};
+    if (cells > 0) {
+        HG_HIP(hipMemsetAsync(c->mg_flag.p, 0, 4, c->stream));
+        HG_HIP(hipMemsetAsync(c->mg_flag.as<char>() + 4, 0xFF, 4, c->stream));
+        SideMergeArgs a;
+        a.tabs = (const u32*)dev_tabs_all; a.dst = t.dst->as<u32>(); a.flag = c->mg_flag.as<u32>();
+        a.Q = g.Q; a.Qpad = g.Qpad; a.planes = t.planes; a.check_planes = t.check_planes; a.n_total = c->n_total; a.Gsh = Gsh;
+        c->t_begin(KI_SIDE_MERGE);
+        hipLaunchKernelGGL(k_side_merge, dim3((unsigned)g.nQT), dim3(SM_THREADS), 0, c->stream, a);
+        c->t_end();
+        HG_TRY(c->check_launch("k_side_merge"));
+        HG_HIP(hipMemcpyAsync(flag, c->mg_flag.p, 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    HG_TRY(c->sync());                                 // (the flag words decide the call)
+    if (flag[0] & 1u)
+        return fail(HG_ERR_STATE, "hg_merge_side_table: a cell of the merged %s table does not fit 32 bits (overflow flag; %d blocks)", t.name, Gsh);
+    if (flag[0] & 2u)
+        return fail(HG_ERR_STATE, "hg_merge_side_table: the merged %s table's column of query %u does not add up to n_total = %lld rows (column-total flag: "
+                    "a shard's block is missing, counted twice or stale; %d blocks)", t.name, flag[1], (long long)c->n_total, Gsh);
+    if (which == HG_SIDE_JOINT) c->mjh_G = t.Gc;
+    t.merged->finish(c, g.Q, g.Qpad, t.dim);
+    return HG_OK;
+}
+
 // ---- getters: the copies on the context's stream, one synchronisation
 int hg_get_rel_hist(hg_ctx* c, uint32_t* host_all, uint32_t* host_rel) {
     HG_TRY(need(c, ST_DB | ST_Q, "hg_get_rel_hist", "hg_rel_hist"));
@@ -391,6 +498,33 @@ int hg_get_joint_hist(hg_ctx* c, uint32_t* host_hist) {
     if (!c->jh.current(c)) return fail(HG_ERR_STATE, "hg_get_joint_hist called before hg_joint_hist (on the tables loaded now)");
     if (!host_hist) return fail(HG_ERR_ARG, "hg_get_joint_hist: null pointer");
     HG_TRY(download_pitched(c, host_hist, c->jh_tab, c->jh.Q, c->jh.Qpad, c->jh.dim));
+    return c->sync();
+}
+
+int hg_get_merged_rel_hist(hg_ctx* c, uint32_t* host_all, uint32_t* host_rel) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_merged_rel_hist", "hg_merge_side_table"));
+    if (!c->mrh.current(c)) return fail(HG_ERR_STATE, "hg_get_merged_rel_hist called before hg_merge_side_table of the rel table (on the tables loaded now)");
+    const SideResult& m = c->mrh;
+    if (host_all) HG_TRY(download_pitched(c, host_all, c->mg_rel, m.Q, m.Qpad, m.dim));
+    if (host_rel)                                      // (the second half of the block)
+        HG_HIP(hipMemcpy2DAsync(host_rel, (size_t)m.Q * 4, c->mg_rel.as<u32>() + m.dim * m.Qpad, (size_t)m.Qpad * 4, (size_t)m.Q * 4, (size_t)m.dim,
+                                hipMemcpyDeviceToHost, c->stream));
+    return c->sync();
+}
+
+int hg_get_merged_grade_hist(hg_ctx* c, uint32_t* host_hist) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_merged_grade_hist", "hg_merge_side_table"));
+    if (!c->mgh.current(c)) return fail(HG_ERR_STATE, "hg_get_merged_grade_hist called before hg_merge_side_table of the grade table (on the tables loaded now)");
+    if (!host_hist) return fail(HG_ERR_ARG, "hg_get_merged_grade_hist: null pointer");
+    HG_TRY(download_pitched(c, host_hist, c->mg_grade, c->mgh.Q, c->mgh.Qpad, c->mgh.dim));
+    return c->sync();
+}
+
+int hg_get_merged_joint_hist(hg_ctx* c, uint32_t* host_hist) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_merged_joint_hist", "hg_merge_side_table"));
+    if (!c->mjh.current(c)) return fail(HG_ERR_STATE, "hg_get_merged_joint_hist called before hg_merge_side_table of the joint table (on the tables loaded now)");
+    if (!host_hist) return fail(HG_ERR_ARG, "hg_get_merged_joint_hist: null pointer");
+    HG_TRY(download_pitched(c, host_hist, c->mg_joint, c->mjh.Q, c->mjh.Qpad, c->mjh.dim));
     return c->sync();
 }
 

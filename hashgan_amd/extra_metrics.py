@@ -379,6 +379,31 @@ def _tie_tables(q_codes, db_codes, q_labels, db_labels, Rs, device):
     return Rs, t, total_rel
 
 
+def map_from_tie_tables(ap, p_hit):
+    """map[j] = sum_q p_hit * ap / sum_q p_hit over the queries with p_hit > 0, NaN when the denominator is 0 (NumPy only; tie_aware_map's
+    docstring says what it is the expectation of).  ap, p_hit: [Q, nR] (Context.get_tie_ap).  -> float64 [nR]"""
+    w = p_hit
+    den = w.sum(0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        m = np.where(den > 0, np.where(w > 0, w * ap, 0.0).sum(0) / den, np.nan)
+    return m
+
+
+def tie_map_from_tables(t, total_rel):
+    """tie_aware_map's dict from Context.get_tie_ap()'s tables and the relevant rows of the whole database per query (NumPy only)."""
+    pq = dict(t)
+    pq["total_rel"] = total_rel
+    return {"map": map_from_tie_tables(t["ap"], t["p_hit"]), "per_query": pq}
+
+
+def tie_precision_recall_from_tables(rel_exp, total_rel, ks):
+    """tie_aware_precision_recall_at_k's two means from rel_exp [Q, len(ks)] and total_rel [Q] (NumPy only)."""
+    precision = (rel_exp / ks[None, :]).mean(0)
+    ok = total_rel > 0
+    recall = (rel_exp[ok] / total_rel[ok, None]).mean(0) if ok.any() else np.full(len(ks), np.nan)
+    return precision, recall
+
+
 def tie_aware_map(q_codes, db_codes, q_labels, db_labels, Rs, device=0):
     """Tie-aware mAP@R of a Hamming ranking at the strictly ascending cut-offs Rs (at most 64, each in 1..N), binary codes
     ({0,1} or +-1).  Per query and R, over uniformly random orders inside every group of rows at equal distance:
@@ -394,13 +419,7 @@ def tie_aware_map(q_codes, db_codes, q_labels, db_labels, Rs, device=0):
     of the reference's numerator and denominator, not the expectation of their ratio.
     -> dict(map [nR], per_query=dict(ap, p_hit, ap_min, ap_max, rel_exp, rel_lo, rel_hi [Q, nR], total_rel [Q]))"""
     Rs, t, total_rel = _tie_tables(q_codes, db_codes, q_labels, db_labels, Rs, device)
-    w = t["p_hit"]
-    den = w.sum(0)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        m = np.where(den > 0, np.where(w > 0, w * t["ap"], 0.0).sum(0) / den, np.nan)
-    pq = dict(t)
-    pq["total_rel"] = total_rel
-    return {"map": m, "per_query": pq}
+    return tie_map_from_tables(t, total_rel)
 
 
 def tie_aware_precision_recall_at_k(q_codes, db_codes, q_labels, db_labels, ks, device=0):
@@ -410,11 +429,7 @@ def tie_aware_precision_recall_at_k(q_codes, db_codes, q_labels, db_labels, ks, 
     at most 64, each in 1..N.  The same device call as tie_aware_map: no ranking, no lists.
     -> (precision [len(ks)], recall [len(ks)])"""
     ks, t, total_rel = _tie_tables(q_codes, db_codes, q_labels, db_labels, ks, device)
-    rel_exp = t["rel_exp"]
-    precision = (rel_exp / ks[None, :]).mean(0)
-    ok = total_rel > 0
-    recall = (rel_exp[ok] / total_rel[ok, None]).mean(0) if ok.any() else np.full(len(ks), np.nan)
-    return precision, recall
+    return tie_precision_recall_from_tables(t["rel_exp"], total_rel, ks)
 
 
 def _ap_at_tables(q, db, q_labels, db_labels, ks, features, device):

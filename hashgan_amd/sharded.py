@@ -18,6 +18,11 @@ context's stream, ordered with its kernels):
   their queries where engine and communicator can (hg_alltoall: `route_by_owner`, the default): a GPU then receives
   its own queries' share of every shard's table -- 10.6 MB per step at C4 on 8 GPUs -- instead of all of it (80 MB).
 
+The order-free side metrics -- lookup curves over the Hamming radius, tie-aware mAP / precision / recall, tie-aware NDCG / ACG,
+IDCG -- need no ranking at all: each shard's histogram table is additive, so one all-gather of a small table and a sum on the
+device (hg_pack_side_table / hg_merge_side_table) give every rank the whole database's table, and the `*_shard` functions below
+return what their extra_metrics namesakes return on one context, bit for bit.
+
 `gather_topr` additionally all-gathers the ranked (idx, dist) lists themselves
 (the exchange BASELINE.json's north star names, hg_allgather_topr) for callers
 that want them.
@@ -36,6 +41,8 @@ import threading
 import time
 
 import numpy as np
+
+from . import extra_metrics, metric
 
 # A device allocation handed between an engine and a communicator: raw address + size.
 DevBuf = collections.namedtuple("DevBuf", "ptr nbytes")
@@ -553,6 +560,111 @@ def evaluate_query_split(ctx, comm, q_code_words, q_label_words, R):
     ap = np.concatenate([every[r, :bounds[r][1], 0] for r in range(comm.world)])
     rel = np.concatenate([every[r, :bounds[r][1], 1] for r in range(comm.world)]).astype(np.int64)
     return ap, rel
+
+
+# ------------------------------------------------------------------ order-free side metrics on a shard
+# Each takes a shard's loaded context (set_database* with idx_base / n_total, the replicated queries) and a communicator (RcclComm or
+# LocalComm) and returns, on EVERY rank, what the extra_metrics function of the same name returns for the whole database.  Collective:
+# every rank calls the same function with the same arguments.  Argument errors are raised before anything is exchanged.
+_SIDE_PASS = {"rel": ("rel_hist", "rel_hist_current"), "grade": ("grade_hist", "grade_hist_current"), "joint": ("joint_hist", "joint_hist_current")}
+
+
+def _check_binary(ctx):
+    """Binary codes only, like extra_metrics._load: what the float loaders found (packed uploads are binary by construction)."""
+    qk, dk = metric._kind(ctx, 1), metric._kind(ctx, 0)
+    binary = ("pm1", "bits", "ones")
+    if qk not in binary or dk not in binary or {qk, dk} == {"pm1", "bits"}:
+        raise ValueError("codes must be binary: all {-1,+1} or all {0,1} (found %s queries, %s database)" % (qk, dk))
+
+
+def _check_shard(ctx):
+    if None in (ctx.Q, ctx.N, ctx.n_total):
+        raise ValueError("the context holds no database and queries: load this rank's shard (idx_base, n_total) and the queries first")
+
+
+def merge_side_table(ctx, comm, which):
+    """This shard's table `which` ("rel", "grade", "joint") -- its pass run first unless the table of the loaded queries and database
+    is there -- packed, all-gathered and summed into the context's merged table of the whole database (hg_pack_side_table,
+    comm.all_gather, hg_merge_side_table: the table never leaves the device).  The joint table's common grade count is agreed on with
+    one all_gather_host of an integer.  A table that fails the merge's checks raises on every rank alike (the gathered data are the same)."""
+    run, current = _SIDE_PASS[which]
+    if not ctx.get_stat(current):
+        getattr(ctx, run)()
+    Gc = 0
+    if which == "joint":
+        Gc = int(comm.all_gather_host(np.array([ctx.get_stat("joint_hist_grades")], dtype=np.int64)).max())
+    ptr, nbytes = ctx.pack_side_table(which, Gc)
+    gathered = comm.all_gather(DevBuf(ptr, nbytes))
+    ctx.merge_side_table(which, gathered.ptr, comm.world, Gc)
+
+
+def lookup_histograms_shard(ctx, comm):
+    """extra_metrics.lookup_histograms of the whole database -> (all_hist, rel_hist), int64 [Q, b+1]"""
+    _check_shard(ctx)
+    _check_binary(ctx)
+    merge_side_table(ctx, comm, "rel")
+    a, r = ctx.get_merged_rel_hist()
+    return a.T.astype(np.int64), r.T.astype(np.int64)
+
+
+def hamming_radius_curves_shard(ctx, comm):
+    """extra_metrics.hamming_radius_curves of the whole database -> curves_from_histograms' dict"""
+    return extra_metrics.curves_from_histograms(*lookup_histograms_shard(ctx, comm))
+
+
+def _tie_tables_shard(ctx, comm, Rs):
+    """-> (Rs int64, Context.get_tie_ap()'s dict, total_rel int64 [Q]) of the whole database (extra_metrics._tie_tables)."""
+    _check_shard(ctx)
+    Rs = extra_metrics._check_ks(Rs, ctx.n_total)
+    _check_binary(ctx)
+    merge_side_table(ctx, comm, "rel")
+    ctx.tie_ap(Rs)                                      # (k_tie_ap on the merged table)
+    t = ctx.get_tie_ap()
+    total_rel = ctx.get_merged_rel_hist()[1].astype(np.int64).sum(0)
+    return Rs, t, total_rel
+
+
+def tie_aware_map_shard(ctx, comm, Rs):
+    """extra_metrics.tie_aware_map of the whole database at the cut-offs Rs (1..n_total) -> its dict"""
+    Rs, t, total_rel = _tie_tables_shard(ctx, comm, Rs)
+    return extra_metrics.tie_map_from_tables(t, total_rel)
+
+
+def tie_aware_precision_recall_at_k_shard(ctx, comm, ks):
+    """extra_metrics.tie_aware_precision_recall_at_k of the whole database -> (precision [len(ks)], recall [len(ks)])"""
+    ks, t, total_rel = _tie_tables_shard(ctx, comm, ks)
+    return extra_metrics.tie_precision_recall_from_tables(t["rel_exp"], total_rel, ks)
+
+
+def _check_graded_shard(ctx):
+    _check_shard(ctx)
+    if ctx.C > extra_metrics.MAX_CLASSES:
+        raise ValueError("graded relevance takes up to %d classes (have %d)" % (extra_metrics.MAX_CLASSES, ctx.C))
+    _check_binary(ctx)
+
+
+def grade_histograms_shard(ctx, comm):
+    """extra_metrics.grade_histograms of the whole database -> int64 [Q, C + 1]"""
+    _check_graded_shard(ctx)
+    merge_side_table(ctx, comm, "grade")
+    return ctx.get_merged_grade_hist().T.astype(np.int64)
+
+
+def distance_grade_histograms_shard(ctx, comm):
+    """extra_metrics.distance_grade_histograms of the whole database -> int64 [Q, b + 1, G], G the largest of the shards' grade counts"""
+    _check_graded_shard(ctx)
+    merge_side_table(ctx, comm, "joint")
+    return np.ascontiguousarray(ctx.get_merged_joint_hist().transpose(2, 0, 1)).astype(np.int64)
+
+
+def tie_aware_graded_at_k_shard(ctx, comm, ks, gain="exp"):
+    """extra_metrics.tie_aware_graded_at_k of the whole database at the cut-offs ks (1..n_total) -> tie_graded_from_tables' dict"""
+    _check_graded_shard(ctx)
+    ks = extra_metrics._check_ks(ks, ctx.n_total)
+    tab = extra_metrics.gain_table(gain, ctx.C)
+    disc = extra_metrics.discount_table(ks[-1])
+    joint = distance_grade_histograms_shard(ctx, comm)
+    return extra_metrics.tie_graded_from_tables(joint, ks, tab[:joint.shape[2]], disc)
 
 
 def shard_bounds(n_total, world):

@@ -376,8 +376,10 @@ int hg_get_grades(hg_ctx* ctx, uint8_t* host_grades);                   /* [Q][R
  *   p_hit    the probability of that condition
  *   ap_min, ap_max   the exact minimum and maximum of AP@R over all those orders (NaN when no order has a hit)
  *   rel_exp, rel_lo, rel_hi   expectation, minimum and maximum of the relevant rows among the top R
- * Rs: nR (1..64) strictly ascending values in 1..N, anything else HG_ERR_ARG; copied before the call returns.  The context must hold the
- * whole database (idx_base 0, N = n_total; HG_ERR_STATE otherwise).  float64 throughout; the order of every addition is a function of
+ * Rs: nR (1..64) strictly ascending values in 1..N, anything else HG_ERR_ARG; copied before the call returns.  The context holds the
+ * whole database (idx_base 0, N = n_total) -- or a shard of it together with a merged rel table of the loaded queries and database
+ * (hg_merge_side_table, below): the same kernel then reads the merged table, never runs the pass, and the cut-offs reach 1..n_total.  A
+ * shard without a current merged table: HG_ERR_STATE.  A whole-database context never looks at a merged table.  float64 throughout; the order of every addition is a function of
  * the query's two table columns and R, so equal inputs give equal bits whatever Q is.  Tables of its own: the staged pipeline's
  * state, hg_hist's histogram, lists, match bits, APs and a step of hg_map_begin in flight are left as they were.  A database or query
  * reload and hg_trim invalidate the results (hg_get_tie_ap then returns HG_ERR_STATE, as it does before the first pass). */
@@ -420,6 +422,41 @@ int hg_votes(hg_ctx* ctx, const int64_t* host_ks, int nk);
 int hg_get_vote_pred(hg_ctx* ctx, int32_t* host_pred, int64_t* host_top);   /* [Q][nk] each; null: skipped */
 int hg_get_vote_confusion(hg_ctx* ctx, int64_t* host_conf);             /* [nk][C][C] */
 int hg_get_votes(hg_ctx* ctx, uint32_t* host_votes);                    /* [Q][nk][C] */
+
+/* ---- the histogram tables of a database-sharded context: pack, exchange, merge -------------------------------------------------
+ * hg_rel_hist's, hg_grade_hist's and hg_joint_hist's tables are additive over shards (contexts loaded with idx_base / n_total; the
+ * queries replicated, so Q, b and C are equal on every rank).  Everything read from them -- the lookup curves over the Hamming radius,
+ * tie-aware AP and precision / recall, tie-aware NDCG / ACG, IDCG -- is a function of the whole database's table alone, so a rank
+ * that holds the SUM of the shards' tables gives the bits one context with the whole database gives.  The tables stay on the device:
+ *   hg_<pass>  ->  hg_pack_side_table  ->  all-gather of the block (hg_allgather, or the caller's)  ->  hg_merge_side_table
+ * The exchange unit is one contiguous block of uint32 planes [planes][Qpad], q fastest, Qpad = Q rounded up to 64:
+ *   HG_SIDE_REL    [2][b+1][Qpad]     all, then rel
+ *   HG_SIDE_GRADE  [C+1][Qpad]
+ *   HG_SIDE_JOINT  [b+1][Gc][Qpad]    the shard's [b+1][Gs][Qpad] with zero planes for g = Gs..Gc-1.  A shard's Gs (stat
+ *                                     "joint_hist_grades") depends on its own rows: the ranks agree on Gc = max Gs before they pack
+ * hg_pack_side_table: needs the shard's table `which` of the loaded queries and database (HG_ERR_STATE, naming the pass, otherwise).
+ *   Gc is ignored unless which is HG_SIDE_JOINT; there Gc < Gs or Gc > C + 1 is HG_ERR_ARG.  *dev_ptr / *nbytes: the block, owned by
+ *   the context, valid until the next hg_pack_side_table, a reload or hg_trim.  One kernel (k_side_pack); ends like a staged call
+ *   (synchronises unless "stage_sync" is 0).  Changes no result.
+ * hg_merge_side_table: dev_tabs_all = Gsh (1..4096) such blocks back to back, 16-byte aligned (what hg_allgather leaves); Gc as packed
+ *   (ignored unless joint).  One kernel (k_side_merge) sums them cell by cell in 64 bits into a merged table of the context's own and
+ *   checks, for every query q < Q, that the column total -- over the `all` planes for rel, over g for grade, over (d, g) for joint --
+ *   is n_total.  A cell of a real query that does not fit uint32 (overflow flag) or a column total other than n_total (column-total
+ *   flag: a shard is missing, counted twice or stale) fails the call with HG_ERR_STATE and a message naming the flag.  Both flags are
+ *   integer and independent of any order.  The host reads them: the call synchronises whatever "stage_sync" says.
+ * A merged table belongs to the queries and database it was merged on: it is ended by its own merge call when that is refused or fails,
+ * by a reload of the queries or the database and by hg_trim -- by nothing else.  The shard's own tables and their getters keep meaning
+ * "this shard".  Stage, geometry, lists, match bits, APs, the other side results and a step of hg_map_begin in flight are left as they
+ * were by all five calls.  Getters: [b+1][Q] twice, [C+1][Q], [b+1][Gc][Q] with Gc = stat "merged_joint_grades"; HG_ERR_STATE without
+ * a current merged table.  hg_tie_ap on a shard reads the merged rel table (above). */
+#define HG_SIDE_REL 0
+#define HG_SIDE_GRADE 1
+#define HG_SIDE_JOINT 2
+int hg_pack_side_table(hg_ctx* ctx, int which, int Gc, void** dev_ptr, int64_t* nbytes);
+int hg_merge_side_table(hg_ctx* ctx, int which, const void* dev_tabs_all, int Gsh, int Gc);
+int hg_get_merged_rel_hist(hg_ctx* ctx, uint32_t* host_all, uint32_t* host_rel);   /* [b+1][Q] each, the whole database; null: skipped */
+int hg_get_merged_grade_hist(hg_ctx* ctx, uint32_t* host_hist);                    /* [C+1][Q] */
+int hg_get_merged_joint_hist(hg_ctx* ctx, uint32_t* host_hist);                    /* [b+1][Gc][Q] */
 
 /* ---- collectives: RCCL over xGMI, one process per GPU (the reference has no counterpart --
  * main.py:260-263 only sets CUDA_VISIBLE_DEVICES) --------------------------------------------------------
@@ -505,7 +542,7 @@ int hg_set_option(hg_ctx* ctx, const char* key, int64_t value);
 /* Counters and facts about the last call (37 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
  * "optimistic_requeried" (single queries rerun exactly after losing their bet), "optimistic_rebets" (second and widened bets), "last_optimistic",
  * "rank_leftovers" (queries the LDS-resident rank kernel left to the general one), "select_variant" (1 k_select, 2 k_select_dense, 3 k_select_mx,
- * 5 k_select_mx3, 6 k_select_mx4), "rank_variant" (1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>), "hist_variant" (the kernel of the last histogram pass, full or sampled: 1 k_hist, 2 k_hist_mx, 3 k_hist_i8; 6 / 7: k_hist_mx / k_hist_i8 with one dword counter per query tile instead of 16-bit halves; 0: no pass yet), "rank_lds_recs" (records the last k_rank_lean / k_rank_cnt launch had LDS room for), "slice_cap" (capacity of a (segment, query) slice of the last bet), "rel_hist_variant" (the kernel of the last hg_rel_hist: 1 k_hist_rel, the vector-ALU pass -- the only one so far, whatever "hist_mfma" says; 0: no pass yet), "ap_at_cutoffs" (cut-offs of the last hg_ap_at; 0: no pass yet), "votes_cutoffs" (cut-offs of the last hg_votes; 0: no pass yet), "joint_hist_grades" / "joint_hist_bands" (grades G and distance bands of the last hg_joint_hist; 0: no pass yet), "ap_fused",
+ * 5 k_select_mx3, 6 k_select_mx4), "rank_variant" (1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>), "hist_variant" (the kernel of the last histogram pass, full or sampled: 1 k_hist, 2 k_hist_mx, 3 k_hist_i8; 6 / 7: k_hist_mx / k_hist_i8 with one dword counter per query tile instead of 16-bit halves; 0: no pass yet), "rank_lds_recs" (records the last k_rank_lean / k_rank_cnt launch had LDS room for), "slice_cap" (capacity of a (segment, query) slice of the last bet), "rel_hist_variant" (the kernel of the last hg_rel_hist: 1 k_hist_rel, the vector-ALU pass -- the only one so far, whatever "hist_mfma" says; 0: no pass yet), "ap_at_cutoffs" (cut-offs of the last hg_ap_at; 0: no pass yet), "votes_cutoffs" (cut-offs of the last hg_votes; 0: no pass yet), "joint_hist_grades" / "joint_hist_bands" (grades G and distance bands of the last hg_joint_hist; 0: no pass yet), "merged_joint_grades" (the common grade count Gc of the last joint hg_merge_side_table that succeeded; 0: none yet), "rel_hist_current" / "grade_hist_current" / "joint_hist_current" (1: this shard's table of the loaded queries and database is there -- what hg_pack_side_table needs), "ap_fused",
  * "cap_boost", "crowding_x100", "segments", "records_kept" (records the last bet's select left in the slices: a download, not part of a step),
  * "device_bytes" (every device buffer the context and its requery child hold, the second stream's workspace included), "graph_replays", "map_async_steps" / "map_async_redone" / "map_overlapped_steps" (hg_map_begin: steps enqueued blind / of those, run again by hg_map_end /
  * of those, run on the second stream);
