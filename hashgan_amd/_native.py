@@ -91,6 +91,8 @@ _SIGNATURES = {
     "hg_get_grades": [_p, _p],
     "hg_pack_side_table": [_p, C.c_int, C.c_int, C.POINTER(_p), C.POINTER(_i64)],
     "hg_merge_side_table": [_p, C.c_int, _p, C.c_int, C.c_int],
+    "hg_pack_list_table": [_p, C.c_int, _p, C.c_int, C.POINTER(_p), C.POINTER(_i64)],
+    "hg_merge_list_table": [_p, C.c_int, _p, C.c_int, _p, C.c_int],
     "hg_get_merged_rel_hist": [_p, _p, _p],
     "hg_get_merged_grade_hist": [_p, _p],
     "hg_get_merged_joint_hist": [_p, _p],
@@ -140,6 +142,9 @@ OUT_ITEMS = {"idx": HG_OUT_IDX, "dist": HG_OUT_DIST, "score": HG_OUT_SCORE, "mat
 # hg_pack_side_table / hg_merge_side_table: which
 HG_SIDE_REL, HG_SIDE_GRADE, HG_SIDE_JOINT = range(3)
 SIDE_TABLES = {"rel": HG_SIDE_REL, "grade": HG_SIDE_GRADE, "joint": HG_SIDE_JOINT}
+# hg_pack_list_table / hg_merge_list_table: which
+HG_LIST_GRADES, HG_LIST_VOTES = range(2)
+LIST_TABLES = {"grades": HG_LIST_GRADES, "votes": HG_LIST_VOTES}
 
 
 class DevArrayStruct(C.Structure):
@@ -222,6 +227,7 @@ class Context:
         self.Q = self.N = self.R = self.b = self.C = None
         self.n_total = None                # rows of the whole database the loaded one is a shard of (N unless set_database* said otherwise)
         self.options_touched = set()       # keys set through set_option (metric's engine pool only recycles contexts on their defaults)
+        self.option_values = {}            # ... and the values they were last set to (the library has no getter)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -663,6 +669,24 @@ class Context:
         check(self._lib.hg_get_merged_joint_hist(self._h, _ptr(h)))
         return h
 
+    # -- a shard's part of the ranked lists: pack, (all-gather,) merge -------------------
+    def pack_list_table(self, which, ks=None):
+        """This shard's part of the whole database's ranked lists (a staged select with lists) as one block in the exchange layout
+        (hg_pack_list_table): which = "grades" -- uint8 [Q][Rp] + uint32 own[Qpad], ks ignored -- or "votes" -- uint32 [nk][C+1][Qpad]
+        at the cut-offs ks -- or an HG_LIST_* value -> (device address, bytes)."""
+        p, n = _p(), _i64()
+        ks = None if ks is None else _carray(ks, np.int64).ravel()
+        check(self._lib.hg_pack_list_table(self._h, LIST_TABLES.get(which, which), None if ks is None else _ptr(ks), 0 if ks is None else len(ks),
+                                           C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def merge_list_table(self, which, dev_blocks_all, Gsh, ks=None):
+        """The Gsh gathered blocks merged into the grade plane / the vote counts of the whole database's lists, owned slots checked
+        against R and the cut-offs (hg_merge_list_table).  graded() / votes() on a shard then run from the merged table."""
+        ks = None if ks is None else _carray(ks, np.int64).ravel()
+        check(self._lib.hg_merge_list_table(self._h, LIST_TABLES.get(which, which), _p(dev_blocks_all) if dev_blocks_all else None, int(Gsh),
+                                            None if ks is None else _ptr(ks), 0 if ks is None else len(ks)))
+
     # -- collectives (RCCL) -------------------------------------------------------
     def comm_init(self, unique_id, rank, world):
         buf = (C.c_uint8 * COMM_ID_BYTES).from_buffer_copy(bytes(unique_id))
@@ -735,6 +759,7 @@ class Context:
     def set_option(self, key, value):
         check(self._lib.hg_set_option(self._h, key.encode(), int(value)))
         self.options_touched.add(key)
+        self.option_values[key] = int(value)
 
     def preload(self):
         """One-time costs of every path now instead of on first use (hg_preload)."""

@@ -5,7 +5,8 @@
 //   hg_seq.hip         the Hamming sequences: geometry, histogram -> plan -> select -> rank, staged (sharded) and one-shot forms
 //   hg_rank.hip        their rank stage: the choice of the kernel (RankChoice), one launcher per kernel, the leftovers of a fused step, k_order
 //   hg_side.hip        the side metrics (hg_rel_hist, hg_graded, hg_grade_hist, hg_tie_ap, hg_ap_at, hg_joint_hist, hg_votes) and their getters: one SideResult each;
-//                      the shards' histogram tables packed and merged into the whole database's (hg_pack_side_table, hg_merge_side_table)
+//                      the shards' histogram tables packed and merged into the whole database's (hg_pack_side_table, hg_merge_side_table), and the
+//                      grades and votes along a shard's partial lists (hg_pack_list_table, hg_merge_list_table)
 //   hg_rerank.hip      the re-ranked Hamming ranking (hg_topr_rerank, hg_map_rerank): distance, then float32 inner product inside equal distances
 //   hg_pairs_valu.hip  launchers of the vector-ALU pair passes (k_hist, k_select, k_select_dense)
 //   hg_pairs_mx.hip    launchers of the matrix-core pair passes (k_select_mx3 / mx4, k_hist_mx, k_hist_i8) and their images
@@ -215,7 +216,8 @@ enum KernelId { KI_HIST = 0, KI_HIST_REDUCE, KI_PLAN, KI_SEG_COUNTS, KI_SEG_LAYO
                 KI_ORDER, KI_RANK_FUSED, KI_MATCH, KI_AP, KI_MERGE, KI_PACK, KI_REAL_SAMPLE, KI_REAL_GUESS, KI_REAL_SELECT,
                 KI_RADIX, KI_REAL_FINISH, KI_SELECT_MX, KI_RANK_LDS, KI_COMM, KI_STEP, KI_REAL_RESCORE, KI_HIST_REL, KI_HIST_REL_REDUCE,
                 KI_GRADED, KI_GRADE_HIST, KI_GRADE_HIST_REDUCE, KI_TIE_AP, KI_AP_AT, KI_LABEL_MAX, KI_HIST_JOINT, KI_HIST_JOINT_REDUCE,
-                KI_RR_SCAN, KI_RR_COLLECT, KI_RR_SCORE, KI_RR_ORDER, KI_EXPORT, KI_VOTES, KI_VOTE_CONFUSION, KI_SIDE_PACK, KI_SIDE_MERGE, KI_COUNT };
+                KI_RR_SCAN, KI_RR_COLLECT, KI_RR_SCORE, KI_RR_ORDER, KI_EXPORT, KI_VOTES, KI_VOTE_CONFUSION, KI_SIDE_PACK, KI_SIDE_MERGE,
+                KI_LIST_GRADES, KI_LIST_MERGE_GRADES, KI_LIST_MERGE_VOTES, KI_VOTE_PICK, KI_COUNT };
 enum Stage { ST_NONE = 0, ST_DB = 1, ST_Q = 2, ST_HIST = 4, ST_PLAN = 8, ST_SELECT = 16, ST_MATCH = 32, ST_AP = 64 };
 extern const char* const kKernelNames[KI_COUNT];
 // the kernel that took the last record pass / the last rank stage (stats "select_variant", "rank_variant"), and what the rank stage is asked for
@@ -423,6 +425,9 @@ struct hg_ctx : StepBufs, StepState {
     SideResult vt;             // hg_votes: vt_votes [Q][nk][C], vt_pred's pred / top [Q][nk], vt_conf [nk][C][C] of the ranked lists it found; dim = nk, also stat "votes_cutoffs"
     SideResult mrh, mgh, mjh;  // hg_merge_side_table: the shards' tables summed into the whole database's -- mg_rel [2][NB][Qpad] (all, then rel; dim = NB),
                                // mg_grade [C + 1][Qpad], mg_joint [NB * Gc][Qpad] (dim = NB * Gc).  Ended by the merge's own refusal or failure, a reload, hg_trim
+    SideResult mlg, mlv;       // hg_merge_list_table (hg_list_merge.hpp): the shards' grade planes merged into lm_grades [Q][Rp] (Qpad = Rp, dim = R), their vote tables
+                               // into lm_votes [Q][nk][C] (dim = nk, the cut-offs in mlv_ks).  They belong to the ranked lists too: ended like gr and vt (lists_changed), and by their own merge's refusal
+    i64 mlv_ks[64] = {0};      // the cut-offs of the merged vote table: hg_votes on a shard takes these and no others
     int mjh_G = 0;             // stat "merged_joint_grades": the common grade count Gc of the last joint merge that succeeded (0: none yet)
     SideResult rr;             // the last ranking was a re-rank (hg_rerank.hip) of these tables: rr_scores [Q][R]; dim = R.  Not a side metric -- set_R ends it
     i64 rr_records = 0, rr_chunks = 0, rr_groups_lds = 0, rr_groups_global = 0;   // stats "rerank_records" / "rerank_chunks" / "rerank_groups_lds" / "rerank_groups_global" of the last re-rank
@@ -431,7 +436,7 @@ struct hg_ctx : StepBufs, StepState {
     bool gr_kept = false; i64 gr_R = 0;   // gr_grades holds the grade bytes [Q][gr_R] of gr's pass
     i64 aa_recip_n = -1;       // aa_recip holds RN(1 / k) for k = 1 .. this (+ AP_RECIP_SLACK)
     i64 export_bytes = 0; int export_variant = 0;   // stats "export_bytes" / "export_variant" of the last hg_export: bytes written; bit 0 a 16-byte-store kernel ran, bit 1 an element-wise one
-    void lists_changed() { gr.begin(); vt.begin(); }   // the ranked lists are no longer the ones hg_graded / hg_votes walked (a merge into them)
+    void lists_changed() { gr.begin(); vt.begin(); mlg.begin(); mlv.begin(); }   // the ranked lists are no longer the ones hg_graded / hg_votes walked (a merge into them)
     void bitmap_changed() { aa.begin(); }     // the match bitmap is no longer the one hg_ap_at walked (hg_match, the merges, a blind step)
     bool mbits_merged = false; // G > 1: the shards' bitmaps have been merged into mbits for all queries (hg_merge_match, hg_merge_ranked)
     bool mbits_in_ws_b = false;   // the last ranking was a blind step on stream_b: its bitmap is ws_b's, not mbits
@@ -517,6 +522,8 @@ struct hg_ctx : StepBufs, StepState {
     DevBuf vt_tab, vt_votes, vt_pred, vt_conf;   // hg_votes: the cut-offs [64 x i64], votes [Q][nk][C] x 4, pred [Q][nk] x 4 then top [Q][nk] x 4, conf [nk][C][C] x 8 (vt)
     DevBuf mg_pack, mg_flag;   // hg_pack_side_table's block in the exchange layout (one at a time: the next pack overwrites it); hg_merge_side_table's two flag words
     DevBuf mg_rel, mg_grade, mg_joint;   // the merged tables (mrh, mgh, mjh)
+    DevBuf lm_pack, lm_flag, lm_tab;   // hg_pack_list_table's block in the exchange layout (one at a time: the next pack overwrites it); hg_merge_list_table's four flag words; the cut-offs [64 x i64] of the vote pack / merge
+    DevBuf lm_grades, lm_votes;   // the merged grade plane and vote counts (mlg, mlv)
     DevBuf aa_recip;           // hg_ap_at's own reciprocals (aa_recip_n) when the ranking's table (ap_recip, recip_for_R) is not there
     DevBuf rr_recs, rr_tmp;    // re-rank: a chunk's records (row index, then the sort key), the radix passes' second buffer (groups beyond the LDS only)
     DevBuf rr_base, rr_msz, rr_cnt, rr_scores;   // re-rank: a query's first record in its chunk [Q] x 8, records per query [Q] x 4, {groups in LDS, groups by radix}, the score lists [Q][R]
@@ -548,7 +555,7 @@ struct hg_ctx : StepBufs, StepState {
         for (DevBuf* d : {&seglt, &segtie, &mbits2, &part, &obuf[0], &obuf[1], &beyond, &stage_in, &badcnt, &flist, &dbytes, &samp, &thr,
                           &sortA, &sortB, &scores, &gtab, &sampx, &cntq, &krows, &thr2, &hist2, &comm_tmp, &gath_idx, &gath_dist, &rh_part, &rh_all, &rh_rel,
                           &gr_tab, &gr_out, &gr_grades, &gh_part, &gh_tab, &ta_tab, &ta_out, &aa_tab, &aa_out, &jh_max, &jh_part, &jh_tab, &vt_tab, &vt_votes, &vt_pred, &vt_conf,
-                          &mg_pack, &mg_flag, &mg_rel, &mg_grade, &mg_joint, &rr_recs, &rr_tmp, &rr_base, &rr_msz, &rr_cnt, &rr_scores})
+                          &mg_pack, &mg_flag, &mg_rel, &mg_grade, &mg_joint, &lm_pack, &lm_flag, &lm_tab, &lm_grades, &lm_votes, &rr_recs, &rr_tmp, &rr_base, &rr_msz, &rr_cnt, &rr_scores})
             f(*d, BUF_WORK);
         for (DevBuf& d : gathered) f(d, BUF_WORK);
         for (DevBuf& d : scratch) f(d, BUF_WORK);
@@ -558,7 +565,7 @@ struct hg_ctx : StepBufs, StepState {
     // the keys of the BUF_DERIVED buffers: after this each is rebuilt on its next use
     void forget_derived() {
         dbx_valid = qx_valid = dbx8_valid = dbx3_valid = dbx4_valid = dbfx_valid = dbfb_valid = false;
-        for (SideResult* r : {&rh, &gr, &gh, &ta, &aa, &jh, &vt, &mrh, &mgh, &mjh, &rr}) r->begin();   // (hg_trim releases their tables with the other work buffers)
+        for (SideResult* r : {&rh, &gr, &gh, &ta, &aa, &jh, &vt, &mrh, &mgh, &mjh, &mlg, &mlv, &rr}) r->begin();   // (hg_trim releases their tables with the other work buffers)
         shapes_for_R = recip_for_R = aa_recip_n = -1;
         outblk_q = ws_b.outblk_q = -1;
     }

@@ -43,6 +43,7 @@ struct GradedArgs {
     i64 R, N;
     int nk, LW;
     u64 lastmask;                      // the classes of the last label word
+    const u8* plane; i64 Rp;           // PLANE: the grade bytes [Q][Rp] of the whole database's lists (hg_list_merge.hpp) instead of idx / dblab / qlab
 };
 
 __device__ __forceinline__ u32 grade_of(const GradedArgs& a, const u64* __restrict__ ql, const u32 gi) {
@@ -72,7 +73,10 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
-static __global__ __launch_bounds__(GR_THREADS) void k_graded(const GradedArgs a) {
+// PLANE: the grade of rank i is plane[q][i], a shard's merged grade plane, not gathered through idx.  Everything after the grade is
+// the same code, so the sums have the bits the gather gives on one context with the whole database.
+template <bool PLANE>
+__global__ __launch_bounds__(GR_THREADS) void k_graded(const GradedArgs a) {
     __shared__ u32 sg[GR_THREADS / 64], sh[GR_THREADS / 64];
     __shared__ double sd[GR_THREADS / 64], sw[GR_THREADS / 64];
     const int q = (int)blockIdx.x;
@@ -80,6 +84,7 @@ static __global__ __launch_bounds__(GR_THREADS) void k_graded(const GradedArgs a
     const u32* __restrict__ idx = a.idx + (i64)q * a.R;
     const u64* __restrict__ ql = a.qlab + (i64)q * a.LW;
     u8* __restrict__ gr = a.grades ? a.grades + (i64)q * a.R : nullptr;
+    const u8* __restrict__ pg = PLANE ? a.plane + (i64)q * a.Rp : nullptr;
 
     i64 S = 0, H = 0;                  // running totals, the same in every thread
     double dcg = 0.0, ws = 0.0;
@@ -89,7 +94,9 @@ static __global__ __launch_bounds__(GR_THREADS) void k_graded(const GradedArgs a
         const i64 end = pos + GR_THREADS < kj ? pos + GR_THREADS : kj;
         const i64 i = pos + tid;
         const bool act = i < end;
-        const u32 g = act ? grade_of(a, ql, idx[i]) : 0u;
+        u32 g = 0u;
+        if constexpr (PLANE) g = act ? (u32)pg[i] : 0u;
+        else g = act ? grade_of(a, ql, idx[i]) : 0u;
         if (act && gr) gr[i] = (u8)g;
         const u32 incl = wave_scan_u32(g, lane);
         const u32 wh = (u32)__popcll(__ballot(g > 0u));
@@ -125,7 +132,7 @@ static __global__ __launch_bounds__(GR_THREADS) void k_graded(const GradedArgs a
         }
     }
     if (gr)                            // the grade bytes of the ranks past the last cut-off
-        for (i64 i = pos + tid; i < a.R; i += GR_THREADS) gr[i] = (u8)grade_of(a, ql, idx[i]);
+        for (i64 i = pos + tid; i < a.R; i += GR_THREADS) gr[i] = PLANE ? pg[i] : (u8)grade_of(a, ql, idx[i]);
 }
 
 // Rows per scalar-load batch: the current and the prefetched batch of label words stay within 64 SGPRs.

@@ -9,6 +9,7 @@
 #include "hg_hist_joint.hpp"
 #include "hg_votes.hpp"
 #include "hg_side_merge.hpp"
+#include "hg_list_merge.hpp"
 
 // the classes of the last label word
 static u64 lastmask(int C) { return C % 64 ? (1ull << (C % 64)) - 1ull : ~0ull; }
@@ -23,8 +24,9 @@ static int check_cutoffs(const char* who, const char* name, const int64_t* host,
     return HG_OK;
 }
 
+static bool is_shard(const hg_ctx* c) { return !(c->idx_base == 0 && c->N == c->n_total); }
 static int whole_database(const hg_ctx* c, const char* who, const char* why) {
-    if (c->idx_base == 0 && c->N == c->n_total) return HG_OK;
+    if (!is_shard(c)) return HG_OK;
     return fail(HG_ERR_STATE, "%s: the context holds rows [%lld, %lld) of %lld: %s", who, (long long)c->idx_base, (long long)(c->idx_base + c->N), (long long)c->n_total, why);
 }
 
@@ -106,6 +108,25 @@ static int side_table(hg_ctx* c, const char* who, int which, int Gc, bool packin
     }
 }
 
+// The sizes of the two list exchange units (hg_list_merge.hpp) for the ranking and tables held now.
+struct ListGeo { i64 Q, Qpad, R, Rp; };
+static ListGeo list_geometry(const hg_ctx* c) {
+    const Geo g = full_geometry(c);
+    return ListGeo{g.Q, g.Qpad, c->geo.R, (c->geo.R + 15) / 16 * 16};
+}
+// the cut-offs into lm_tab as a kernel argument: no host array has to outlive the call, so the pack need not synchronise
+static int put_cutoffs(hg_ctx* c, const int64_t* host_ks, int nk) {
+    Cutoffs k{};
+    for (int j = 0; j < nk; ++j) k.v[j] = host_ks[j];
+    hipLaunchKernelGGL(k_put_cutoffs, dim3(1), dim3(64), 0, c->stream, k, c->lm_tab.as<i64>(), nk);
+    return c->check_launch("k_put_cutoffs");
+}
+static int list_kind(hg_ctx* c, const char* who, int which) {
+    if (which != HG_LIST_GRADES && which != HG_LIST_VOTES) return fail(HG_ERR_ARG, "%s: which=%d (HG_LIST_GRADES or HG_LIST_VOTES)", who, which);
+    if (c->C > GR_MAX_C) return fail(HG_ERR_ARG, "%s: C=%d classes (at most %d)", who, c->C, GR_MAX_C);
+    return HG_OK;
+}
+
 extern "C" {
 
 // The relevant-row histogram (hg_hist_rel.hpp): one pass over the pairs leaves all[d][q] (rows at distance d) and rel[d][q] (those
@@ -137,12 +158,14 @@ int hg_rel_hist(hg_ctx* c) {
 int hg_graded(hg_ctx* c, const int64_t* host_ks, int nk, const double* host_gain, const double* host_disc, int keep_grades) {
     HG_TRY(need(c, ST_DB | ST_Q, "hg_graded", "hg_set_database + hg_set_queries"));
     c->gr.begin();
-    HG_TRY(whole_database(c, "hg_graded", "graded sums need the whole database in one context (lists of a shard are partial)"));
-    if (!(c->stage & ST_SELECT) || !(c->lists_valid || c->real_lists))
+    // a shard: the merged grade plane of the whole database's lists (hg_merge_list_table) stands in for the gather through out_idx
+    const bool plane_fed = is_shard(c) && c->mlg.current(c);
+    if (!plane_fed) HG_TRY(whole_database(c, "hg_graded", "graded sums need the whole database in one context (lists of a shard are partial)"));
+    if (!plane_fed && (!(c->stage & ST_SELECT) || !(c->lists_valid || c->real_lists)))
         return fail(HG_ERR_STATE, "hg_graded: no ranked lists on the device (hg_map and hg_map_real write none): call hg_topr / hg_topr_real first");
     if (c->C > GR_MAX_C) return fail(HG_ERR_ARG, "hg_graded: C=%d classes (a grade is a byte: at most %d)", c->C, GR_MAX_C);
     if (!host_gain || !host_disc) return fail(HG_ERR_ARG, "hg_graded: null pointer");
-    const i64 Q = c->geo.Q, R = c->geo.R;
+    const i64 Q = plane_fed ? c->mlg.Q : c->geo.Q, R = plane_fed ? c->mlg.dim : c->geo.R;
     HG_TRY(check_cutoffs("hg_graded", "ks", host_ks, nk, GR_MAX_K, R, "R"));
     const i64 kmax = host_ks[nk - 1];
     const size_t o_gain = GR_MAX_K * 8, o_disc = o_gain + (size_t)(c->C + 1) * 8, tab = o_disc + (size_t)kmax * 8;
@@ -164,8 +187,10 @@ int hg_graded(hg_ctx* c, const int64_t* host_ks, int nk, const double* host_gain
     a.grades = keep_grades ? c->gr_grades.as<u8>() : nullptr;
     a.R = R; a.N = c->N; a.nk = nk; a.LW = c->LW;
     a.lastmask = lastmask(c->C);
+    a.plane = plane_fed ? c->lm_grades.as<u8>() : nullptr; a.Rp = plane_fed ? c->mlg.Qpad : 0;
     c->t_begin(KI_GRADED);
-    hipLaunchKernelGGL(k_graded, dim3((unsigned)Q), dim3(GR_THREADS), 0, c->stream, a);
+    if (plane_fed) hipLaunchKernelGGL(k_graded<true>, dim3((unsigned)Q), dim3(GR_THREADS), 0, c->stream, a);
+    else hipLaunchKernelGGL(k_graded<false>, dim3((unsigned)Q), dim3(GR_THREADS), 0, c->stream, a);
     c->t_end();
     HG_TRY(c->check_launch("k_graded"));
     HG_TRY(c->sync());                                 // (the host tables are the caller's)
@@ -349,12 +374,16 @@ int hg_ap_at(hg_ctx* c, const int64_t* host_Rs, int nR) {
 int hg_votes(hg_ctx* c, const int64_t* host_ks, int nk) {
     HG_TRY(need(c, ST_DB | ST_Q, "hg_votes", "hg_set_database + hg_set_queries"));
     c->vt.begin();
-    HG_TRY(whole_database(c, "hg_votes", "class votes need the whole database in one context (lists of a shard are partial)"));
-    if (!(c->stage & ST_SELECT) || !(c->lists_valid || c->real_lists))
+    // a shard: the merged vote counts of the whole database's lists (hg_merge_list_table) stand in for the walk along out_idx
+    const bool merged_fed = is_shard(c) && c->mlv.current(c);
+    if (!merged_fed) HG_TRY(whole_database(c, "hg_votes", "class votes need the whole database in one context (lists of a shard are partial)"));
+    if (!merged_fed && (!(c->stage & ST_SELECT) || !(c->lists_valid || c->real_lists)))
         return fail(HG_ERR_STATE, "hg_votes: no ranked lists on the device (hg_map and hg_map_real write none): call hg_topr / hg_topr_real first");
     if (c->C > VT_MAX_C) return fail(HG_ERR_ARG, "hg_votes: C=%d classes (at most %d)", c->C, VT_MAX_C);
-    const i64 Q = c->geo.Q, R = c->geo.R;
+    const i64 Q = merged_fed ? c->mlv.Q : c->geo.Q, R = c->geo.R;
     HG_TRY(check_cutoffs("hg_votes", "ks", host_ks, nk, VT_MAX_K, R, "R"));
+    if (merged_fed && (nk != (int)c->mlv.dim || memcmp(host_ks, c->mlv_ks, (size_t)nk * 8)))
+        return fail(HG_ERR_ARG, "hg_votes: on a shard ks must be the %d cut-offs the vote tables were merged at (hg_merge_list_table)", (int)c->mlv.dim);
     const size_t n = (size_t)Q * nk, conf_bytes = (size_t)nk * c->C * c->C * 8;
     const FirstReservations first;
     HG_TRY(c->vt_tab.reserve(VT_MAX_K * 8));
@@ -369,14 +398,25 @@ int hg_votes(hg_ctx* c, const int64_t* host_ks, int nk) {
     a.votes = c->vt_votes.as<u32>(); a.pred = c->vt_pred.as<int>(); a.top = c->vt_pred.as<u32>() + n;
     a.R = R; a.N = c->N; a.nk = nk; a.LW = c->LW; a.C = c->C;
     a.lastmask = lastmask(c->C);
-    c->t_begin(KI_VOTES);
+    a.idx_base = 0; a.Qpad = 0;
+    if (merged_fed) {
+        HG_HIP(hipMemcpyAsync(c->vt_votes.p, c->lm_votes.p, n * c->C * 4, hipMemcpyDeviceToDevice, c->stream));
+        VotePickArgs k;
+        k.votes = a.votes; k.pred = a.pred; k.top = a.top; k.n = (i64)n; k.C = c->C;
+        c->t_begin(KI_VOTE_PICK);
+        if (n > 0) hipLaunchKernelGGL(k_vote_pick, dim3(grid_for((i64)n, 4)), dim3(256), 0, c->stream, k);
+        c->t_end();
+        HG_TRY(c->check_launch("k_vote_pick"));
+    } else {
+        c->t_begin(KI_VOTES);
 #if HG_PROBES
-    if (c->opt.probe_votes) hipLaunchKernelGGL(k_votes<true>, dim3((unsigned)Q), dim3(VT_THREADS), 0, c->stream, a);
-    else
+        if (c->opt.probe_votes) hipLaunchKernelGGL(k_votes<true>, dim3((unsigned)Q), dim3(VT_THREADS), 0, c->stream, a);
+        else
 #endif
-    hipLaunchKernelGGL(k_votes<false>, dim3((unsigned)Q), dim3(VT_THREADS), 0, c->stream, a);
-    c->t_end();
-    HG_TRY(c->check_launch("k_votes"));
+        hipLaunchKernelGGL(k_votes<false>, dim3((unsigned)Q), dim3(VT_THREADS), 0, c->stream, a);
+        c->t_end();
+        HG_TRY(c->check_launch("k_votes"));
+    }
     ConfArgs f;
     f.votes = a.votes; f.qlab = c->qlab.as<u64>(); f.conf = c->vt_conf.as<unsigned long long>();
     f.Q = Q; f.nk = nk; f.LW = c->LW; f.C = c->C;
@@ -456,6 +496,124 @@ int hg_merge_side_table(hg_ctx* c, int which, const void* dev_tabs_all, int Gsh,
                     "a shard's block is missing, counted twice or stale; %d blocks)", t.name, flag[1], (long long)c->n_total, Gsh);
     if (which == HG_SIDE_JOINT) c->mjh_G = t.Gc;
     t.merged->finish(c, g.Q, g.Qpad, t.dim);
+    return HG_OK;
+}
+
+// This shard's part of the whole database's ranked lists as one block in the exchange layout (hg_list_merge.hpp): the grade plane
+// u8 [Q][Rp] + u32 own[Qpad], or the vote table u32 [nk][C + 1][Qpad] at the cut-offs `host_ks`.  Needs the lists of the exact staged
+// sequence -- global indices in global rank positions.  The block is the context's (lm_pack) and holds until the next pack.
+int hg_pack_list_table(hg_ctx* c, int which, const int64_t* host_ks, int nk, void** dev_ptr, int64_t* nbytes) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_pack_list_table", "hg_set_database + hg_set_queries"));
+    if (!dev_ptr || !nbytes) return fail(HG_ERR_ARG, "hg_pack_list_table: null pointer");
+    HG_TRY(list_kind(c, "hg_pack_list_table", which));
+    if (c->real_lists)
+        return fail(HG_ERR_STATE, "hg_pack_list_table: the ranked lists are real-valued (hg_topr_real): that ranking splits the queries, every rank holds the whole table");
+    if (c->ranked_local)
+        return fail(HG_ERR_STATE, "hg_pack_list_table: the last ranking is in this shard's local rank order (hg_select_ranked): rank with hg_plan + hg_select (\"staged_lists\")");
+    if (!(c->stage & ST_SELECT) || !c->lists_valid)
+        return fail(HG_ERR_STATE, "hg_pack_list_table: no ranked lists in global rank positions on the device: rank with hg_plan + hg_select (\"staged_lists\") or hg_topr first");
+    const ListGeo L = list_geometry(c);
+    if (which == HG_LIST_VOTES) HG_TRY(check_cutoffs("hg_pack_list_table", "ks", host_ks, nk, VT_MAX_K, L.R, "R"));
+    const size_t plane = (size_t)L.Q * L.Rp;
+    const size_t bytes = which == HG_LIST_GRADES ? plane + (size_t)L.Qpad * 4 : (size_t)nk * (c->C + 1) * L.Qpad * 4;
+    const FirstReservations first;
+    HG_TRY(c->lm_pack.reserve(bytes));
+    if (which == HG_LIST_VOTES) HG_TRY(c->lm_tab.reserve(VT_MAX_K * 8));
+    first.keep(c);
+    if (which == HG_LIST_GRADES) {
+        HG_HIP(hipMemsetAsync(c->lm_pack.as<char>() + plane, 0, (size_t)L.Qpad * 4, c->stream));      // (own of the pad queries)
+        ListGradesArgs a;
+        a.idx = c->out_idx.as<u32>(); a.dblab = c->dblab.as<u64>(); a.qlab = c->qlab.as<u64>();
+        a.plane = c->lm_pack.as<u8>(); a.own = (u32*)(c->lm_pack.as<char>() + plane);
+        a.R = L.R; a.Rp = L.Rp; a.N = c->N; a.idx_base = c->idx_base; a.LW = c->LW;
+        a.lastmask = lastmask(c->C);
+        c->t_begin(KI_LIST_GRADES);
+        if (L.Q > 0) hipLaunchKernelGGL(k_list_grades, dim3((unsigned)L.Q), dim3(LG_THREADS), 0, c->stream, a);
+        c->t_end();
+        HG_TRY(c->check_launch("k_list_grades"));
+    } else {
+        HG_TRY(put_cutoffs(c, host_ks, nk));
+        HG_HIP(hipMemsetAsync(c->lm_pack.p, 0, bytes, c->stream));                                     // (the pad columns)
+        VotesArgs a;
+        a.idx = c->out_idx.as<u32>(); a.dblab = c->dblab.as<u64>(); a.ks = c->lm_tab.as<i64>();
+        a.votes = c->lm_pack.as<u32>(); a.pred = nullptr; a.top = nullptr;
+        a.R = L.R; a.N = c->N; a.nk = nk; a.LW = c->LW; a.C = c->C;
+        a.lastmask = lastmask(c->C);
+        a.idx_base = c->idx_base; a.Qpad = L.Qpad;
+        c->t_begin(KI_VOTES);
+        if (L.Q > 0) hipLaunchKernelGGL((k_votes<false, true>), dim3((unsigned)L.Q), dim3(VT_THREADS), 0, c->stream, a);
+        c->t_end();
+        HG_TRY(c->check_launch("k_votes"));
+    }
+    *dev_ptr = c->lm_pack.p;
+    *nbytes = (int64_t)bytes;
+    return c->stage_end();
+}
+
+// The Gsh gathered blocks of kind `which` merged into the grade plane / the vote counts of the whole database's lists, with the
+// checks of hg_list_merge.hpp; the flag words are read before the call returns (it synchronises whatever "stage_sync" says).
+int hg_merge_list_table(hg_ctx* c, int which, const void* dev_blocks_all, int Gsh, const int64_t* host_ks, int nk) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_merge_list_table", "hg_set_database + hg_set_queries"));
+    if (which == HG_LIST_GRADES) c->mlg.begin();
+    else if (which == HG_LIST_VOTES) c->mlv.begin();
+    HG_TRY(list_kind(c, "hg_merge_list_table", which));
+    if (!dev_blocks_all || ((uintptr_t)dev_blocks_all & 15)) return fail(HG_ERR_ARG, "hg_merge_list_table: dev_blocks_all must be a 16-byte aligned device address");
+    if (Gsh < 1 || Gsh > 4096) return fail(HG_ERR_ARG, "hg_merge_list_table: %d shards (1..4096)", Gsh);
+    if (!(c->stage & ST_SELECT) || c->ranked_local || c->real_lists)
+        return fail(HG_ERR_STATE, "hg_merge_list_table: no ranking whose lists the blocks could belong to: rank with hg_plan + hg_select or hg_topr first");
+    const ListGeo L = list_geometry(c);
+    if (which == HG_LIST_VOTES) HG_TRY(check_cutoffs("hg_merge_list_table", "ks", host_ks, nk, VT_MAX_K, L.R, "R"));
+    const bool grades = which == HG_LIST_GRADES;
+    const size_t out_bytes = grades ? (size_t)L.Q * L.Rp : (size_t)L.Q * nk * c->C * 4;
+    const FirstReservations first;
+    HG_TRY(c->lm_flag.reserve(16));
+    HG_TRY((grades ? c->lm_grades : c->lm_votes).reserve(out_bytes > 0 ? out_bytes : 1));
+    if (!grades) HG_TRY(c->lm_tab.reserve(VT_MAX_K * 8));
+    first.keep(c);
+    u32 flag[4] = {0u, LIST_NO_QUERY, LIST_NO_QUERY, LIST_NO_QUERY};
+    if (L.Q > 0) {
+        HG_HIP(hipMemsetAsync(c->lm_flag.p, 0, 4, c->stream));
+        HG_HIP(hipMemsetAsync(c->lm_flag.as<char>() + 4, 0xFF, 12, c->stream));
+        if (grades) {
+            ListMergeGradesArgs a;
+            a.blocks = (const u8*)dev_blocks_all; a.dst = c->lm_grades.as<u8>(); a.flag = c->lm_flag.as<u32>();
+            a.Q = L.Q; a.Qpad = L.Qpad; a.R = L.R; a.Rp = L.Rp; a.Gsh = Gsh; a.C = c->C;
+            c->t_begin(KI_LIST_MERGE_GRADES);
+            hipLaunchKernelGGL(k_list_merge_grades, dim3(grid_for(L.Q * (L.Rp >> 4) + L.Q)), dim3(256), 0, c->stream, a);
+            c->t_end();
+            HG_TRY(c->check_launch("k_list_merge_grades"));
+        } else {
+            HG_TRY(put_cutoffs(c, host_ks, nk));
+            ListMergeVotesArgs a;
+            a.tabs = (const u32*)dev_blocks_all; a.dst = c->lm_votes.as<u32>(); a.flag = c->lm_flag.as<u32>(); a.ks = c->lm_tab.as<i64>();
+            a.Q = L.Q; a.Qpad = L.Qpad; a.nk = nk; a.C = c->C; a.Gsh = Gsh;
+            c->t_begin(KI_LIST_MERGE_VOTES);
+            hipLaunchKernelGGL(k_list_merge_votes, dim3((unsigned)(L.Qpad / 64)), dim3(SM_THREADS), 0, c->stream, a);
+            c->t_end();
+            HG_TRY(c->check_launch("k_list_merge_votes"));
+        }
+        HG_HIP(hipMemcpyAsync(flag, c->lm_flag.p, 16, hipMemcpyDeviceToHost, c->stream));
+    }
+    HG_TRY(c->sync());                                 // (the flag words decide the call)
+    const char* const kind = grades ? "grade plane" : "vote table";
+    if (grades) {
+        if (flag[0] & 1u)
+            return fail(HG_ERR_STATE, "hg_merge_list_table: the blocks' owned slots of query %u do not add up to R = %lld (owned-slots flag: a shard's block is missing, "
+                        "counted twice, zeroed or stale; %d blocks)", flag[1], (long long)L.R, Gsh);
+        if (flag[0] & 2u)
+            return fail(HG_ERR_STATE, "hg_merge_list_table: a slot of query %u is non-zero in two blocks of the %s (slot-claimed-twice flag; %d blocks)", flag[2], kind, Gsh);
+        if (flag[0] & 4u)
+            return fail(HG_ERR_STATE, "hg_merge_list_table: a grade of query %u in the %s exceeds C = %d (grade-range flag; %d blocks)", flag[3], kind, c->C, Gsh);
+        c->mlg.finish(c, L.Q, L.Rp, L.R);
+    } else {
+        if (flag[0] & 2u)
+            return fail(HG_ERR_STATE, "hg_merge_list_table: the blocks' owned slots of query %u do not add up to a cut-off (owned-slots flag: a shard's block is missing, "
+                        "counted twice, zeroed or stale; %d blocks)", flag[2], Gsh);
+        if (flag[0] & 1u)
+            return fail(HG_ERR_STATE, "hg_merge_list_table: a cell of query %u in the merged %s does not fit 32 bits (overflow flag; %d blocks)", flag[1], kind, Gsh);
+        memcpy(c->mlv_ks, host_ks, (size_t)nk * 8);
+        c->mlv.finish(c, L.Q, L.Q, nk);
+    }
     return HG_OK;
 }
 

@@ -23,6 +23,7 @@
 // class are latency a wavefront with three neighbours on its SIMD cannot hide, while the adds leave the lane at once.  With every row
 // of a chunk in one class -- 64 adds on one address, the adds' worst case -- the ballots win at the CIFAR evaluation, but that worst
 // case is still faster than the ballots are on ordinary labels there.
+// On a shard's partial lists the same walk writes the shard's vote table for the exchange (OWN = true, below; hg_list_merge.hpp).
 // An index >= N (IDX_NONE included) votes for nothing and is never followed; bits past class C - 1 of the last label word are masked
 // off before anything is counted, so they never index a counter.
 //
@@ -52,6 +53,7 @@ struct VotesArgs {
     i64 R, N;
     int nk, LW, C;
     u64 lastmask;                      // the classes of the last label word
+    u32 idx_base; i64 Qpad;            // OWN: the first row of this shard's table; the pitch of the vote table's planes
 };
 
 __device__ __forceinline__ u64 wave_or_u64(u64 v) {
@@ -89,8 +91,13 @@ __device__ __forceinline__ VtChunk vt_next(const i64* ks, const int nk, const Vt
 
 // BALLOT: the form without LDS atomics (above; measurement build only) -- sacc holds a row of counters per wavefront instead of row 0 for
 // the block, written from the accumulator registers at a cut-off.
-template <bool BALLOT>
+// OWN: the pass on a shard's lists for the exchange (hg_list_merge.hpp) -- idx holds global row indices in global rank positions and
+// IDX_NONE where a slot is another shard's; a rank counts when idx - idx_base is a row of this table, the slots that count are counted
+// themselves in counter C (one ballot per wavefront and chunk), and the C + 1 counters of a cut-off go to the vote table's planes
+// votes[j][c][q] (pitch Qpad) instead of votes[q][j][c].  No prediction: that is the merged counts' (k_vote_pick).
+template <bool BALLOT, bool OWN = false>
 __global__ __launch_bounds__(VT_THREADS) void k_votes(const VotesArgs a) {
+    static_assert(!(BALLOT && OWN), "the measurement form counts whole lists only");
     __shared__ u32 sacc[VT_THREADS / 64][VT_WORDS * 64];
     __shared__ u64 skey[VT_THREADS / 64];
     __shared__ i64 ks[VT_MAX_K];
@@ -107,19 +114,25 @@ __global__ __launch_bounds__(VT_THREADS) void k_votes(const VotesArgs a) {
         const i64 i = c.pos + tid;
         return i < c.end ? idx[i] : IDX_NONE;
     };
-    const auto load_words = [&](const u32 gi, u64 (&m)[VT_WORDS]) {
-        const bool row = (i64)gi < a.N;                    // (IDX_NONE -- a lane past the chunk's end too -- included: N < 2^32 - 1)
-        const u64* __restrict__ dl = a.dblab + (i64)(row ? gi : 0u) * a.LW;
+    const auto load_words = [&](const u32 gi, u64 (&m)[VT_WORDS]) -> bool {
+        const u32 li = OWN ? gi - a.idx_base : gi;
+        const bool row = (i64)li < a.N && (!OWN || gi != IDX_NONE);      // (IDX_NONE -- a lane past the chunk's end too -- included: N < 2^32 - 1)
+        const u64* __restrict__ dl = a.dblab + (i64)(row ? li : 0u) * a.LW;
 #pragma unroll
         for (int w = 0; w < VT_WORDS; ++w) m[w] = row && w < a.LW ? dl[w] : 0ull;
+        return row;
     };
     VtChunk cur = vt_chunk(ks, a.nk, 0, 0), nxt = vt_next(ks, a.nk, cur);
     u64 m[VT_WORDS], mn[VT_WORDS];
-    load_words(load_idx(cur), m);
+    bool own = load_words(load_idx(cur), m);
     u32 gin = load_idx(nxt);
     while (cur.j < a.nk) {
         const int j = cur.j;
-        load_words(gin, mn);
+        const bool own_n = load_words(gin, mn);
+        if constexpr (OWN) {
+            const u32 n = (u32)__popcll(__ballot(own));
+            if (lane == 0 && n) atomicAdd(&sacc[0][a.C], n);         // (C <= 255: counter C is no class's)
+        }
         const VtChunk nn = vt_next(ks, a.nk, nxt);
         gin = load_idx(nn);
 #pragma unroll
@@ -148,16 +161,17 @@ __global__ __launch_bounds__(VT_THREADS) void k_votes(const VotesArgs a) {
             }
             __syncthreads();
             u32 tot = 0;
-            if (tid < a.C) {
+            if (tid < a.C + (OWN ? 1 : 0)) {
 #pragma unroll
                 for (int v = 0; v < (BALLOT ? VT_THREADS / 64 : 1); ++v) tot += sacc[v][tid];
-                a.votes[((i64)q * a.nk + j) * a.C + tid] = tot;
+                if constexpr (OWN) a.votes[((i64)j * (a.C + 1) + tid) * a.Qpad + q] = tot;
+                else a.votes[((i64)q * a.nk + j) * a.C + tid] = tot;
             }
             // the largest count, the smallest class among equals: max of (count, 255 - class)
-            const u64 key = wave_max_u64(tid < a.C ? (u64)tot << 8 | (u64)(255 - tid) : 0ull);
+            const u64 key = OWN ? 0ull : wave_max_u64(tid < a.C ? (u64)tot << 8 | (u64)(255 - tid) : 0ull);
             if (lane == 0) skey[wave] = key;
             __syncthreads();               // (sacc is written again only after this barrier, skey only after the next cut-off's first one)
-            if (tid == 0) {
+            if (tid == 0 && !OWN) {
                 u64 best = skey[0];
 #pragma unroll
                 for (int v = 1; v < VT_THREADS / 64; ++v) best = skey[v] > best ? skey[v] : best;
@@ -168,6 +182,7 @@ __global__ __launch_bounds__(VT_THREADS) void k_votes(const VotesArgs a) {
         }
 #pragma unroll
         for (int w = 0; w < VT_WORDS; ++w) m[w] = mn[w];
+        own = own_n;
         cur = nxt; nxt = nn;
     }
 }

@@ -23,6 +23,12 @@ IDCG -- need no ranking at all: each shard's histogram table is additive, so one
 device (hg_pack_side_table / hg_merge_side_table) give every rank the whole database's table, and the `*_shard` functions below
 return what their extra_metrics namesakes return on one context, bit for bit.
 
+The list-based side metrics -- ACG / NDCG / WAP at k by database index, kNN votes and the confusion matrix, mAP at many k -- need
+the ranked lists, and a shard's are partial.  The exact staged sequence with lists leaves a shard's rows in their global rank
+positions, so every slot has one owner: the grade of each own slot (one byte) and the per-class counts of the own slots at the cut-offs
+are all-gathered and merged on the device (hg_pack_list_table / hg_merge_list_table), and hg_graded / hg_votes / hg_ap_at then run on
+every rank from the merged tables -- `rank_lists_shard`, `map_at_k_shard`, `graded_relevance_at_k_shard`, `knn_vote_at_k_shard` below.
+
 `gather_topr` additionally all-gathers the ranked (idx, dist) lists themselves
 (the exchange BASELINE.json's north star names, hg_allgather_topr) for callers
 that want them.
@@ -665,6 +671,88 @@ def tie_aware_graded_at_k_shard(ctx, comm, ks, gain="exp"):
     disc = extra_metrics.discount_table(ks[-1])
     joint = distance_grade_histograms_shard(ctx, comm)
     return extra_metrics.tie_graded_from_tables(joint, ks, tab[:joint.shape[2]], disc)
+
+
+# ------------------------------------------------------------------ list-based side metrics on a shard
+# The exact staged sequence with lists leaves a shard's members of the global top R in their global rank positions, so every slot of a
+# query's list belongs to exactly one shard: the grades of a shard's own slots (one byte each) and its per-class counts at the cut-offs
+# are exchanged (hg_pack_list_table, comm.all_gather, hg_merge_list_table), and hg_graded / hg_votes then run on every rank from the
+# merged tables with the bits one context with the whole database gives.  The bets and the owner-routed exchanges are not used here.
+def rank_lists_shard(ctx, comm, R):
+    """The exact staged sequence with the ranked lists kept (histograms gathered, hg_plan, hg_select with "staged_lists", match bits
+    gathered, hg_merge_match, hg_ap) -> (ap, rel) as evaluate_shard returns them.  Afterwards the context holds this shard's lists in
+    global rank positions and the merged match bitmap: what merge_list_table and Context.ap_at need.  The context's "staged_lists"
+    option is left as it was set through Context.set_option (the library's default, 1, if it never was)."""
+    _check_shard(ctx)
+    _check_binary(ctx)
+    before = ctx.option_values.get("staged_lists", 1)
+    touched = "staged_lists" in ctx.options_touched
+    try:
+        engine = HipShardEngine(ctx, want_lists=True)
+        return _evaluate_shard(engine, comm, int(R), False, False, False, False)
+    finally:
+        ctx.set_option("staged_lists", before)
+        if not touched:
+            ctx.options_touched.discard("staged_lists")
+            ctx.option_values.pop("staged_lists", None)
+
+
+def merge_list_table(ctx, comm, which, ks=None):
+    """This shard's part of the ranked lists rank_lists_shard left -- which = "grades": the grade of every own slot, "votes": the class
+    counts of the own slots at the cut-offs ks -- packed, all-gathered and merged into the context's table of the whole database's lists
+    (hg_pack_list_table, comm.all_gather, hg_merge_list_table: nothing leaves the device).  Blocks that fail the merge's checks raise on
+    every rank alike (the gathered data are the same)."""
+    ptr, nbytes = ctx.pack_list_table(which, ks)
+    gathered = comm.all_gather(DevBuf(ptr, nbytes))
+    ctx.merge_list_table(which, gathered.ptr, comm.world, ks)
+
+
+def map_at_k_shard(ctx, comm, ks):
+    """extra_metrics.map_at_k of the whole database at the cut-offs ks (1..n_total) -> map_from_ap_tables' dict"""
+    _check_shard(ctx)
+    ks = extra_metrics._check_ks(ks, ctx.n_total)
+    _check_binary(ctx)
+    rank_lists_shard(ctx, comm, int(ks[-1]))
+    ap, hits = [], []
+    for i in range(0, len(ks), extra_metrics.MAX_CUTOFFS):
+        ctx.ap_at(ks[i:i + extra_metrics.MAX_CUTOFFS])               # (k_ap_at on the merged bitmap)
+        a, h = ctx.get_ap_at()
+        ap.append(a)
+        hits.append(h)
+    total_rel = lookup_histograms_shard(ctx, comm)[1].sum(1)
+    return extra_metrics.map_from_ap_tables(np.concatenate(ap, axis=1), np.concatenate(hits, axis=1), total_rel, ks)
+
+
+def graded_relevance_at_k_shard(ctx, comm, ks, gain="exp"):
+    """extra_metrics.graded_relevance_at_k of the whole database at the cut-offs ks (1..n_total) -> graded_from_tables' dict"""
+    _check_graded_shard(ctx)
+    ks = extra_metrics._check_ks(ks, ctx.n_total)
+    tab = extra_metrics.gain_table(gain, ctx.C)
+    disc = extra_metrics.discount_table(ks[-1])
+    rank_lists_shard(ctx, comm, int(ks[-1]))
+    merge_list_table(ctx, comm, "grades")
+    ctx.graded(ks, tab, disc)                           # (k_graded on the merged grade plane)
+    gsum, hits, dcg, wsum = ctx.get_graded()
+    hist = grade_histograms_shard(ctx, comm)
+    return extra_metrics.graded_from_tables(gsum, hits, dcg, wsum, hist, ks, tab, disc)
+
+
+def knn_vote_at_k_shard(ctx, comm, ks, q_labels):
+    """extra_metrics.knn_vote_at_k of the whole database at the cut-offs ks (1..n_total) -> knn_from_tables' dict.  q_labels [Q, C]: the
+    {0,1} labels of the queries the caller loaded into the context -- the context keeps them packed on the device and hands none back,
+    and knn_from_tables scores the predictions against them on the host."""
+    _check_shard(ctx)
+    if ctx.C > extra_metrics.MAX_CLASSES:
+        raise ValueError("class votes take up to %d classes (have %d)" % (extra_metrics.MAX_CLASSES, ctx.C))
+    ks = extra_metrics._check_ks(ks, ctx.n_total)
+    q_labels = np.asarray(q_labels)
+    if q_labels.shape != (ctx.Q, ctx.C):
+        raise ValueError("q_labels must be the [Q, C] = [%d, %d] labels of the loaded queries" % (ctx.Q, ctx.C))
+    _check_binary(ctx)
+    rank_lists_shard(ctx, comm, int(ks[-1]))
+    merge_list_table(ctx, comm, "votes", ks)
+    ctx.votes(ks)                                       # (k_vote_pick and k_vote_confusion on the merged counts)
+    return extra_metrics.knn_from_tables(ctx.get_vote_pred()[0], ctx.get_vote_confusion(), q_labels, ks)
 
 
 def shard_bounds(n_total, world):

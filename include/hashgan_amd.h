@@ -358,7 +358,9 @@ int hg_export(hg_ctx* ctx, const hg_export_item* items, int n);     /* 1 <= n <=
  *   gsum = sum_{i<=k} g_i,  hits = #{i<=k : g_i > 0},  dcg = sum_{i<=k} gain[g_i] * disc[i-1],  wsum = sum_{i<=k, g_i>0} (sum_{m<=i} g_m) / i
  * ks: nk (1..64) strictly ascending values in 1..R of the lists; gain: C + 1 doubles; disc: ks[nk-1] doubles (disc[i-1] belongs to rank i);
  * C <= 255; anything else HG_ERR_ARG.  The host arrays are copied before the call returns.  Indices outside the table count as grade 0.
- * The context must hold the whole database (idx_base 0, N = n_total; HG_ERR_STATE otherwise).  The summation order depends on ks
+ * The context must hold the whole database (idx_base 0, N = n_total) -- or a shard of it together with a current merged grade plane
+ * (hg_merge_list_table, below): the same kernel then reads the grade of every rank from the plane; HG_ERR_STATE on a shard without one.
+ * The summation order depends on ks
  * alone (chunks of 256 ranks cut at every k, fixed trees inside), so equal inputs give equal bits; float64 throughout, no atomics.
  * keep_grades != 0 also keeps the grade bytes of every rank for hg_get_grades.  The results belong to the lists they were computed on:
  * any later ranking, hg_merge_topr, a database or query reload and hg_trim invalidate them (the getters then return HG_ERR_STATE, as
@@ -406,7 +408,9 @@ int hg_get_ap_at(hg_ctx* ctx, double* host_ap, int64_t* host_rel);   /* [Q][nR] 
 /* ---- class votes along the ranked lists (kNN accuracy, retrieval confusion matrix) ------------------------------------------------
  * "Which classes did the query retrieve?"  hg_votes walks the ranked index lists the last ranking left on the device -- hg_graded's
  * precondition: hg_topr, a staged hg_select with lists, hg_topr_real, hg_topr_rerank; HG_ERR_STATE after anything that writes none
- * (hg_map, hg_map_real) and on a context that holds a shard (idx_base != 0 or N != n_total) -- and leaves, per query q, cut-off
+ * (hg_map, hg_map_real) and on a context that holds a shard (idx_base != 0 or N != n_total) without a current merged vote table
+ * (hg_merge_list_table, below; with one, pred / top come from k_vote_pick and conf from k_vote_confusion on the merged counts, and ks
+ * must be the merge's) -- and leaves, per query q, cut-off
  * k = ks[j] and class c:
  *   votes[q][j][c] = #{ranks i < k whose row idx[q][i] carries label c}                   uint32 [Q][nk][C]
  *   top[q][j]      = max_c votes[q][j][c];   pred[q][j] = the smallest c that reaches it, -1 when top is 0   [Q][nk]
@@ -457,6 +461,43 @@ int hg_merge_side_table(hg_ctx* ctx, int which, const void* dev_tabs_all, int Gs
 int hg_get_merged_rel_hist(hg_ctx* ctx, uint32_t* host_all, uint32_t* host_rel);   /* [b+1][Q] each, the whole database; null: skipped */
 int hg_get_merged_grade_hist(hg_ctx* ctx, uint32_t* host_hist);                    /* [C+1][Q] */
 int hg_get_merged_joint_hist(hg_ctx* ctx, uint32_t* host_hist);                    /* [b+1][Gc][Q] */
+
+/* ---- the list-based side metrics of a database-sharded context: pack, exchange, merge ------------------------------------------
+ * hg_graded and hg_votes walk the ranked lists, and a shard's lists are partial.  The exact staged sequence (hg_hist -> hg_plan ->
+ * hg_select with "staged_lists" = 1) leaves a shard's members of the global top R in their GLOBAL rank positions -- the global row
+ * index where slot i is the shard's, IDX_NONE where it is another's --, so every slot belongs to exactly one shard and two small
+ * tables per shard carry everything the two passes need:
+ *   HG_LIST_GRADES  uint8 [Q][Rp] then uint32 own[Qpad]   Rp = R rounded up to 16, Qpad = Q rounded up to 64.  Byte i of row q: the
+ *                   labels query q shares with the shard's own row in slot i; 0 where the slot is another shard's and for i >= R.
+ *                   own[q]: the slots i < R of query q that are this shard's.  Q Rp + 4 Qpad bytes.
+ *   HG_LIST_VOTES   uint32 [nk][C+1][Qpad], q fastest.  Plane (j, c), c < C: the shard's own slots i < ks[j] whose row carries class
+ *                   c; plane (j, C): the shard's own slots i < ks[j].  4 nk (C+1) Qpad bytes.
+ *   ranking  ->  hg_pack_list_table  ->  all-gather of the block (hg_allgather, or the caller's)  ->  hg_merge_list_table  ->  hg_graded / hg_votes
+ * hg_pack_list_table: needs position-space lists of the loaded tables -- a staged hg_select with lists, or hg_topr on a context that
+ *   holds the whole database (one block, Gsh = 1); HG_ERR_STATE before such a ranking, after hg_select_ranked (local rank order) and on
+ *   real-valued lists.  At most 255 classes (HG_ERR_ARG).  Grades: ks is ignored and may be NULL (the plane covers all R slots).  Votes:
+ *   ks as hg_votes takes them -- nk (1..64) strictly ascending values in 1..R, else HG_ERR_ARG.  *dev_ptr / *nbytes: the block, owned by
+ *   the context, valid until the next hg_pack_list_table, a reload or hg_trim.  One kernel (k_list_grades, or k_votes in its
+ *   owned-slots form); ends like a staged call (synchronises unless "stage_sync" is 0).  Changes no result.
+ * hg_merge_list_table: dev_blocks_all = Gsh (1..4096) such blocks back to back, 16-byte aligned; ks / nk as packed (ignored for
+ *   grades).  NULL, Gsh out of range, a misaligned address or an unknown `which`: HG_ERR_ARG.  One kernel merges them into a table of
+ *   the context's own -- k_list_merge_grades ORs the planes, k_list_merge_votes sums the tables in 64 bits -- and checks every query
+ *   q < Q: grades -- the own words sum to R (owned-slots flag), no byte i < R is non-zero in two blocks (slot-claimed-twice flag), no
+ *   byte exceeds C (grade-range flag: the merged plane indexes hg_graded's gain table); votes -- plane (j, C) sums to ks[j]
+ *   (owned-slots flag), every cell fits uint32 (overflow flag).  A raised flag fails the call with HG_ERR_STATE and a message naming
+ *   the flag and the smallest offending query, and leaves no merged table of that kind; the flags are integer and independent of any
+ *   order; pad bytes and pad queries are never checked.  The host reads the flags: the call synchronises whatever "stage_sync" says.
+ * With a current merged grade plane hg_graded on a shard runs from it (the same kernel, its grade read from the plane: the bits one
+ * context gives; keep_grades copies the plane out); with a current merged vote table hg_votes on a shard picks the predictions
+ * (k_vote_pick) and builds the confusion matrix from it -- its ks must be the merge's, else HG_ERR_ARG.  Without one both refuse a
+ * shard as before.  The getters are hg_graded's and hg_votes'.  A context that holds the whole database never looks at a merged table.
+ * A merged list table belongs to the ranking and tables it was made from: a new ranking, hg_merge_topr, a reload of the queries or
+ * the database, hg_trim and a refused merge of its own kind end it; a side-table pass or merge, hg_ap_at and hg_tie_ap do not.  Stage,
+ * geometry, lists, match bits, APs, the other side results and a step of hg_map_begin in flight are left as they were by both calls. */
+#define HG_LIST_GRADES 0
+#define HG_LIST_VOTES 1
+int hg_pack_list_table(hg_ctx* ctx, int which, const int64_t* host_ks, int nk, void** dev_ptr, int64_t* nbytes);
+int hg_merge_list_table(hg_ctx* ctx, int which, const void* dev_blocks_all, int Gsh, const int64_t* host_ks, int nk);
 
 /* ---- collectives: RCCL over xGMI, one process per GPU (the reference has no counterpart --
  * main.py:260-263 only sets CUDA_VISIBLE_DEVICES) --------------------------------------------------------
