@@ -77,6 +77,8 @@ _SIGNATURES = {
     "hg_map_real": [_p, _i64, _p, _p],
     "hg_topr_real": [_p, _i64],
     "hg_get_topr_real": [_p, _p, _p],
+    "hg_map_asym": [_p, _i64, _p, _p],
+    "hg_topr_asym": [_p, _i64],
     "hg_topr_rerank": [_p, _i64],
     "hg_map_rerank": [_p, _i64, _p, _p],
     "hg_get_rerank_scores": [_p, _p],
@@ -512,6 +514,26 @@ class Context:
     def topr_real(self, R, download=True):
         """download=False: the lists stay on the device (for graded())."""
         check(self._lib.hg_topr_real(self._h, int(R)))
+        self.R = int(R)
+        if not download:
+            return None
+        idx = np.empty((self.Q, self.R), dtype=np.uint32)
+        score = np.empty((self.Q, self.R), dtype=np.float32)
+        check(self._lib.hg_get_topr_real(self._h, _ptr(idx), _ptr(score)))
+        return idx, score
+
+    # -- asymmetric ranking: real-valued queries against the database's codes read as +-1 ------
+    def map_asym(self, R):
+        """(ap, rel) of hg_map_asym: needs the queries loaded under set_option("keep_query_floats", 1); any database loader."""
+        ap = np.empty(self.Q, dtype=np.float64)
+        rel = np.empty(self.Q, dtype=np.int64)
+        check(self._lib.hg_map_asym(self._h, int(R), _ptr(ap), _ptr(rel)))
+        self.R = int(R)
+        return ap, rel
+
+    def topr_asym(self, R, download=True):
+        """-> (idx, score) of hg_topr_asym through hg_get_topr_real; download=False: the lists stay on the device (graded(), votes(), export())."""
+        check(self._lib.hg_topr_asym(self._h, int(R)))
         self.R = int(R)
         if not download:
             return None

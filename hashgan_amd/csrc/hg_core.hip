@@ -29,7 +29,7 @@ const char* const kKernelNames[KI_COUNT] = {"k_hist", "k_hist_reduce", "k_plan",
                                             "k_hist_rel", "k_hist_rel_reduce", "k_graded", "k_grade_hist", "k_grade_hist_reduce", "k_tie_ap", "k_ap_at",
                                             "k_label_max", "k_hist_joint", "k_hist_joint_reduce",
                                             "k_rr_scan", "k_rr_collect", "k_rr_score", "k_rr_order", "k_export", "k_votes", "k_vote_confusion", "k_side_pack", "k_side_merge",
-                                            "k_list_grades", "k_list_merge_grades", "k_list_merge_votes", "k_vote_pick"};
+                                            "k_list_grades", "k_list_merge_grades", "k_list_merge_votes", "k_vote_pick", "k_asym_image16", "k_asym_rescore", "k_asym_expand_rows"};
 // Flatten NumPy's pairwise-summation tree for a chunk of n elements (n <= 8192):
 // numpy/_core/src/umath/loops_utils.h.src, pairwise_sum: n <= 128 is a leaf,
 // otherwise split at n/2 rounded down to a multiple of 8.
@@ -377,6 +377,7 @@ int hg_set_database(hg_ctx* c, const uint64_t* codes, const uint64_t* labels, in
     c->dbx3_valid = false;
     c->dbx4_valid = false;
     c->dbx8_valid = false;
+    c->asym.forget();
     c->bet_consecutive_fail = c->shard_bet_fail = 0;    // a new database: earlier lost bets say nothing about it
     c->cap_boost = c->real_cap_boost = 1;
     c->crowd_probed = false;
@@ -575,6 +576,7 @@ static void database_loaded(hg_ctx* c) {
     c->dbx8_valid = false;
     c->dbfx_valid = false;
     c->dbfb_valid = false;
+    c->asym.forget();
     c->bet_consecutive_fail = c->shard_bet_fail = 0;
     c->cap_boost = c->real_cap_boost = 1;
     c->crowd_probed = false;
@@ -641,9 +643,10 @@ int hg_set_queries_f32(hg_ctx* c, const float* host_x, const int64_t* host_label
     const bool had_q = (c->stage & ST_Q) != 0;
     c->Q = Q;
     if (c->opt.host_pack) {
-        // the query table is small: its floats follow whenever the database's are there (the inner-product ranking needs both)
+        // the query table is small: its floats follow whenever the database's are there (the inner-product ranking needs both) --
+        // or the caller asks for them (option keep_query_floats: the asymmetric ranking needs the queries' alone)
         const int saved_bpad = c->bpad;
-        HG_TRY(pack_on_host(c, host_x, host_labels, Q, c->qc, c->qlab, c->qf, c->dbf_resident ? 1 : 0, &c->qf_resident,
+        HG_TRY(pack_on_host(c, host_x, host_labels, Q, c->qc, c->qlab, c->qf, c->dbf_resident || c->opt.keep_query_floats ? 1 : 0, &c->qf_resident,
                             bad_codes, bad_labels, c->census_q));
         if (!c->qf_resident) c->bpad = saved_bpad;
     } else {
@@ -761,8 +764,8 @@ int hg_set_queries_dev(hg_ctx* c, const hg_dev_array* features, const hg_dev_arr
     const i64 old_q = c->Q;
     const bool had_q = (c->stage & ST_Q) != 0;
     c->Q = features->rows;
-    // the queries' floats follow the database's (the inner-product ranking needs both); without them c->bpad stays as it is
-    HG_TRY(pack_from_device(c, *features, *labels, c->qc, c->qlab, c->qf, c->dbf_resident ? 1 : 0, &c->qf_resident, bad_codes, bad_labels,
+    // the queries' floats follow the database's (the inner-product ranking needs both) or option keep_query_floats; without them c->bpad stays as it is
+    HG_TRY(pack_from_device(c, *features, *labels, c->qc, c->qlab, c->qf, c->dbf_resident || c->opt.keep_query_floats ? 1 : 0, &c->qf_resident, bad_codes, bad_labels,
                             c->census_q));
     queries_loaded(c, old_q, had_q);
     return HG_OK;
@@ -1207,6 +1210,7 @@ const OptionKey kOptionKeys[] = {
     ranged("timing_every", &Options::timing_every, 1, 1024, "timing_every must be 1..1024"),
     flag("host_pack", &Options::host_pack),
     ranged("keep_floats", &Options::keep_floats, 0, 2, "keep_floats must be 0, 1 or 2"),
+    ranged("keep_query_floats", &Options::keep_query_floats, 0, 1, "keep_query_floats must be 0 or 1"),
     ranged("real_mfma", &Options::real_mfma, 0, 2, "real_mfma must be 0, 1 or 2"),
     flag("real_sample_half", &Options::real_sample_half),
     flag("real_second_sample", &Options::real_second_sample),
@@ -1319,7 +1323,9 @@ int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "real_requeried")) *value = c->real_requeried;
     // how the last real-valued ranking ran: bit 0 = bf16 filter + exact rescoring, bit 1 = ranked by the LDS-resident kernel,
     // bit 2 = record lists beyond the LDS ordered group by group (k_real_group_*), bit 3 = the filter ran in IEEE half (else bfloat16)
-    else if (!strcmp(key, "real_path")) *value = (c->real.filtered ? 1 : 0) | (c->real.lds_ranked ? 2 : 0) | (c->real.grouped ? 4 : 0) | (c->real.filtered && c->dbfb_half ? 8 : 0);
+    else if (!strcmp(key, "real_path")) *value = (c->real.filtered ? 1 : 0) | (c->real.lds_ranked ? 2 : 0) | (c->real.grouped ? 4 : 0) | (c->real.filtered && c->real.half ? 8 : 0);
+    else if (!strcmp(key, "asym_calls")) *value = c->asym_calls;
+    else if (!strcmp(key, "asym_float_rows")) *value = c->asym_float_rows;
     else if (!strcmp(key, "device_bytes")) *value = device_bytes(c);
 #ifdef HG_RANK_PROFILE
 #ifdef HG_RANK_PROFILE                        // (tools/rank_phase_profile.py: where k_rank_cnt left its phase timestamps)

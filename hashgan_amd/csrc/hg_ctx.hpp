@@ -11,7 +11,8 @@
 //   hg_pairs_valu.hip  launchers of the vector-ALU pair passes (k_hist, k_select, k_select_dense)
 //   hg_pairs_mx.hip    launchers of the matrix-core pair passes (k_select_mx3 / mx4, k_hist_mx, k_hist_i8) and their images
 //   hg_pairs_mx1.hip   launcher of k_select_mx (every code length: the longest compile)
-//   hg_real.hip        real-valued (float32 inner product) ranking: a ladder of attempts, each with one RealReq down and one RealState (hg_ctx::real) up
+//   hg_real.hip        real-valued (float32 inner product) ranking: a ladder of attempts, each with one RealReq down and one RealState (hg_ctx::real) up;
+//                      its asymmetric form (hg_topr_asym, hg_map_asym): the database's rows are its packed codes read as +-1 (hg_asym.hpp)
 //   hg_comm.hip        RCCL collectives (library dlopen'ed on first use)
 //
 // No torch, no CPU compute path: every entry point either runs HIP kernels or fails.
@@ -217,7 +218,7 @@ enum KernelId { KI_HIST = 0, KI_HIST_REDUCE, KI_PLAN, KI_SEG_COUNTS, KI_SEG_LAYO
                 KI_RADIX, KI_REAL_FINISH, KI_SELECT_MX, KI_RANK_LDS, KI_COMM, KI_STEP, KI_REAL_RESCORE, KI_HIST_REL, KI_HIST_REL_REDUCE,
                 KI_GRADED, KI_GRADE_HIST, KI_GRADE_HIST_REDUCE, KI_TIE_AP, KI_AP_AT, KI_LABEL_MAX, KI_HIST_JOINT, KI_HIST_JOINT_REDUCE,
                 KI_RR_SCAN, KI_RR_COLLECT, KI_RR_SCORE, KI_RR_ORDER, KI_EXPORT, KI_VOTES, KI_VOTE_CONFUSION, KI_SIDE_PACK, KI_SIDE_MERGE,
-                KI_LIST_GRADES, KI_LIST_MERGE_GRADES, KI_LIST_MERGE_VOTES, KI_VOTE_PICK, KI_COUNT };
+                KI_LIST_GRADES, KI_LIST_MERGE_GRADES, KI_LIST_MERGE_VOTES, KI_VOTE_PICK, KI_ASYM_IMAGE, KI_ASYM_RESCORE, KI_ASYM_EXPAND, KI_COUNT };
 enum Stage { ST_NONE = 0, ST_DB = 1, ST_Q = 2, ST_HIST = 4, ST_PLAN = 8, ST_SELECT = 16, ST_MATCH = 32, ST_AP = 64 };
 extern const char* const kKernelNames[KI_COUNT];
 // the kernel that took the last record pass / the last rank stage (stats "select_variant", "rank_variant"), and what the rank stage is asked for
@@ -276,6 +277,7 @@ struct Options {
     // hand-over of float32 / int64 arrays
     i64 host_pack = 1;             // packed on the host by a thread pool before the upload (hg_host_pack.hpp); 0 = upload the raw arrays, pack on the GPU
     i64 keep_floats = 2;           // database float table on the GPU -- 0 never, 1 always, 2 only if it is not a +-1 code
+    i64 keep_query_floats = 0;     // 1: the query float table stays on the GPU whether or not the database's is there (the asymmetric ranking: hg_map_asym)
     // real-valued ranking
     i64 real_mfma = 2;             // 2 = bf16 filter on the matrix cores + exact rescoring of the survivors, 1 = exact float32 MFMA pass, 0 = vector ALU
     i64 real_sample_half = 1;      // the sampled cut's scores in the filter's 16-bit arithmetic (k_real_sample_h) instead of exact float32 chains
@@ -366,6 +368,7 @@ struct RealState {
     bool lds_ranked = false;   // the LDS-resident rank kernel produced the lists
     bool grouped = false;      // the record lists were ordered group by group (k_real_group_*)
     bool lists_made = false;   // out_idx / scores hold the ranked lists (hg_map_real skips them on the paths that rank in LDS)
+    bool half = false;         // the filter ran in IEEE half (else bfloat16): bit 3 of stat "real_path"
     i64 attempts = 0;          // stat "real_attempts": attempts of the last call (1 = the first bet held)
 };
 
@@ -373,6 +376,17 @@ struct RealState {
 // pitch Qpad (where the table is pitched), the second dimension (NB, C + 1, nk, nR or NB * G).  The entry point calls begin() first and finish()
 // last, so a refused or failed call leaves none; the getters, and hg_tie_ap for the histogram it reuses, ask current().  DESIGN.md, "Side metrics: the host side".
 struct hg_ctx;
+// The asymmetric ranking's own set of what the real-valued path reads and derives from the database's rows (hg_real.hip, hg_asym.hpp):
+// swapped in for the length of a call (hg_ctx::swap_rows) -- like ws_b for a blind step -- so an image built from codes and one built
+// from a float table never meet, and hg_map_real finds its own untouched.  A database load forgets all of it.
+struct AsymBufs {
+    DevBuf rows;               // f32 [N][bpad] of +-1.0 (pads 0) expanded from the codes on first need (k_asym_expand_rows): a work buffer for the
+                               // paths that still read float rows (no cut, vector fallbacks, real_mfma < 2), freed by hg_trim
+    DevBuf rowsx;              // ... and its float32 MFMA image (what dbfx is to dbf)
+    DevBuf img, xmax2;         // the filter's 16-bit image built from the codes (k_asym_image16) and its norm word (the host writes (float)b)
+    bool rows_valid = false, rowsx_valid = false, img_valid = false, img_half = false;
+    void forget() { rows_valid = rowsx_valid = img_valid = false; }
+};
 struct SideResult {
     bool done = false;
     unsigned long long q_gen = 0, db_gen = 0;
@@ -487,6 +501,16 @@ struct hg_ctx : StepBufs, StepState {
     bool ranked_local = false; // mbits holds this shard's bitmap in LOCAL rank order (hg_select_ranked)
     bool dbfx_valid = false, dbfb_valid = false;
     bool dbfb_half = false;    // dbfb is in IEEE half instead of bfloat16 (no feature of the database can overflow it: ensure_filter_image)
+    // the asymmetric ranking (hg_topr_asym / hg_map_asym): while a call runs its buffers stand where the float table's do
+    AsymBufs asym;
+    bool asym_on = false;      // swapped in: dbf / dbfx / dbfb / xmax2 and their keys are the asymmetric call's, the row source is c->db
+    i64 asym_calls = 0;        // stat "asym_calls": asymmetric calls that succeeded (cumulative)
+    i64 asym_float_rows = 0;   // stat "asym_float_rows": the last asymmetric call read the expanded float rows (asym.rows)
+    void swap_rows() {
+        std::swap(dbf, asym.rows); std::swap(dbfx, asym.rowsx); std::swap(dbfb, asym.img); std::swap(xmax2, asym.xmax2);
+        std::swap(dbf_resident, asym.rows_valid); std::swap(dbfx_valid, asym.rowsx_valid); std::swap(dbfb_valid, asym.img_valid); std::swap(dbfb_half, asym.img_half);
+        asym_on = !asym_on;
+    }
     i64 real_requeried = 0;       // queries that lost the first real-valued bet and were ranked again on their own (cumulative)
     int bpad = 0;              // feature count padded to a multiple of 16 (0: no float tables loaded)
     i64 census_db[3] = {0, 0, 0}, census_q[3] = {0, 0, 0};
@@ -551,7 +575,8 @@ struct hg_ctx : StepBufs, StepState {
     // Every device buffer of the context, each once, with its class: hg_destroy, hg_trim and the stat "device_bytes" walk this.
     template <class F> void for_each_buf(F&& f) {
         for (DevBuf* d : {&db, &dblab, &qc, &qlab, &dbf, &qf}) f(*d, BUF_TABLE);
-        for (DevBuf* d : {&dbx, &qx, &dbx8, &dbx3, &dbx4, &dbfx, &dbfb, &xmax2, &shapes, &ap_recip, &aa_recip}) f(*d, BUF_DERIVED);
+        for (DevBuf* d : {&dbx, &qx, &dbx8, &dbx3, &dbx4, &dbfx, &dbfb, &xmax2, &asym.rowsx, &asym.img, &asym.xmax2, &shapes, &ap_recip, &aa_recip}) f(*d, BUF_DERIVED);
+        f(asym.rows, BUF_WORK);
         for (DevBuf* d : {&seglt, &segtie, &mbits2, &part, &obuf[0], &obuf[1], &beyond, &stage_in, &badcnt, &flist, &dbytes, &samp, &thr,
                           &sortA, &sortB, &scores, &gtab, &sampx, &cntq, &krows, &thr2, &hist2, &comm_tmp, &gath_idx, &gath_dist, &rh_part, &rh_all, &rh_rel,
                           &gr_tab, &gr_out, &gr_grades, &gh_part, &gh_tab, &ta_tab, &ta_out, &aa_tab, &aa_out, &jh_max, &jh_part, &jh_tab, &vt_tab, &vt_votes, &vt_pred, &vt_conf,
@@ -565,6 +590,7 @@ struct hg_ctx : StepBufs, StepState {
     // the keys of the BUF_DERIVED buffers: after this each is rebuilt on its next use
     void forget_derived() {
         dbx_valid = qx_valid = dbx8_valid = dbx3_valid = dbx4_valid = dbfx_valid = dbfb_valid = false;
+        asym.forget();
         for (SideResult* r : {&rh, &gr, &gh, &ta, &aa, &jh, &vt, &mrh, &mgh, &mjh, &mlg, &mlv, &rr}) r->begin();   // (hg_trim releases their tables with the other work buffers)
         shapes_for_R = recip_for_R = aa_recip_n = -1;
         outblk_q = ws_b.outblk_q = -1;

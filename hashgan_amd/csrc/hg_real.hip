@@ -1,12 +1,17 @@
 // libhashgan_amd.so -- real-valued (float32 inner product) ranking, what main.py:157,164 feeds lib/metric.py:13-14:
 // sampled cut -> bf16 filter on the matrix cores -> exact float32 rescoring -> LDS ranking.
 //
-// One call is a ladder of attempts (run_real -> real_ladder -> real_attempt).  An attempt builds one RealReq and passes it down by
+// One call is a ladder of attempts (run_real -> real_call -> real_ladder -> real_attempt).  An attempt builds one RealReq and passes it down by
 // const reference; what it leaves behind is c->real (RealState), assigned afresh when the attempt begins.
+//
+// The asymmetric form (run_asym: hg_topr_asym, hg_map_asym) is the same ladder with a second row source, the database's packed codes read
+// as +-1: for the length of the call the context's asymmetric buffers stand where the float table's do (hg_ctx::swap_rows), the filter's
+// image and the rescore come from the codes (hg_asym.hpp), and a stage that reads float rows asks float_rows() for them.
 #include "hg_ctx.hpp"
 #include "hg_real_kernels.hpp"
 #include "hg_real_mx.hpp"
 #include "hg_real_bf.hpp"
+#include "hg_asym.hpp"
 #include <type_traits>
 
 constexpr double REAL_FIRST_SIGMA = 5.0;        // depth of the first cut in deviations of the sampled count: one query in ~3e5 loses it and is ranked again on its
@@ -60,9 +65,37 @@ void cut_segments(Geo& g, i64 L) {
     g.nBlk = (int)((g.nUnits + WPB - 1) / WPB);
 }
 
+// ---- the row source ----
+// The database's float rows [N][bpad]: the loaded table -- or, while an asymmetric call runs, +-1.0 rows expanded from the codes into the
+// call's own work buffer on first need per database (k_asym_expand_rows; stat "asym_float_rows" says that a call came here)
+int float_rows(hg_ctx* c, const float** rows) {
+    if (c->asym_on) {
+        c->asym_float_rows = 1;
+        if (!c->dbf_resident) {
+            HG_TRY(c->dbf.reserve((size_t)c->N * c->bpad * 4 + 256));
+            c->t_begin(KI_ASYM_EXPAND);
+            hipLaunchKernelGGL(k_asym_expand_rows, dim3(grid_for(c->N * (c->bpad / 4))), dim3(256), 0, c->stream, c->db.as<u32>(), c->dbf.as<float4>(),
+                               (i64)c->N, c->bpad, c->NW, c->b, (i64)1);
+            c->t_end();
+            HG_TRY(c->check_launch("k_asym_expand_rows"));
+            c->dbf_resident = true;
+        }
+    }
+    *rows = c->dbf.as<float>();
+    return HG_OK;
+}
+
 // ---- pair passes ----
 // 16-bit image (IEEE half or bfloat16: c->dbfb_half) of every stride-th database row, `rows` of them padded to rows16, in MFMA fragment order
 void expand_image16(hg_ctx* c, DevBuf& dst, i64 rows, i64 rows16, int KP, i64 stride) {
+    if (c->asym_on) {
+        with_bool(c->dbfb_half, [&](auto half) {
+            hipLaunchKernelGGL(k_asym_image16<half>, dim3(grid_for(rows16 * (KP / 8))), dim3(256), 0, c->stream, c->db.as<u32>(),
+                               dst.as<uint4>(), rows, rows16, KP, c->NW, c->b, stride);
+            return HG_OK;
+        });
+        return;
+    }
     with_bool(c->dbfb_half, [&](auto half) {
         hipLaunchKernelGGL(k_expand_dbf_bf16<half>, dim3(grid_for(rows16 * (KP / 8))), dim3(256), 0, c->stream, c->dbf.as<float>(),
                            dst.as<uint4>(), rows, rows16, KP, stride);
@@ -75,9 +108,11 @@ bool sample_in_16bit(const hg_ctx* c) { return c->bpad <= 128 && c->opt.real_mfm
 template <int BP> int real_launch_sample(hg_ctx* c, i64 M, i64 stride) {
     const Geo& g = c->geo;
     const i64 units = (M + 63) / 64 * g.nQT;
+    const float* dbf;
+    HG_TRY(float_rows(c, &dbf));
     c->t_begin(KI_REAL_SAMPLE);
     hipLaunchKernelGGL(k_real_sample<BP>, dim3(grid_for(units, WPB)), dim3(256), (size_t)WPB * 64 * 65 * 4, c->stream,
-                       c->qf.as<float>(), c->dbf.as<float>(), c->samp.as<float>(), M, stride, g);
+                       c->qf.as<float>(), dbf, c->samp.as<float>(), M, stride, g);
     c->t_end();
     return c->check_launch("k_real_sample");
 }
@@ -85,9 +120,11 @@ template <int BP> int real_launch_sample(hg_ctx* c, i64 M, i64 stride) {
 template <int BP> int real_launch_select(hg_ctx* c) {
     const Geo& g = c->geo;
     RealSelArgs a{c->thr.as<float>(), c->sl_cnt.as<u32>(), c->failq.as<u32>(), c->cap, c->crow};
+    const float* dbf;
+    HG_TRY(float_rows(c, &dbf));
     c->t_begin(KI_REAL_SELECT);
     hipLaunchKernelGGL((k_real_select<BP, 1>), dim3(padded_grid(g.nBlk)), dim3(256), 0, c->stream, c->qf.as<float>(),
-                       c->dbf.as<float>(), a, c->cand.as<u64>(), g);
+                       dbf, a, c->cand.as<u64>(), g);
     c->t_end();
     return c->check_launch("k_real_select");
 }
@@ -97,8 +134,10 @@ template <int KP> int real_launch_select_mx(hg_ctx* c) {
         const i64 n16 = (c->N + 15) / 16 * 16;
         HG_TRY(c->dbfx.reserve((size_t)n16 * KP * 4));
         const i64 items = n16 * (KP / 4);
+        const float* dbf;
+        HG_TRY(float_rows(c, &dbf));
         c->t_begin(KI_PACK);
-        hipLaunchKernelGGL(k_expand_dbf, dim3(grid_for(items)), dim3(256), 0, c->stream, c->dbf.as<float>(), c->dbfx.as<float4>(),
+        hipLaunchKernelGGL(k_expand_dbf, dim3(grid_for(items)), dim3(256), 0, c->stream, dbf, c->dbfx.as<float4>(),
                            (i64)c->N, n16, KP, (i64)1);
         c->t_end();
         HG_TRY(c->check_launch("k_expand_dbf"));
@@ -114,7 +153,29 @@ template <int KP> int real_launch_select_mx(hg_ctx* c) {
 }
 // filter + rescore (hg_real_bf.hpp): bf16 pair pass with a rigorous margin, then the exact chain for the survivors
 // the filter's 16-bit image of the database (and the choice between IEEE half and bfloat16), built on first use
+// (an asymmetric call's, from the codes: +-1 is exact in either format and every row's norm^2 is exactly b -- the host writes that itself,
+// a fill on the stream: no k_row_norm_max, no download, no wait)
+int ensure_code_image(hg_ctx* c) {
+    const int KP = c->bpad;
+    if (!c->dbfb_valid) {
+        const i64 n16 = (c->N + 15) / 16 * 16;
+        HG_TRY(c->dbfb.reserve((size_t)n16 * KP * 2));
+        HG_TRY(c->xmax2.reserve(4));
+        const float xm = (float)c->b;
+        u32 xbits;
+        memcpy(&xbits, &xm, 4);
+        HG_HIP(hipMemsetD32Async((hipDeviceptr_t)c->xmax2.p, (int)xbits, 1, c->stream));
+        c->dbfb_half = c->opt.real_mfma == 2 && xm >= 1.0f && xm < 1073741824.0f;          // (ensure_filter_image's rule)
+        c->t_begin(KI_ASYM_IMAGE);
+        expand_image16(c, c->dbfb, c->N, n16, KP, 1);
+        c->t_end();
+        HG_TRY(c->check_launch("k_asym_image16"));
+        c->dbfb_valid = true;
+    }
+    return HG_OK;
+}
 int ensure_filter_image(hg_ctx* c) {
+    if (c->asym_on) return ensure_code_image(c);
     const int KP = c->bpad;
     if (!c->dbfb_valid) {
         const i64 n16 = (c->N + 15) / 16 * 16;
@@ -164,9 +225,33 @@ int rescore_slices_per_wave(double per_slice) {
     return SG;
 #endif
 }
+// the asymmetric call's rescore: the kept rows' code words instead of their float rows (k_asym_rescore: no LDS)
+int launch_asym_rescore(hg_ctx* c, const RealReq& r, int SG, i64 waves, int KP) {
+    const Geo& g = c->geo;
+    const int nwt = c->NW <= 2 ? c->NW : 0;
+    c->t_begin(KI_ASYM_RESCORE);
+#define HG_ARESCORE(nw, sg)                                                                                                              \
+    hipLaunchKernelGGL((k_asym_rescore<nw, sg>), dim3(grid_for(waves, WPB)), dim3(256), 0, c->stream, c->qf.as<float>(), c->db.as<u32>(),  \
+                       c->sl_cnt.as<u32>(), c->krows.as<u32>(), c->cand.as<u64>(), c->cap, c->crow, c->thr.as<float>(), c->sl_cnt.as<u32>(), \
+                       c->cntq.as<u32>(), c->dblab.as<u64>(), c->qlab.as<u64>(), r.no_cut ? 0 : 1, KP, c->NW, c->b, g)
+#define HG_ARESCORE_SG(sg)                                                                                                               \
+    case sg:                                                                                                                             \
+        if (nwt == 1) HG_ARESCORE(1, sg); else if (nwt == 2) HG_ARESCORE(2, sg); else HG_ARESCORE(0, sg);                                \
+        break;
+#ifdef HG_RS_FORCE
+    switch (SG) { HG_ARESCORE_SG(HG_RS_FORCE) }
+#else
+    switch (SG) { HG_ARESCORE_SG(8) HG_ARESCORE_SG(6) HG_ARESCORE_SG(4) HG_ARESCORE_SG(3) HG_ARESCORE_SG(2) HG_ARESCORE_SG(1) }
+#endif
+#undef HG_ARESCORE_SG
+#undef HG_ARESCORE
+    c->t_end();
+    return c->check_launch("k_asym_rescore");
+}
 template <int KP> int real_launch_select_bf(hg_ctx* c, const RealReq& r) {
     constexpr int QT = KP <= 128 ? 2 : 1;
     HG_TRY(ensure_filter_image(c));
+    c->real.half = c->dbfb_half;
     const Geo& g = c->geo;
     HG_TRY(c->thr2.reserve((size_t)g.Qpad * 4));
     c->t_begin(KI_REAL_GUESS);
@@ -195,11 +280,14 @@ template <int KP> int real_launch_select_bf(hg_ctx* c, const RealReq& r) {
     const int SG = rescore_slices_per_wave(1.03 * r.expect / (double)g.S);
     const i64 waves = (i64)((g.S + SG - 1) / SG) * g.Q;
     HG_TRY(c->cntq.reserve((size_t)g.Q * g.S * 4));
+    if (c->asym_on) return launch_asym_rescore(c, r, SG, waves, KP);
+    const float* dbf;
+    HG_TRY(float_rows(c, &dbf));
     c->t_begin(KI_REAL_RESCORE);
 #define HG_RESCORE(sg)                                                                                                                   \
     case sg:                                                                                                                             \
         hipLaunchKernelGGL((k_real_rescore<(KP <= 128 ? KP : 0), sg>), dim3(grid_for(waves, WPB)), dim3(256), rescore_lds_bytes(), c->stream, c->qf.as<float>(),  \
-                           c->dbf.as<float>(), c->sl_cnt.as<u32>(), c->krows.as<u32>(), c->cand.as<u64>(), c->cap, c->crow, c->thr.as<float>(), \
+                           dbf, c->sl_cnt.as<u32>(), c->krows.as<u32>(), c->cand.as<u64>(), c->cap, c->crow, c->thr.as<float>(), \
                            c->sl_cnt.as<u32>(), c->cntq.as<u32>(), c->dblab.as<u64>(), c->qlab.as<u64>(), r.no_cut ? 0 : 1, KP, g);                         \
         break;
 #ifdef HG_RS_FORCE
@@ -215,8 +303,10 @@ template <int KP> int real_launch_select_bf(hg_ctx* c, const RealReq& r) {
 template <int KP> int real_launch_sample_mx(hg_ctx* c, i64 M, i64 stride, i64 mstride) {
     const i64 m16 = (M + 15) / 16 * 16;
     HG_TRY(c->sampx.reserve((size_t)m16 * KP * 4));
+    const float* dbf;
+    HG_TRY(float_rows(c, &dbf));
     c->t_begin(KI_REAL_SAMPLE);
-    hipLaunchKernelGGL(k_expand_dbf, dim3(grid_for(m16 * (KP / 4))), dim3(256), 0, c->stream, c->dbf.as<float>(), c->sampx.as<float4>(),
+    hipLaunchKernelGGL(k_expand_dbf, dim3(grid_for(m16 * (KP / 4))), dim3(256), 0, c->stream, dbf, c->sampx.as<float4>(),
                        M, m16, KP, stride);
     const Geo g = pair_geometry(c->geo, M, 32, REAL_MX_QPB);
     hipLaunchKernelGGL((k_real_sample_mx<KP>), dim3(padded_grid(g.nBlk)), dim3(256), 0, c->stream, c->qf.as<float>(), c->sampx.as<u8>(),
@@ -273,8 +363,18 @@ int real_sample(hg_ctx* c, const RealReq& r, i64 M, i64 stride, i64 mstride) {
         const i64 units = (M + 63) / 64 * g.nQT;
         const size_t lds = (size_t)WPB * (64 * 65 * 4 + 16 * 128);
         HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_real_sample_any), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        // (an asymmetric call: the M sampled rows alone are expanded, into the sample's own per-call buffer -- a few MB, like the 16-bit
+        // sample images -- so that a bet on more than 128 features never asks for the whole database as floats)
+        const float* dbf = nullptr;
+        if (c->asym_on) HG_TRY(c->sampx.reserve((size_t)M * c->bpad * 4 + 256)); else HG_TRY(float_rows(c, &dbf));
         c->t_begin(KI_REAL_SAMPLE);
-        hipLaunchKernelGGL(k_real_sample_any, dim3(grid_for(units, WPB)), dim3(256), lds, c->stream, c->qf.as<float>(), c->dbf.as<float>(),
+        if (c->asym_on) {
+            hipLaunchKernelGGL(k_asym_expand_rows, dim3(grid_for(M * (c->bpad / 4))), dim3(256), 0, c->stream, c->db.as<u32>(), c->sampx.as<float4>(),
+                               M, c->bpad, c->NW, c->b, stride);
+            dbf = c->sampx.as<float>();
+            stride = 1;
+        }
+        hipLaunchKernelGGL(k_real_sample_any, dim3(grid_for(units, WPB)), dim3(256), lds, c->stream, c->qf.as<float>(), dbf,
                            c->samp.as<float>(), M, stride, c->bpad, g);
         c->t_end();
         return c->check_launch("k_real_sample_any");
@@ -544,7 +644,7 @@ int real_attempt(hg_ctx* c, int64_t R, bool bet, double sigma, double budget, bo
     return rank_by_radix(c, req, rows, lost);
 }
 
-int run_real(hg_ctx* c, int64_t R, bool with_ap);
+int real_call(hg_ctx* c, int64_t R, bool with_ap);
 
 // A few queries lost the first bet (their cut kept fewer than R rows, or their rows crowd into one slice): those alone run again,
 // on a child context that borrows the database's tables, with the usual escalation; their lists and match bits go back into the
@@ -563,8 +663,12 @@ int real_requery_lost(hg_ctx* c, int64_t R, bool with_ap, bool* handled) {
     if (nF == 0 || nF * 16 > g.Q) return HG_OK;
     hg_ctx* s = requery_child(c, nF);
     s->real_cap_boost = c->real_cap_boost;
-    s->dbf.borrow(c->dbf); s->dbf_resident = true;
+    // (the child borrows the tables the parent ran on: an asymmetric call's are its images from the codes, and its expanded rows if it has any --
+    // a child that needs them without builds its own; the float32 MFMA image is the child's, so it is never carried from one source to the other)
+    s->dbf.borrow(c->dbf); s->dbf_resident = c->dbf_resident;
     s->dbfb.borrow(c->dbfb); s->xmax2.borrow(c->xmax2); s->dbfb_valid = c->dbfb_valid; s->dbfb_half = c->dbfb_half;
+    if (c->asym_on || s->asym_on) s->dbfx_valid = false;
+    s->asym_on = c->asym_on; s->asym_float_rows = 0;
     HG_TRY(c->flist.reserve((size_t)nF * 4));
     HG_HIP(hipMemcpyAsync(c->flist.p, lost.data(), (size_t)nF * 4, hipMemcpyHostToDevice, c->stream));
     HG_TRY(s->qf.reserve((size_t)nF * c->bpad * 4 + 256));
@@ -578,7 +682,8 @@ int real_requery_lost(hg_ctx* c, int64_t R, bool with_ap, bool* handled) {
     HG_TRY(c->check_launch("k_move_rows"));
     s->qf_resident = true;
     s->stage = ST_DB | ST_Q;
-    HG_TRY(run_real(s, R, false));
+    HG_TRY(real_call(s, R, false));
+    if (s->asym_on && s->asym_float_rows) c->asym_float_rows = 1;
     if (s->RW != c->RW) return fail(HG_ERR_HIP, "real-valued ranking: internal error, the requeried lists have another width");
     move(s->mbits.p, c->mbits.p, c->RW * 8, 0);
     if (c->real.lists_made) {
@@ -627,10 +732,8 @@ int real_ladder(hg_ctx* c, int64_t R, bool with_ap) {
     return HG_OK;
 }
 
-int run_real(hg_ctx* c, int64_t R, bool with_ap) {
-    if (!c->bpad || !c->dbf.p || !c->qf.p || !c->dbf_resident || !c->qf_resident)
-        return fail(HG_ERR_STATE, "real-valued ranking needs the float features on the GPU: load them with hg_set_database_f32 / "
-                                  "hg_set_queries_f32 (option keep_floats = 1 if the database is a +-1 code)");
+// a call on the row source the context holds now (the float table; the codes while asym_on), whose tables the caller has checked
+int real_call(hg_ctx* c, int64_t R, bool with_ap) {
     if (c->n_total != c->N) return fail(HG_ERR_STATE, "real-valued ranking is single-shard");
     if (R < 1 || R > c->N) return fail(HG_ERR_ARG, "R=%lld outside 1..N (N=%lld rows in the database)", (long long)R, (long long)c->N);
     if (c->N > 0x7FFFFFFFll) return fail(HG_ERR_ARG, "real-valued ranking takes up to 2^31 - 1 rows (have %lld)", (long long)c->N);   // (bit 31 of a record's index half is its match bit)
@@ -640,6 +743,29 @@ int run_real(hg_ctx* c, int64_t R, bool with_ap) {
     HG_TRY(real_ladder(c, R, with_ap));
     c->real_lists = c->real.lists_made;
     return HG_OK;
+}
+
+int run_real(hg_ctx* c, int64_t R, bool with_ap) {
+    if (!c->bpad || !c->dbf.p || !c->qf.p || !c->dbf_resident || !c->qf_resident)
+        return fail(HG_ERR_STATE, "real-valued ranking needs the float features on the GPU: load them with hg_set_database_f32 / "
+                                  "hg_set_queries_f32 (option keep_floats = 1 if the database is a +-1 code)");
+    return real_call(c, R, with_ap);
+}
+
+// The asymmetric call: the same ladder on the database's CODES (any loader left them in c->db) and the queries' floats.  Its buffers are
+// swapped in for the call and out again whatever it returns; what it leaves is what run_real leaves.
+int run_asym(hg_ctx* c, int64_t R, bool with_ap) {
+    c->real_lists = false;                             // a refused call leaves no lists either
+    c->lists_valid = false;                            // ... and the call writes out_idx: a Hamming ranking's lists end here (hg_get_topr refuses)
+    if (!c->bpad || !c->qf.p || !c->qf_resident || !c->db.p)
+        return fail(HG_ERR_STATE, "asymmetric ranking needs the queries' float features on the GPU: set option keep_query_floats = 1, then load "
+                                  "them with hg_set_queries_f32 / hg_set_queries_dev");
+    c->asym_float_rows = 0;
+    c->swap_rows();
+    const int rc = real_call(c, R, with_ap);
+    c->swap_rows();
+    if (rc == HG_OK) c->asym_calls++;
+    return rc;
 }
 
 }  // namespace
@@ -657,6 +783,17 @@ int hg_map_real(hg_ctx* c, int64_t R, double* host_ap, int64_t* host_rel) {
     return hg_get_ap(c, host_ap, host_rel);
 }
 
+int hg_topr_asym(hg_ctx* c, int64_t R) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_topr_asym", "a database load + hg_set_queries_f32 (option keep_query_floats = 1)"));
+    return run_asym(c, R, false);
+}
+
+int hg_map_asym(hg_ctx* c, int64_t R, double* host_ap, int64_t* host_rel) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_map_asym", "a database load + hg_set_queries_f32 (option keep_query_floats = 1)"));
+    HG_TRY(run_asym(c, R, true));
+    return hg_get_ap(c, host_ap, host_rel);
+}
+
 }  // extern "C"
 
 // hg_preload: the runtime loads a translation unit's code object when one of its kernels is first needed (milliseconds);
@@ -664,5 +801,8 @@ int hg_map_real(hg_ctx* c, int64_t R, double* host_ap, int64_t* host_rel) {
 int preload_real() {
     hipFuncAttributes a;
     HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_real_thr2)));
+    HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_asym_image16<true>)));      // (the same code object: the asymmetric kernels' names for a reader)
+    HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_asym_rescore<2, 6>)));
+    HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_asym_expand_rows)));
     return HG_OK;
 }

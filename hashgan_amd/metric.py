@@ -151,7 +151,7 @@ class _Pool:
     def release(cls, eng):
         keep = False
         try:
-            touched = eng.ctx.options_touched - {"keep_floats"}         # (set by every load)
+            touched = eng.ctx.options_touched - {"keep_floats", "keep_query_floats"}         # (set by every load / by _rank to what its mode needs)
             pending = getattr(eng.ctx, "_in_flight", None)
             if not touched and not pending and eng.ctx._h and not getattr(eng, "poisoned", False):
                 eng.forget()
@@ -265,10 +265,12 @@ def _check_cutoffs(Rs, N, what="Rs"):
     return Rs
 
 
-def _ap_at(ctx, Rs, real, rerank=False):
+def _ap_at(ctx, Rs, real, rerank=False, asym=False):
     """One ranking at the largest cut-off, then every cut-off from its match bitmap (hg_ap_at) -> (ap [Q, nR], rel [Q, nR])."""
     if rerank:
         ctx.topr_rerank(int(Rs[-1]), download=False)
+    elif asym:
+        ctx.topr_asym(int(Rs[-1]), download=False)
     elif real:
         ctx.topr_real(int(Rs[-1]), download=False)
     else:
@@ -293,7 +295,8 @@ def _load_database(eng, db_codes, db_labels, mode="reference", floats=None):
     memory (hg_set_database_dev; 'reference' mode keeps the floats at once).  The float table itself goes to the GPU only when it may be ranked
     by inner product: never for the spellings that binarise or insist on binary codes, and in 'reference' mode only if
     the database is not a +-1 code (a +-1 database meeting real-valued queries is uploaded again with it, below); 'rerank' mode always
-    keeps it (keep_floats = 1): the floats order the rows inside equal Hamming distances."""
+    keeps it (keep_floats = 1): the floats order the rows inside equal Hamming distances; 'asymmetric' mode never does (keep_floats = 0:
+    the loader signs the database, its floats never go to the GPU -- or, for device arrays, are never copied)."""
     eng.b = eng.C = eng.N = eng.db_kind = eng.db_src = None      # nothing is resident until this load has succeeded
     eng.resident = None                               # whoever loads another database (extra_metrics, MAPs) ends _evaluate's shortcut
     on_device = isinstance(db_codes, DeviceArray)
@@ -330,10 +333,22 @@ def _rank(eng, q_codes, q_labels, R, mode, Rs=None, lists=False):
        'codes'      MAP / calc_map (north-star spelling): binary codes only, {0,1} bits or +-1, ranked by Hamming
                     distance; anything else is an error;
        'rerank'     MAPs(rerank=True): sign() first, Hamming distance, then the float32 inner product of the features inside
-                    equal distances, then the index (hg_topr_rerank): both float tables are on the GPU (_load_database)."""
+                    equal distances, then the index (hg_topr_rerank): both float tables are on the GPU (_load_database);
+       'asymmetric' MAPs(asymmetric=True): the queries' float32 features against the database's sign() codes read as +-1
+                    (hg_topr_asym / hg_map_asym): the queries keep their floats on the GPU (keep_query_floats = 1), the database none."""
+    want_qf = 1 if mode == "asymmetric" else 0         # (set only when it changes: every hg_set_option ends hg_map_begin's licence to enqueue blind)
+    if eng.ctx.option_values.get("keep_query_floats", 0) != want_qf:
+        eng.ctx.set_option("keep_query_floats", want_qf)
     qbad_c, qbad_l = _set_queries(eng, q_codes, q_labels)
     if qbad_l:
         raise ValueError("labels must be {0,1} indicator matrices")
+    if mode == "asymmetric":
+        if q_codes.shape[1] > 255:
+            raise ValueError("inner-product ranking supports up to 255 features (have %d)" % q_codes.shape[1])
+        if lists:
+            eng.ctx.topr_asym(R, download=False)
+            return "inner_product"
+        return eng.ctx.map_asym(R) if Rs is None else _ap_at(eng.ctx, Rs, True, asym=True)
     if mode == "rerank":
         if q_codes.shape[1] > 255:
             raise ValueError("inner-product ranking supports up to 255 features (have %d)" % q_codes.shape[1])
@@ -451,14 +466,20 @@ class MAPs:
     calls (explicit), and a database whose arrays are the SAME read-only objects as last time is reused
     automatically (a writable array may have changed in place, so it is uploaded again)."""
 
-    def __init__(self, r, device=0, binarize=False, rerank=False):
+    def __init__(self, r, device=0, binarize=False, rerank=False, asymmetric=False):
         """rerank=True: sign() first (it implies binarize), rank by Hamming distance, and inside equal distances by the float32 inner
         product of the features (descending), then by database index -- the ties of the Hamming ranking resolved by the
-        magnitudes sign() throws away; the threshold group's rows with the highest inner product make the cut at R."""
+        magnitudes sign() throws away; the threshold group's rows with the highest inner product make the cut at R.
+        asymmetric=True: what a deployed hashing system ranks -- the database is its sign() codes (bit = feature > 0, read as +-1; its
+        floats never go to the GPU), the query keeps its float32 features, rows are ranked by their inner product (descending), then by
+        database index (hg_map_asym).  Not together with binarize or rerank (ValueError)."""
+        if asymmetric and (binarize or rerank):
+            raise ValueError("asymmetric=True ranks real-valued queries against sign() codes: not together with binarize or rerank")
         self.R = r
         self.device = device
         self.binarize = binarize or rerank
         self.rerank = rerank
+        self.asymmetric = asymmetric
         self._eng = None
         self._lock = threading.RLock()
         self._resident = None          # (output array, label array) the engine holds, or ("explicit",)
@@ -474,7 +495,7 @@ class MAPs:
         return self._eng
 
     def _mode(self):
-        return "rerank" if self.rerank else "sign" if self.binarize else "reference"
+        return "asymmetric" if self.asymmetric else "rerank" if self.rerank else "sign" if self.binarize else "reference"
 
     def close(self):
         with self._lock:

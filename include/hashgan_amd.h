@@ -277,6 +277,31 @@ int hg_map_real(hg_ctx* ctx, int64_t R, double* host_ap, int64_t* host_rel);
 int hg_topr_real(hg_ctx* ctx, int64_t R);
 int hg_get_topr_real(hg_ctx* ctx, uint32_t* host_idx, float* host_scores);   /* [Q][R] each */
 
+/* ---- asymmetric ranking: real-valued queries against the database's packed codes (asymmetric distance, Gordo et al.) ----
+ * What a deployed hashing system runs: the database is stored as codes, the fresh query keeps its float32 features, and rows are ranked
+ * by s(q, n) = sum_k q_k x_nk with x_nk = +1.0f where bit k of row n's code is set (feature > 0, the loaders' rule: a zero feature is
+ * -1) and -1.0f elsewhere -- in the fixed arithmetic of the real-valued ranking above: acc = fmaf(q_k, x_nk, acc) for k = 0 .. b - 1
+ * from +0.0, then + 0.0.  Order: s descending, database index ascending; label match, AP and hit counts as hg_map_real's.  Bit for bit
+ * what hg_topr_real / hg_map_real return on the same queries and the float table where(code bit, +1, -1), and what
+ * oracle/real_map.py::map_from_features returns on that table -- without that table: the filter's image and the exact rescoring read
+ * the codes (k_asym_image16, k_asym_rescore: 8 bytes per kept row at 64 bits instead of 256).
+ *   Tables    the database's codes and labels from ANY loader (hg_set_database packed, hg_set_database_f32 with any "keep_floats",
+ *             hg_set_database_dev): its float table is never needed and never created by a load.  The queries' float table: load them
+ *             with hg_set_queries_f32 / hg_set_queries_dev under option "keep_query_floats" = 1 (0, the default: the query floats stay
+ *             only when the database's do).  Without it: HG_ERR_STATE, and the message names the option.
+ *   Limits    hg_map_real's: b <= 255, N < 2^31, one shard (HG_ERR_STATE on a shard), 1 <= R <= N (else HG_ERR_ARG).
+ *   State     a successful call leaves what hg_topr_real / hg_map_real leave: hg_get_topr_real, hg_get_ap, hg_get_match, hg_ap_at,
+ *             hg_graded, hg_votes and hg_export work on it unchanged (hg_export refuses HG_OUT_DIST as after any inner-product ranking).
+ *             A failed or refused call leaves no lists.
+ *   Fallback  a bet (R * 8 <= N, N >= 65536) under "real_mfma" = 2 runs from the codes alone.  The paths that read plain float rows
+ *             (no cut: R = N or an exhausted ladder; "real_mfma" < 2; the vector kernels) get them from a work buffer of +-1.0 rows
+ *             expanded from the codes on first need per database (k_asym_expand_rows; N x bpad x 4 bytes, counted in "device_bytes",
+ *             freed by hg_trim, forgotten by a database load).
+ *   Stats     "real_path" / "real_attempts" / "real_requeried" as for hg_map_real; "asym_calls" (successful asymmetric calls,
+ *             cumulative); "asym_float_rows" (1: the last asymmetric call read the expanded float rows; 0: codes only). */
+int hg_map_asym(hg_ctx* ctx, int64_t R, double* host_ap, int64_t* host_rel);
+int hg_topr_asym(hg_ctx* ctx, int64_t R);
+
 /* ---- Hamming ranking with the tie groups re-ranked by the features ("sign, rank by Hamming distance, re-rank inside equal
  * distances by the real-valued inner product") ----
  * Row n against query q has d = popcount(code_q xor code_n) on the codes the loaders make (bit = feature > 0) and s = the float32
@@ -575,12 +600,13 @@ int hg_set_stream(hg_ctx* ctx, void* hip_stream);
  *                 bet's verdict), "staged_lists" (1: the staged hg_select materialises the idx / dist lists), "step_graph" (0; 1: hg_map replays its
  *                 sequence as a hipGraph), "timing_every" (1: kernel timing brackets every n-th step)
  *   loading       "host_pack" (1: hg_set_*_f32 pack on the host's cores before the upload), "keep_floats" (hg_set_*_f32: 0 never / 1 always / 2 = only
- *                 if not a +-1 code: keep the float table on the device)
+ *                 if not a +-1 code: keep the float table on the device), "keep_query_floats" (0; 1: hg_set_queries_f32 / hg_set_queries_dev keep
+ *                 the query float table whether or not the database's is there -- what hg_map_asym needs)
  *   real-valued   "real_mfma" (2: bf16 matrix-core filter + exact float32 rescoring; 1: every pair on the float32 matrix-core instruction; 0: vector
  *                 ALU), "real_sample_half" (1: the sampled cut's scores in the filter's 16-bit arithmetic -- they only place the cut; 0: exact float32 chains), "real_second_sample" (1: a second, counting sample four times as large tightens that cut), "real_sort_lds" (1: ranked by the LDS-resident kernel when the records fit), "real_groups" (1: lists beyond the LDS ordered group by group), "real_map_lists" (0; 1: hg_map_real also writes the ranked idx / score lists), "real_whole_rounds" (3: without a cut -- R = N -- the database is cut so that k_real_select_mx's blocks fill whole rounds of that many per CU; 0: the plain geometry)
  *   ("probe_select" and "probe_votes" exist only in the measurement build, python -m hashgan_amd.build --probes) */
 int hg_set_option(hg_ctx* ctx, const char* key, int64_t value);
-/* Counters and facts about the last call (37 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
+/* Counters and facts about the last call (39 keys; the process-wide "cache_*" and "host_*" keys are listed at hg_release_cache): "optimistic_runs", "optimistic_fallbacks" (all queries rerun exactly),
  * "optimistic_requeried" (single queries rerun exactly after losing their bet), "optimistic_rebets" (second and widened bets), "last_optimistic",
  * "rank_leftovers" (queries the LDS-resident rank kernel left to the general one), "select_variant" (1 k_select, 2 k_select_dense, 3 k_select_mx,
  * 5 k_select_mx3, 6 k_select_mx4), "rank_variant" (1 k_rank_fused, 3 k_rank_cnt, 6 k_rank_lean, 7 k_rank_dense, 8 k_rank_dense<slices>), "hist_variant" (the kernel of the last histogram pass, full or sampled: 1 k_hist, 2 k_hist_mx, 3 k_hist_i8; 6 / 7: k_hist_mx / k_hist_i8 with one dword counter per query tile instead of 16-bit halves; 0: no pass yet), "rank_lds_recs" (records the last k_rank_lean / k_rank_cnt launch had LDS room for), "slice_cap" (capacity of a (segment, query) slice of the last bet), "rel_hist_variant" (the kernel of the last hg_rel_hist: 1 k_hist_rel, the vector-ALU pass -- the only one so far, whatever "hist_mfma" says; 0: no pass yet), "ap_at_cutoffs" (cut-offs of the last hg_ap_at; 0: no pass yet), "votes_cutoffs" (cut-offs of the last hg_votes; 0: no pass yet), "joint_hist_grades" / "joint_hist_bands" (grades G and distance bands of the last hg_joint_hist; 0: no pass yet), "merged_joint_grades" (the common grade count Gc of the last joint hg_merge_side_table that succeeded; 0: none yet), "rel_hist_current" / "grade_hist_current" / "joint_hist_current" (1: this shard's table of the loaded queries and database is there -- what hg_pack_side_table needs), "ap_fused",
@@ -590,7 +616,7 @@ int hg_set_option(hg_ctx* ctx, const char* key, int64_t value);
  * "export_bytes" / "export_variant" (see hg_export);
  * "cut_beyond_planes" (1: the last hg_guess_finish met a query whose cut lies beyond the b/2 + 2 planes the owner-routed exchange carries -- its bet
  * cannot be won by wider slices; a download); real-valued path: "real_attempts", "real_requeried" (queries that lost the first cut and were ranked again on their own, cumulative), "real_cap_boost", "real_path" (bit 0 filter + rescoring, bit 1 ranked in LDS,
- * bit 2 lists ordered group by group); re-rank: "rerank_records", "rerank_chunks", "rerank_groups_lds", "rerank_groups_global" (see hg_topr_rerank). */
+ * bit 2 lists ordered group by group), "asym_calls" / "asym_float_rows" (see hg_map_asym); re-rank: "rerank_records", "rerank_chunks", "rerank_groups_lds", "rerank_groups_global" (see hg_topr_rerank). */
 int hg_get_stat(hg_ctx* ctx, const char* key, int64_t* value);
 /* What hg_set_database_f32 (queries = 0) / hg_set_queries_f32 (queries = 1) found in the float table: out[0] entries outside
  * {-1, 0, +1}, out[1] zeros, out[2] minus ones, out[3] = 1 if the float table is resident on the device -- from which the caller
