@@ -367,7 +367,7 @@ int hg_set_database(hg_ctx* c, const uint64_t* codes, const uint64_t* labels, in
     c->NW = (b + 31) / 32; c->NB = b + 1; c->LW = (C + 63) / 64;
     c->idx_base = (u32)idx_base;
     c->bpad = 0;                                       // packed input: no float tables for the real-valued path
-    c->dbf_resident = false;
+    c->from_floats.rows_valid = false;
     HG_TRY(upload_codes(c, c->db, codes, N, (b + 63) / 64, c->NW));
     HG_TRY(c->dblab.reserve((size_t)(N > 0 ? N : 1) * c->LW * 8));
     if (N) HG_HIP(hipMemcpyAsync(c->dblab.p, labels, (size_t)N * c->LW * 8, hipMemcpyHostToDevice, c->stream));
@@ -377,7 +377,7 @@ int hg_set_database(hg_ctx* c, const uint64_t* codes, const uint64_t* labels, in
     c->dbx3_valid = false;
     c->dbx4_valid = false;
     c->dbx8_valid = false;
-    c->asym.forget();
+    c->forget_rows();
     c->bet_consecutive_fail = c->shard_bet_fail = 0;    // a new database: earlier lost bets say nothing about it
     c->cap_boost = c->real_cap_boost = 1;
     c->crowd_probed = false;
@@ -568,15 +568,13 @@ static int pack_on_host(hg_ctx* c, const float* x, const int64_t* lab, i64 n, De
 // What a successful load of the database's float32 / device arrays ends with (hg_set_database_f32, hg_set_database_dev): queries must
 // be set again, everything derived from the old tables is invalid, earlier lost bets say nothing about the new one.
 static void database_loaded(hg_ctx* c) {
-    if (!c->dbf_resident) c->bpad = 0;
+    if (!c->from_floats.rows_valid) c->bpad = 0;
     c->stage = ST_DB;
     c->dbx_valid = false;
     c->dbx3_valid = false;
     c->dbx4_valid = false;
     c->dbx8_valid = false;
-    c->dbfx_valid = false;
-    c->dbfb_valid = false;
-    c->asym.forget();
+    c->forget_rows();
     c->bet_consecutive_fail = c->shard_bet_fail = 0;
     c->cap_boost = c->real_cap_boost = 1;
     c->crowd_probed = false;
@@ -598,11 +596,11 @@ int hg_set_database_f32(hg_ctx* c, const float* host_x, const int64_t* host_labe
     c->NW = (b + 31) / 32; c->NB = b + 1; c->LW = (C + 63) / 64;
     c->idx_base = (u32)idx_base;
     if (c->opt.host_pack) {
-        HG_TRY(pack_on_host(c, host_x, host_labels, N, c->db, c->dblab, c->dbf, (int)c->opt.keep_floats, &c->dbf_resident,
+        HG_TRY(pack_on_host(c, host_x, host_labels, N, c->db, c->dblab, c->from_floats.rows, (int)c->opt.keep_floats, &c->from_floats.rows_valid,
                             bad_codes, bad_labels, c->census_db));
     } else {
-        HG_TRY(pack_on_device(c, host_x, host_labels, N, c->db, c->dblab, c->dbf, bad_codes, bad_labels, c->census_db));
-        c->dbf_resident = true;
+        HG_TRY(pack_on_device(c, host_x, host_labels, N, c->db, c->dblab, c->from_floats.rows, bad_codes, bad_labels, c->census_db));
+        c->from_floats.rows_valid = true;
     }
     database_loaded(c);
     return HG_OK;
@@ -646,7 +644,7 @@ int hg_set_queries_f32(hg_ctx* c, const float* host_x, const int64_t* host_label
         // the query table is small: its floats follow whenever the database's are there (the inner-product ranking needs both) --
         // or the caller asks for them (option keep_query_floats: the asymmetric ranking needs the queries' alone)
         const int saved_bpad = c->bpad;
-        HG_TRY(pack_on_host(c, host_x, host_labels, Q, c->qc, c->qlab, c->qf, c->dbf_resident || c->opt.keep_query_floats ? 1 : 0, &c->qf_resident,
+        HG_TRY(pack_on_host(c, host_x, host_labels, Q, c->qc, c->qlab, c->qf, c->from_floats.rows_valid || c->opt.keep_query_floats ? 1 : 0, &c->qf_resident,
                             bad_codes, bad_labels, c->census_q));
         if (!c->qf_resident) c->bpad = saved_bpad;
     } else {
@@ -752,7 +750,7 @@ int hg_set_database_dev(hg_ctx* c, const hg_dev_array* features, const hg_dev_ar
     c->N = N; c->b = b; c->C = C; c->n_total = n_total;
     c->NW = (b + 31) / 32; c->NB = b + 1; c->LW = (C + 63) / 64;
     c->idx_base = (u32)idx_base;
-    HG_TRY(pack_from_device(c, *features, *labels, c->db, c->dblab, c->dbf, (int)c->opt.keep_floats, &c->dbf_resident, bad_codes,
+    HG_TRY(pack_from_device(c, *features, *labels, c->db, c->dblab, c->from_floats.rows, (int)c->opt.keep_floats, &c->from_floats.rows_valid, bad_codes,
                             bad_labels, c->census_db));
     database_loaded(c);
     return HG_OK;
@@ -765,7 +763,7 @@ int hg_set_queries_dev(hg_ctx* c, const hg_dev_array* features, const hg_dev_arr
     const bool had_q = (c->stage & ST_Q) != 0;
     c->Q = features->rows;
     // the queries' floats follow the database's (the inner-product ranking needs both) or option keep_query_floats; without them c->bpad stays as it is
-    HG_TRY(pack_from_device(c, *features, *labels, c->qc, c->qlab, c->qf, c->dbf_resident || c->opt.keep_query_floats ? 1 : 0, &c->qf_resident, bad_codes, bad_labels,
+    HG_TRY(pack_from_device(c, *features, *labels, c->qc, c->qlab, c->qf, c->from_floats.rows_valid || c->opt.keep_query_floats ? 1 : 0, &c->qf_resident, bad_codes, bad_labels,
                             c->census_q));
     queries_loaded(c, old_q, had_q);
     return HG_OK;
@@ -1325,7 +1323,7 @@ int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     // bit 2 = record lists beyond the LDS ordered group by group (k_real_group_*), bit 3 = the filter ran in IEEE half (else bfloat16)
     else if (!strcmp(key, "real_path")) *value = (c->real.filtered ? 1 : 0) | (c->real.lds_ranked ? 2 : 0) | (c->real.grouped ? 4 : 0) | (c->real.filtered && c->real.half ? 8 : 0);
     else if (!strcmp(key, "asym_calls")) *value = c->asym_calls;
-    else if (!strcmp(key, "asym_float_rows")) *value = c->asym_float_rows;
+    else if (!strcmp(key, "asym_float_rows")) *value = c->from_codes.rows_read;
     else if (!strcmp(key, "device_bytes")) *value = device_bytes(c);
 #ifdef HG_RANK_PROFILE
 #ifdef HG_RANK_PROFILE                        // (tools/rank_phase_profile.py: where k_rank_cnt left its phase timestamps)
@@ -1387,7 +1385,7 @@ int hg_get_census(hg_ctx* c, int queries, int64_t out[4]) {
     if (!c || !out) return fail(HG_ERR_ARG, "hg_get_census: null argument");
     const i64* cs = queries ? c->census_q : c->census_db;
     out[0] = cs[0]; out[1] = cs[1]; out[2] = cs[2];
-    out[3] = (queries ? c->qf_resident : c->dbf_resident) ? 1 : 0;
+    out[3] = (queries ? c->qf_resident : c->from_floats.rows_valid) ? 1 : 0;
     return HG_OK;
 }
 

@@ -12,7 +12,7 @@
 //   hg_pairs_mx.hip    launchers of the matrix-core pair passes (k_select_mx3 / mx4, k_hist_mx, k_hist_i8) and their images
 //   hg_pairs_mx1.hip   launcher of k_select_mx (every code length: the longest compile)
 //   hg_real.hip        real-valued (float32 inner product) ranking: a ladder of attempts, each with one RealReq down and one RealState (hg_ctx::real) up;
-//                      its asymmetric form (hg_topr_asym, hg_map_asym): the database's rows are its packed codes read as +-1 (hg_asym.hpp)
+//                      its asymmetric form (hg_topr_asym, hg_map_asym): the same call on the other RowSource, the database's packed codes read as +-1 (hg_asym.hpp)
 //   hg_comm.hip        RCCL collectives (library dlopen'ed on first use)
 //
 // No torch, no CPU compute path: every entry point either runs HIP kernels or fails.
@@ -349,7 +349,9 @@ struct StepReq {
 // What one attempt of the real-valued ranking (hg_real.hip) is asked to do.  Built by real_attempt and passed down by const reference
 // to the sample and select stages and their launchers; the stage that places the cut writes what it learns into the attempt's copy
 // before the stages after it see it, so a request ends with its attempt.
+struct RowSource;
 struct RealReq {
+    RowSource* src = nullptr;  // the database's rows this call ranks: the context's from_floats or from_codes (a requery child: its parent's)
     i64 R = 0;
     bool bet = false;          // cut at a sampled threshold `sigma` deviations deep, slices sized for `budget` x R records per query
     double sigma = 0.0, budget = 0.0;
@@ -372,21 +374,25 @@ struct RealState {
     i64 attempts = 0;          // stat "real_attempts": attempts of the last call (1 = the first bet held)
 };
 
+// What the real-valued ranking (hg_real.hip) reads and derives from the database's rows.  The context holds one per kind, each with its
+// own buffers and keys -- an image built from codes and one built from a float table never meet -- and a call is handed the one it runs
+// on (RealReq::src: hg_map_real from_floats, hg_map_asym from_codes); hg_real.hip's row-source section alone looks at the kind.
+struct RowSource {
+    enum Kind { FLOATS, CODES } kind;   // the loaded float table (hg_set_database_f32 / _dev with keep_floats) | the packed codes c->db read as +-1 (hg_asym.hpp)
+    DevBuf rows;               // f32 [N][bpad].  FLOATS: the table as loaded (BUF_TABLE; rows_valid: it is resident).  CODES: +-1.0 (pads 0) expanded on first
+                               // need per database (k_asym_expand_rows) for the paths that read float rows (no cut, vector fallbacks, real_mfma < 2): BUF_WORK
+    DevBuf rowsx;              // rows in MFMA A-fragment order (k_real_select_mx)
+    DevBuf img, xmax2;         // filter + rescore path (hg_real_bf.hpp): 16-bit image of the rows, their max norm^2 (ensure_filter_image)
+    bool rows_valid = false, rowsx_valid = false, img_valid = false;
+    bool img_half = false;     // img is in IEEE half instead of bfloat16 (no feature of the database can overflow it)
+    i64 rows_read = 0;         // CODES, stat "asym_float_rows": the last call read the expanded rows
+    void forget_derived() { rowsx_valid = img_valid = false; if (kind == CODES) rows_valid = false; }   // a database load, hg_trim: each is rebuilt on its next use
+};
+
 // The results of one side metric (hg_side.hip) and what they were computed from: the generations of the two tables, the rows Q, their
 // pitch Qpad (where the table is pitched), the second dimension (NB, C + 1, nk, nR or NB * G).  The entry point calls begin() first and finish()
 // last, so a refused or failed call leaves none; the getters, and hg_tie_ap for the histogram it reuses, ask current().  DESIGN.md, "Side metrics: the host side".
 struct hg_ctx;
-// The asymmetric ranking's own set of what the real-valued path reads and derives from the database's rows (hg_real.hip, hg_asym.hpp):
-// swapped in for the length of a call (hg_ctx::swap_rows) -- like ws_b for a blind step -- so an image built from codes and one built
-// from a float table never meet, and hg_map_real finds its own untouched.  A database load forgets all of it.
-struct AsymBufs {
-    DevBuf rows;               // f32 [N][bpad] of +-1.0 (pads 0) expanded from the codes on first need (k_asym_expand_rows): a work buffer for the
-                               // paths that still read float rows (no cut, vector fallbacks, real_mfma < 2), freed by hg_trim
-    DevBuf rowsx;              // ... and its float32 MFMA image (what dbfx is to dbf)
-    DevBuf img, xmax2;         // the filter's 16-bit image built from the codes (k_asym_image16) and its norm word (the host writes (float)b)
-    bool rows_valid = false, rowsx_valid = false, img_valid = false, img_half = false;
-    void forget() { rows_valid = rowsx_valid = img_valid = false; }
-};
 struct SideResult {
     bool done = false;
     unsigned long long q_gen = 0, db_gen = 0;
@@ -499,18 +505,10 @@ struct hg_ctx : StepBufs, StepState {
     int qstage_next = 0;
     bool ap_staged = false;
     bool ranked_local = false; // mbits holds this shard's bitmap in LOCAL rank order (hg_select_ranked)
-    bool dbfx_valid = false, dbfb_valid = false;
-    bool dbfb_half = false;    // dbfb is in IEEE half instead of bfloat16 (no feature of the database can overflow it: ensure_filter_image)
-    // the asymmetric ranking (hg_topr_asym / hg_map_asym): while a call runs its buffers stand where the float table's do
-    AsymBufs asym;
-    bool asym_on = false;      // swapped in: dbf / dbfx / dbfb / xmax2 and their keys are the asymmetric call's, the row source is c->db
+    // the two row sources of the real-valued ranking: hg_topr_real / hg_map_real run on the first, hg_topr_asym / hg_map_asym on the second
+    RowSource from_floats{RowSource::FLOATS}, from_codes{RowSource::CODES};
+    void forget_rows() { from_floats.forget_derived(); from_codes.forget_derived(); }
     i64 asym_calls = 0;        // stat "asym_calls": asymmetric calls that succeeded (cumulative)
-    i64 asym_float_rows = 0;   // stat "asym_float_rows": the last asymmetric call read the expanded float rows (asym.rows)
-    void swap_rows() {
-        std::swap(dbf, asym.rows); std::swap(dbfx, asym.rowsx); std::swap(dbfb, asym.img); std::swap(xmax2, asym.xmax2);
-        std::swap(dbf_resident, asym.rows_valid); std::swap(dbfx_valid, asym.rowsx_valid); std::swap(dbfb_valid, asym.img_valid); std::swap(dbfb_half, asym.img_half);
-        asym_on = !asym_on;
-    }
     i64 real_requeried = 0;       // queries that lost the first real-valued bet and were ranked again on their own (cumulative)
     int bpad = 0;              // feature count padded to a multiple of 16 (0: no float tables loaded)
     i64 census_db[3] = {0, 0, 0}, census_q[3] = {0, 0, 0};
@@ -522,7 +520,7 @@ struct hg_ctx : StepBufs, StepState {
     hipEvent_t fstage_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     void* hpk = nullptr;       // pinned staging for the packed tables
     size_t hpk_cap = 0;
-    bool dbf_resident = false, qf_resident = false;   // float tables as loaded: entries outside {-1,0,+1}, zeros, minus ones
+    bool qf_resident = false;  // the query float table as loaded is on the GPU (the database's: from_floats.rows_valid)
     RealState real;            // what the last attempt of a real-valued ranking left behind
     bool real_lists = false;   // hg_get_topr_real may hand out out_idx / scores: cleared where run_real begins, set once its ladder has succeeded
     i64 shapes_for_R = -1;
@@ -534,7 +532,7 @@ struct hg_ctx : StepBufs, StepState {
 
     // device buffers beyond the step's (StepBufs)
     DevBuf db, dblab, qc, qlab;                 // the packed tables: database codes and label words, query codes and label words
-    DevBuf dbf, qf;                             // the float tables (hg_set_*_f32 with keep_floats)
+    DevBuf qf;                                  // the queries' float table (hg_set_queries_f32 with the floats kept; the database's: from_floats.rows)
     DevBuf dbx, qx;            // fp4 images of db / qc in MFMA fragment order for k_select_mx (dbx_valid, qx_valid)
     DevBuf dbx8;               // i8 image of the database codes in A-fragment order (k_hist_i8; dbx8_valid)
     DevBuf rh_part, rh_all, rh_rel;   // hg_rel_hist: per-segment counters [S][2 NB][Qpad], the tables all / rel [NB][Qpad] (rh)
@@ -553,8 +551,6 @@ struct hg_ctx : StepBufs, StepState {
     DevBuf rr_base, rr_msz, rr_cnt, rr_scores;   // re-rank: a query's first record in its chunk [Q] x 8, records per query [Q] x 4, {groups in LDS, groups by radix}, the score lists [Q][R]
     DevBuf dbx3;               // fp4 image for k_select_mx3 (48-row supertiles, three rows per accumulator; dbx3_valid)
     DevBuf dbx4;               // fp4 image for k_select_mx4 (32-row supertiles, two rows per accumulator; codes of 65..128 bits; dbx4_valid)
-    DevBuf dbfx;               // float features of the database in MFMA A-fragment order (k_real_select_mx; dbfx_valid)
-    DevBuf dbfb, xmax2;        // filter + rescore path (hg_real_bf.hpp): 16-bit image of the database, max row norm^2 (dbfb_valid)
     DevBuf shapes, ap_recip;   // k_ap's summation trees (shapes_for_R) and reciprocals (recip_for_R)
     DevBuf seglt, segtie;
     DevBuf mbits2;             // hg_merge_ranked's output (swapped with mbits)
@@ -574,9 +570,10 @@ struct hg_ctx : StepBufs, StepState {
 
     // Every device buffer of the context, each once, with its class: hg_destroy, hg_trim and the stat "device_bytes" walk this.
     template <class F> void for_each_buf(F&& f) {
-        for (DevBuf* d : {&db, &dblab, &qc, &qlab, &dbf, &qf}) f(*d, BUF_TABLE);
-        for (DevBuf* d : {&dbx, &qx, &dbx8, &dbx3, &dbx4, &dbfx, &dbfb, &xmax2, &asym.rowsx, &asym.img, &asym.xmax2, &shapes, &ap_recip, &aa_recip}) f(*d, BUF_DERIVED);
-        f(asym.rows, BUF_WORK);
+        for (DevBuf* d : {&db, &dblab, &qc, &qlab, &from_floats.rows, &qf}) f(*d, BUF_TABLE);
+        for (DevBuf* d : {&dbx, &qx, &dbx8, &dbx3, &dbx4, &shapes, &ap_recip, &aa_recip}) f(*d, BUF_DERIVED);
+        for (RowSource* s : {&from_floats, &from_codes}) for (DevBuf* d : {&s->rowsx, &s->img, &s->xmax2}) f(*d, BUF_DERIVED);
+        f(from_codes.rows, BUF_WORK);
         for (DevBuf* d : {&seglt, &segtie, &mbits2, &part, &obuf[0], &obuf[1], &beyond, &stage_in, &badcnt, &flist, &dbytes, &samp, &thr,
                           &sortA, &sortB, &scores, &gtab, &sampx, &cntq, &krows, &thr2, &hist2, &comm_tmp, &gath_idx, &gath_dist, &rh_part, &rh_all, &rh_rel,
                           &gr_tab, &gr_out, &gr_grades, &gh_part, &gh_tab, &ta_tab, &ta_out, &aa_tab, &aa_out, &jh_max, &jh_part, &jh_tab, &vt_tab, &vt_votes, &vt_pred, &vt_conf,
@@ -589,8 +586,8 @@ struct hg_ctx : StepBufs, StepState {
     }
     // the keys of the BUF_DERIVED buffers: after this each is rebuilt on its next use
     void forget_derived() {
-        dbx_valid = qx_valid = dbx8_valid = dbx3_valid = dbx4_valid = dbfx_valid = dbfb_valid = false;
-        asym.forget();
+        dbx_valid = qx_valid = dbx8_valid = dbx3_valid = dbx4_valid = false;
+        forget_rows();
         for (SideResult* r : {&rh, &gr, &gh, &ta, &aa, &jh, &vt, &mrh, &mgh, &mjh, &mlg, &mlv, &rr}) r->begin();   // (hg_trim releases their tables with the other work buffers)
         shapes_for_R = recip_for_R = aa_recip_n = -1;
         outblk_q = ws_b.outblk_q = -1;

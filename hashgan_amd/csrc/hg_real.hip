@@ -4,9 +4,10 @@
 // One call is a ladder of attempts (run_real -> real_call -> real_ladder -> real_attempt).  An attempt builds one RealReq and passes it down by
 // const reference; what it leaves behind is c->real (RealState), assigned afresh when the attempt begins.
 //
-// The asymmetric form (run_asym: hg_topr_asym, hg_map_asym) is the same ladder with a second row source, the database's packed codes read
-// as +-1: for the length of the call the context's asymmetric buffers stand where the float table's do (hg_ctx::swap_rows), the filter's
-// image and the rescore come from the codes (hg_asym.hpp), and a stage that reads float rows asks float_rows() for them.
+// The database's rows come from a RowSource that travels with the call (RealReq::src): run_real picks the context's from_floats (the loaded
+// float table), run_asym (hg_topr_asym, hg_map_asym) from_codes (the packed codes read as +-1, hg_asym.hpp), and a requery child runs on its
+// parent's.  What differs between the two kinds -- float rows, 16-bit images, the filter's norm word, the rescore, the rows of the staged
+// sample -- is the section "the row source" below; nothing outside it reads RowSource::kind.
 #include "hg_ctx.hpp"
 #include "hg_real_kernels.hpp"
 #include "hg_real_mx.hpp"
@@ -38,6 +39,18 @@ template <int MAXKP, class F> int with_features(const hg_ctx* c, F&& f) {
 #undef HG_KP
     return fail(HG_ERR_ARG, "real-valued ranking supports up to %d features (have %d)", MAXKP, c->b);
 }
+// f(std::integral_constant<int, SG>{}) for the slices per wavefront the rescore kernels are built for (rescore_slices_per_wave picks among them;
+// a build with -DHG_RS_FORCE=n has that one alone)
+template <class F> int with_slices(int SG, F&& f) {
+#define HG_SG(sg) case sg: return f(std::integral_constant<int, sg>{});
+#ifdef HG_RS_FORCE
+    switch (SG) { HG_SG(HG_RS_FORCE) }
+#else
+    switch (SG) { HG_SG(8) HG_SG(6) HG_SG(4) HG_SG(3) HG_SG(2) HG_SG(1) }
+#endif
+#undef HG_SG
+    return fail(HG_ERR_ARG, "real-valued ranking: no rescore kernel for %d slices per wavefront", SG);
+}
 
 // ---- launch geometry ----
 inline int seg_pairs(const Geo& g) { return (g.S + 1) / 2; }
@@ -65,51 +78,124 @@ void cut_segments(Geo& g, i64 L) {
     g.nBlk = (int)((g.nUnits + WPB - 1) / WPB);
 }
 
-// ---- the row source ----
-// The database's float rows [N][bpad]: the loaded table -- or, while an asymmetric call runs, +-1.0 rows expanded from the codes into the
-// call's own work buffer on first need per database (k_asym_expand_rows; stat "asym_float_rows" says that a call came here)
-int float_rows(hg_ctx* c, const float** rows) {
-    if (c->asym_on) {
-        c->asym_float_rows = 1;
-        if (!c->dbf_resident) {
-            HG_TRY(c->dbf.reserve((size_t)c->N * c->bpad * 4 + 256));
+// ---- the row source (RealReq::src): what the FLOATS and the CODES kind do differently, and the only readers of RowSource::kind ----
+// The database's float rows [N][bpad]: the loaded table; from the codes, +-1.0 rows expanded into the source's work buffer on first need
+// per database (k_asym_expand_rows; stat "asym_float_rows" says that a call came here)
+int float_rows(hg_ctx* c, const RealReq& r, const float** rows) {
+    RowSource& s = *r.src;
+    if (s.kind == RowSource::CODES) {
+        s.rows_read = 1;
+        if (!s.rows_valid) {
+            HG_TRY(s.rows.reserve((size_t)c->N * c->bpad * 4 + 256));
             c->t_begin(KI_ASYM_EXPAND);
-            hipLaunchKernelGGL(k_asym_expand_rows, dim3(grid_for(c->N * (c->bpad / 4))), dim3(256), 0, c->stream, c->db.as<u32>(), c->dbf.as<float4>(),
+            hipLaunchKernelGGL(k_asym_expand_rows, dim3(grid_for(c->N * (c->bpad / 4))), dim3(256), 0, c->stream, c->db.as<u32>(), s.rows.as<float4>(),
                                (i64)c->N, c->bpad, c->NW, c->b, (i64)1);
             c->t_end();
             HG_TRY(c->check_launch("k_asym_expand_rows"));
-            c->dbf_resident = true;
+            s.rows_valid = true;
         }
     }
-    *rows = c->dbf.as<float>();
+    *rows = s.rows.as<float>();
+    return HG_OK;
+}
+// 16-bit image (IEEE half or bfloat16: the source's img_half) of every stride-th database row, `rows` of them padded to rows16, in MFMA fragment order
+void expand_image16(hg_ctx* c, const RealReq& r, DevBuf& dst, i64 rows, i64 rows16, int KP, i64 stride) {
+    const RowSource& s = *r.src;
+    const dim3 grid(grid_for(rows16 * (KP / 8)));
+    with_bool(s.img_half, [&](auto half) {
+        if (s.kind == RowSource::CODES)
+            hipLaunchKernelGGL(k_asym_image16<half>, grid, dim3(256), 0, c->stream, c->db.as<u32>(), dst.as<uint4>(), rows, rows16, KP, c->NW, c->b, stride);
+        else
+            hipLaunchKernelGGL(k_expand_dbf_bf16<half>, grid, dim3(256), 0, c->stream, s.rows.as<float>(), dst.as<uint4>(), rows, rows16, KP, stride);
+        return HG_OK;
+    });
+}
+// The filter's 16-bit image of the database, built on first use, and with it the largest row norm^2 (xmax2: k_real_thr2's margin) and the
+// choice between IEEE half and bfloat16 -- once per database.  FLOATS: k_row_norm_max, one 4-byte download and a wait.  CODES: +-1 is exact
+// in either format and every row's norm^2 is exactly b -- the host writes that itself, a fill on the stream: no kernel, no download, no wait.
+int ensure_filter_image(hg_ctx* c, const RealReq& r) {
+    RowSource& s = *r.src;
+    if (s.img_valid) return HG_OK;
+    const bool codes = s.kind == RowSource::CODES;
+    const int KP = c->bpad;
+    const i64 n16 = (c->N + 15) / 16 * 16;
+    HG_TRY(s.img.reserve((size_t)n16 * KP * 2));
+    HG_TRY(s.xmax2.reserve(4));
+    float xm = (float)c->b;
+    if (codes) {
+        u32 xbits;
+        memcpy(&xbits, &xm, 4);
+        HG_HIP(hipMemsetD32Async((hipDeviceptr_t)s.xmax2.p, (int)xbits, 1, c->stream));
+        c->t_begin(KI_ASYM_IMAGE);
+    } else {
+        HG_HIP(hipMemsetAsync(s.xmax2.p, 0, 4, c->stream));
+        c->t_begin(KI_PACK);
+        hipLaunchKernelGGL(k_row_norm_max, dim3(grid_for(c->N)), dim3(256), 0, c->stream, s.rows.as<float>(), (i64)c->N, KP, s.xmax2.as<u32>());
+        HG_HIP(hipMemcpyAsync(&xm, s.xmax2.p, 4, hipMemcpyDeviceToHost, c->stream));
+        HG_TRY(c->sync());
+    }
+    // IEEE half (three more significant bits: a margin an eighth of bfloat16's) when no feature can overflow it (every |x_k| <= the row's
+    // norm < 2^15) and the rows are not tiny either: half's error has an absolute floor -- subnormals, flushed or not -- that outgrows the
+    // relative term once norms fall below ~0.1; bfloat16 has float32's exponents and no such floor
+    s.img_half = c->opt.real_mfma == 2 && xm >= 1.0f && xm < 1073741824.0f;         // 1 <= largest row norm^2 < 2^30 (inf and the NaN marker fail the test)
+    expand_image16(c, r, s.img, c->N, n16, KP, 1);
+    c->t_end();
+    HG_TRY(c->check_launch(codes ? "k_asym_image16" : "k_expand_dbf_bf16"));
+    s.img_valid = true;
+    return HG_OK;
+}
+// The exact scores of the rows the filter kept: wavefront = (SG slices, query), `waves` of them.  FLOATS: k_real_rescore gathers the kept
+// rows' float rows through LDS.  CODES: k_asym_rescore reads their code words instead (no LDS), the word count a template argument up to two.
+template <int KP> int launch_rescore(hg_ctx* c, const RealReq& r, int SG, i64 waves) {
+    const Geo& g = c->geo;
+    const bool codes = r.src->kind == RowSource::CODES;
+    const float* rows = nullptr;
+    if (!codes) HG_TRY(float_rows(c, r, &rows));
+    c->t_begin(codes ? KI_ASYM_RESCORE : KI_REAL_RESCORE);
+    HG_TRY(with_slices(SG, [&](auto sg) {
+        auto from_codes = [&](auto nwt) {
+            hipLaunchKernelGGL((k_asym_rescore<nwt, sg>), dim3(grid_for(waves, WPB)), dim3(256), 0, c->stream, c->qf.as<float>(), c->db.as<u32>(),
+                               c->sl_cnt.as<u32>(), c->krows.as<u32>(), c->cand.as<u64>(), c->cap, c->crow, c->thr.as<float>(), c->sl_cnt.as<u32>(),
+                               c->cntq.as<u32>(), c->dblab.as<u64>(), c->qlab.as<u64>(), r.no_cut ? 0 : 1, KP, c->NW, c->b, g);
+            return HG_OK;
+        };
+        if (codes)       // (the code words: one, two, or NW at run time)
+            return c->NW == 1 ? from_codes(std::integral_constant<int, 1>{}) : c->NW == 2 ? from_codes(std::integral_constant<int, 2>{}) : from_codes(std::integral_constant<int, 0>{});
+        hipLaunchKernelGGL((k_real_rescore<(KP <= 128 ? KP : 0), sg>), dim3(grid_for(waves, WPB)), dim3(256), rescore_lds_bytes(), c->stream, c->qf.as<float>(),
+                           rows, c->sl_cnt.as<u32>(), c->krows.as<u32>(), c->cand.as<u64>(), c->cap, c->crow, c->thr.as<float>(),
+                           c->sl_cnt.as<u32>(), c->cntq.as<u32>(), c->dblab.as<u64>(), c->qlab.as<u64>(), r.no_cut ? 0 : 1, KP, g);
+        return HG_OK;
+    }));
+    c->t_end();
+    return c->check_launch(codes ? "k_asym_rescore" : "k_real_rescore");
+}
+// Float rows for the staged sample beyond 128 features (k_real_sample_any), inside its timing slot, which this opens and the caller closes:
+// every *stride-th row of the table -- or, from the codes, the M sampled rows alone expanded into the sample's own per-call buffer (a few MB,
+// like the 16-bit sample images; *stride becomes 1), so that a bet on more than 128 features never asks for the whole database as floats
+int sampled_rows(hg_ctx* c, const RealReq& r, i64 M, i64* stride, const float** rows) {
+    if (r.src->kind == RowSource::CODES) {
+        HG_TRY(c->sampx.reserve((size_t)M * c->bpad * 4 + 256));
+        c->t_begin(KI_REAL_SAMPLE);
+        hipLaunchKernelGGL(k_asym_expand_rows, dim3(grid_for(M * (c->bpad / 4))), dim3(256), 0, c->stream, c->db.as<u32>(), c->sampx.as<float4>(),
+                           M, c->bpad, c->NW, c->b, *stride);
+        *rows = c->sampx.as<float>();
+        *stride = 1;
+        return HG_OK;
+    }
+    HG_TRY(float_rows(c, r, rows));
+    c->t_begin(KI_REAL_SAMPLE);
     return HG_OK;
 }
 
 // ---- pair passes ----
-// 16-bit image (IEEE half or bfloat16: c->dbfb_half) of every stride-th database row, `rows` of them padded to rows16, in MFMA fragment order
-void expand_image16(hg_ctx* c, DevBuf& dst, i64 rows, i64 rows16, int KP, i64 stride) {
-    if (c->asym_on) {
-        with_bool(c->dbfb_half, [&](auto half) {
-            hipLaunchKernelGGL(k_asym_image16<half>, dim3(grid_for(rows16 * (KP / 8))), dim3(256), 0, c->stream, c->db.as<u32>(),
-                               dst.as<uint4>(), rows, rows16, KP, c->NW, c->b, stride);
-            return HG_OK;
-        });
-        return;
-    }
-    with_bool(c->dbfb_half, [&](auto half) {
-        hipLaunchKernelGGL(k_expand_dbf_bf16<half>, dim3(grid_for(rows16 * (KP / 8))), dim3(256), 0, c->stream, c->dbf.as<float>(),
-                           dst.as<uint4>(), rows, rows16, KP, stride);
-        return HG_OK;
-    });
-}
 // the sample's scores feed only the cut: with the 16-bit filter behind it the sample runs in the same arithmetic ("real_mfma" 1 keeps the exact chains)
 bool sample_in_16bit(const hg_ctx* c) { return c->bpad <= 128 && c->opt.real_mfma == 2 && c->opt.real_sample_half && c->geo.L % 16 == 0; }
 
-template <int BP> int real_launch_sample(hg_ctx* c, i64 M, i64 stride) {
+template <int BP> int real_launch_sample(hg_ctx* c, const RealReq& r, i64 M, i64 stride) {
     const Geo& g = c->geo;
     const i64 units = (M + 63) / 64 * g.nQT;
     const float* dbf;
-    HG_TRY(float_rows(c, &dbf));
+    HG_TRY(float_rows(c, r, &dbf));
     c->t_begin(KI_REAL_SAMPLE);
     hipLaunchKernelGGL(k_real_sample<BP>, dim3(grid_for(units, WPB)), dim3(256), (size_t)WPB * 64 * 65 * 4, c->stream,
                        c->qf.as<float>(), dbf, c->samp.as<float>(), M, stride, g);
@@ -117,11 +203,11 @@ template <int BP> int real_launch_sample(hg_ctx* c, i64 M, i64 stride) {
     return c->check_launch("k_real_sample");
 }
 // (one query per lane: the call's own geometry, a unit = one segment x 64 queries)
-template <int BP> int real_launch_select(hg_ctx* c) {
+template <int BP> int real_launch_select(hg_ctx* c, const RealReq& r) {
     const Geo& g = c->geo;
     RealSelArgs a{c->thr.as<float>(), c->sl_cnt.as<u32>(), c->failq.as<u32>(), c->cap, c->crow};
     const float* dbf;
-    HG_TRY(float_rows(c, &dbf));
+    HG_TRY(float_rows(c, r, &dbf));
     c->t_begin(KI_REAL_SELECT);
     hipLaunchKernelGGL((k_real_select<BP, 1>), dim3(padded_grid(g.nBlk)), dim3(256), 0, c->stream, c->qf.as<float>(),
                        dbf, a, c->cand.as<u64>(), g);
@@ -129,75 +215,28 @@ template <int BP> int real_launch_select(hg_ctx* c) {
     return c->check_launch("k_real_select");
 }
 // real-valued select on the matrix cores: blocks = (pair of segments) x (256 queries)
-template <int KP> int real_launch_select_mx(hg_ctx* c) {
-    if (!c->dbfx_valid) {
+template <int KP> int real_launch_select_mx(hg_ctx* c, const RealReq& r) {
+    RowSource& s = *r.src;
+    if (!s.rowsx_valid) {
         const i64 n16 = (c->N + 15) / 16 * 16;
-        HG_TRY(c->dbfx.reserve((size_t)n16 * KP * 4));
+        HG_TRY(s.rowsx.reserve((size_t)n16 * KP * 4));
         const i64 items = n16 * (KP / 4);
         const float* dbf;
-        HG_TRY(float_rows(c, &dbf));
+        HG_TRY(float_rows(c, r, &dbf));
         c->t_begin(KI_PACK);
-        hipLaunchKernelGGL(k_expand_dbf, dim3(grid_for(items)), dim3(256), 0, c->stream, dbf, c->dbfx.as<float4>(),
+        hipLaunchKernelGGL(k_expand_dbf, dim3(grid_for(items)), dim3(256), 0, c->stream, dbf, s.rowsx.as<float4>(),
                            (i64)c->N, n16, KP, (i64)1);
         c->t_end();
         HG_TRY(c->check_launch("k_expand_dbf"));
-        c->dbfx_valid = true;
+        s.rowsx_valid = true;
     }
     const Geo g = pair_geometry(c->geo, c->geo.N, 0, REAL_MX_QPB);
     RealSelArgs a{c->thr.as<float>(), c->sl_cnt.as<u32>(), c->failq.as<u32>(), c->cap, c->crow};
     c->t_begin(KI_REAL_SELECT);
     hipLaunchKernelGGL((k_real_select_mx<KP>), dim3(padded_grid(g.nBlk)), dim3(256), 0, c->stream,
-                       c->qf.as<float>(), c->dbfx.as<u8>(), a, c->cand.as<u64>(), g);
+                       c->qf.as<float>(), s.rowsx.as<u8>(), a, c->cand.as<u64>(), g);
     c->t_end();
     return c->check_launch("k_real_select_mx");
-}
-// filter + rescore (hg_real_bf.hpp): bf16 pair pass with a rigorous margin, then the exact chain for the survivors
-// the filter's 16-bit image of the database (and the choice between IEEE half and bfloat16), built on first use
-// (an asymmetric call's, from the codes: +-1 is exact in either format and every row's norm^2 is exactly b -- the host writes that itself,
-// a fill on the stream: no k_row_norm_max, no download, no wait)
-int ensure_code_image(hg_ctx* c) {
-    const int KP = c->bpad;
-    if (!c->dbfb_valid) {
-        const i64 n16 = (c->N + 15) / 16 * 16;
-        HG_TRY(c->dbfb.reserve((size_t)n16 * KP * 2));
-        HG_TRY(c->xmax2.reserve(4));
-        const float xm = (float)c->b;
-        u32 xbits;
-        memcpy(&xbits, &xm, 4);
-        HG_HIP(hipMemsetD32Async((hipDeviceptr_t)c->xmax2.p, (int)xbits, 1, c->stream));
-        c->dbfb_half = c->opt.real_mfma == 2 && xm >= 1.0f && xm < 1073741824.0f;          // (ensure_filter_image's rule)
-        c->t_begin(KI_ASYM_IMAGE);
-        expand_image16(c, c->dbfb, c->N, n16, KP, 1);
-        c->t_end();
-        HG_TRY(c->check_launch("k_asym_image16"));
-        c->dbfb_valid = true;
-    }
-    return HG_OK;
-}
-int ensure_filter_image(hg_ctx* c) {
-    if (c->asym_on) return ensure_code_image(c);
-    const int KP = c->bpad;
-    if (!c->dbfb_valid) {
-        const i64 n16 = (c->N + 15) / 16 * 16;
-        HG_TRY(c->dbfb.reserve((size_t)n16 * KP * 2));
-        HG_TRY(c->xmax2.reserve(4));
-        HG_HIP(hipMemsetAsync(c->xmax2.p, 0, 4, c->stream));
-        c->t_begin(KI_PACK);
-        hipLaunchKernelGGL(k_row_norm_max, dim3(grid_for(c->N)), dim3(256), 0, c->stream, c->dbf.as<float>(), (i64)c->N, KP, c->xmax2.as<u32>());
-        // Which 16-bit format the filter's image takes -- once per database, one 4-byte download: IEEE half (three more significant
-        // bits: a margin an eighth of bfloat16's) when no feature can overflow it (every |x_k| <= the row's norm < 2^15), else bfloat16
-        float xm = 0.0f;
-        HG_HIP(hipMemcpyAsync(&xm, c->xmax2.p, 4, hipMemcpyDeviceToHost, c->stream));
-        HG_TRY(c->sync());
-        // (... and when the rows are not tiny either: half's error has an absolute floor -- subnormals, flushed or not -- that outgrows
-        // the relative term once norms fall below ~0.1; bfloat16 has float32's exponents and no such floor)
-        c->dbfb_half = c->opt.real_mfma == 2 && xm >= 1.0f && xm < 1073741824.0f;         // 1 <= largest row norm^2 < 2^30 (inf and the NaN marker fail the test)
-        expand_image16(c, c->dbfb, c->N, n16, KP, 1);
-        c->t_end();
-        HG_TRY(c->check_launch("k_expand_dbf_bf16"));
-        c->dbfb_valid = true;
-    }
-    return HG_OK;
 }
 // Slices per wavefront of the rescoring pass.  The kernel's time follows its ROUNDS of 64 rows and its wavefronts, hardly its rows
 // (10k x 1M x 64, R = 5000, 17 rows per slice: 1 slice 4.04 ms, 2 2.41, 3 2.06, 4 2.12, 5 2.05, 6 1.90, 7 1.92, 8 2.07, 11 2.20), so
@@ -225,38 +264,17 @@ int rescore_slices_per_wave(double per_slice) {
     return SG;
 #endif
 }
-// the asymmetric call's rescore: the kept rows' code words instead of their float rows (k_asym_rescore: no LDS)
-int launch_asym_rescore(hg_ctx* c, const RealReq& r, int SG, i64 waves, int KP) {
-    const Geo& g = c->geo;
-    const int nwt = c->NW <= 2 ? c->NW : 0;
-    c->t_begin(KI_ASYM_RESCORE);
-#define HG_ARESCORE(nw, sg)                                                                                                              \
-    hipLaunchKernelGGL((k_asym_rescore<nw, sg>), dim3(grid_for(waves, WPB)), dim3(256), 0, c->stream, c->qf.as<float>(), c->db.as<u32>(),  \
-                       c->sl_cnt.as<u32>(), c->krows.as<u32>(), c->cand.as<u64>(), c->cap, c->crow, c->thr.as<float>(), c->sl_cnt.as<u32>(), \
-                       c->cntq.as<u32>(), c->dblab.as<u64>(), c->qlab.as<u64>(), r.no_cut ? 0 : 1, KP, c->NW, c->b, g)
-#define HG_ARESCORE_SG(sg)                                                                                                               \
-    case sg:                                                                                                                             \
-        if (nwt == 1) HG_ARESCORE(1, sg); else if (nwt == 2) HG_ARESCORE(2, sg); else HG_ARESCORE(0, sg);                                \
-        break;
-#ifdef HG_RS_FORCE
-    switch (SG) { HG_ARESCORE_SG(HG_RS_FORCE) }
-#else
-    switch (SG) { HG_ARESCORE_SG(8) HG_ARESCORE_SG(6) HG_ARESCORE_SG(4) HG_ARESCORE_SG(3) HG_ARESCORE_SG(2) HG_ARESCORE_SG(1) }
-#endif
-#undef HG_ARESCORE_SG
-#undef HG_ARESCORE
-    c->t_end();
-    return c->check_launch("k_asym_rescore");
-}
+// filter + rescore (hg_real_bf.hpp): bf16 pair pass with a rigorous margin, then the exact chain for the survivors
 template <int KP> int real_launch_select_bf(hg_ctx* c, const RealReq& r) {
     constexpr int QT = KP <= 128 ? 2 : 1;
-    HG_TRY(ensure_filter_image(c));
-    c->real.half = c->dbfb_half;
+    HG_TRY(ensure_filter_image(c, r));
+    const RowSource& s = *r.src;
+    c->real.half = s.img_half;
     const Geo& g = c->geo;
     HG_TRY(c->thr2.reserve((size_t)g.Qpad * 4));
     c->t_begin(KI_REAL_GUESS);
     hipLaunchKernelGGL(k_real_thr2, dim3(grid_for(g.Q)), dim3(256), 0, c->stream, c->qf.as<float>(), c->thr.as<float>(),
-                       c->xmax2.as<u32>(), c->thr2.as<float>(), g.Q, KP, c->dbfb_half ? 1.0 / 1024.0 : 1.0 / 256.0, c->dbfb_half ? 1.0 / 16384.0 : 0.0);
+                       s.xmax2.as<u32>(), c->thr2.as<float>(), g.Q, KP, s.img_half ? 1.0 / 1024.0 : 1.0 / 256.0, s.img_half ? 1.0 / 16384.0 : 0.0);
     c->t_end();
     HG_TRY(c->check_launch("k_real_thr2"));
     const Geo gs = pair_geometry(g, g.N, 0, WPB * 32 * QT);
@@ -267,11 +285,11 @@ template <int KP> int real_launch_select_bf(hg_ctx* c, const RealReq& r) {
     // furthest it can get is the wavefront's 64 record rows plus one segment)
     const bool far_rows = (64ull * (unsigned long long)c->crow + (unsigned long long)g.L) * 4ull >= (1ull << 32);
     c->t_begin(KI_REAL_SELECT);
-    HG_TRY(with_bool(c->dbfb_half, [&](auto half) { return with_bool(far_rows, [&](auto far_) {
+    HG_TRY(with_bool(s.img_half, [&](auto half) { return with_bool(far_rows, [&](auto far_) {
         if (real_bf_lds_bytes(KP) > 64 * 1024)
             HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_real_select_bf<KP, QT, half, far_>), hipFuncAttributeMaxDynamicSharedMemorySize, real_bf_lds_bytes(KP)));
         hipLaunchKernelGGL((k_real_select_bf<KP, QT, half, far_>), dim3(padded_grid(gs.nBlk)), dim3(256), real_bf_lds_bytes(KP), c->stream,
-                           c->qf.as<float>(), c->dbfb.as<u8>(), c->thr2.as<float>(), a, c->krows.as<u32>(), gs);
+                           c->qf.as<float>(), s.img.as<u8>(), c->thr2.as<float>(), a, c->krows.as<u32>(), gs);
         return HG_OK;
     }); }));
     c->t_end();
@@ -280,31 +298,14 @@ template <int KP> int real_launch_select_bf(hg_ctx* c, const RealReq& r) {
     const int SG = rescore_slices_per_wave(1.03 * r.expect / (double)g.S);
     const i64 waves = (i64)((g.S + SG - 1) / SG) * g.Q;
     HG_TRY(c->cntq.reserve((size_t)g.Q * g.S * 4));
-    if (c->asym_on) return launch_asym_rescore(c, r, SG, waves, KP);
-    const float* dbf;
-    HG_TRY(float_rows(c, &dbf));
-    c->t_begin(KI_REAL_RESCORE);
-#define HG_RESCORE(sg)                                                                                                                   \
-    case sg:                                                                                                                             \
-        hipLaunchKernelGGL((k_real_rescore<(KP <= 128 ? KP : 0), sg>), dim3(grid_for(waves, WPB)), dim3(256), rescore_lds_bytes(), c->stream, c->qf.as<float>(),  \
-                           dbf, c->sl_cnt.as<u32>(), c->krows.as<u32>(), c->cand.as<u64>(), c->cap, c->crow, c->thr.as<float>(), \
-                           c->sl_cnt.as<u32>(), c->cntq.as<u32>(), c->dblab.as<u64>(), c->qlab.as<u64>(), r.no_cut ? 0 : 1, KP, g);                         \
-        break;
-#ifdef HG_RS_FORCE
-    switch (SG) { HG_RESCORE(HG_RS_FORCE) }
-#else
-    switch (SG) { HG_RESCORE(8) HG_RESCORE(6) HG_RESCORE(4) HG_RESCORE(3) HG_RESCORE(2) HG_RESCORE(1) }
-#endif
-#undef HG_RESCORE
-    c->t_end();
-    return c->check_launch("k_real_rescore");
+    return launch_rescore<KP>(c, r, SG, waves);
 }
 // sample pass on the float32 MFMA: image of the M sampled rows (rebuilt per call: a few MB), ~32 segments (16 pairs)
-template <int KP> int real_launch_sample_mx(hg_ctx* c, i64 M, i64 stride, i64 mstride) {
+template <int KP> int real_launch_sample_mx(hg_ctx* c, const RealReq& r, i64 M, i64 stride, i64 mstride) {
     const i64 m16 = (M + 15) / 16 * 16;
     HG_TRY(c->sampx.reserve((size_t)m16 * KP * 4));
     const float* dbf;
-    HG_TRY(float_rows(c, &dbf));
+    HG_TRY(float_rows(c, r, &dbf));
     c->t_begin(KI_REAL_SAMPLE);
     hipLaunchKernelGGL(k_expand_dbf, dim3(grid_for(m16 * (KP / 4))), dim3(256), 0, c->stream, dbf, c->sampx.as<float4>(),
                        M, m16, KP, stride);
@@ -316,13 +317,13 @@ template <int KP> int real_launch_sample_mx(hg_ctx* c, i64 M, i64 stride, i64 ms
 }
 // sample pass in the filter's 16-bit arithmetic (k_real_sample_h): the sampled rows' image rebuilt per call (1.6 MB at 10k x 1M), ~32 segments
 template <int KP> int real_launch_sample_h(hg_ctx* c, const RealReq& r, i64 M, i64 stride, i64 mstride) {
-    HG_TRY(ensure_filter_image(c));                      // (decides half / bfloat16 for this database)
+    HG_TRY(ensure_filter_image(c, r));                   // (decides half / bfloat16 for this database)
     const i64 m16 = (M + 15) / 16 * 16;
     HG_TRY(c->sampx.reserve((size_t)m16 * KP * 2));
     c->t_begin(KI_REAL_SAMPLE);
-    expand_image16(c, c->sampx, M, m16, KP, stride);
+    expand_image16(c, r, c->sampx, M, m16, KP, stride);
     const Geo g = pair_geometry(c->geo, M, 32, WPB * 64);
-    with_bool(c->dbfb_half, [&](auto half) { return with_bool(r.samp16, [&](auto o16) {
+    with_bool(r.src->img_half, [&](auto half) { return with_bool(r.samp16, [&](auto o16) {
         hipLaunchKernelGGL((k_real_sample_h<KP, half, o16>), dim3(padded_grid(g.nBlk)), dim3(256), 0, c->stream, c->qf.as<float>(),
                            c->sampx.as<u8>(), c->samp.as<float>(), mstride, g);
         return HG_OK;
@@ -331,17 +332,17 @@ template <int KP> int real_launch_sample_h(hg_ctx* c, const RealReq& r, i64 M, i
     return c->check_launch("k_real_sample_h");
 }
 // the second, counting sample (k_real_sample_count + k_real_guess2): thr[q] moves up to the deepest cut a four times larger sample supports
-template <int KP> int real_launch_sample_count(hg_ctx* c, i64 M2, i64 stride2, u32 need2) {
+template <int KP> int real_launch_sample_count(hg_ctx* c, const RealReq& r, i64 M2, i64 stride2, u32 need2) {
     const Geo& g0 = c->geo;
     const i64 m16 = (M2 + 15) / 16 * 16;
     HG_TRY(c->sampx.reserve((size_t)m16 * KP * 2));     // (sized for this pass before the first one ran: place_cut)
     c->t_begin(KI_REAL_SAMPLE);
-    expand_image16(c, c->sampx, M2, m16, KP, stride2);
+    expand_image16(c, r, c->sampx, M2, m16, KP, stride2);
     const Geo g = pair_geometry(g0, M2, 64, WPB * 64);   // ~64 segments (32 pairs; 16 .. 256 segments measured: 32 and up the same)
     const int nSP = seg_pairs(g);
     HG_TRY(c->hist2.reserve((size_t)nSP * g.Qpad * RC_BINS * 4 + (size_t)WPB * 64 * RC_BINS * 4));      // [segment pair][Qpad][bin], every word written (+ a block's overhang past Qpad)
     constexpr int lds = real_count_lds_bytes(KP);
-    HG_TRY(with_bool(c->dbfb_half, [&](auto half) {
+    HG_TRY(with_bool(r.src->img_half, [&](auto half) {
         if (lds > 64 * 1024) HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_real_sample_count<KP, half>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         hipLaunchKernelGGL((k_real_sample_count<KP, half>), dim3(padded_grid(g.nBlk)), dim3(256), lds, c->stream, c->qf.as<float>(), c->sampx.as<u8>(),
                            c->thr.as<float>(), c->hist2.as<u32>(), g);
@@ -357,30 +358,21 @@ template <int KP> int real_launch_sample_count(hg_ctx* c, i64 M2, i64 stride2, u
 // scores of every stride-th row (M of them) into samp[q][mstride]
 int real_sample(hg_ctx* c, const RealReq& r, i64 M, i64 stride, i64 mstride) {
     if (sample_in_16bit(c)) return with_features<128>(c, [&](auto kp) { return real_launch_sample_h<kp>(c, r, M, stride, mstride); });
-    if (c->bpad <= 128 && c->opt.real_mfma) return with_features<128>(c, [&](auto kp) { return real_launch_sample_mx<kp>(c, M, stride, mstride); });
+    if (c->bpad <= 128 && c->opt.real_mfma) return with_features<128>(c, [&](auto kp) { return real_launch_sample_mx<kp>(c, r, M, stride, mstride); });
     if (c->bpad > 128) {                                 // k_real_sample keeps the query in registers: the staged form beyond
         const Geo& g = c->geo;
         const i64 units = (M + 63) / 64 * g.nQT;
         const size_t lds = (size_t)WPB * (64 * 65 * 4 + 16 * 128);
         HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_real_sample_any), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        // (an asymmetric call: the M sampled rows alone are expanded, into the sample's own per-call buffer -- a few MB, like the 16-bit
-        // sample images -- so that a bet on more than 128 features never asks for the whole database as floats)
         const float* dbf = nullptr;
-        if (c->asym_on) HG_TRY(c->sampx.reserve((size_t)M * c->bpad * 4 + 256)); else HG_TRY(float_rows(c, &dbf));
-        c->t_begin(KI_REAL_SAMPLE);
-        if (c->asym_on) {
-            hipLaunchKernelGGL(k_asym_expand_rows, dim3(grid_for(M * (c->bpad / 4))), dim3(256), 0, c->stream, c->db.as<u32>(), c->sampx.as<float4>(),
-                               M, c->bpad, c->NW, c->b, stride);
-            dbf = c->sampx.as<float>();
-            stride = 1;
-        }
+        HG_TRY(sampled_rows(c, r, M, &stride, &dbf));      // (opens the sample's timing slot)
         hipLaunchKernelGGL(k_real_sample_any, dim3(grid_for(units, WPB)), dim3(256), lds, c->stream, c->qf.as<float>(), dbf,
                            c->samp.as<float>(), M, stride, c->bpad, g);
         c->t_end();
         return c->check_launch("k_real_sample_any");
     }
     // (the vector kernels write samp[q][M] densely: the caller passes mstride = M)
-    return with_features<128>(c, [&](auto kp) { return real_launch_sample<kp / 2>(c, M, stride); });
+    return with_features<128>(c, [&](auto kp) { return real_launch_sample<kp / 2>(c, r, M, stride); });
 }
 // the pair pass over the whole database; *filtered = it left unscored candidates that k_real_rescore completed
 int real_select(hg_ctx* c, const RealReq& r, bool* filtered) {
@@ -393,8 +385,8 @@ int real_select(hg_ctx* c, const RealReq& r, bool* filtered) {
         *filtered = true;
         return HG_OK;
     }
-    if (c->opt.real_mfma && c->geo.L % 16 == 0) return with_features<128>(c, [&](auto kp) { return real_launch_select_mx<kp>(c); });
-    return with_features<128>(c, [&](auto kp) { return real_launch_select<kp / 2>(c); });
+    if (c->opt.real_mfma && c->geo.L % 16 == 0) return with_features<128>(c, [&](auto kp) { return real_launch_select_mx<kp>(c, r); });
+    return with_features<128>(c, [&](auto kp) { return real_launch_select<kp / 2>(c, r); });
 }
 
 // ---- one attempt, stage by stage: geometry -> cut (or none) -> select -> one of three rank tails ----
@@ -461,7 +453,7 @@ int place_cut(hg_ctx* c, RealReq& r) {
     if (second) {
         const double fr2 = (double)R * (double)M2 / (double)c->N;
         const u32 need2 = (u32)std::ceil(fr2 + r.sigma * std::sqrt(fr2)) + 1u;
-        HG_TRY(with_features<128>(c, [&](auto kp) { return real_launch_sample_count<kp>(c, M2, stride2, need2); }));
+        HG_TRY(with_features<128>(c, [&](auto kp) { return real_launch_sample_count<kp>(c, r, M2, stride2, need2); }));
         r.expect = (double)R * (1.0 + r.sigma / std::sqrt(fr2 > 1.0 ? fr2 : 1.0));
     }
     const double mean = r.budget * (double)R / (double)g.S;
@@ -596,12 +588,12 @@ int rank_by_radix(hg_ctx* c, const RealReq& r, size_t rows, int* lost) {
 
 // ---- real-valued ranking: sample -> guess -> select (filter + rescore) -> rank in LDS, group by group, or by radix passes ----
 // one attempt; *lost = some query came up short of R records or overflowed a slice (bet mode only)
-int real_attempt(hg_ctx* c, int64_t R, bool bet, double sigma, double budget, bool with_ap, int* lost) {
+int real_attempt(hg_ctx* c, RowSource& src, int64_t R, bool bet, double sigma, double budget, bool with_ap, int* lost) {
     RealState fresh;
     fresh.attempts = c->real.attempts + 1;
     c->real = fresh;
     RealReq req;
-    req.R = R; req.bet = bet; req.sigma = sigma; req.budget = budget; req.with_ap = with_ap;
+    req.src = &src; req.R = R; req.bet = bet; req.sigma = sigma; req.budget = budget; req.with_ap = with_ap;
     req.no_cut = !bet;
     req.expect = bet ? (double)R * (1.0 + sigma / std::sqrt((double)REAL_SAMPLE_HITS)) : (double)c->N;      // (a second sample lowers it: place_cut)
     // hg_map_real wants match bits and APs: the kernels that rank in LDS skip the idx / score lists then (Q x R x 8 bytes of stores: 0.4 GB at
@@ -644,13 +636,13 @@ int real_attempt(hg_ctx* c, int64_t R, bool bet, double sigma, double budget, bo
     return rank_by_radix(c, req, rows, lost);
 }
 
-int real_call(hg_ctx* c, int64_t R, bool with_ap);
+int real_call(hg_ctx* c, RowSource& src, int64_t R, bool with_ap);
 
 // A few queries lost the first bet (their cut kept fewer than R rows, or their rows crowd into one slice): those alone run again,
-// on a child context that borrows the database's tables, with the usual escalation; their lists and match bits go back into the
+// on a child context that borrows the database's tables and runs on the parent's row source, with the usual escalation; their lists and match bits go back into the
 // parent's rows and the parent evaluates all queries.  The whole call is redone only when many queries lost (real_ladder).  Because a
 // lost query now costs a fraction of a millisecond instead of the call, the first cut can sit shallower (REAL_FIRST_SIGMA).
-int real_requery_lost(hg_ctx* c, int64_t R, bool with_ap, bool* handled) {
+int real_requery_lost(hg_ctx* c, RowSource& src, int64_t R, bool with_ap, bool* handled) {
     *handled = false;
     if (c->is_sub || !c->real.lds_ranked || !c->real.filtered) return HG_OK;
     const Geo g = c->geo;
@@ -663,18 +655,12 @@ int real_requery_lost(hg_ctx* c, int64_t R, bool with_ap, bool* handled) {
     if (nF == 0 || nF * 16 > g.Q) return HG_OK;
     hg_ctx* s = requery_child(c, nF);
     s->real_cap_boost = c->real_cap_boost;
-    // (the child borrows the tables the parent ran on: an asymmetric call's are its images from the codes, and its expanded rows if it has any --
-    // a child that needs them without builds its own; the float32 MFMA image is the child's, so it is never carried from one source to the other)
-    s->dbf.borrow(c->dbf); s->dbf_resident = c->dbf_resident;
-    s->dbfb.borrow(c->dbfb); s->xmax2.borrow(c->xmax2); s->dbfb_valid = c->dbfb_valid; s->dbfb_half = c->dbfb_half;
-    if (c->asym_on || s->asym_on) s->dbfx_valid = false;
-    s->asym_on = c->asym_on; s->asym_float_rows = 0;
     HG_TRY(c->flist.reserve((size_t)nF * 4));
     HG_HIP(hipMemcpyAsync(c->flist.p, lost.data(), (size_t)nF * 4, hipMemcpyHostToDevice, c->stream));
     HG_TRY(s->qf.reserve((size_t)nF * c->bpad * 4 + 256));
     HG_TRY(s->qlab.reserve((size_t)nF * c->LW * 8));
-    auto move = [&](const void* src, void* dst, i64 rowbytes, int gather) {
-        hipLaunchKernelGGL(k_move_rows, dim3((unsigned)nF), dim3(256), 0, c->stream, (const u8*)src, (u8*)dst,
+    auto move = [&](const void* from, void* to, i64 rowbytes, int gather) {
+        hipLaunchKernelGGL(k_move_rows, dim3((unsigned)nF), dim3(256), 0, c->stream, (const u8*)from, (u8*)to,
                            c->flist.as<u32>(), rowbytes, gather);
     };
     move(c->qf.p, s->qf.p, (i64)c->bpad * 4, 1);
@@ -682,8 +668,7 @@ int real_requery_lost(hg_ctx* c, int64_t R, bool with_ap, bool* handled) {
     HG_TRY(c->check_launch("k_move_rows"));
     s->qf_resident = true;
     s->stage = ST_DB | ST_Q;
-    HG_TRY(real_call(s, R, false));
-    if (s->asym_on && s->asym_float_rows) c->asym_float_rows = 1;
+    HG_TRY(real_call(s, src, R, false));               // (the same stream, strictly in sequence: an image the child builds is the source's)
     if (s->RW != c->RW) return fail(HG_ERR_HIP, "real-valued ranking: internal error, the requeried lists have another width");
     move(s->mbits.p, c->mbits.p, c->RW * 8, 0);
     if (c->real.lists_made) {
@@ -702,14 +687,14 @@ int real_requery_lost(hg_ctx* c, int64_t R, bool with_ap, bool* handled) {
 
 // The attempts of one call, until one holds: the bet on a sampled cut; its few lost queries alone; deeper cuts with wider slices;
 // every row a record.
-int real_ladder(hg_ctx* c, int64_t R, bool with_ap) {
+int real_ladder(hg_ctx* c, RowSource& src, int64_t R, bool with_ap) {
     int lost = 0;
     if (R * 8 <= c->N && c->N >= 65536) {              // bet on a sampled cut; retry once deeper, then give up betting
         const double boost0 = (double)c->real_cap_boost;
-        HG_TRY(real_attempt(c, R, true, c->is_sub ? 6.0 : REAL_FIRST_SIGMA, 3.0 * boost0, with_ap, &lost));
+        HG_TRY(real_attempt(c, src, R, true, c->is_sub ? 6.0 : REAL_FIRST_SIGMA, 3.0 * boost0, with_ap, &lost));
         if (!lost) return HG_OK;
         bool handled = false;
-        HG_TRY(real_requery_lost(c, R, with_ap, &handled));
+        HG_TRY(real_requery_lost(c, src, R, with_ap, &handled));
         if (handled) return HG_OK;
         // a deeper cut with twice the budget; then -- features that follow the labels in a database stored class by class
         // put a query's top rows into a tenth of its slices -- eight and sixty-four times the slices' capacity, kept for
@@ -719,7 +704,7 @@ int real_ladder(hg_ctx* c, int64_t R, bool with_ap) {
                 if (c->cap >= (u32)((c->geo.L + 15) & ~15ll)) break;      // a slice already holds its segment
                 c->real_cap_boost = c->real_cap_boost * 8 > 4096 ? 4096 : c->real_cap_boost * 8;
             }
-            HG_TRY(real_attempt(c, R, true, 16.0, 6.0 * (double)c->real_cap_boost, with_ap, &lost));
+            HG_TRY(real_attempt(c, src, R, true, 16.0, 6.0 * (double)c->real_cap_boost, with_ap, &lost));
             if (!lost) {
                 if (attempt > 0 && c->real_cap_boost < 4096) c->real_cap_boost *= 2;     // (the budget that held: 6 = 2 x 3; a held plain retry changes nothing)
                 return HG_OK;
@@ -727,45 +712,43 @@ int real_ladder(hg_ctx* c, int64_t R, bool with_ap) {
         }
         c->real_cap_boost = (i64)boost0;
     }
-    HG_TRY(real_attempt(c, R, false, 0.0, 0.0, with_ap, &lost));
+    HG_TRY(real_attempt(c, src, R, false, 0.0, 0.0, with_ap, &lost));
     if (lost) return fail(HG_ERR_HIP, "real-valued ranking: internal error, exhaustive pass came up short");
     return HG_OK;
 }
 
-// a call on the row source the context holds now (the float table; the codes while asym_on), whose tables the caller has checked
-int real_call(hg_ctx* c, int64_t R, bool with_ap) {
+// a call on the row source `src`, whose tables the caller has checked
+int real_call(hg_ctx* c, RowSource& src, int64_t R, bool with_ap) {
     if (c->n_total != c->N) return fail(HG_ERR_STATE, "real-valued ranking is single-shard");
     if (R < 1 || R > c->N) return fail(HG_ERR_ARG, "R=%lld outside 1..N (N=%lld rows in the database)", (long long)R, (long long)c->N);
     if (c->N > 0x7FFFFFFFll) return fail(HG_ERR_ARG, "real-valued ranking takes up to 2^31 - 1 rows (have %lld)", (long long)c->N);   // (bit 31 of a record's index half is its match bit)
     c->real_lists = false;                             // from here on the list buffers are this call's: nothing to hand out unless it succeeds
     c->real.attempts = 0;
     if (with_ap && !c->is_sub) HG_TRY(ensure_out_block(c));      // verdict, APs and hit counts side by side: one download
-    HG_TRY(real_ladder(c, R, with_ap));
+    HG_TRY(real_ladder(c, src, R, with_ap));
     c->real_lists = c->real.lists_made;
     return HG_OK;
 }
 
 int run_real(hg_ctx* c, int64_t R, bool with_ap) {
-    if (!c->bpad || !c->dbf.p || !c->qf.p || !c->dbf_resident || !c->qf_resident)
+    if (!c->bpad || !c->from_floats.rows.p || !c->qf.p || !c->from_floats.rows_valid || !c->qf_resident)
         return fail(HG_ERR_STATE, "real-valued ranking needs the float features on the GPU: load them with hg_set_database_f32 / "
                                   "hg_set_queries_f32 (option keep_floats = 1 if the database is a +-1 code)");
-    return real_call(c, R, with_ap);
+    return real_call(c, c->from_floats, R, with_ap);
 }
 
-// The asymmetric call: the same ladder on the database's CODES (any loader left them in c->db) and the queries' floats.  Its buffers are
-// swapped in for the call and out again whatever it returns; what it leaves is what run_real leaves.
+// The asymmetric call: the same ladder on the database's CODES (any loader left them in c->db) and the queries' floats; what it leaves is
+// what run_real leaves.
 int run_asym(hg_ctx* c, int64_t R, bool with_ap) {
     c->real_lists = false;                             // a refused call leaves no lists either
     c->lists_valid = false;                            // ... and the call writes out_idx: a Hamming ranking's lists end here (hg_get_topr refuses)
     if (!c->bpad || !c->qf.p || !c->qf_resident || !c->db.p)
         return fail(HG_ERR_STATE, "asymmetric ranking needs the queries' float features on the GPU: set option keep_query_floats = 1, then load "
                                   "them with hg_set_queries_f32 / hg_set_queries_dev");
-    c->asym_float_rows = 0;
-    c->swap_rows();
-    const int rc = real_call(c, R, with_ap);
-    c->swap_rows();
-    if (rc == HG_OK) c->asym_calls++;
-    return rc;
+    c->from_codes.rows_read = 0;
+    HG_TRY(real_call(c, c->from_codes, R, with_ap));
+    c->asym_calls++;
+    return HG_OK;
 }
 
 }  // namespace

@@ -29,7 +29,7 @@ template <int NW> int launch_collect_t(hg_ctx* c, const RerankArgs& a, int qt0, 
 int launch_collect(hg_ctx* c, const RerankArgs& a, int qt0, int nqt) { HG_DISPATCH_NW(launch_collect_t, c, a, qt0, nqt) }
 
 int run_rerank(hg_ctx* c, int64_t R, bool with_ap) {
-    if (!c->bpad || !c->dbf.p || !c->qf.p || !c->dbf_resident || !c->qf_resident)
+    if (!c->bpad || !c->from_floats.rows.p || !c->qf.p || !c->from_floats.rows_valid || !c->qf_resident)
         return fail(HG_ERR_STATE, "real-valued ranking needs the float features on the GPU: load them with hg_set_database_f32 / "
                                   "hg_set_queries_f32 (option keep_floats = 1 if the database is a +-1 code)");
     if (c->idx_base != 0 || c->N != c->n_total)
@@ -106,7 +106,7 @@ int run_rerank(hg_ctx* c, int64_t R, bool with_ap) {
         if (per < 1) per = 1;
         if (per > 65535) per = 65535;
         c->t_begin(KI_RR_SCORE);
-        hipLaunchKernelGGL(k_rr_score, dim3((unsigned)ch.nq, (unsigned)per), dim3(256), 0, c->stream, c->qf.as<float>(), c->dbf.as<float>(), c->bpad, a, g);
+        hipLaunchKernelGGL(k_rr_score, dim3((unsigned)ch.nq, (unsigned)per), dim3(256), 0, c->stream, c->qf.as<float>(), c->from_floats.rows.as<float>(), c->bpad, a, g);
         c->t_end();
         HG_TRY(c->check_launch("k_rr_score"));
         c->t_begin(KI_RR_ORDER);

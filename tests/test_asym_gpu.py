@@ -302,6 +302,48 @@ def test_class_sorted_database_where_queries_may_lose_the_first_bet():
         r.close()
 
 
+def test_both_row_sources_alternate_on_one_context_where_queries_may_lose_the_bet():
+    """One context holds the tanh float table and its codes; real-valued and asymmetric calls alternate on it, through every
+    real_mfma, without a reload -- on the class-sorted case, where the requery child may be engaged by either.  Each call finds what
+    belongs to its own source: the oracle's bits, whatever the path.  The rows expanded from the codes stay a work buffer."""
+    c = case(*BET, kind="sorted")
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        _, apf, idxf, scoref = RM.map_from_features(c.qf, c.dbf, c.ql.astype(np.int8), c.dl.astype(np.int8), c.R)
+    relf = (c.dl[idxf].astype(bool) & c.ql[:, None, :].astype(bool)).any(-1).sum(1).astype(np.int64)
+    table = c.N * 64 * 4                                             # f32 [N][bpad]
+    ctx = _native.Context(0)
+    try:
+        ctx.set_option("keep_floats", 1)
+        ctx.set_database_f32(c.dbf, c.dl)
+        ctx.set_queries_f32(c.qf, c.ql)
+
+        def real_lists(what):
+            idx, score = ctx.topr_real(c.R)
+            assert np.array_equal(idx, idxf) and np.array_equal(score.view(np.uint32), scoref.view(np.uint32)), what
+
+        before_rows = None
+        for mfma in (2, 1, 0):
+            what = "real_mfma %d" % mfma
+            ctx.set_option("real_mfma", mfma)
+            real_lists(what)
+            if mfma < 2 and before_rows is None:
+                before_rows = ctx.get_stat("device_bytes")
+            same_lists(ctx.topr_asym(c.R), c, what=what)
+            ap, rel = ctx.map_real(c.R)
+            assert np.array_equal(ap, apf, equal_nan=True) and np.array_equal(rel, relf), what
+            ap, rel = ctx.map_asym(c.R)
+            assert np.array_equal(ap, c.ap, equal_nan=True) and np.array_equal(rel, c.rel), what
+            real_lists(what + ", after the asymmetric calls")
+        ctx.trim()
+        assert ctx.get_stat("device_bytes") < before_rows + table
+        assert ctx.census(0)[3], "the float table is a loaded table: hg_trim keeps it"
+        real_lists("after trim")
+        same_lists(ctx.topr_asym(c.R), c, what="after trim")
+    finally:
+        ctx.close()
+
+
 # ------------------------------------------------------------------ 6. state
 def test_a_hamming_ranking_ends_the_real_lists_and_the_other_way_round():
     c = case(40, 3000, 20, 700, 7)
