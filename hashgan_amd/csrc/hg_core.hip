@@ -1259,6 +1259,7 @@ int hg_trim(hg_ctx* c) {
     HG_TRY(c->sync());
     c->for_each_buf([](DevBuf& d, BufClass k) { if (k != BUF_TABLE) d.release(); });
     c->forget_derived();
+    c->hist_tot_zero = c->ws_b.hist_tot_zero = nullptr;   // (the plane totals went with the work buffers: a new allocation is cleared before its first pass)
     if (c->sub) { hg_ctx* s = c->sub; c->sub = nullptr; (void)hg_destroy(s); }
     c->stage &= (ST_DB | ST_Q);
     c->lists_valid = false;

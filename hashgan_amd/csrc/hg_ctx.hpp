@@ -303,8 +303,13 @@ struct StepBufs {
            cand, out_idx, out_dist, mbits, ap, rel, qbad, bigq, hwq;
     DevBuf outblk;             // [verdict 16 B][ap Q x 8][rel Q x 4]: err, ap and rel are views of it (ensure_out_block), so a call's results come home in ONE copy
     i64 outblk_q = -1;         // the Q those views were cut for
+    // The one-shot bet's plane totals, two planes to a u64 word, [(planes the sampled pass writes + 1) / 2][Qpad]: k_hist_i8 adds each segment pair's counts, k_guess_direct
+    // reads a query's column in one trip and stores zeros over it.  hist_tot_zero is the allocation known to hold zeros behind everything
+    // enqueued so far (nullptr: not known -- a fresh allocation, a pass with no guess behind it); the next bet then clears it first.
+    DevBuf hist_tot;
+    const void* hist_tot_zero = nullptr;
     template <class F> void for_each_step_buf(F&& f) {
-        for (DevBuf* d : {&hist, &hown, &posbase, &t, &tguess, &sstar, &cnt_lt, &quota, &tie_before, &n_lt, &err, &sl_start, &sl_tie,
+        for (DevBuf* d : {&hist_tot, &hist, &hown, &posbase, &t, &tguess, &sstar, &cnt_lt, &quota, &tie_before, &n_lt, &err, &sl_start, &sl_tie,
                           &sl_cnt, &tot, &failq, &cand, &out_idx, &out_dist, &mbits, &ap, &rel, &qbad, &bigq, &hwq})
             f(*d, BUF_WORK);
         f(outblk, BUF_DERIVED);
@@ -773,7 +778,8 @@ int launch_select_valu(hg_ctx* c, int lw, bool optimistic);   // k_select<NW, LW
 int launch_select_dense(hg_ctx* c, int lw);      // k_select_dense<NW, LW>
 // hg_pairs_mx.hip (k_select_mx: hg_pairs_mx1.hip)
 int ensure_mx_images(hg_ctx* c, bool need_db);  // fp4 images of database / query codes, built on first use
-int launch_hist_mx(hg_ctx* c);                   // k_hist_i8 / k_hist_mx
+int launch_hist_mx(hg_ctx* c, u64* tot = nullptr);   // k_hist_i8 / k_hist_mx; tot: k_hist_i8 adds its planes into this table too (StepBufs::hist_tot)
+bool hist_i8_applies(const hg_ctx* c);           // launch_hist_mx takes k_hist_i8
 // (cut: each query's threshold -- c->tguess, or c->t for StepReq::exact_cut)
 int launch_select_mx(hg_ctx* c, int lw, const int* cut);    // k_select_mx<NW, LW, QT, COMPACT>
 int launch_select_mx3(hg_ctx* c, int lw, const int* cut);   // k_select_mx3 (codes of <= 64 bits, one-byte records)

@@ -345,11 +345,13 @@ static __global__ __launch_bounds__(256) void k_guess(const u32* __restrict__ hs
 // One-shot, single-shard form of k_hist_reduce + k_guess: sums the sampled pass's per-segment histograms
 // itself, bucket by bucket, and stops at the guessed cut -- a third of the planes at C2, no reduced copy,
 // one launch less.  Also clears the bet's per-query overflow flags and the lost-bet flag (two fills less).
+// Handed `tot` (k_hist_i8 summed its planes over the segment pairs on its way out) it does not sum at all: the cut comes from
+// one trip over the query's totals, only the cut's own plane is read per segment, and the totals are zero again when it ends.
 // PARTS lanes per query (4, 16 or 64 -- more when the sampled pass has many segments): 64 / PARTS queries per wavefront
 template <int PARTS>
 __global__ __launch_bounds__(256) void k_guess_direct(const u32* __restrict__ hseg, int Sh, int ratio, double sigma,
                                                       i64 n_total, u32 sampled, int* __restrict__ T, int* __restrict__ sstar,
-                                                      u32* __restrict__ failq, int* __restrict__ err, u32* __restrict__ crowd, const Geo g) {
+                                                      u32* __restrict__ failq, int* __restrict__ err, u32* __restrict__ crowd, u64* tot, const Geo g) {
     constexpr int QPW = 64 / PARTS;                    // lane = part * QPW + query-in-wave
     const int lane = threadIdx.x & 63, part = lane / QPW;
     const int q = (blockIdx.x * WPB + (threadIdx.x >> 6)) * QPW + (lane % QPW);
@@ -371,7 +373,27 @@ __global__ __launch_bounds__(256) void k_guess_direct(const u32* __restrict__ hs
     // at C2, where a lane sums 13 segments per plane and stops at the 19th; C5 0.083 -> 0.049).
     constexpr int PL = 4;                              // planes per trip (round 3: 2 -> 4, 32 loads in flight: 0.0255 -> 0.0205 ms at C2, C5 0.047 -> 0.034)
     u32 gmax = 0, gtot = 0;                            // crowding probe: the fullest sampled segment of the last plane group, the group's total
-    for (int d = 0; d < dn && !found; d += PL) {
+    // tot: k_hist_i8 left the planes' totals over the segment pairs, two planes to a 64-bit word: [(dn + 1) / 2][Qpad] -- no chain:
+    // every part of a query loads its column in one trip (18 words: all 34 planes of a 64-bit code) and finds the cut by the same
+    // comparisons.  The crowding probe needs the fullest segment and keeps the walk.
+    const bool walk = !tot || crowd;
+    const int dn2 = (dn + 1) >> 1;
+    constexpr int TL = 18;
+    for (int d2 = 0; !walk && d2 < dn2 && !found; d2 += TL) {
+        u64 v[TL];
+#pragma unroll
+        for (int p = 0; p < TL; ++p) v[p] = tot[(i64)(d2 + p < dn2 ? d2 + p : dn2 - 1) * g.Qpad + qq];     // (unconditional: all in flight at once)
+#pragma unroll
+        for (int p = 0; p < 2 * TL; ++p) {
+            const int d = 2 * d2 + p;
+            if (live && !found && d < dn) {                        // (dead lanes: nothing found, no column read)
+                below = cum;
+                cum += (u32)(v[p >> 1] >> (32 * (p & 1)));
+                if (cum >= need) { t = d; found = true; }
+            }
+        }
+    }
+    for (int d = 0; walk && d < dn && !found; d += PL) {
         u32 cs[PL];
         const u32* __restrict__ col[PL];
         gmax = 0;
@@ -427,8 +449,18 @@ __global__ __launch_bounds__(256) void k_guess_direct(const u32* __restrict__ hs
     if (found) {
         // {dist < T} everywhere + {dist == T} up to a segment: first segment (in order) where the count reaches need
         const u32* __restrict__ col = hseg + (i64)t * g.Qpad + qq;
+        constexpr int SR = 16;                         // a part of up to 16 segments (always, with 4 lanes per query): its column of plane T in
+        const bool inreg = per <= SR;                  // registers, one trip for the sum and the search (else two passes, the second a chain)
+        u32 cv[SR];
+#pragma unroll
+        for (int k = 0; k < SR; ++k) cv[k] = inreg ? col[(i64)(s0 + k < s1 ? s0 + k : 0) * plane] : 0u;     // past the part: any valid segment, not counted
         u32 mine = 0;
-        for (int sh = s0; sh < s1; ++sh) mine += col[(i64)sh * plane];
+        if (inreg) {
+#pragma unroll
+            for (int k = 0; k < SR; ++k) mine += s0 + k < s1 ? cv[k] : 0u;
+        } else {
+            for (int sh = s0; sh < s1; ++sh) mine += col[(i64)sh * plane];
+        }
         u32 incl = mine;                               // inclusive prefix over the query's parts (lanes QPW apart)
 #pragma unroll
         for (int off = QPW; off < 64; off <<= 1) {
@@ -437,9 +469,19 @@ __global__ __launch_bounds__(256) void k_guess_direct(const u32* __restrict__ hs
         }
         u64 have = below + (u64)(incl - mine);
         int cand = 0x7FFFFFFF;
-        for (int sh = s0; sh < s1; ++sh) {
-            have += col[(i64)sh * plane];
-            if (have >= need) { cand = sh; break; }
+        if (inreg) {
+#pragma unroll
+            for (int k = 0; k < SR; ++k) {
+                if (cand == 0x7FFFFFFF && s0 + k < s1) {
+                    have += cv[k];
+                    if (have >= need) cand = s0 + k;
+                }
+            }
+        } else {
+            for (int sh = s0; sh < s1; ++sh) {
+                have += col[(i64)sh * plane];
+                if (have >= need) { cand = sh; break; }
+            }
         }
 #pragma unroll
         for (int off = QPW; off < 64; off <<= 1) {
@@ -450,6 +492,10 @@ __global__ __launch_bounds__(256) void k_guess_direct(const u32* __restrict__ hs
         if (ss > g.S - 1) ss = g.S - 1;
     }
     if (live && part == 0) { T[q] = t; sstar[q] = ss; }
+    // zeros over the totals for the next sampled pass on this workspace, the column's words dealt out to the query's parts (they are
+    // lanes of this wavefront: their loads above are complete)
+    if (tot && q < g.Qpad)
+        for (int d2 = part; d2 < dn2; d2 += PARTS) tot[(i64)d2 * g.Qpad + q] = 0ull;
 }
 
 // ----------------------------------------------------------------------------

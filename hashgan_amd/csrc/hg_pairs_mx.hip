@@ -111,7 +111,7 @@ template <int NW, int LW> int launch_select_mx4_t(hg_ctx* c, const int* cut) {  
 }
 
 // the same pass with the integer matrix instruction delivering the counter addresses (hg_hist_i8.hpp); codes of <= 128 bits
-template <int NW> int launch_hist_i8_t(hg_ctx* c) {
+template <int NW> int launch_hist_i8_t(hg_ctx* c, u64* tot) {
     if (!c->dbx8_valid) {
         const i64 n16 = (c->N + 15) / 16 * 16;
         HG_TRY(c->dbx8.reserve((size_t)n16 * NW * 32));
@@ -138,27 +138,30 @@ template <int NW> int launch_hist_i8_t(hg_ctx* c) {
         if (lds > 64 * 1024)
             HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hist_i8<NW, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL((k_hist_i8<NW, true>), dim3(padded_grid(g.nBlk)), dim3(256), lds, c->stream, c->qc.as<u32>(), c->dbx8.as<u8>(),
-                           c->hist.as<u32>(), g);
+                           c->hist.as<u32>(), tot, g);
     } else {
         if (lds > 64 * 1024)
             HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_hist_i8<NW, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL((k_hist_i8<NW, false>), dim3(padded_grid(g.nBlk)), dim3(256), lds, c->stream, c->qc.as<u32>(), c->dbx8.as<u8>(),
-                           c->hist.as<u32>(), g);
+                           c->hist.as<u32>(), tot, g);
     }
     c->t_end();
     return c->check_launch("k_hist_i8");
 }
 }  // namespace
 
-int launch_hist_mx(hg_ctx* c) {
-    if (c->opt.hist_mfma == 2 && c->NW <= 4) {
+bool hist_i8_applies(const hg_ctx* c) { return c->opt.hist_mfma == 2 && c->NW <= 4; }
+
+int launch_hist_mx(hg_ctx* c, u64* tot) {              // tot: k_hist_i8 also sums its planes over the segment pairs into this table (else nullptr)
+    if (hist_i8_applies(c)) {
         switch (c->NW) {
-            case 1: return launch_hist_i8_t<1>(c);
-            case 2: return launch_hist_i8_t<2>(c);
-            case 3: return launch_hist_i8_t<3>(c);
-            default: return launch_hist_i8_t<4>(c);
+            case 1: return launch_hist_i8_t<1>(c, tot);
+            case 2: return launch_hist_i8_t<2>(c, tot);
+            case 3: return launch_hist_i8_t<3>(c, tot);
+            default: return launch_hist_i8_t<4>(c, tot);
         }
     }
+    if (tot) return fail(HG_ERR_STATE, "launch_hist_mx: plane totals come from k_hist_i8 only");
     HG_DISPATCH_NW(launch_hist_mx_t, c)
 }
 

@@ -159,7 +159,16 @@ i64 sampled_rows(hg_ctx* c, int stride) {
 // =============================================================================
 extern "C" {
 
-static int do_hist(hg_ctx* c, int stride, bool reduce = true, bool pairs_ok = false, int hcap = 0) {
+// Compile-time A/B switch (tools/ab_build.sh): 0 = the one-shot bet's guess walks the segment pairs' planes itself, as it did before
+// k_hist_i8 summed them on its way out.
+#ifndef HG_GUESS_TOTALS
+#define HG_GUESS_TOTALS 1
+#endif
+
+// tot_out (the one-shot bet's sampled pass): where k_hist_i8 takes the pass on a whole-database context it also leaves the planes'
+// totals over the segment pairs in c->hist_tot -- *tot_out, which the caller hands to k_guess_direct (that kernel reads them and
+// stores zeros over them again); nullptr where another kernel takes the pass.
+static int do_hist(hg_ctx* c, int stride, bool reduce = true, bool pairs_ok = false, int hcap = 0, u64** tot_out = nullptr) {
     make_geometry(c);
     c->geo.hist_stride = stride;
     const bool mx = hist_mx_applies(c, stride, pairs_ok);
@@ -168,6 +177,19 @@ static int do_hist(hg_ctx* c, int stride, bool reduce = true, bool pairs_ok = fa
     const Geo& g = c->geo;
     const size_t plane = (size_t)g.NB * g.Qpad * 4;
     HG_TRY(c->hist.reserve(plane * g.S));
+    u64* tot = nullptr;
+    if (tot_out) *tot_out = nullptr;
+    if (HG_GUESS_TOTALS && tot_out && mx && hist_i8_applies(c) && c->N == c->n_total && !c->is_sub) {
+        const int dn = g.hcap > 0 && g.hcap < g.NB ? g.hcap : g.NB;
+        const size_t cap0 = c->hist_tot.cap;
+        HG_TRY(c->hist_tot.reserve((size_t)((dn + 1) / 2) * g.Qpad * 8));   // two planes to a 64-bit word
+        // a new allocation (the block cache may hand the grown table the very block it gave back: same address, the bytes beyond
+        // the old table never cleared), or a pass that no guess followed: never in the steady state
+        if (c->hist_tot_zero != c->hist_tot.p || c->hist_tot.cap != cap0)
+            HG_HIP(hipMemsetAsync(c->hist_tot.p, 0, c->hist_tot.cap, c->stream));
+        c->hist_tot_zero = nullptr;                    // until the guess that clears it is enqueued
+        *tot_out = tot = c->hist_tot.as<u64>();
+    }
     HG_TRY(c->hown.reserve(plane + TAIL_WORDS * 4));
     if (reduce) {   // tail of the exported histogram: [0] overflow flag, [1] rows this pass visited
         const u32 visited = (u32)(stride == 1 ? g.N : sampled_rows(c, stride));
@@ -175,7 +197,7 @@ static int do_hist(hg_ctx* c, int stride, bool reduce = true, bool pairs_ok = fa
         hipLaunchKernelGGL(k_set_tail, dim3(1), dim3(64), 0, c->stream, (u32*)(c->hown.as<char>() + plane), visited);
         HG_TRY(c->check_launch("k_set_tail"));
     }
-    HG_TRY(mx ? launch_hist_mx(c) : launch_hist(c));
+    HG_TRY(mx ? launch_hist_mx(c, tot) : launch_hist(c));
     if (!reduce) { c->stage = ST_DB | ST_Q; return HG_OK; }      // the caller reads the per-segment histograms itself
     const Geo gh = hist_geometry(c);
     c->t_begin(KI_HIST_REDUCE);
@@ -793,7 +815,8 @@ static int enqueue_optimistic(hg_ctx* c, int64_t R, int stride, const StepReq& r
     // the guess stops at the cut, far below b/2 when R <= N/8 on any data whose queries resemble the database: the
     // sampled pass writes only those planes (130 -> 68 MB per launch at C2).  A cut beyond them reads as a thin
     // sample -- everything is taken, the slices overflow, the exact sequence answers.
-    HG_TRY(do_hist(c, stride, false, false, c->NB / 2 + 2));
+    u64* tot = nullptr;                                // the planes' totals over the segment pairs, where k_hist_i8 took the pass
+    HG_TRY(do_hist(c, stride, false, false, c->NB / 2 + 2, &tot));
     HG_TRY(set_R(c, R, 1, 0));
     const Geo& g = c->geo;
     HG_TRY(reserve_guess(c));
@@ -812,7 +835,7 @@ static int enqueue_optimistic(hg_ctx* c, int64_t R, int stride, const StepReq& r
 #define HG_GUESS(P)                                                                                                     \
         hipLaunchKernelGGL(k_guess_direct<P>, dim3(grid_for(g.Qpad, WPB * (64 / P))), dim3(256), 0, c->stream,          \
                            c->hist.as<u32>(), gh.S, ratio, sigma, (i64)c->n_total, srows,                \
-                           c->tguess.as<int>(), c->sstar.as<int>(), c->failq.as<u32>(), c->err.as<int>(), crowd, g)
+                           c->tguess.as<int>(), c->sstar.as<int>(), c->failq.as<u32>(), c->err.as<int>(), crowd, tot, g)
         // (more lanes per query shorten a lane's share of a plane but scatter a wavefront's loads over more lines: with 64
         // lanes for every query that the chip has room for, Q = 1000 went 0.068 -> 0.090 ms, C3 0.032 -> 0.061)
         if (gh.S <= 64) HG_GUESS(4);
@@ -822,6 +845,7 @@ static int enqueue_optimistic(hg_ctx* c, int64_t R, int stride, const StepReq& r
     }
     c->t_end();
     HG_TRY(c->check_launch("k_guess_direct"));
+    if (tot) c->hist_tot_zero = tot;                   // the guess stored zeros over every total it was handed
     if (probe) {
         // One host round trip, once per database: sum over the queries of (fullest sampled segment) * segments / (their total)
         // is ~2 for rows in random order (the maximum of ~50 small Poisson counts) and ~the number of classes for a database
