@@ -103,6 +103,12 @@ _SIGNATURES = {
     "hg_get_vote_pred": [_p, _p, _p],
     "hg_get_vote_confusion": [_p, _p],
     "hg_get_votes": [_p, _p],
+    "hg_set_neighbours": [_p, _p, _i64, C.c_int],
+    "hg_neighbours_from_lists": [_p, C.c_int],
+    "hg_get_neighbours": [_p, _p, _p],
+    "hg_match_neighbours": [_p],
+    "hg_nbr_hist": [_p],
+    "hg_get_nbr_hist": [_p, _p, _p],
     "hg_comm_unique_id": [_p],
     "hg_comm_init": [_p, _p, C.c_int, C.c_int],
     "hg_comm_destroy": [_p],
@@ -365,6 +371,48 @@ class Context:
         ks = _carray(ks, np.int64).ravel()
         check(self._lib.hg_votes(self._h, _ptr(ks), len(ks)))
         self._votes_nk = len(ks)
+
+    # -- label-free relevance: neighbour sets ----------------------------------------
+    def set_neighbours(self, ids):
+        """The ground-truth neighbour sets (hg_set_neighbours): ids [Q, G], a row the set of one loaded query in any order, IDX_NONE
+        (0xFFFFFFFF) or a negative value padding a shorter set; 1 <= G <= 16384.  Duplicates and ids >= n_total are refused."""
+        a = np.asarray(ids)
+        if a.ndim != 2:
+            raise ValueError("ids must be [Q, G]")
+        if a.dtype != np.uint32:
+            a = np.where(np.asarray(a, dtype=np.int64) < 0, IDX_NONE, a).astype(np.uint32)
+        a = _carray(a, np.uint32)
+        check(self._lib.hg_set_neighbours(self._h, _ptr(a), a.shape[0], a.shape[1]))
+        self._nbr_G = a.shape[1]
+
+    def neighbours_from_lists(self, G):
+        """The first G ranks of the ranked lists the last topr() / topr_real() / topr_asym() / topr_rerank() left on the device become
+        the neighbour sets (hg_neighbours_from_lists); nothing crosses to the host."""
+        check(self._lib.hg_neighbours_from_lists(self._h, int(G)))
+        self._nbr_G = int(G)
+
+    def get_neighbours(self, ids=True):
+        """-> (ids uint32 [Q, G] ascending, IDX_NONE pads at the end; count uint32 [Q]).  ids=False: the counts alone (ids is None)."""
+        ids = np.empty((self.Q or 0, getattr(self, "_nbr_G", 0)), dtype=np.uint32) if ids else None
+        cnt = np.empty(self.Q or 0, dtype=np.uint32)
+        check(self._lib.hg_get_neighbours(self._h, _ptr(ids), _ptr(cnt)))
+        return ids, cnt
+
+    def match_neighbours(self):
+        """The match bitmap of the last ranking's lists from the neighbour sets instead of the labels (hg_match_neighbours); ap(),
+        ap_at(), get_match() and export() then work on it.  The next ranking brings the label bits back."""
+        check(self._lib.hg_match_neighbours(self._h))
+
+    def nbr_hist(self):
+        """Neighbours per (Hamming distance, query) (hg_nbr_hist).  Results: get_nbr_hist()."""
+        check(self._lib.hg_nbr_hist(self._h))
+
+    def get_nbr_hist(self):
+        """-> (nbr uint32 [b+1, Q], count uint32 [Q]) (after nbr_hist())."""
+        h = np.empty(((self.b or 0) + 1, self.Q or 0), dtype=np.uint32)
+        cnt = np.empty(self.Q or 0, dtype=np.uint32)
+        check(self._lib.hg_get_nbr_hist(self._h, _ptr(h), _ptr(cnt)))
+        return h, cnt
 
     def hist_buffer(self):
         p, n = _p(), _i64()

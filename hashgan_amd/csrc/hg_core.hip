@@ -29,7 +29,8 @@ const char* const kKernelNames[KI_COUNT] = {"k_hist", "k_hist_reduce", "k_plan",
                                             "k_hist_rel", "k_hist_rel_reduce", "k_graded", "k_grade_hist", "k_grade_hist_reduce", "k_tie_ap", "k_ap_at",
                                             "k_label_max", "k_hist_joint", "k_hist_joint_reduce",
                                             "k_rr_scan", "k_rr_collect", "k_rr_score", "k_rr_order", "k_export", "k_votes", "k_vote_confusion", "k_side_pack", "k_side_merge",
-                                            "k_list_grades", "k_list_merge_grades", "k_list_merge_votes", "k_vote_pick", "k_asym_image16", "k_asym_rescore", "k_asym_expand_rows"};
+                                            "k_list_grades", "k_list_merge_grades", "k_list_merge_votes", "k_vote_pick", "k_asym_image16", "k_asym_rescore", "k_asym_expand_rows",
+                                            "k_nbr_sort", "k_nbr_match", "k_nbr_hist"};
 // Flatten NumPy's pairwise-summation tree for a chunk of n elements (n <= 8192):
 // numpy/_core/src/umath/loops_utils.h.src, pairwise_sum: n <= 128 is a leaf,
 // otherwise split at n/2 rounded down to a multiple of 8.
@@ -1301,6 +1302,7 @@ int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "rel_hist_variant")) *value = c->last_rel_hist;
     else if (!strcmp(key, "ap_at_cutoffs")) *value = c->aa.dim;
     else if (!strcmp(key, "votes_cutoffs")) *value = c->vt.dim;
+    else if (!strcmp(key, "match_source")) *value = c->match_source;
     else if (!strcmp(key, "joint_hist_grades")) *value = c->jh_G;
     else if (!strcmp(key, "joint_hist_bands")) *value = c->jh_bands;
     else if (!strcmp(key, "merged_joint_grades")) *value = c->mjh_G;

@@ -4,7 +4,8 @@
 //   hg_core.hip        context, tables (hg_set_*), options / statistics / timing, label match, AP, downloads, results into device arrays (hg_export)
 //   hg_seq.hip         the Hamming sequences: geometry, histogram -> plan -> select -> rank, staged (sharded) and one-shot forms
 //   hg_rank.hip        their rank stage: the choice of the kernel (RankChoice), one launcher per kernel, the leftovers of a fused step, k_order
-//   hg_side.hip        the side metrics (hg_rel_hist, hg_graded, hg_grade_hist, hg_tie_ap, hg_ap_at, hg_joint_hist, hg_votes) and their getters: one SideResult each;
+//   hg_side.hip        the side metrics (hg_rel_hist, hg_graded, hg_grade_hist, hg_tie_ap, hg_ap_at, hg_joint_hist, hg_votes, hg_nbr_hist) and their getters: one SideResult each;
+//                      the neighbour sets of label-free relevance and the match bitmap from them (hg_set_neighbours, hg_neighbours_from_lists, hg_match_neighbours);
 //                      the shards' histogram tables packed and merged into the whole database's (hg_pack_side_table, hg_merge_side_table), and the
 //                      grades and votes along a shard's partial lists (hg_pack_list_table, hg_merge_list_table)
 //   hg_rerank.hip      the re-ranked Hamming ranking (hg_topr_rerank, hg_map_rerank): distance, then float32 inner product inside equal distances
@@ -218,7 +219,8 @@ enum KernelId { KI_HIST = 0, KI_HIST_REDUCE, KI_PLAN, KI_SEG_COUNTS, KI_SEG_LAYO
                 KI_RADIX, KI_REAL_FINISH, KI_SELECT_MX, KI_RANK_LDS, KI_COMM, KI_STEP, KI_REAL_RESCORE, KI_HIST_REL, KI_HIST_REL_REDUCE,
                 KI_GRADED, KI_GRADE_HIST, KI_GRADE_HIST_REDUCE, KI_TIE_AP, KI_AP_AT, KI_LABEL_MAX, KI_HIST_JOINT, KI_HIST_JOINT_REDUCE,
                 KI_RR_SCAN, KI_RR_COLLECT, KI_RR_SCORE, KI_RR_ORDER, KI_EXPORT, KI_VOTES, KI_VOTE_CONFUSION, KI_SIDE_PACK, KI_SIDE_MERGE,
-                KI_LIST_GRADES, KI_LIST_MERGE_GRADES, KI_LIST_MERGE_VOTES, KI_VOTE_PICK, KI_ASYM_IMAGE, KI_ASYM_RESCORE, KI_ASYM_EXPAND, KI_COUNT };
+                KI_LIST_GRADES, KI_LIST_MERGE_GRADES, KI_LIST_MERGE_VOTES, KI_VOTE_PICK, KI_ASYM_IMAGE, KI_ASYM_RESCORE, KI_ASYM_EXPAND,
+                KI_NBR_SORT, KI_NBR_MATCH, KI_NBR_HIST, KI_COUNT };
 enum Stage { ST_NONE = 0, ST_DB = 1, ST_Q = 2, ST_HIST = 4, ST_PLAN = 8, ST_SELECT = 16, ST_MATCH = 32, ST_AP = 64 };
 extern const char* const kKernelNames[KI_COUNT];
 // the kernel that took the last record pass / the last rank stage (stats "select_variant", "rank_variant"), and what the rank stage is asked for
@@ -452,6 +454,9 @@ struct hg_ctx : StepBufs, StepState {
                                // mg_grade [C + 1][Qpad], mg_joint [NB * Gc][Qpad] (dim = NB * Gc).  Ended by the merge's own refusal or failure, a reload, hg_trim
     SideResult mlg, mlv;       // hg_merge_list_table (hg_list_merge.hpp): the shards' grade planes merged into lm_grades [Q][Rp] (Qpad = Rp, dim = R), their vote tables
                                // into lm_votes [Q][nk][C] (dim = nk, the cut-offs in mlv_ks).  They belong to the ranked lists too: ended like gr and vt (lists_changed), and by their own merge's refusal
+    SideResult nb;             // hg_set_neighbours / hg_neighbours_from_lists: nb_ids [Q][G] sorted, nb_cnt [Q]; dim = G.  A table of the loaded queries and database
+    SideResult nh;             // hg_nbr_hist: nh_tab [NB][Qpad] of nb's sets (a new set ends it)
+    int match_source = 0;      // stat "match_source": the match bitmap came from the labels (0) or from the neighbour sets (1: hg_match_neighbours); every ranking resets it (set_R)
     i64 mlv_ks[64] = {0};      // the cut-offs of the merged vote table: hg_votes on a shard takes these and no others
     int mjh_G = 0;             // stat "merged_joint_grades": the common grade count Gc of the last joint merge that succeeded (0: none yet)
     SideResult rr;             // the last ranking was a re-rank (hg_rerank.hip) of these tables: rr_scores [Q][R]; dim = R.  Not a side metric -- set_R ends it
@@ -551,6 +556,8 @@ struct hg_ctx : StepBufs, StepState {
     DevBuf mg_rel, mg_grade, mg_joint;   // the merged tables (mrh, mgh, mjh)
     DevBuf lm_pack, lm_flag, lm_tab;   // hg_pack_list_table's block in the exchange layout (one at a time: the next pack overwrites it); hg_merge_list_table's four flag words; the cut-offs [64 x i64] of the vote pack / merge
     DevBuf lm_grades, lm_votes;   // the merged grade plane and vote counts (mlg, mlv)
+    DevBuf nb_ids, nb_cnt, nb_flag, nb_stage;   // neighbour sets: sorted ids [Q][G] (pads at the end), valid ids [Q], k_nbr_sort's flag word, the caller's table on its way to the sort
+    DevBuf nh_tab;             // hg_nbr_hist: the table [NB][Qpad] (nh)
     DevBuf aa_recip;           // hg_ap_at's own reciprocals (aa_recip_n) when the ranking's table (ap_recip, recip_for_R) is not there
     DevBuf rr_recs, rr_tmp;    // re-rank: a chunk's records (row index, then the sort key), the radix passes' second buffer (groups beyond the LDS only)
     DevBuf rr_base, rr_msz, rr_cnt, rr_scores;   // re-rank: a query's first record in its chunk [Q] x 8, records per query [Q] x 4, {groups in LDS, groups by radix}, the score lists [Q][R]
@@ -582,7 +589,8 @@ struct hg_ctx : StepBufs, StepState {
         for (DevBuf* d : {&seglt, &segtie, &mbits2, &part, &obuf[0], &obuf[1], &beyond, &stage_in, &badcnt, &flist, &dbytes, &samp, &thr,
                           &sortA, &sortB, &scores, &gtab, &sampx, &cntq, &krows, &thr2, &hist2, &comm_tmp, &gath_idx, &gath_dist, &rh_part, &rh_all, &rh_rel,
                           &gr_tab, &gr_out, &gr_grades, &gh_part, &gh_tab, &ta_tab, &ta_out, &aa_tab, &aa_out, &jh_max, &jh_part, &jh_tab, &vt_tab, &vt_votes, &vt_pred, &vt_conf,
-                          &mg_pack, &mg_flag, &mg_rel, &mg_grade, &mg_joint, &lm_pack, &lm_flag, &lm_tab, &lm_grades, &lm_votes, &rr_recs, &rr_tmp, &rr_base, &rr_msz, &rr_cnt, &rr_scores})
+                          &mg_pack, &mg_flag, &mg_rel, &mg_grade, &mg_joint, &lm_pack, &lm_flag, &lm_tab, &lm_grades, &lm_votes, &rr_recs, &rr_tmp, &rr_base, &rr_msz, &rr_cnt, &rr_scores,
+                          &nb_ids, &nb_cnt, &nb_flag, &nb_stage, &nh_tab})
             f(*d, BUF_WORK);
         for (DevBuf& d : gathered) f(d, BUF_WORK);
         for (DevBuf& d : scratch) f(d, BUF_WORK);
@@ -593,7 +601,7 @@ struct hg_ctx : StepBufs, StepState {
     void forget_derived() {
         dbx_valid = qx_valid = dbx8_valid = dbx3_valid = dbx4_valid = false;
         forget_rows();
-        for (SideResult* r : {&rh, &gr, &gh, &ta, &aa, &jh, &vt, &mrh, &mgh, &mjh, &mlg, &mlv, &rr}) r->begin();   // (hg_trim releases their tables with the other work buffers)
+        for (SideResult* r : {&rh, &gr, &gh, &ta, &aa, &jh, &vt, &mrh, &mgh, &mjh, &mlg, &mlv, &rr, &nb, &nh}) r->begin();   // (hg_trim releases their tables with the other work buffers)
         shapes_for_R = recip_for_R = aa_recip_n = -1;
         outblk_q = ws_b.outblk_q = -1;
     }

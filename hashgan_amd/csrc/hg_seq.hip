@@ -231,6 +231,7 @@ extern "C++" int set_R(hg_ctx* c, int64_t R, int G, int rank) {
     c->lists_changed();                                // every ranking comes through here: hg_graded's tables were the previous lists'
     c->bitmap_changed();                               // ... and hg_ap_at's the previous bitmap's
     c->mbits_merged = c->mbits_in_ws_b = false;
+    c->match_source = 0;                               // ... and its bits are the labels' again (hg_match_neighbours)
     c->rr.begin();                                     // ... and a re-rank's score list goes with its lists
     c->geo.R = R;
     c->RW = (R + 63) / 64;

@@ -10,6 +10,7 @@
 #include "hg_votes.hpp"
 #include "hg_side_merge.hpp"
 #include "hg_list_merge.hpp"
+#include "hg_neighbours.hpp"
 
 // the classes of the last label word
 static u64 lastmask(int C) { return C % 64 ? (1ull << (C % 64)) - 1ull : ~0ull; }
@@ -126,6 +127,42 @@ static int list_kind(hg_ctx* c, const char* who, int which) {
     if (c->C > GR_MAX_C) return fail(HG_ERR_ARG, "%s: C=%d classes (at most %d)", who, c->C, GR_MAX_C);
     return HG_OK;
 }
+
+// Neighbour sets (hg_neighbours.hpp): k_nbr_sort on row q = src + q * stride of Q rows into nb_ids / nb_cnt, then its flag word back to
+// the host (one synchronisation).  *flag: NB_FLAG_DUP | NB_FLAG_RANGE.
+static int sort_neighbours(hg_ctx* c, const u32* src, i64 stride, i64 Q, int G, u32* flag) {
+    int P = 64;
+    while (P < G) P <<= 1;
+    const size_t lds = (size_t)(P + NB_SORT_EXTRA) * 4;
+    static std::atomic<unsigned long long> lds_allowed{0};
+    if (lds > 64 * 1024 && !(lds_allowed.load() >> (c->device & 63) & 1ull)) {
+        HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nbr_sort), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        lds_allowed.fetch_or(1ull << (c->device & 63));
+    }
+    HG_HIP(hipMemsetAsync(c->nb_flag.p, 0, 4, c->stream));
+    NbrSortArgs a;
+    a.src = src; a.stride = stride;
+    a.ids = c->nb_ids.as<u32>(); a.count = c->nb_cnt.as<u32>(); a.flag = c->nb_flag.as<u32>();
+    a.G = G; a.P = P; a.n_total = c->n_total;
+    c->t_begin(KI_NBR_SORT);
+    if (Q > 0) hipLaunchKernelGGL(k_nbr_sort, dim3((unsigned)Q), dim3(P <= NB_SORT_SMALL ? 256 : NB_SORT_THREADS), lds, c->stream, a);
+    c->t_end();
+    HG_TRY(c->check_launch("k_nbr_sort"));
+    HG_HIP(hipMemcpyAsync(flag, c->nb_flag.p, 4, hipMemcpyDeviceToHost, c->stream));
+    return c->sync();
+}
+// the set's buffers for Q sets of G ids (first reservations: no buffer of a blind step moves)
+static int reserve_neighbours(hg_ctx* c, i64 Q, int G, bool staged) {
+    const FirstReservations first;
+    HG_TRY(c->nb_ids.reserve((size_t)(Q > 0 ? Q : 1) * G * 4));
+    HG_TRY(c->nb_cnt.reserve((size_t)(Q > 0 ? Q : 1) * 4));
+    HG_TRY(c->nb_flag.reserve(16));
+    if (staged) HG_TRY(c->nb_stage.reserve((size_t)(Q > 0 ? Q : 1) * G * 4));
+    first.keep(c);
+    return HG_OK;
+}
+// the ranked index lists hg_votes accepts on a whole-database context
+static bool lists_on_device(const hg_ctx* c) { return (c->stage & ST_SELECT) && (c->lists_valid || c->real_lists); }
 
 extern "C" {
 
@@ -427,6 +464,107 @@ int hg_votes(hg_ctx* c, const int64_t* host_ks, int nk) {
     HG_TRY(c->sync());                                 // (the host array is the caller's)
     c->vt.finish(c, Q, Q, nk);
     return HG_OK;
+}
+
+// Label-free relevance (hg_neighbours.hpp): NB(q), a set of at most G distinct global row numbers per loaded query, sorted on the device.
+// A table of the loaded queries and database like every side result (nb): a reload of either and hg_trim end it, and so does a refused
+// call.  A new set also ends the histogram of the previous one (nh).
+int hg_set_neighbours(hg_ctx* c, const uint32_t* host_ids, int64_t Q, int G) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_set_neighbours", "hg_set_database + hg_set_queries"));
+    c->nb.begin(); c->nh.begin();
+    HG_TRY(whole_database(c, "hg_set_neighbours", "neighbour sets need the whole database in one context"));
+    if (!host_ids) return fail(HG_ERR_ARG, "hg_set_neighbours: null pointer");
+    if (Q != c->Q) return fail(HG_ERR_ARG, "hg_set_neighbours: Q=%lld sets for %lld loaded queries", (long long)Q, (long long)c->Q);
+    if (G < 1 || G > NB_MAX_G) return fail(HG_ERR_ARG, "hg_set_neighbours: G=%d ids per set (1..%d)", G, NB_MAX_G);
+    HG_TRY(reserve_neighbours(c, Q, G, true));
+    if (Q > 0) HG_HIP(hipMemcpyAsync(c->nb_stage.p, host_ids, (size_t)Q * G * 4, hipMemcpyHostToDevice, c->stream));
+    u32 flag = 0;
+    HG_TRY(sort_neighbours(c, c->nb_stage.as<u32>(), G, Q, G, &flag));    // (synchronises: the host table is the caller's again)
+    if (flag)
+        return fail(HG_ERR_ARG, "hg_set_neighbours: %s%s%s", flag & NB_FLAG_DUP ? "a set holds the same id twice" : "", flag == (NB_FLAG_DUP | NB_FLAG_RANGE) ? "; " : "",
+                    flag & NB_FLAG_RANGE ? "a set holds an id outside the database (0xFFFFFFFF pads a shorter set)" : "");
+    c->nb.finish(c, Q, Q, G);
+    return HG_OK;
+}
+
+// ... the same from the first G ranks of the ranked index lists the last ranking left on the device (hg_votes' precondition): the exact
+// float32 top G of hg_topr_real becomes the ground truth without leaving the GPU.  The lists are read only.
+int hg_neighbours_from_lists(hg_ctx* c, int G) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_neighbours_from_lists", "hg_set_database + hg_set_queries"));
+    c->nb.begin(); c->nh.begin();
+    HG_TRY(whole_database(c, "hg_neighbours_from_lists", "neighbour sets need the whole database in one context"));
+    if (!lists_on_device(c))
+        return fail(HG_ERR_STATE, "hg_neighbours_from_lists: no ranked lists on the device (hg_map and hg_map_real write none): call hg_topr / hg_topr_real first");
+    const i64 Q = c->geo.Q, R = c->geo.R;
+    if (G < 1 || G > NB_MAX_G || G > R) return fail(HG_ERR_ARG, "hg_neighbours_from_lists: G=%d (1..min(R=%lld, %d))", G, (long long)R, NB_MAX_G);
+    HG_TRY(reserve_neighbours(c, Q, G, false));
+    u32 flag = 0;
+    HG_TRY(sort_neighbours(c, c->out_idx.as<u32>(), R, Q, G, &flag));
+    if (flag) return fail(HG_ERR_STATE, "hg_neighbours_from_lists: the first %d ranks of a list hold a repeated or foreign row (flag %u)", G, flag);
+    c->nb.finish(c, Q, Q, G);
+    return HG_OK;
+}
+
+// The match bitmap from the neighbour sets instead of the label words: slot k of query q matches iff idx[q][k] is in NB(q).  Through
+// the ranked index lists in global rank order for all queries -- the lists hg_votes accepts on a whole-database context.  Sets the match
+// stage, clears the AP stage; hg_ap, hg_ap_at, hg_get_match and hg_export go on unchanged.  The next ranking brings the label bits back.
+int hg_match_neighbours(hg_ctx* c) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_match_neighbours", "hg_set_database + hg_set_queries"));
+    if (!c->nb.current(c)) return fail(HG_ERR_STATE, "hg_match_neighbours: no neighbour sets of the tables loaded now: call hg_set_neighbours or hg_neighbours_from_lists first");
+    HG_TRY(whole_database(c, "hg_match_neighbours", "neighbour sets need the whole database in one context"));
+    if (!lists_on_device(c))
+        return fail(HG_ERR_STATE, "hg_match_neighbours: no ranked lists on the device (hg_map, hg_map_real and hg_map_begin write none): call hg_topr, hg_topr_real, hg_topr_asym or hg_topr_rerank first");
+    if (c->ranked_local) return fail(HG_ERR_STATE, "hg_match_neighbours: the lists are in this shard's local rank order (hg_select_ranked)");
+    if (c->G > 1) return fail(HG_ERR_STATE, "hg_match_neighbours: the lists hold one of %d shards' rows", c->G);
+    if (c->mbits_in_ws_b || c->ms_n) return fail(HG_ERR_STATE, "hg_match_neighbours: a step of hg_map_begin is in flight or was the last ranking: rank with hg_topr first");
+    if (c->verdict_pending) return fail(HG_ERR_STATE, "hg_match_neighbours: the bet's verdict is pending (defer_verdict): ask hg_bet_verdict first");
+    const i64 Q = c->geo.Q, R = c->geo.R;
+    if (Q != c->nb.Q) return fail(HG_ERR_STATE, "hg_match_neighbours: %lld ranked queries, %lld neighbour sets", (long long)Q, (long long)c->nb.Q);
+    const int G = (int)c->nb.dim;
+    const i64 nCB = (R + NM_CHUNK - 1) / NM_CHUNK;
+    if (nCB * Q > 0x7FFFFFFFll) return fail(HG_ERR_ARG, "hg_match_neighbours: Q*R too large for one launch");
+    HG_TRY(c->mbits.reserve((size_t)Q * c->RW * 8));       // (the ranking's own: it is large enough already)
+    const size_t lds = (size_t)G * 4;
+    static std::atomic<unsigned long long> lds_allowed{0};
+    if (lds > 48 * 1024 && !(lds_allowed.load() >> (c->device & 63) & 1ull)) {
+        HG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nbr_match), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        lds_allowed.fetch_or(1ull << (c->device & 63));
+    }
+    NbrMatchArgs a;
+    a.idx = c->out_idx.as<u32>(); a.ids = c->nb_ids.as<u32>(); a.count = c->nb_cnt.as<u32>(); a.mbits = c->mbits.as<u64>();
+    a.R = R; a.RW = c->RW; a.N = c->N; a.G = G; a.nCB = (int)nCB; a.idx_base = c->idx_base;
+    c->t_begin(KI_NBR_MATCH);
+    if (Q > 0) hipLaunchKernelGGL(k_nbr_match, dim3((unsigned)(nCB * Q)), dim3(NM_THREADS), lds, c->stream, a);
+    c->t_end();
+    HG_TRY(c->check_launch("k_nbr_match"));
+    c->stage |= ST_MATCH;
+    c->stage &= ~(unsigned)ST_AP;
+    c->bitmap_changed();
+    c->match_source = 1;
+    return c->stage_end();
+}
+
+// The neighbour distance histogram: nbr[d][q] = the neighbours of q at Hamming distance d, Q x G pairs through the packed codes.  The
+// shape and meaning of hg_rel_hist's relevant table; a table of its own (nh), the staged pipeline's state and the other results untouched.
+int hg_nbr_hist(hg_ctx* c) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_nbr_hist", "hg_set_database + hg_set_queries"));
+    c->nh.begin();
+    if (!c->nb.current(c)) return fail(HG_ERR_STATE, "hg_nbr_hist: no neighbour sets of the tables loaded now: call hg_set_neighbours or hg_neighbours_from_lists first");
+    const Geo g = full_geometry(c);
+    if (g.Q != c->nb.Q) return fail(HG_ERR_STATE, "hg_nbr_hist: %d loaded queries, %lld neighbour sets", g.Q, (long long)c->nb.Q);
+    if (g.NB > 256 || g.NW > 8) return fail(HG_ERR_ARG, "hg_nbr_hist: codes of %d words", g.NW);
+    const FirstReservations first;
+    HG_TRY(c->nh_tab.reserve((size_t)g.NB * g.Qpad * 4));
+    first.keep(c);
+    NbrHistArgs a;
+    a.qc = c->qc.as<u32>(); a.db = c->db.as<u32>(); a.ids = c->nb_ids.as<u32>(); a.nbr = c->nh_tab.as<u32>();
+    a.N = c->N; a.Qpad = g.Qpad; a.G = (int)c->nb.dim; a.NW = g.NW; a.NB = g.NB;
+    c->t_begin(KI_NBR_HIST);
+    if (g.Q > 0) hipLaunchKernelGGL(k_nbr_hist, dim3((unsigned)g.Q), dim3(NH_THREADS), 0, c->stream, a);
+    c->t_end();
+    HG_TRY(c->check_launch("k_nbr_hist"));
+    c->nh.finish(c, g.Q, g.Qpad, g.NB);
+    return c->stage_end();
 }
 
 // A shard's current table `which` as one block in the exchange layout (hg_side_merge.hpp): u32 [planes][Qpad], for the joint table
@@ -735,10 +873,29 @@ int hg_get_votes(hg_ctx* c, uint32_t* host_votes) {
     return c->sync();
 }
 
+int hg_get_neighbours(hg_ctx* c, uint32_t* host_ids_sorted, uint32_t* host_count) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_neighbours", "hg_set_neighbours"));
+    if (!c->nb.current(c)) return fail(HG_ERR_STATE, "hg_get_neighbours called before hg_set_neighbours / hg_neighbours_from_lists (on the tables loaded now)");
+    if (host_ids_sorted) HG_HIP(hipMemcpyAsync(host_ids_sorted, c->nb_ids.p, (size_t)c->nb.Q * c->nb.dim * 4, hipMemcpyDeviceToHost, c->stream));
+    if (host_count) HG_HIP(hipMemcpyAsync(host_count, c->nb_cnt.p, (size_t)c->nb.Q * 4, hipMemcpyDeviceToHost, c->stream));
+    return c->sync();
+}
+
+int hg_get_nbr_hist(hg_ctx* c, uint32_t* host_nbr, uint32_t* host_count) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_get_nbr_hist", "hg_nbr_hist"));
+    if (!c->nh.current(c) || !c->nb.current(c)) return fail(HG_ERR_STATE, "hg_get_nbr_hist called before hg_nbr_hist (on the neighbour sets and tables held now)");
+    if (host_nbr) HG_TRY(download_pitched(c, host_nbr, c->nh_tab, c->nh.Q, c->nh.Qpad, c->nh.dim));
+    if (host_count) HG_HIP(hipMemcpyAsync(host_count, c->nb_cnt.p, (size_t)c->nb.Q * 4, hipMemcpyDeviceToHost, c->stream));
+    return c->sync();
+}
+
 }  // extern "C"
 
 int preload_side() {   // (hg_preload: see preload_seq)
     hipFuncAttributes a;
     HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_tie_ap)));
+    HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_nbr_sort)));
+    HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_nbr_match)));
+    HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_nbr_hist)));
     return HG_OK;
 }

@@ -452,6 +452,45 @@ int hg_get_vote_pred(hg_ctx* ctx, int32_t* host_pred, int64_t* host_top);   /* [
 int hg_get_vote_confusion(hg_ctx* ctx, int64_t* host_conf);             /* [nk][C][C] */
 int hg_get_votes(hg_ctx* ctx, uint32_t* host_votes);                    /* [Q][nk][C] */
 
+/* ---- label-free relevance: ground-truth neighbour sets ----------------------------------------------------------------------------
+ * Everything above calls a row relevant when it shares a class label with the query.  Unsupervised hashing, ANN benchmarks and
+ * binary-embedding quantisation have no labels: the ground truth of a query q is a SET of database rows NB(q) -- its true nearest
+ * neighbours in the original feature space -- and the question is how much of it a ranking recovers.  NB(q) holds n_q distinct global
+ * row numbers in [0, n_total), 0 <= n_q <= G, 1 <= G <= 16384.  The sets are a table of the loaded queries and database like every side
+ * result: a reload of either and hg_trim end them, and so does a refused call of the two that make them.  They need the whole database
+ * in one context (idx_base == 0, N == n_total): HG_ERR_STATE on a shard.
+ *   hg_set_neighbours         host_ids [Q][G] in any order, 0xFFFFFFFF pads a shorter set; Q must be the loaded query count, G in
+ *                             1..16384 (HG_ERR_ARG otherwise).  Each row is sorted ascending on the device and n_q counted (k_nbr_sort);
+ *                             a row with a duplicate or an id >= n_total is found there and refused with HG_ERR_ARG after one flag word
+ *                             has come back.  Synchronises whatever "stage_sync" says.
+ *   hg_neighbours_from_lists  the first G ranks (G <= R, else HG_ERR_ARG) of the ranked index lists the last ranking left on the device
+ *                             -- hg_votes' precondition: hg_topr, hg_topr_real, hg_topr_asym, hg_topr_rerank, a staged hg_select with
+ *                             lists; HG_ERR_STATE otherwise -- become the sets: after hg_topr_real the exact float32 top G is the ground
+ *                             truth without ever leaving the GPU.  The lists are only read.
+ *   hg_get_neighbours         the sorted table [Q][G], pads at the end, and n_q [Q]; either may be null.
+ *   hg_match_neighbours       rewrites the match bitmap (uint64 [Q][ceil(R/64)], bits past R zero): slot k of query q matches iff
+ *                             idx[q][k] is in NB(q); a slot holding 0xFFFFFFFF or an index >= N never matches (k_nbr_match).  Needs
+ *                             the sets and ranked index lists in global rank order for all Q queries -- the lists hg_votes accepts on a
+ *                             whole-database context; HG_ERR_STATE without either, after the list-free hg_map / hg_map_real /
+ *                             hg_map_begin, and for lists in a shard's local rank order.  It sets the match stage, clears the AP stage
+ *                             and ends hg_ap_at's tables; hg_ap, hg_get_ap, hg_get_match, hg_ap_at and hg_export (match, ap, hits) then
+ *                             work unchanged on the neighbour bits: AP is the reference's (hits inside the top R in the denominator, NaN
+ *                             where there are none), recall@k = hits@k / n_q.  hg_match is not changed: it sees the match stage set and
+ *                             returns, so the label bits come back only with the next ranking.  Stat "match_source": 0 the bitmap came
+ *                             from the labels, 1 from the neighbour sets; every ranking resets it to 0.
+ *   hg_nbr_hist               nbr[d][q] = #{n in NB(q) : Hamming distance of q and n = d}, the shape and meaning of hg_rel_hist's rel
+ *                             table: with that pass's all table, recall and precision over the Hamming radius for neighbour relevance,
+ *                             no ranking needed.  Q x G pairs through the packed codes (k_nbr_hist), b up to HG_MAX_BITS, integers only:
+ *                             independent of Q and of the order the set was given in.  A table of its own: stage, lists, bitmap, the
+ *                             other side results and a step of hg_map_begin in flight are left as they were; a new set ends it.
+ *   hg_get_nbr_hist           nbr [b+1][Q] and n_q [Q]; either may be null. */
+int hg_set_neighbours(hg_ctx* ctx, const uint32_t* host_ids, int64_t Q, int G);
+int hg_neighbours_from_lists(hg_ctx* ctx, int G);
+int hg_get_neighbours(hg_ctx* ctx, uint32_t* host_ids_sorted, uint32_t* host_count);
+int hg_match_neighbours(hg_ctx* ctx);
+int hg_nbr_hist(hg_ctx* ctx);
+int hg_get_nbr_hist(hg_ctx* ctx, uint32_t* host_nbr, uint32_t* host_count);
+
 /* ---- the histogram tables of a database-sharded context: pack, exchange, merge -------------------------------------------------
  * hg_rel_hist's, hg_grade_hist's and hg_joint_hist's tables are additive over shards (contexts loaded with idx_base / n_total; the
  * queries replicated, so Q, b and C are equal on every rank).  Everything read from them -- the lookup curves over the Hamming radius,
