@@ -15,7 +15,7 @@ context's stream, ordered with its kernels):
   3. (the bet with locally ranked records) 16 bytes per query: every rank stitches and evaluates only its own
      share of the queries, the per-query APs and the verdict are gathered.
   The bet's tables (1: sampled histograms, 2: record counts + local bitmaps) travel by ALL-TO-ALL to the owner of
-  their queries where engine and communicator can (hg_alltoall: `route_by_owner`, the default): a GPU then receives
+  their queries where the engine declares that form (hg_alltoall: `route_by_owner`, the default): a GPU then receives
   its own queries' share of every shard's table -- 10.6 MB per step at C4 on 8 GPUs -- instead of all of it (80 MB).
 
 The order-free side metrics -- lookup curves over the Hamming radius, tie-aware mAP / precision / recall, tie-aware NDCG / ACG,
@@ -39,7 +39,15 @@ instead (`evaluate_real_queries`): its float table is small enough to replicate.
 The reference has no counterpart (lib/metric.py runs in one process); the
 result is bit-identical to the single-GPU path, which the tests check with
 virtual shards on one GPU (LocalComm) and, for the orchestration, with a NumPy
-engine over a two-process gloo group on CPU (tests/torch_comm.py).
+engine over a two-process gloo group on CPU (tests/torch_comm.py) and call by
+call with a recording engine (tests/test_shard_orchestration.py).
+
+A communicator is: rank, world; all_gather(buf) -> [world] blocks, block r from rank r;
+all_to_all(buf): [world] equal blocks, block r for rank r -> [world] blocks, block r from
+rank r; barrier(); all_gather_host(arr) -> [world, ...] host array (query splits, side
+metrics); and allreduce_max(x) where the routed form checks itself, on RcclComm only.
+Buffers are opaque to evaluate_shard: what an engine returns goes to the communicator and
+back.  An engine is the exact sequence plus the forms of the bet it declares: BET_FORMS below.
 """
 import collections
 import os
@@ -219,6 +227,30 @@ class LocalComm:
         sh = cls._Shared(world)
         return [cls(sh, r) for r in range(world)]
 
+    @classmethod
+    def run(cls, world, work):
+        """work(rank, comm) -> result on `world` threads, one virtual rank each -> [result per rank].  A rank that raises aborts
+        the shared barrier, so its peers leave their exchanges (BrokenBarrierError) instead of waiting for it; every thread is
+        joined and the first error re-raised.  The work sets comm.ctx to its context before the first device exchange."""
+        comms = cls.create(world)
+        results, errors = [None] * world, []
+
+        def one_rank(r):
+            try:
+                results[r] = work(r, comms[r])
+            except Exception as e:       # noqa: BLE001
+                errors.append(e)
+                comms[r]._s.barrier.abort()
+
+        threads = [threading.Thread(target=one_rank, args=(r,)) for r in range(world)]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+        if errors:
+            raise errors[0]
+        return results
+
     def all_gather(self, buf):
         self._s.slots[self.rank] = buf          # the producing stage has synchronised (stage_sync = 1)
         self._s.barrier.wait()
@@ -256,9 +288,42 @@ class LocalComm:
         return out
 
 
-# ------------------------------------------------------------------ HIP shard engine
-class HipShardEngine:
+# ------------------------------------------------------------------ shard engines
+# Every engine has the exact sequence: hist, plan, select_match, match_bits, finish, verdict, and topr_buffers / merge_topr for gathered
+# lists.  The forms of the bet it may DECLARE, and the methods evaluate_shard then calls -- nothing is probed: a declared form whose
+# method is missing raises AttributeError, an undeclared form is never called:
+#   "candidates"  bet_eligible, sample_hist, guess, select_candidates, rank_candidates
+#   "ranked"      ranked_merge_ok, bet_eligible, widen_slices, sample_hist, guess, select_ranked, merge_ranked (every rank merges whole)
+#   "split"       merge_ap_part, unpack_parts: the merge and the AP of the ranked bet split over the ranks by query
+#   "routed"      pack_sample_by_owner, guess_owned, guess_finish, pack_ranked_by_owner, merge_ap_owned, unpack_parts
+#   "one_call"    shard_step: the routed bet as one library call over the context's own communicator (RcclComm)
+BET_FORMS = frozenset(("candidates", "ranked", "split", "routed", "one_call"))
+
+
+class ShardEngine:
+    """No form of the bet, and the bets' three questions answered "no".  A subclass names its forms in `bet_forms` (checked here); an
+    engine of any other class that names none (no `bet_forms` at all) has none either: the exact sequence is all it is asked for."""
+    bet_forms = frozenset()
+
+    def __init_subclass__(cls, **kw):
+        super().__init_subclass__(**kw)
+        cls.bet_forms = frozenset(cls.bet_forms)
+        if not cls.bet_forms <= BET_FORMS:
+            raise TypeError("%s.bet_forms: unknown form(s) %s" % (cls.__name__, sorted(cls.bet_forms - BET_FORMS)))
+
+    def bet_eligible(self, R, world):
+        return False
+
+    def ranked_merge_ok(self, world):
+        return False
+
+    def widen_slices(self):
+        return False
+
+
+class HipShardEngine(ShardEngine):
     """The staged C ABI of one context (one shard on one GPU), speaking raw device buffers."""
+    bet_forms = BET_FORMS
 
     def __init__(self, ctx, want_lists=False, async_stages=False):
         """async_stages: stop synchronising per stage -- kernels and RCCL collectives are ordered on the context's
@@ -395,9 +460,10 @@ class HipShardEngine:
 def evaluate_shard(engine, comm, R, gather_topr=False, always_gather=False, bet=True, route_by_owner=True, one_call=True):
     """Run one rank's part of the sharded evaluation.
 
-    engine: HipShardEngine (or any object with the same five methods -- the CPU
-    tests drive this very function with a NumPy engine over gloo).
-    route_by_owner: the bet's exchanges as all-to-alls by query owner when engine and communicator can (else, or with
+    engine: HipShardEngine, or any ShardEngine -- the CPU tests drive this very function with NumPy engines over gloo and with a
+    recording engine.  The ranked bet runs if the engine declares it (not with gather_topr), else the candidates bet if declared,
+    else -- with bet=False, or after a lost bet -- the exact sequence: _sequence below.
+    route_by_owner: the ranked bet's exchanges as all-to-alls by query owner where the engine declares "routed" (else, or with
     False, the all-gather form: same results).  Over a real RCCL communicator with more than one rank the routed form has
     to EARN that default: the first call on a communicator runs the all-gather form (ncclAllGather only), then the routed
     form (grouped ncclSend / ncclRecv), compares the two per-query results bit for bit, and the ranks agree (one
@@ -405,19 +471,24 @@ def evaluate_shard(engine, comm, R, gather_topr=False, always_gather=False, bet=
     (`comm.routed_verified`; HG_ROUTE_BY_OWNER=0 / 1 skips the check and forces the form).
     one_call: over an RcclComm the routed bet runs as ONE library call (hg_shard_step: every stage and exchange enqueued back to back);
     False keeps the same stages driven from here, call by call -- the form the tests hold the one-call form against.
+    always_gather: exercise the collectives even with one rank.
     Returns (ap [Q] float64 with nan for skipped queries, rel [Q] int64) -- and
     (idx, dist) of the merged global top-R when gather_topr is set.
     """
+    def sequence(routed):
+        return _sequence(engine, comm, R, gather_topr=gather_topr, multi=comm.world > 1 or always_gather, bet=bet, routed=routed,
+                         one_call=one_call)
+
     if (route_by_owner and bet and not gather_topr and isinstance(comm, RcclComm) and comm.world > 1
-            and hasattr(engine, "merge_ap_owned")):
+            and "routed" in getattr(engine, "bet_forms", ())):
         forced = os.environ.get("HG_ROUTE_BY_OWNER")
         if forced in ("0", "1"):
             route_by_owner = forced == "1"
         elif comm.routed_verified is None:
-            ref = _evaluate_shard(engine, comm, R, False, always_gather, bet, False, one_call)
+            ref = sequence(False)
             bad = 0.0
             try:
-                got = _evaluate_shard(engine, comm, R, False, always_gather, bet, True, one_call)
+                got = sequence(True)
                 if not (np.array_equal(got[0], ref[0], equal_nan=True) and np.array_equal(got[1], ref[1])):
                     bad = 1.0
             except Exception:      # noqa: BLE001 -- an hg_alltoall failure on this rank: every rank must learn of it
@@ -426,98 +497,132 @@ def evaluate_shard(engine, comm, R, gather_topr=False, always_gather=False, bet=
             return ref
         else:
             route_by_owner = comm.routed_verified
-    return _evaluate_shard(engine, comm, R, gather_topr, always_gather, bet, route_by_owner, one_call)
+    return sequence(route_by_owner)
 
 
-def _evaluate_shard(engine, comm, R, gather_topr, always_gather, bet, route_by_owner, one_call=True):
-    multi = comm.world > 1 or always_gather          # always_gather: exercise the collectives even with one rank
-    gather = (lambda t: comm.all_gather(t)) if multi else (lambda t: None)
-    bits = None
-    if (bet and not gather_topr and hasattr(engine, "select_ranked") and engine.ranked_merge_ok(comm.world)
-            and engine.bet_eligible(R, comm.world)):
-        # the bet with one record pass and one exchange after the guess: every shard ranks its own records, the
-        # global bitmap is stitched from the gathered local ones (hg_merge_ranked)
-        routed = route_by_owner and multi and hasattr(engine, "merge_ap_owned") and hasattr(comm, "all_to_all")
-        while True:
-            if routed and one_call and isinstance(comm, RcclComm) and hasattr(engine, "shard_step"):
-                # the same owner-routed sequence as ONE library call: every stage and every RCCL exchange enqueued back to back
-                # on the context's stream, one synchronisation at the final download (hg_shard_step)
-                ap, rel, lost = engine.shard_step(R)
-                if lost is False:
-                    return ap, rel
-                if lost is None or not (hasattr(engine, "widen_slices") and engine.widen_slices()):
-                    break
-                continue
-            if routed:
-                # every table goes only to the owner of its queries (all-to-all): the sampled histograms to the rank that
-                # guesses for them, its answers back, the record counts + local bitmaps to the rank that stitches and
-                # evaluates them -- a GPU receives its own queries' share of each table, not all of it
-                engine.sample_hist(R)
-                answers = engine.guess_owned(R, comm.all_to_all(engine.pack_sample_by_owner(comm.world)), comm.world, comm.rank)
-                engine.guess_finish(R, comm.all_to_all(answers), comm.world, comm.rank)
-                engine.select_ranked()
-                part = engine.merge_ap_owned(comm.all_to_all(engine.pack_ranked_by_owner(comm.world)), comm.world, comm.rank)
-                ap, rel, lost = engine.unpack_parts(comm.all_gather(part), comm.world)
-                if not lost:
-                    return ap, rel
-                if not (hasattr(engine, "widen_slices") and engine.widen_slices()):
-                    break
-                continue
-            engine.guess(R, gather(engine.sample_hist(R)), comm.world, comm.rank)
-            h, b = engine.select_ranked()
-            if multi and hasattr(engine, "merge_ap_part"):
-                # the per-query stages split over the ranks: each merges and evaluates its own share of the queries, a third,
-                # tiny all-gather (16 bytes per query) brings every rank all APs and the verdict (the same on every rank)
-                part = engine.merge_ap_part(gather(h), gather(b), comm.world, comm.rank)
-                ap, rel, lost = engine.unpack_parts(comm.all_gather(part), comm.world)
-                if not lost:
-                    return ap, rel
-            else:
-                lost = engine.merge_ranked(gather(h), gather(b), comm.world)
-                if not lost:                              # held, or verdict deferred
-                    ap, rel = engine.finish(None, comm.world)
-                    if lost is not None or not engine.verdict():
-                        return ap, rel
-            # lost, on every rank alike.  A database stored class by class piles a query's near rows into a few slices of
-            # one shard, however good the cut: widen the slices (x8, x64; remembered for the next call) before giving up
-            if not (hasattr(engine, "widen_slices") and engine.widen_slices()):
-                break
-        bet = False                                   # exact sequence below
-    if bet and hasattr(engine, "bet_eligible") and engine.bet_eligible(R, comm.world):
-        # one pass over the pairs: sampled histograms -> shared guess -> candidate records ->
-        # exact record histograms -> shared exact plan.  `lost` is the same on every rank.
-        engine.guess(R, gather(engine.sample_hist(R)), comm.world, comm.rank)
-        lost = engine.rank_candidates(gather(engine.select_candidates()), comm.world, comm.rank)
-        deferred = lost is None                      # engine does not wait for the verdict: carry on as if the bet held
-        if not lost:
-            bits = engine.match_bits()
-    else:
-        deferred = False
-    if bits is None:                                 # exact two-pass sequence
-        engine.plan(R, gather(engine.hist()), comm.world, comm.rank)
-        bits = engine.select_match()
-    B = gather(bits)
-    if deferred and not gather_topr:
-        ap, rel = engine.finish(B, comm.world)
-        if not engine.verdict():                     # the same on every rank (computed from gathered data)
-            return ap, rel
-        engine.plan(R, gather(engine.hist()), comm.world, comm.rank)      # lost after all: exact sequence
-        B = gather(engine.select_match())
-    elif deferred and engine.verdict():
-        engine.plan(R, gather(engine.hist()), comm.world, comm.rank)
-        B = gather(engine.select_match())
-    lists = None
-    if gather_topr:
-        if multi and isinstance(comm, RcclComm):
-            engine.ctx.allgather_topr()               # the north star's exchange, inside the library
-            lists = engine.ctx.get_topr()
-        elif multi:
-            ti, td = engine.topr_buffers()
-            lists = engine.merge_topr(comm.all_gather(ti), comm.all_gather(td), comm.world)
+def _sequence(engine, comm, R, *, gather_topr, multi, bet, routed, one_call):
+    """One pass through the sequences: the ranked bet if it may run, else the candidates bet if it may, else -- or after a lost bet --
+    the exact sequence; then the lists, if wanted, and the AP."""
+    forms = getattr(engine, "bet_forms", ())             # (declared or absent, never inferred from the methods an engine has)
+    gather = comm.all_gather if multi else (lambda buf: None)
+    if bet and not gather_topr and "ranked" in forms and engine.ranked_merge_ok(comm.world) and engine.bet_eligible(R, comm.world):
+        if routed and multi and "routed" in forms:
+            attempt = _bet_one_call if one_call and isinstance(comm, RcclComm) and "one_call" in forms else _bet_routed
         else:
-            lists = engine.ctx.get_topr()
-    ap, rel = engine.finish(B, comm.world)
-    return (ap, rel, lists) if gather_topr else (ap, rel)
+            attempt = _bet_split if multi and "split" in forms else _bet_whole
+        held = _ranked_bet(attempt, engine, comm, R, gather)
+        if held:
+            return held
+        bet = False
+    bits, deferred = None, False
+    if bet and "candidates" in forms and engine.bet_eligible(R, comm.world):
+        bits, deferred = _candidates_bet(engine, comm, R, gather)
+    if bits is None:
+        bits = _exact(engine, comm, R, gather)
+    # a deferred verdict (the engine did not wait for it: carry on as if the bet held) is read as late as it can be: with the AP
+    # download, or before the lists are exchanged.  It is the same on every rank (computed from gathered data)
+    if deferred and not gather_topr:
+        ap, rel = engine.finish(bits, comm.world)
+        if not engine.verdict():
+            return ap, rel
+        bits = _exact(engine, comm, R, gather)             # lost after all
+    elif deferred and engine.verdict():
+        bits = _exact(engine, comm, R, gather)
+    if not gather_topr:
+        return engine.finish(bits, comm.world)
+    if multi and isinstance(comm, RcclComm):
+        engine.ctx.allgather_topr()                         # the north star's exchange, inside the library
+        lists = engine.ctx.get_topr()
+    elif multi:
+        ti, td = engine.topr_buffers()
+        lists = engine.merge_topr(comm.all_gather(ti), comm.all_gather(td), comm.world)
+    else:
+        lists = engine.ctx.get_topr()
+    ap, rel = engine.finish(bits, comm.world)
+    return ap, rel, lists
+
+
+def _exact(engine, comm, R, gather):
+    """The exact two-pass sequence: histograms -> shared plan -> select and match -> the gathered match bits."""
+    engine.plan(R, gather(engine.hist()), comm.world, comm.rank)
+    return gather(engine.select_match())
+
+
+def _candidates_bet(engine, comm, R, gather):
+    """One pass over the pairs: sampled histograms -> shared guess -> candidate records -> exact record histograms -> shared exact
+    plan -> (the gathered match bits, verdict deferred?), or (None, False) when the bet is lost: on every rank alike."""
+    engine.guess(R, gather(engine.sample_hist(R)), comm.world, comm.rank)
+    lost = engine.rank_candidates(gather(engine.select_candidates()), comm.world, comm.rank)
+    if lost:
+        return None, False
+    return gather(engine.match_bits()), lost is None
+
+
+def _ranked_bet(attempt, engine, comm, R, gather):
+    """attempt(...) -> (ap, rel, lost) until a bet holds -> (ap, rel); None when the exact sequence has to run.  A bet is lost on every
+    rank alike.  A database stored class by class piles a query's near rows into a few slices of one shard, however good the cut:
+    widen the slices (x8, x64; remembered for the next call) before giving up.  lost None: no bet was taken, nothing to widen."""
+    while True:
+        ap, rel, lost = attempt(engine, comm, R, gather)
+        if lost is False:
+            return ap, rel
+        if lost is None or not engine.widen_slices():
+            return None
+
+
+def _bet_one_call(engine, comm, R, gather):
+    """The owner-routed sequence as ONE library call: every stage and every RCCL exchange enqueued back to back on the context's
+    stream, one synchronisation at the final download (hg_shard_step)."""
+    return engine.shard_step(R)
+
+
+def _bet_routed(engine, comm, R, gather):
+    """Every table goes only to the owner of its queries (all-to-all): the sampled histograms to the rank that guesses for them, its
+    answers back, the record counts + local bitmaps to the rank that stitches and evaluates them -- a GPU receives its own queries'
+    share of each table, not all of it."""
+    engine.sample_hist(R)
+    answers = engine.guess_owned(R, comm.all_to_all(engine.pack_sample_by_owner(comm.world)), comm.world, comm.rank)
+    engine.guess_finish(R, comm.all_to_all(answers), comm.world, comm.rank)
+    engine.select_ranked()
+    part = engine.merge_ap_owned(comm.all_to_all(engine.pack_ranked_by_owner(comm.world)), comm.world, comm.rank)
+    ap, rel, lost = engine.unpack_parts(comm.all_gather(part), comm.world)
+    return ap, rel, bool(lost)
+
+
+def _bet_split(engine, comm, R, gather):
+    """All-gathered tables, the per-query stages split over the ranks: each merges and evaluates its own share of the queries, a
+    third, tiny all-gather (16 bytes per query) brings every rank all APs and the verdict."""
+    engine.guess(R, gather(engine.sample_hist(R)), comm.world, comm.rank)
+    h, b = engine.select_ranked()
+    part = engine.merge_ap_part(gather(h), gather(b), comm.world, comm.rank)
+    ap, rel, lost = engine.unpack_parts(comm.all_gather(part), comm.world)
+    return ap, rel, bool(lost)
+
+
+def _bet_whole(engine, comm, R, gather):
+    """Every rank stitches the whole global bitmap from the gathered local ones (hg_merge_ranked) and evaluates every query.  A
+    deferred verdict is read after the AP download."""
+    engine.guess(R, gather(engine.sample_hist(R)), comm.world, comm.rank)
+    h, b = engine.select_ranked()
+    lost = engine.merge_ranked(gather(h), gather(b), comm.world)
+    if lost:
+        return None, None, True
+    ap, rel = engine.finish(None, comm.world)
+    return ap, rel, lost is None and bool(engine.verdict())
+
+
+def _split_queries(comm, Q, rank_share):
+    """The queries split over the ranks: rank_share(lo, n) -> (ap [n], rel [n]) of this rank's contiguous share, one all_gather_host
+    of a padded [width, 2] float64 block (AP, count) per rank -> (ap [Q] float64, rel [Q] int64) in query order, on every rank."""
+    bounds = shard_bounds(Q, comm.world)
+    lo, n = bounds[comm.rank]
+    mine = np.zeros((max(b[1] for b in bounds), 2), np.float64)
+    if n:
+        mine[:n, 0], mine[:n, 1] = rank_share(lo, n)       # (a count <= R: exact in a double)
+    every = comm.all_gather_host(mine)
+    ap = np.concatenate([every[r, :bounds[r][1], 0] for r in range(comm.world)])
+    rel = np.concatenate([every[r, :bounds[r][1], 1] for r in range(comm.world)]).astype(np.int64)
+    return ap, rel
 
 
 def evaluate_real_queries(ctx, comm, q_feats, q_labels, R):
@@ -527,20 +632,12 @@ def evaluate_real_queries(ctx, comm, q_feats, q_labels, R):
     the all-gather of 16 bytes per query (AP, relevant count).  -> (ap[Q] float64, rel[Q] int64), identical on every
     rank and equal to the one-GPU hg_map_real bit for bit (a query's result does not depend on the others)."""
     q_feats, q_labels = np.asarray(q_feats), np.asarray(q_labels)
-    Q = q_feats.shape[0]
-    bounds = shard_bounds(Q, comm.world)
-    lo, n = bounds[comm.rank]
-    width = max(b[1] for b in bounds)
-    mine = np.zeros((width, 2), np.float64)
-    if n:
+
+    def rank_share(lo, n):
         ctx.set_queries_f32(np.ascontiguousarray(q_feats[lo:lo + n], np.float32), np.ascontiguousarray(q_labels[lo:lo + n], np.int64))
-        ap, rel = ctx.map_real(R)
-        mine[:n, 0] = ap
-        mine[:n, 1] = rel                          # a count <= R: exact in a double
-    every = comm.all_gather_host(mine)
-    ap = np.concatenate([every[r, :bounds[r][1], 0] for r in range(comm.world)])
-    rel = np.concatenate([every[r, :bounds[r][1], 1] for r in range(comm.world)]).astype(np.int64)
-    return ap, rel
+        return ctx.map_real(R)
+
+    return _split_queries(comm, q_feats.shape[0], rank_share)
 
 
 def evaluate_query_split(ctx, comm, q_code_words, q_label_words, R):
@@ -552,20 +649,12 @@ def evaluate_query_split(ctx, comm, q_code_words, q_label_words, R):
     does not depend on the other queries).  Database sharding (evaluate_shard) is what BASELINE.json's north star
     prescribes and what `bench.py --gpus G` reports as `value`; this form is reported beside it (`query_split`)."""
     q_code_words, q_label_words = np.asarray(q_code_words), np.asarray(q_label_words)
-    Q = q_code_words.shape[0]
-    bounds = shard_bounds(Q, comm.world)
-    lo, n = bounds[comm.rank]
-    width = max(b[1] for b in bounds)
-    mine = np.zeros((width, 2), np.float64)
-    if n:
+
+    def rank_share(lo, n):
         ctx.set_queries(np.ascontiguousarray(q_code_words[lo:lo + n]), np.ascontiguousarray(q_label_words[lo:lo + n]))
-        ap, rel = ctx.map(R)
-        mine[:n, 0] = ap
-        mine[:n, 1] = rel                          # a count <= R: exact in a double
-    every = comm.all_gather_host(mine)
-    ap = np.concatenate([every[r, :bounds[r][1], 0] for r in range(comm.world)])
-    rel = np.concatenate([every[r, :bounds[r][1], 1] for r in range(comm.world)]).astype(np.int64)
-    return ap, rel
+        return ctx.map(R)
+
+    return _split_queries(comm, q_code_words.shape[0], rank_share)
 
 
 # ------------------------------------------------------------------ order-free side metrics on a shard
@@ -689,7 +778,7 @@ def rank_lists_shard(ctx, comm, R):
     touched = "staged_lists" in ctx.options_touched
     try:
         engine = HipShardEngine(ctx, want_lists=True)
-        return _evaluate_shard(engine, comm, int(R), False, False, False, False)
+        return evaluate_shard(engine, comm, int(R), bet=False)
     finally:
         ctx.set_option("staged_lists", before)
         if not touched:

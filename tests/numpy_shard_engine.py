@@ -1,13 +1,17 @@
-"""A CPU stand-in for HipShardEngine, used ONLY to drive
-hashgan_amd.sharded.evaluate_shard under gloo (world_size 2, no GPU): same five
-methods, NumPy + the oracle's expressions inside.  It restates the counting
-plan of k_plan / k_order in the simplest possible form."""
+"""CPU stand-ins for HipShardEngine, used ONLY to drive
+hashgan_amd.sharded.evaluate_shard under gloo (world_size 2 and 3, no GPU): the
+methods of the exact sequence, and of the forms of the bet each engine declares
+(sharded.ShardEngine.bet_forms), with NumPy + the oracle's expressions inside.
+They restate the counting plan of k_plan / k_order in the simplest possible form."""
 import numpy as np
 import torch
 from oracle import hamming_map as O
+from hashgan_amd.sharded import ShardEngine
 
 
-class NumpyShardEngine:
+class NumpyShardEngine(ShardEngine):
+    """The exact sequence only: no form of the bet."""
+
     def __init__(self, qbits, qlab, dbbits, dblab, idx_base):
         self.q, self.ql, self.db, self.dl, self.base = qbits, qlab, dbbits, dblab, idx_base
         self.D = O.hamming_matrix(O.pack_bits(qbits), O.pack_bits(dbbits))      # [Q, Nshard]
@@ -75,6 +79,7 @@ class NumpyRankedEngine(NumpyShardEngine):
     """Adds the one-exchange form of the bet (HipShardEngine.select_ranked / merge_ranked): every shard ranks its
     own rows, the global bitmap is stitched from the gathered local ones.  The "guess" here keeps every row,
     which is a valid (if useless) superset; the merge is k_merge_ranked restated with Python loops."""
+    bet_forms = ("ranked", "split")
 
     def bet_eligible(self, R, world):
         return True
@@ -151,6 +156,7 @@ class NumpyRoutedEngine(NumpyRankedEngine):
     """The same bet with its exchanges routed by query owner (HipShardEngine.pack_sample_by_owner ... merge_ap_owned over
     comm.all_to_all): every table is cut into one block per owner of its queries, block o holding rows q0(o) .. of them, and
     the owner stitches and evaluates only what it received.  Blocks are [world, ...] tensors, like the HIP engine's."""
+    bet_forms = ("ranked", "split", "routed")
 
     def _owners(self, world):
         from hashgan_amd.sharded import shard_bounds

@@ -7,7 +7,6 @@ Every comparison is ==: the merged tables are integers, and k_graded's float sum
 alone.  Shapes, cut-offs and the host model of the two exchange units: tests/shard_list_cases.py (checked by
 tests/test_shard_lists_host.py)."""
 import functools
-import threading
 
 import numpy as np
 import pytest
@@ -62,31 +61,15 @@ def whole_ctx(name):
 
 def run_shards(name, G, fn):
     """fn(ctx, comm, rank) on G virtual shards -> [its result per rank]."""
-    comms = sharded.LocalComm.create(G)
-    results, errors = [None] * G, []
-
-    def work(r):
-        ctx = None
+    def work(r, comm):
+        ctx = shard_ctx(name, r, G)
         try:
-            ctx = shard_ctx(name, r, G)
-            comms[r].ctx = ctx
-            results[r] = fn(ctx, comms[r], r)
-        except Exception as e:       # noqa: BLE001
-            errors.append(e)
-            try:
-                comms[r]._s.barrier.abort()
-            except Exception:        # noqa: BLE001
-                pass
+            comm.ctx = ctx
+            return fn(ctx, comm, r)
         finally:
-            if ctx is not None:
-                ctx.close()
+            ctx.close()
 
-    th = [threading.Thread(target=work, args=(r,)) for r in range(G)]
-    [t.start() for t in th]
-    [t.join() for t in th]
-    if errors:
-        raise errors[0]
-    return results
+    return sharded.LocalComm.run(G, work)
 
 
 def three(ctx, comm, ks, ql):
@@ -349,7 +332,7 @@ def test_state_rules_on_a_shard():
         for kind, k in (("grades", None), ("votes", ks)):                     # the pack before a ranking with lists
             raises(STATE, ctx.pack_list_table, kind, k)
         ctx.set_option("staged_lists", 0)
-        sharded._evaluate_shard(sharded.HipShardEngine(ctx, want_lists=False), comm, R, False, False, False, False)
+        sharded.evaluate_shard(sharded.HipShardEngine(ctx, want_lists=False), comm, R, bet=False)
         assert "no ranked lists" in raises(STATE, ctx.pack_list_table, "grades")      # ... and after one without
         ctx.set_option("staged_lists", 1)
         good = ranked_and_merged()

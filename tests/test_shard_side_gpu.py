@@ -5,7 +5,6 @@ contexts, LocalComm, tests/test_sharded_gpu.py's idiom -- against the extra_metr
 Every comparison is ==: the merged tables are integers, and k_tie_ap and the NumPy reductions are functions of a query's table and the
 cut-offs alone.  Shapes and their properties: tests/shard_side_cases.py (checked by tests/test_shard_side_host.py)."""
 import functools
-import threading
 
 import numpy as np
 import pytest
@@ -60,31 +59,15 @@ def whole_ctx(name):
 
 def run_shards(name, G, fn):
     """fn(ctx, comm, rank) on G virtual shards -> [its result per rank]."""
-    comms = sharded.LocalComm.create(G)
-    results, errors = [None] * G, []
-
-    def work(r):
-        ctx = None
+    def work(r, comm):
+        ctx = shard_ctx(name, r, G)
         try:
-            ctx = shard_ctx(name, r, G)
-            comms[r].ctx = ctx
-            results[r] = fn(ctx, comms[r], r)
-        except Exception as e:       # noqa: BLE001
-            errors.append(e)
-            try:
-                comms[r]._s.barrier.abort()
-            except Exception:        # noqa: BLE001
-                pass
+            comm.ctx = ctx
+            return fn(ctx, comm, r)
         finally:
-            if ctx is not None:
-                ctx.close()
+            ctx.close()
 
-    th = [threading.Thread(target=work, args=(r,)) for r in range(G)]
-    [t.start() for t in th]
-    [t.join() for t in th]
-    if errors:
-        raise errors[0]
-    return results
+    return sharded.LocalComm.run(G, work)
 
 
 def seven(ctx, comm):

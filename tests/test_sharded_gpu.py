@@ -2,7 +2,6 @@
 (hashgan_amd.sharded.evaluate_shard) with an in-process communicator.  The
 sharded result must equal the single-shard result bit for bit -- AP, mAP and the
 merged ranked lists."""
-import threading
 import warnings
 import numpy as np
 import pytest
@@ -16,43 +15,26 @@ def _run_virtual(c, G, gather_topr, defer=False, routed=True, options=None):
     """options: engine options (hg_set_option) set on every shard's context before its tables are loaded."""
     N = c["dbbits"].shape[0]
     qw, ql = metric.pack_codes(c["qbits"]), metric.pack_labels(c["qlab"])
-    comms = sharded.LocalComm.create(G)
-    results = [None] * G
-    stats = [None] * G
-    boosts = [None] * G
-    errors = []
 
-    def work(r):
-        try:
-            base, rows = sharded.shard_bounds(N, G)[r]
-            ctx = _native.Context(0)
-            for key, value in (options or {}).items():
-                ctx.set_option(key, value)
-            ctx.set_database(metric.pack_codes(c["dbbits"][base:base + rows]), metric.pack_labels(c["dblab"][base:base + rows]),
-                             c["b"], c["dblab"].shape[1], idx_base=base, n_total=N)
-            ctx.set_queries(qw, ql)
-            comms[r].ctx = ctx
-            eng = sharded.HipShardEngine(ctx, want_lists=gather_topr)
-            if defer:
-                ctx.set_option("defer_verdict", 1)      # hg_rank does not wait; the verdict comes with the AP download
-            results[r] = sharded.evaluate_shard(eng, comms[r], c["R"], gather_topr=gather_topr, route_by_owner=routed)
-            stats[r] = (ctx.get_stat("optimistic_runs"), ctx.get_stat("optimistic_fallbacks"))
-            boosts[r] = ctx.get_stat("cap_boost")
-            ctx.close()
-        except Exception as e:       # noqa: BLE001
-            errors.append(e)
-            try:
-                comms[r]._s.barrier.abort()
-            except Exception:
-                pass
+    def work(r, comm):
+        base, rows = sharded.shard_bounds(N, G)[r]
+        ctx = _native.Context(0)
+        for key, value in (options or {}).items():
+            ctx.set_option(key, value)
+        ctx.set_database(metric.pack_codes(c["dbbits"][base:base + rows]), metric.pack_labels(c["dblab"][base:base + rows]),
+                         c["b"], c["dblab"].shape[1], idx_base=base, n_total=N)
+        ctx.set_queries(qw, ql)
+        comm.ctx = ctx
+        eng = sharded.HipShardEngine(ctx, want_lists=gather_topr)
+        if defer:
+            ctx.set_option("defer_verdict", 1)      # hg_rank does not wait; the verdict comes with the AP download
+        result = sharded.evaluate_shard(eng, comm, c["R"], gather_topr=gather_topr, route_by_owner=routed)
+        stats = (ctx.get_stat("optimistic_runs"), ctx.get_stat("optimistic_fallbacks"))
+        boost = ctx.get_stat("cap_boost")
+        ctx.close()
+        return result, stats, boost
 
-    th = [threading.Thread(target=work, args=(r,)) for r in range(G)]
-    [t.start() for t in th]
-    [t.join() for t in th]
-    if errors:
-        raise errors[0]
-    _run_virtual.last_stats = stats
-    _run_virtual.last_boosts = boosts
+    results, _run_virtual.last_stats, _run_virtual.last_boosts = (list(x) for x in zip(*sharded.LocalComm.run(G, work)))
     return results
 
 
@@ -328,26 +310,16 @@ def test_query_split_equals_one_gpu(G):
             ctx.close()
         assert np.array_equal(ap, ap0, equal_nan=True) and np.array_equal(rel, rel0)
         return
-    comms = sharded.LocalComm.create(G)
-    results, errors = [None] * G, []
 
-    def work(r):
-        try:
-            ctx = _native.Context(0)
-            ctx.set_database(dw, dl, c["b"], C)
-            comms[r].ctx = ctx
-            results[r] = sharded.evaluate_query_split(ctx, comms[r], qw, ql, c["R"])
-            ctx.close()
-        except Exception as e:       # noqa: BLE001
-            errors.append(e)
-            comms[r]._s.barrier.abort()
+    def work(r, comm):
+        ctx = _native.Context(0)
+        ctx.set_database(dw, dl, c["b"], C)
+        comm.ctx = ctx
+        result = sharded.evaluate_query_split(ctx, comm, qw, ql, c["R"])
+        ctx.close()
+        return result
 
-    th = [threading.Thread(target=work, args=(r,)) for r in range(G)]
-    [t.start() for t in th]
-    [t.join() for t in th]
-    if errors:
-        raise errors[0]
-    for ap, rel in results:
+    for ap, rel in sharded.LocalComm.run(G, work):
         assert np.array_equal(ap, ap0, equal_nan=True) and np.array_equal(rel, rel0)
 
 
@@ -401,25 +373,15 @@ def test_real_valued_ranking_splits_queries_over_ranks(G):
             ctx.close()
         assert np.array_equal(ap, ap0, equal_nan=True) and np.array_equal(rel, rel0)
         return
-    comms = sharded.LocalComm.create(G)
-    results, errors = [None] * G, []
 
-    def work(r):
-        try:
-            ctx = _native.Context(0)
-            ctx.set_database_f32(dbf, dl)
-            comms[r].ctx = ctx
-            results[r] = sharded.evaluate_real_queries(ctx, comms[r], qf, ql, R)
-            ctx.close()
-        except Exception as e:       # noqa: BLE001
-            errors.append(e)
-            comms[r]._s.barrier.abort()
+    def work(r, comm):
+        ctx = _native.Context(0)
+        ctx.set_database_f32(dbf, dl)
+        comm.ctx = ctx
+        result = sharded.evaluate_real_queries(ctx, comm, qf, ql, R)
+        ctx.close()
+        return result
 
-    th = [threading.Thread(target=work, args=(r,)) for r in range(G)]
-    [t.start() for t in th]
-    [t.join() for t in th]
-    if errors:
-        raise errors[0]
-    for ap, rel in results:
+    for ap, rel in sharded.LocalComm.run(G, work):
         assert np.array_equal(ap, ap0, equal_nan=True) and np.array_equal(rel, rel0)
     assert rel0[3] == 0

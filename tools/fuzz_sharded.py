@@ -1,32 +1,23 @@
 #!/usr/bin/env python3
 """One-off stress run on ONE GPU: the sharded sequences (hashgan_amd.sharded.evaluate_shard over G virtual ranks, threads +
 device-to-device copies standing in for RCCL) against the single-context result, over random shapes."""
-import sys, time, threading
+import sys, time
 import numpy as np
 sys.path.insert(0, __file__.rsplit("/", 2)[0])
 from hashgan_amd import _native, synth, metric, sharded
 
 def virtual(qw, ql, db, dl, b, C, N, G, R, gather_topr):
-    comms = sharded.LocalComm.create(G)
-    results, errors = [None] * G, []
-    def work(r):
-        try:
-            base, rows = sharded.shard_bounds(N, G)[r]
-            ctx = _native.Context(0)
-            ctx.set_database(metric.pack_codes(db[base:base + rows]), metric.pack_labels(dl[base:base + rows]), b, C, idx_base=base, n_total=N)
-            ctx.set_queries(qw, ql)
-            comms[r].ctx = ctx
-            eng = sharded.HipShardEngine(ctx, want_lists=gather_topr)
-            results[r] = sharded.evaluate_shard(eng, comms[r], R, gather_topr=gather_topr)
-            ctx.close()
-        except Exception as e:       # noqa: BLE001
-            errors.append(e)
-            try: comms[r]._s.barrier.abort()
-            except Exception: pass
-    th = [threading.Thread(target=work, args=(r,)) for r in range(G)]
-    [t.start() for t in th]; [t.join() for t in th]
-    if errors: raise errors[0]
-    return results
+    def work(r, comm):
+        base, rows = sharded.shard_bounds(N, G)[r]
+        ctx = _native.Context(0)
+        ctx.set_database(metric.pack_codes(db[base:base + rows]), metric.pack_labels(dl[base:base + rows]), b, C, idx_base=base, n_total=N)
+        ctx.set_queries(qw, ql)
+        comm.ctx = ctx
+        eng = sharded.HipShardEngine(ctx, want_lists=gather_topr)
+        result = sharded.evaluate_shard(eng, comm, R, gather_topr=gather_topr)
+        ctx.close()
+        return result
+    return sharded.LocalComm.run(G, work)
 
 def one(seed):
     rng = np.random.default_rng(seed)

@@ -16,7 +16,7 @@ compared with one context's in every round.
 
     python tools/shard_lists_timing.py            # from the repository root, on an MI355X
 """
-import argparse, json, os, sys, threading, time
+import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests import cases
@@ -71,60 +71,50 @@ def run(label, c, G, args):
     ref_gsum, ref_votes = ref[0][0], one.get_votes()
     one.close()
 
-    comms = sharded.LocalComm.create(G)
     bounds = sharded.shard_bounds(N, G)
     walls = np.zeros((rounds, G, 3))
-    events, errors, same, host_wall = [], [], [], []
+    events, same, host_wall = [], [], []
 
-    def work(r):
-        try:
-            lo, n = bounds[r]
-            ctx = _native.Context(0)
-            ctx.set_database(dc[lo:lo + n], dw[lo:lo + n], b, C, idx_base=lo, n_total=N)
-            ctx.set_queries(qc, qw)
-            ctx.timing_enable(2)
-            comm = comms[r]
-            comm.ctx = ctx
-            for rep in range(rounds):
-                comm.barrier()
-                t0 = time.perf_counter()
-                sharded.rank_lists_shard(ctx, comm, R)
-                ctx.synchronize()
-                ctx.timing_reset()
-                comm.barrier()
-                t1 = time.perf_counter()
-                sharded.merge_list_table(ctx, comm, "grades")
-                ctx.graded(KS, gain, disc)
-                sharded.merge_list_table(ctx, comm, "votes", KS)
-                ctx.votes(KS)
-                t2 = time.perf_counter()
-                if r == 0:
-                    events.append(ctx.timing_read())
-                    got = (ctx.get_graded(), ctx.get_vote_pred(), ctx.get_vote_confusion())
-                    same.append(all(np.array_equal(a, b_, equal_nan=True) for x, y in zip(got, ref)
-                                    for a, b_ in (zip(x, y) if isinstance(x, tuple) else [(x, y)])))
-                comm.barrier()
-                t3 = time.perf_counter()
-                engine = sharded.HipShardEngine(ctx, want_lists=True)
-                idx = sharded.evaluate_shard(engine, comm, R, gather_topr=True, always_gather=True, bet=False)[2][0]
-                t4 = time.perf_counter()
-                walls[rep, r] = ((t1 - t0) * 1e3, (t2 - t1) * 1e3, (t4 - t3) * 1e3)
-                if r == 0 and rep == rounds - 1 and G == args.shards[0]:       # (the lists, and so this figure, do not depend on G)
-                    t5 = time.perf_counter()
-                    gsum, votes = host_tables(idx, ql.astype(np.int8), dl.astype(np.int8), KS)
-                    host_wall.append((time.perf_counter() - t5) * 1e3)
-                    same.append(np.array_equal(gsum, ref_gsum) and np.array_equal(votes, ref_votes.astype(np.int64)))
-                comm.barrier()
-            ctx.close()
-        except Exception as e:       # noqa: BLE001
-            errors.append(e)
-            comms[r]._s.barrier.abort()
+    def work(r, comm):
+        lo, n = bounds[r]
+        ctx = _native.Context(0)
+        ctx.set_database(dc[lo:lo + n], dw[lo:lo + n], b, C, idx_base=lo, n_total=N)
+        ctx.set_queries(qc, qw)
+        ctx.timing_enable(2)
+        comm.ctx = ctx
+        for rep in range(rounds):
+            comm.barrier()
+            t0 = time.perf_counter()
+            sharded.rank_lists_shard(ctx, comm, R)
+            ctx.synchronize()
+            ctx.timing_reset()
+            comm.barrier()
+            t1 = time.perf_counter()
+            sharded.merge_list_table(ctx, comm, "grades")
+            ctx.graded(KS, gain, disc)
+            sharded.merge_list_table(ctx, comm, "votes", KS)
+            ctx.votes(KS)
+            t2 = time.perf_counter()
+            if r == 0:
+                events.append(ctx.timing_read())
+                got = (ctx.get_graded(), ctx.get_vote_pred(), ctx.get_vote_confusion())
+                same.append(all(np.array_equal(a, b_, equal_nan=True) for x, y in zip(got, ref)
+                                for a, b_ in (zip(x, y) if isinstance(x, tuple) else [(x, y)])))
+            comm.barrier()
+            t3 = time.perf_counter()
+            engine = sharded.HipShardEngine(ctx, want_lists=True)
+            idx = sharded.evaluate_shard(engine, comm, R, gather_topr=True, always_gather=True, bet=False)[2][0]
+            t4 = time.perf_counter()
+            walls[rep, r] = ((t1 - t0) * 1e3, (t2 - t1) * 1e3, (t4 - t3) * 1e3)
+            if r == 0 and rep == rounds - 1 and G == args.shards[0]:       # (the lists, and so this figure, do not depend on G)
+                t5 = time.perf_counter()
+                gsum, votes = host_tables(idx, ql.astype(np.int8), dl.astype(np.int8), KS)
+                host_wall.append((time.perf_counter() - t5) * 1e3)
+                same.append(np.array_equal(gsum, ref_gsum) and np.array_equal(votes, ref_votes.astype(np.int64)))
+            comm.barrier()
+        ctx.close()
 
-    th = [threading.Thread(target=work, args=(r,)) for r in range(G)]
-    [t.start() for t in th]
-    [t.join() for t in th]
-    if errors:
-        raise errors[0]
+    sharded.LocalComm.run(G, work)
     keep = slice(args.warmup, rounds)
     Qpad, Rp, nk = (Q + 63) // 64 * 64, (R + 15) // 16 * 16, len(KS)
     out = {"case": label, "Q": Q, "N": N, "b": b, "C": C, "R": R, "cutoffs": nk, "shards": G,

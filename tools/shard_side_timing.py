@@ -13,7 +13,7 @@ with the one-context results bit for bit in every round.
 
     python tools/shard_side_timing.py            # from the repository root, on an MI355X
 """
-import argparse, json, os, sys, threading, time
+import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests import cases
@@ -43,83 +43,72 @@ def main(args):
     dc, dw = metric.pack_codes(db), metric.pack_labels(dl)
     rounds = args.warmup + args.reps
 
-    one = _native.Context(0)
-    one.set_database(dc, dw, b, C)
-    one.set_queries(qc, qw)
-    one.timing_enable(2)
-    comms = sharded.LocalComm.create(G)
     bounds = sharded.shard_bounds(N, G)
     walls = np.zeros((rounds, G, 2))
-    events, errors, same = [], [], []
+    events, same = [], []
     ref = {}
-    go = threading.Barrier(G + 1, timeout=240)
-
-    def work(r):
-        try:
-            lo, n = bounds[r]
-            ctx = _native.Context(0)
-            ctx.set_database(dc[lo:lo + n], dw[lo:lo + n], b, C, idx_base=lo, n_total=N)
-            ctx.set_queries(qc, qw)
-            ctx.timing_enable(2)
-            comms[r].ctx = ctx
-            for rep in range(rounds):
-                go.wait()                                      # (the one-context call of this round is over)
-                ctx.set_queries(qc, qw)                        # stale tables, like the one-context cold call
-                ctx.synchronize()
-                ctx.timing_reset()
-                comms[r].barrier()
-                t0 = time.perf_counter()
-                ctx.rel_hist()
-                t1 = time.perf_counter()
-                comms[r].barrier()
-                t2 = time.perf_counter()
-                ptr, nbytes = ctx.pack_side_table("rel")
-                gathered = comms[r].all_gather(sharded.DevBuf(ptr, nbytes))
-                ctx.merge_side_table("rel", gathered.ptr, G)
-                ctx.tie_ap(Rs)
-                t3 = time.perf_counter()
-                walls[rep, r] = ((t1 - t0) * 1e3, (t3 - t2) * 1e3)
-                if r == 0:
-                    events.append(ctx.timing_read())
-                    got = ctx.get_tie_ap()
-                    same.append(all(np.array_equal(got[k], ref[k], equal_nan=True) for k in ref))
-                go.wait()
-            ctx.close()
-        except Exception as e:       # noqa: BLE001
-            errors.append(e)
-            for bar in (go, comms[r]._s.barrier):
-                bar.abort()
-
-    th = [threading.Thread(target=work, args=(r,)) for r in range(G)]
-    [t.start() for t in th]
     s = {k: [] for k in ("tie_ap_cold_wall", "tie_ap_warm_wall", "k_hist_rel", "k_hist_rel_reduce", "k_tie_ap")}
-    try:
-        for rep in range(rounds):
+
+    def one_context_round(one, rep):
+        one.set_queries(qc, qw)
+        one.synchronize()
+        one.timing_reset()
+        t0 = time.perf_counter()
+        one.tie_ap(Rs)                                     # cold: no tables
+        t1 = time.perf_counter()
+        cold = one.timing_read()
+        one.timing_reset()
+        t2 = time.perf_counter()
+        one.tie_ap(Rs)                                     # warm: the tables are there
+        t3 = time.perf_counter()
+        warm = one.timing_read()
+        ref.update(one.get_tie_ap())
+        if rep >= args.warmup:
+            s["tie_ap_cold_wall"].append((t1 - t0) * 1e3); s["tie_ap_warm_wall"].append((t3 - t2) * 1e3)
+            s["k_hist_rel"].append(per_launch(cold, "k_hist_rel")); s["k_hist_rel_reduce"].append(per_launch(cold, "k_hist_rel_reduce"))
+            s["k_tie_ap"].append(per_launch(warm, "k_tie_ap"))
+
+    def work(r, comm):
+        lo, n = bounds[r]
+        ctx = _native.Context(0)
+        ctx.set_database(dc[lo:lo + n], dw[lo:lo + n], b, C, idx_base=lo, n_total=N)
+        ctx.set_queries(qc, qw)
+        ctx.timing_enable(2)
+        comm.ctx = ctx
+        if r == 0:                                         # rank 0 also makes the one-context call of every round, the others waiting
+            one = _native.Context(0)
+            one.set_database(dc, dw, b, C)
             one.set_queries(qc, qw)
-            one.synchronize()
-            one.timing_reset()
+            one.timing_enable(2)
+        for rep in range(rounds):
+            if r == 0:
+                one_context_round(one, rep)
+            comm.barrier()                                 # (the one-context call of this round is over)
+            ctx.set_queries(qc, qw)                        # stale tables, like the one-context cold call
+            ctx.synchronize()
+            ctx.timing_reset()
+            comm.barrier()
             t0 = time.perf_counter()
-            one.tie_ap(Rs)                                     # cold: no tables
+            ctx.rel_hist()
             t1 = time.perf_counter()
-            cold = one.timing_read()
-            one.timing_reset()
+            comm.barrier()
             t2 = time.perf_counter()
-            one.tie_ap(Rs)                                     # warm: the tables are there
+            ptr, nbytes = ctx.pack_side_table("rel")
+            gathered = comm.all_gather(sharded.DevBuf(ptr, nbytes))
+            ctx.merge_side_table("rel", gathered.ptr, G)
+            ctx.tie_ap(Rs)
             t3 = time.perf_counter()
-            warm = one.timing_read()
-            ref.update(one.get_tie_ap())
-            go.wait()                                          # the shards' round
-            go.wait()
-            if rep >= args.warmup:
-                s["tie_ap_cold_wall"].append((t1 - t0) * 1e3); s["tie_ap_warm_wall"].append((t3 - t2) * 1e3)
-                s["k_hist_rel"].append(per_launch(cold, "k_hist_rel")); s["k_hist_rel_reduce"].append(per_launch(cold, "k_hist_rel_reduce"))
-                s["k_tie_ap"].append(per_launch(warm, "k_tie_ap"))
-    except threading.BrokenBarrierError:
-        pass
-    [t.join() for t in th]
-    one.close()
-    if errors:
-        raise errors[0]
+            walls[rep, r] = ((t1 - t0) * 1e3, (t3 - t2) * 1e3)
+            if r == 0:
+                events.append(ctx.timing_read())
+                got = ctx.get_tie_ap()
+                same.append(all(np.array_equal(got[k], ref[k], equal_nan=True) for k in ref))
+            comm.barrier()                                 # (the shards' round is over)
+        ctx.close()
+        if r == 0:
+            one.close()
+
+    sharded.LocalComm.run(G, work)
     keep = slice(args.warmup, rounds)
     sh = {"shard_pass_wall": list(walls[keep, :, 0].max(1)), "merged_call_wall": list(walls[keep, :, 1].max(1))}
     for k in ("k_hist_rel", "k_side_pack", "k_side_merge", "k_tie_ap"):
