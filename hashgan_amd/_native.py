@@ -79,6 +79,9 @@ _SIGNATURES = {
     "hg_get_topr_real": [_p, _p, _p],
     "hg_map_asym": [_p, _i64, _p, _p],
     "hg_topr_asym": [_p, _i64],
+    "hg_set_database_pq": [_p, _p, _p, _p, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)],
+    "hg_map_pq": [_p, _i64, _p, _p],
+    "hg_topr_pq": [_p, _i64],
     "hg_topr_rerank": [_p, _i64],
     "hg_map_rerank": [_p, _i64, _p, _p],
     "hg_get_rerank_scores": [_p, _p],
@@ -582,6 +585,42 @@ class Context:
     def topr_asym(self, R, download=True):
         """-> (idx, score) of hg_topr_asym through hg_get_topr_real; download=False: the lists stay on the device (graded(), votes(), export())."""
         check(self._lib.hg_topr_asym(self._h, int(R)))
+        self.R = int(R)
+        if not download:
+            return None
+        idx = np.empty((self.Q, self.R), dtype=np.uint32)
+        score = np.empty((self.Q, self.R), dtype=np.float32)
+        check(self._lib.hg_get_topr_real(self._h, _ptr(idx), _ptr(score)))
+        return idx, score
+
+    # -- quantised databases: real-valued queries against product-quantisation codes ------
+    def set_database_pq(self, codes, codebooks, labels):
+        """uint8 [N, M] codes + float32 [M, K, dsub] codebooks + int64 [N, C] labels (hg_set_database_pq): the context then holds the
+        sign codes of the decoded table, its labels and the PQ tables.  -> (decoded entries outside {-1,0,+1}, label entries outside {0,1})"""
+        from . import pq
+        codes, codebooks = pq.check_tables(codes, codebooks, values=False)      # (the library checks the values: HG_ERR_ARG names the offender)
+        lab = _labels_i64(labels)
+        if lab.ndim != 2 or lab.shape[0] != codes.shape[0]:
+            raise ValueError("labels must be [N, C] with the codes' N")
+        N, M = codes.shape
+        _, K, dsub = codebooks.shape
+        bc, bl = _i64(), _i64()
+        check(self._lib.hg_set_database_pq(self._h, _ptr(codes), _ptr(codebooks), _ptr(lab), N, M, K, dsub, lab.shape[1], 0, N,
+                                           C.byref(bc), C.byref(bl)))
+        self.N, self.b, self.C, self.n_total = N, M * dsub, lab.shape[1], N
+        return bc.value, bl.value
+
+    def map_pq(self, R):
+        """(ap, rel) of hg_map_pq: needs set_database_pq and the queries loaded under set_option("keep_query_floats", 1)."""
+        ap = np.empty(self.Q, dtype=np.float64)
+        rel = np.empty(self.Q, dtype=np.int64)
+        check(self._lib.hg_map_pq(self._h, int(R), _ptr(ap), _ptr(rel)))
+        self.R = int(R)
+        return ap, rel
+
+    def topr_pq(self, R, download=True):
+        """-> (idx, score) of hg_topr_pq through hg_get_topr_real; download=False: the lists stay on the device (graded(), votes(), export())."""
+        check(self._lib.hg_topr_pq(self._h, int(R)))
         self.R = int(R)
         if not download:
             return None

@@ -30,7 +30,7 @@ const char* const kKernelNames[KI_COUNT] = {"k_hist", "k_hist_reduce", "k_plan",
                                             "k_label_max", "k_hist_joint", "k_hist_joint_reduce",
                                             "k_rr_scan", "k_rr_collect", "k_rr_score", "k_rr_order", "k_export", "k_votes", "k_vote_confusion", "k_side_pack", "k_side_merge",
                                             "k_list_grades", "k_list_merge_grades", "k_list_merge_votes", "k_vote_pick", "k_asym_image16", "k_asym_rescore", "k_asym_expand_rows",
-                                            "k_nbr_sort", "k_nbr_match", "k_nbr_hist"};
+                                            "k_nbr_sort", "k_nbr_match", "k_nbr_hist", "k_pq_image16", "k_pq_rescore", "k_pq_expand_rows"};
 // Flatten NumPy's pairwise-summation tree for a chunk of n elements (n <= 8192):
 // numpy/_core/src/umath/loops_utils.h.src, pairwise_sum: n <= 128 is a leaf,
 // otherwise split at n/2 rounded down to a multiple of 8.
@@ -369,6 +369,7 @@ int hg_set_database(hg_ctx* c, const uint64_t* codes, const uint64_t* labels, in
     c->idx_base = (u32)idx_base;
     c->bpad = 0;                                       // packed input: no float tables for the real-valued path
     c->from_floats.rows_valid = false;
+    c->from_pq.forget_tables();
     HG_TRY(upload_codes(c, c->db, codes, N, (b + 63) / 64, c->NW));
     HG_TRY(c->dblab.reserve((size_t)(N > 0 ? N : 1) * c->LW * 8));
     if (N) HG_HIP(hipMemcpyAsync(c->dblab.p, labels, (size_t)N * c->LW * 8, hipMemcpyHostToDevice, c->stream));
@@ -570,6 +571,7 @@ static int pack_on_host(hg_ctx* c, const float* x, const int64_t* lab, i64 n, De
 // be set again, everything derived from the old tables is invalid, earlier lost bets say nothing about the new one.
 static void database_loaded(hg_ctx* c) {
     if (!c->from_floats.rows_valid) c->bpad = 0;
+    c->from_pq.forget_tables();                        // (hg_set_database_pq sets its tables valid behind this)
     c->stage = ST_DB;
     c->dbx_valid = false;
     c->dbx3_valid = false;
@@ -604,6 +606,114 @@ int hg_set_database_f32(hg_ctx* c, const float* host_x, const int64_t* host_labe
         c->from_floats.rows_valid = true;
     }
     database_loaded(c);
+    return HG_OK;
+}
+
+// Product-quantisation codes u8 [N][M], codebooks f32 [M][K][dsub], labels int64 [N][C] (hg_pq.hpp).  The context ends up as
+// hg_set_database_f32 leaves it for the decoded table under keep_floats = 0, plus the PQ tables in from_pq.  The sign codes come from
+// per-codeword sign patterns (dsub bits each, computed once) that host threads OR into the rows' words -- the same pool, the same pinned
+// staging and the same uploads as pack_on_host; the one pass over the codes also checks every byte against K, counts how often each
+// codeword occurs (the census of the decoded table; which codewords bound the rows' norm) -- no N x b floats anywhere.
+int hg_set_database_pq(hg_ctx* c, const uint8_t* host_codes, const float* host_books, const int64_t* host_labels, int64_t N, int M, int K,
+                       int dsub, int C, int64_t idx_base, int64_t n_total, int64_t* bad_codes, int64_t* bad_labels) {
+    if (!c) return fail(HG_ERR_ARG, "hg_set_database_pq: null context");
+    if (N < 1 || !host_codes || !host_books || !host_labels) return fail(HG_ERR_ARG, "hg_set_database_pq: need N >= 1 and data");
+    if (M < 1) return fail(HG_ERR_ARG, "hg_set_database_pq: M=%d subspaces (need >= 1)", M);
+    if (K < 1 || K > 256) return fail(HG_ERR_ARG, "hg_set_database_pq: K=%d codewords outside 1..256", K);
+    if (dsub < 1) return fail(HG_ERR_ARG, "hg_set_database_pq: dsub=%d features per subspace (need >= 1)", dsub);
+    if ((i64)M * dsub > HG_MAX_BITS) return fail(HG_ERR_ARG, "hg_set_database_pq: M * dsub = %lld features, more than %d", (long long)M * dsub, HG_MAX_BITS);
+    if (C < 1) return fail(HG_ERR_ARG, "hg_set_database_pq: C=%d", C);
+    if (idx_base != 0 || n_total != N) return fail(HG_ERR_ARG, "hg_set_database_pq: one shard only (idx_base=%lld, n_total=%lld for N=%lld rows)",
+                                                    (long long)idx_base, (long long)n_total, (long long)N);
+    if (N >= 0xFFFFFFFFll) return fail(HG_ERR_ARG, "hg_set_database_pq: N=%lld rows (need < 2^32 - 1)", (long long)N);
+    const int b = M * dsub, NW = (b + 31) / 32, LW = (C + 63) / 64, PW = (dsub + 31) / 32;
+    // per codeword: finite?  its sign pattern, its census (entries outside {-1, 0, +1}; zeros; minus ones), its norm^2 in float64
+    const size_t ncw = (size_t)M * K;
+    std::vector<u32> pat;
+    std::vector<i64> cw_census;
+    std::vector<double> cw_norm;
+    try { pat.assign(ncw * PW, 0u); cw_census.assign(ncw * 3, 0); cw_norm.assign(ncw, 0.0); }
+    catch (const std::exception& e) { return fail(HG_ERR_NOMEM, "hg_set_database_pq: %s", e.what()); }
+    for (size_t w = 0; w < ncw; ++w) {
+        const float* cw = host_books + w * dsub;
+        for (int j = 0; j < dsub; ++j) {
+            const float f = cw[j];
+            if (!std::isfinite(f))
+                return fail(HG_ERR_ARG, "hg_set_database_pq: codebook entry [%d][%d][%d] is not finite", (int)(w / K), (int)(w % K), j);
+            pat[w * PW + (j >> 5)] |= (u32)(f > 0.0f) << (j & 31);
+            cw_census[w * 3 + 0] += !(f == 1.0f || f == -1.0f || f == 0.0f);
+            cw_census[w * 3 + 1] += f == 0.0f;
+            cw_census[w * 3 + 2] += f == -1.0f;
+            cw_norm[w] += (double)f * (double)f;
+        }
+    }
+    HG_TRY(c->use());
+    const size_t cb = (size_t)N * NW * 4, lbytes = (size_t)N * LW * 8;
+    const size_t need_b = ((cb + 63) & ~(size_t)63) + lbytes;
+    if (c->hpk_cap < need_b) {
+        HG_TRY(c->sync());
+        pin_free(c->hpk, c->hpk_cap);
+        c->hpk = nullptr; c->hpk_cap = 0;
+        HG_HIP(pin_alloc(&c->hpk, need_b, &c->hpk_cap));
+    }
+    u32* hc = (u32*)c->hpk;
+    u64* hl = (u64*)((char*)c->hpk + ((cb + 63) & ~(size_t)63));
+    HostPackCensus cs;
+    std::vector<long long> used;
+    HostPqScan scan;
+    try {
+        HostTimer t_pack(HP_PACK);
+        used.assign(ncw, 0);
+        host_pack(nullptr, host_labels, N, b, C, nullptr, hl, &cs, 0);
+        host_pq_sign(host_codes, N, M, K, dsub, pat.data(), PW, hc, NW, used.data(), &scan, 0);
+    } catch (const std::exception& e) {               // no exception crosses the C ABI
+        return fail(HG_ERR_NOMEM, "hg_set_database_pq: host-side packing failed: %s", e.what());
+    }
+    if (scan.bad_row >= 0)
+        return fail(HG_ERR_ARG, "hg_set_database_pq: code byte %d at row %lld, subspace %d is not below K=%d", scan.bad_code, (long long)scan.bad_row, scan.bad_m, K);
+    i64 census[3] = {0, 0, 0};
+    double bound = 0.0;
+    for (int m = 0; m < M; ++m) {
+        double mx = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const size_t w = (size_t)m * K + k;
+            const i64 n = used[w];
+            if (!n) continue;
+            for (int e = 0; e < 3; ++e) census[e] += n * cw_census[w * 3 + e];
+            if (cw_norm[w] > mx) mx = cw_norm[w];
+        }
+        bound += mx;
+    }
+    float xmax2 = (float)bound;
+    if ((double)xmax2 < bound) xmax2 = std::nextafterf(xmax2, INFINITY);
+    // the context's tables: what hg_set_database_f32 sets for the decoded table, no float table
+    c->N = N; c->b = b; c->C = C; c->n_total = n_total;
+    c->NW = NW; c->NB = b + 1; c->LW = LW;
+    c->idx_base = 0;
+    c->from_floats.rows_valid = false;
+    HG_TRY(c->db.reserve(cb + 64 * 4));
+    HG_TRY(c->dblab.reserve(lbytes));
+    HG_HIP(hipMemcpyAsync(c->db.p, hc, cb, hipMemcpyHostToDevice, c->stream));
+    HG_HIP(hipMemcpyAsync(c->dblab.p, hl, lbytes, hipMemcpyHostToDevice, c->stream));
+    database_loaded(c);
+    RowSource& s = c->from_pq;
+    const int MP = (M + 3) / 4 * 4;
+    HG_TRY(s.pq_codes.reserve((size_t)N * MP + 64));
+    HG_TRY(s.pq_books.reserve(ncw * dsub * 4 + 64));
+    if (MP == M) {
+        HG_HIP(hipMemcpyAsync(s.pq_codes.p, host_codes, (size_t)N * M, hipMemcpyHostToDevice, c->stream));
+    } else {
+        HG_HIP(hipMemsetAsync(s.pq_codes.p, 0, (size_t)N * MP, c->stream));
+        HG_HIP(hipMemcpy2DAsync(s.pq_codes.p, (size_t)MP, host_codes, (size_t)M, (size_t)M, (size_t)N, hipMemcpyHostToDevice, c->stream));
+    }
+    HG_HIP(hipMemcpyAsync(s.pq_books.p, host_books, ncw * dsub * 4, hipMemcpyHostToDevice, c->stream));
+    HG_TRY(c->sync());                                 // the pinned staging and the caller's arrays are free again
+    s.pq_M = M; s.pq_K = K; s.pq_dsub = dsub; s.pq_MP = MP;
+    s.pq_xmax2 = xmax2;
+    s.pq_valid = true;
+    if (bad_codes) *bad_codes = (int64_t)census[0];
+    if (bad_labels) *bad_labels = (int64_t)cs.bad_labels;
+    c->census_db[0] = census[0]; c->census_db[1] = census[1]; c->census_db[2] = census[2];
     return HG_OK;
 }
 
@@ -1327,6 +1437,8 @@ int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "real_path")) *value = (c->real.filtered ? 1 : 0) | (c->real.lds_ranked ? 2 : 0) | (c->real.grouped ? 4 : 0) | (c->real.filtered && c->real.half ? 8 : 0);
     else if (!strcmp(key, "asym_calls")) *value = c->asym_calls;
     else if (!strcmp(key, "asym_float_rows")) *value = c->from_codes.rows_read;
+    else if (!strcmp(key, "pq_calls")) *value = c->pq_calls;
+    else if (!strcmp(key, "pq_float_rows")) *value = c->from_pq.rows_read;
     else if (!strcmp(key, "device_bytes")) *value = device_bytes(c);
 #ifdef HG_RANK_PROFILE
 #ifdef HG_RANK_PROFILE                        // (tools/rank_phase_profile.py: where k_rank_cnt left its phase timestamps)

@@ -13,7 +13,8 @@
 //   hg_pairs_mx.hip    launchers of the matrix-core pair passes (k_select_mx3 / mx4, k_hist_mx, k_hist_i8) and their images
 //   hg_pairs_mx1.hip   launcher of k_select_mx (every code length: the longest compile)
 //   hg_real.hip        real-valued (float32 inner product) ranking: a ladder of attempts, each with one RealReq down and one RealState (hg_ctx::real) up;
-//                      its asymmetric form (hg_topr_asym, hg_map_asym): the same call on the other RowSource, the database's packed codes read as +-1 (hg_asym.hpp)
+//                      its asymmetric form (hg_topr_asym, hg_map_asym): the same call on the other RowSource, the database's packed codes read as +-1 (hg_asym.hpp);
+//                      its quantised form (hg_topr_pq, hg_map_pq): the same call on a third, product-quantisation codes and codebooks (hg_pq.hpp; loaded by hg_set_database_pq, hg_core.hip)
 //   hg_comm.hip        RCCL collectives (library dlopen'ed on first use)
 //
 // No torch, no CPU compute path: every entry point either runs HIP kernels or fails.
@@ -220,7 +221,7 @@ enum KernelId { KI_HIST = 0, KI_HIST_REDUCE, KI_PLAN, KI_SEG_COUNTS, KI_SEG_LAYO
                 KI_GRADED, KI_GRADE_HIST, KI_GRADE_HIST_REDUCE, KI_TIE_AP, KI_AP_AT, KI_LABEL_MAX, KI_HIST_JOINT, KI_HIST_JOINT_REDUCE,
                 KI_RR_SCAN, KI_RR_COLLECT, KI_RR_SCORE, KI_RR_ORDER, KI_EXPORT, KI_VOTES, KI_VOTE_CONFUSION, KI_SIDE_PACK, KI_SIDE_MERGE,
                 KI_LIST_GRADES, KI_LIST_MERGE_GRADES, KI_LIST_MERGE_VOTES, KI_VOTE_PICK, KI_ASYM_IMAGE, KI_ASYM_RESCORE, KI_ASYM_EXPAND,
-                KI_NBR_SORT, KI_NBR_MATCH, KI_NBR_HIST, KI_COUNT };
+                KI_NBR_SORT, KI_NBR_MATCH, KI_NBR_HIST, KI_PQ_IMAGE, KI_PQ_RESCORE, KI_PQ_EXPAND, KI_COUNT };
 enum Stage { ST_NONE = 0, ST_DB = 1, ST_Q = 2, ST_HIST = 4, ST_PLAN = 8, ST_SELECT = 16, ST_MATCH = 32, ST_AP = 64 };
 extern const char* const kKernelNames[KI_COUNT];
 // the kernel that took the last record pass / the last rank stage (stats "select_variant", "rank_variant"), and what the rank stage is asked for
@@ -358,7 +359,7 @@ struct StepReq {
 // before the stages after it see it, so a request ends with its attempt.
 struct RowSource;
 struct RealReq {
-    RowSource* src = nullptr;  // the database's rows this call ranks: the context's from_floats or from_codes (a requery child: its parent's)
+    RowSource* src = nullptr;  // the database's rows this call ranks: the context's from_floats, from_codes or from_pq (a requery child: its parent's)
     i64 R = 0;
     bool bet = false;          // cut at a sampled threshold `sigma` deviations deep, slices sized for `budget` x R records per query
     double sigma = 0.0, budget = 0.0;
@@ -383,17 +384,25 @@ struct RealState {
 
 // What the real-valued ranking (hg_real.hip) reads and derives from the database's rows.  The context holds one per kind, each with its
 // own buffers and keys -- an image built from codes and one built from a float table never meet -- and a call is handed the one it runs
-// on (RealReq::src: hg_map_real from_floats, hg_map_asym from_codes); hg_real.hip's row-source section alone looks at the kind.
+// on (RealReq::src: hg_map_real from_floats, hg_map_asym from_codes, hg_map_pq from_pq); hg_real.hip's row-source section alone looks at the kind.
 struct RowSource {
-    enum Kind { FLOATS, CODES } kind;   // the loaded float table (hg_set_database_f32 / _dev with keep_floats) | the packed codes c->db read as +-1 (hg_asym.hpp)
-    DevBuf rows;               // f32 [N][bpad].  FLOATS: the table as loaded (BUF_TABLE; rows_valid: it is resident).  CODES: +-1.0 (pads 0) expanded on first
-                               // need per database (k_asym_expand_rows) for the paths that read float rows (no cut, vector fallbacks, real_mfma < 2): BUF_WORK
+    enum Kind { FLOATS, CODES, PQ } kind;   // the loaded float table (hg_set_database_f32 / _dev with keep_floats) | the packed codes c->db read as +-1 (hg_asym.hpp)
+                               // | product-quantisation codes and codebooks (hg_set_database_pq, hg_pq.hpp)
+    DevBuf rows;               // f32 [N][bpad].  FLOATS: the table as loaded (BUF_TABLE; rows_valid: it is resident).  CODES, PQ: the rows (pads 0) expanded on first
+                               // need per database (k_asym_expand_rows, k_pq_expand_rows) for the paths that read float rows (no cut, vector fallbacks, real_mfma < 2): BUF_WORK
     DevBuf rowsx;              // rows in MFMA A-fragment order (k_real_select_mx)
     DevBuf img, xmax2;         // filter + rescore path (hg_real_bf.hpp): 16-bit image of the rows, their max norm^2 (ensure_filter_image)
     bool rows_valid = false, rowsx_valid = false, img_valid = false;
     bool img_half = false;     // img is in IEEE half instead of bfloat16 (no feature of the database can overflow it)
-    i64 rows_read = 0;         // CODES, stat "asym_float_rows": the last call read the expanded rows
-    void forget_derived() { rowsx_valid = img_valid = false; if (kind == CODES) rows_valid = false; }   // a database load, hg_trim: each is rebuilt on its next use
+    i64 rows_read = 0;         // CODES, PQ, stats "asym_float_rows" / "pq_float_rows": the last call read the expanded rows
+    // PQ: the tables hg_set_database_pq loaded (BUF_TABLE) -- codes u8 [N][MP], MP = M rounded up to 4 with pad bytes 0, and codebooks f32 [M][K][dsub];
+    // pq_xmax2 >= every row's norm^2: the sum over the subspaces of the largest norm^2 among the codewords that occur, rounded up
+    DevBuf pq_codes, pq_books;
+    int pq_M = 0, pq_K = 0, pq_dsub = 0, pq_MP = 0;
+    float pq_xmax2 = 0.0f;
+    bool pq_valid = false;     // the PQ tables are the loaded database's (any other database loader ends that)
+    void forget_derived() { rowsx_valid = img_valid = false; if (kind != FLOATS) rows_valid = false; }   // a database load, hg_trim: each is rebuilt on its next use
+    void forget_tables() { pq_valid = false; pq_codes.release(); pq_books.release(); }
 };
 
 // The results of one side metric (hg_side.hip) and what they were computed from: the generations of the two tables, the rows Q, their
@@ -515,10 +524,12 @@ struct hg_ctx : StepBufs, StepState {
     int qstage_next = 0;
     bool ap_staged = false;
     bool ranked_local = false; // mbits holds this shard's bitmap in LOCAL rank order (hg_select_ranked)
-    // the two row sources of the real-valued ranking: hg_topr_real / hg_map_real run on the first, hg_topr_asym / hg_map_asym on the second
-    RowSource from_floats{RowSource::FLOATS}, from_codes{RowSource::CODES};
-    void forget_rows() { from_floats.forget_derived(); from_codes.forget_derived(); }
+    // the three row sources of the real-valued ranking: hg_topr_real / hg_map_real run on the first, hg_topr_asym / hg_map_asym on the second,
+    // hg_topr_pq / hg_map_pq on the third
+    RowSource from_floats{RowSource::FLOATS}, from_codes{RowSource::CODES}, from_pq{RowSource::PQ};
+    void forget_rows() { from_floats.forget_derived(); from_codes.forget_derived(); from_pq.forget_derived(); }
     i64 asym_calls = 0;        // stat "asym_calls": asymmetric calls that succeeded (cumulative)
+    i64 pq_calls = 0;          // stat "pq_calls": quantised calls that succeeded (cumulative)
     i64 real_requeried = 0;       // queries that lost the first real-valued bet and were ranked again on their own (cumulative)
     int bpad = 0;              // feature count padded to a multiple of 16 (0: no float tables loaded)
     i64 census_db[3] = {0, 0, 0}, census_q[3] = {0, 0, 0};
@@ -582,10 +593,11 @@ struct hg_ctx : StepBufs, StepState {
 
     // Every device buffer of the context, each once, with its class: hg_destroy, hg_trim and the stat "device_bytes" walk this.
     template <class F> void for_each_buf(F&& f) {
-        for (DevBuf* d : {&db, &dblab, &qc, &qlab, &from_floats.rows, &qf}) f(*d, BUF_TABLE);
+        for (DevBuf* d : {&db, &dblab, &qc, &qlab, &from_floats.rows, &qf, &from_pq.pq_codes, &from_pq.pq_books}) f(*d, BUF_TABLE);
         for (DevBuf* d : {&dbx, &qx, &dbx8, &dbx3, &dbx4, &shapes, &ap_recip, &aa_recip}) f(*d, BUF_DERIVED);
-        for (RowSource* s : {&from_floats, &from_codes}) for (DevBuf* d : {&s->rowsx, &s->img, &s->xmax2}) f(*d, BUF_DERIVED);
+        for (RowSource* s : {&from_floats, &from_codes, &from_pq}) for (DevBuf* d : {&s->rowsx, &s->img, &s->xmax2}) f(*d, BUF_DERIVED);
         f(from_codes.rows, BUF_WORK);
+        f(from_pq.rows, BUF_WORK);
         for (DevBuf* d : {&seglt, &segtie, &mbits2, &part, &obuf[0], &obuf[1], &beyond, &stage_in, &badcnt, &flist, &dbytes, &samp, &thr,
                           &sortA, &sortB, &scores, &gtab, &sampx, &cntq, &krows, &thr2, &hist2, &comm_tmp, &gath_idx, &gath_dist, &rh_part, &rh_all, &rh_rel,
                           &gr_tab, &gr_out, &gr_grades, &gh_part, &gh_tab, &ta_tab, &ta_out, &aa_tab, &aa_out, &jh_max, &jh_part, &jh_tab, &vt_tab, &vt_votes, &vt_pred, &vt_conf,

@@ -26,6 +26,13 @@ void host_pack_ship(const float* x, const int64_t* lab, long long n, int b, int 
 // reaches pinned staging memory at memory speed before it crosses PCIe (a pageable source is staged by the runtime at ~25 GB/s)
 void host_copy_rows(const float* x, long long r0, long long r1, int b, int bpad, float* dst, int threads, int which_pool = 0);
 void host_pack_warm();      // start the pools' threads now (hg_preload)
+// Sign codes of product-quantised rows (hg_set_database_pq): codes u8 [n][M] with K codewords per subspace, pat [M][K][PW] the codewords'
+// sign patterns (dsub bits each, PW = ceil(dsub / 32) words) -> out uint32 [n][NW], row r's bits m * dsub .. the pattern of its code in
+// subspace m.  used [M][K] += how often each codeword occurs.  A code byte >= K: its row keeps the subspace's bits clear, and the lowest
+// such row is reported (bad_row >= 0) with its subspace and byte.
+struct HostPqScan { long long bad_row = -1; int bad_m = 0, bad_code = 0; };
+void host_pq_sign(const uint8_t* codes, long long n, int M, int K, int dsub, const uint32_t* pat, int PW, uint32_t* out, int NW,
+                  long long* used, HostPqScan* scan, int threads);
 
 }  // namespace hg
 
@@ -435,6 +442,47 @@ inline void host_copy_rows(const float* x, long long r0, long long r1, int b, in
     }
     if (threads == 1 || !hostpack::pool(which_pool).run(threads, work))  // (a busy pool: this thread alone)
         for (int t = 0; t < threads; ++t) work(t);
+}
+
+inline void host_pq_sign(const uint8_t* codes, long long n, int M, int K, int dsub, const uint32_t* pat, int PW, uint32_t* out, int NW,
+                         long long* used, HostPqScan* scan, int threads) {
+    if (threads <= 0) threads = default_pack_threads();
+    threads = (int)std::max<long long>(1, std::min<long long>(threads, n >> 13));            // at least 8k rows per thread
+    const size_t ncw = (size_t)M * K;
+    struct Part { std::vector<long long> used; HostPqScan scan; };
+    std::vector<Part> part((size_t)threads);
+    auto work = [&](int t) {
+        Part& p = part[(size_t)t];
+        p.used.assign(ncw, 0);
+        const long long r0 = n * t / threads, r1 = n * (t + 1) / threads;
+        uint32_t row[16];                                                    // (NW <= 8: codes of up to 255 bits; one word of spill-over)
+        for (long long r = r0; r < r1; ++r) {
+            const uint8_t* code = codes + r * M;
+            for (int w = 0; w <= NW; ++w) row[w] = 0u;
+            for (int m = 0; m < M; ++m) {
+                const int k = code[m];
+                if (k >= K) {
+                    if (p.scan.bad_row < 0) { p.scan.bad_row = r; p.scan.bad_m = m; p.scan.bad_code = k; }
+                    continue;
+                }
+                const size_t w = (size_t)m * K + k;
+                p.used[w]++;
+                for (int pw = 0; pw < PW; ++pw) {
+                    const uint32_t bits = pat[w * PW + pw];
+                    const int pos = m * dsub + 32 * pw, at = pos >> 5, sh = pos & 31;
+                    row[at] |= bits << sh;
+                    if (sh) row[at + 1] |= bits >> (32 - sh);
+                }
+            }
+            memcpy(out + r * NW, row, (size_t)NW * 4);
+        }
+    };
+    if (threads == 1 || !hostpack::pool(0).run(threads, work))             // (a busy pool: this thread alone)
+        for (int t = 0; t < threads; ++t) work(t);
+    for (const Part& p : part) {                                             // (parts ascend in row order: the first offender is the lowest row's)
+        for (size_t w = 0; w < ncw; ++w) used[w] += p.used[w];
+        if (scan && scan->bad_row < 0 && p.scan.bad_row >= 0) *scan = p.scan;
+    }
 }
 
 // hg_preload: the pools' threads start with the first job that wants them (a few milliseconds for the packing pool's 4 x 64):

@@ -5,14 +5,16 @@
 // const reference; what it leaves behind is c->real (RealState), assigned afresh when the attempt begins.
 //
 // The database's rows come from a RowSource that travels with the call (RealReq::src): run_real picks the context's from_floats (the loaded
-// float table), run_asym (hg_topr_asym, hg_map_asym) from_codes (the packed codes read as +-1, hg_asym.hpp), and a requery child runs on its
-// parent's.  What differs between the two kinds -- float rows, 16-bit images, the filter's norm word, the rescore, the rows of the staged
-// sample -- is the section "the row source" below; nothing outside it reads RowSource::kind.
+// float table), run_asym (hg_topr_asym, hg_map_asym) from_codes (the packed codes read as +-1, hg_asym.hpp), run_pq (hg_topr_pq, hg_map_pq)
+// from_pq (product-quantisation codes and codebooks, hg_pq.hpp), and a requery child runs on its parent's.  What differs between the kinds
+// -- float rows, 16-bit images, the filter's norm word, the rescore, the rows of the staged sample -- is the section "the row source" below;
+// nothing outside it reads RowSource::kind.
 #include "hg_ctx.hpp"
 #include "hg_real_kernels.hpp"
 #include "hg_real_mx.hpp"
 #include "hg_real_bf.hpp"
 #include "hg_asym.hpp"
+#include "hg_pq.hpp"
 #include <type_traits>
 
 constexpr double REAL_FIRST_SIGMA = 5.0;        // depth of the first cut in deviations of the sampled count: one query in ~3e5 loses it and is ranked again on its
@@ -78,20 +80,29 @@ void cut_segments(Geo& g, i64 L) {
     g.nBlk = (int)((g.nUnits + WPB - 1) / WPB);
 }
 
-// ---- the row source (RealReq::src): what the FLOATS and the CODES kind do differently, and the only readers of RowSource::kind ----
-// The database's float rows [N][bpad]: the loaded table; from the codes, +-1.0 rows expanded into the source's work buffer on first need
-// per database (k_asym_expand_rows; stat "asym_float_rows" says that a call came here)
+// ---- the row source (RealReq::src): what the FLOATS, the CODES and the PQ kind do differently, and the only readers of RowSource::kind ----
+PqTab pq_tab(const RowSource& s) { return PqTab{s.pq_codes.as<u8>(), s.pq_books.as<float>(), s.pq_M, s.pq_K, s.pq_dsub, s.pq_MP}; }
+// `rows` float rows [rows][bpad] of every stride-th database row from the codes (+-1.0) or the PQ tables (decoded), pad features 0
+void expand_rows(hg_ctx* c, const RowSource& s, DevBuf& dst, i64 rows, i64 stride) {
+    const dim3 grid(grid_for(rows * (c->bpad / 4)));
+    if (s.kind == RowSource::PQ)
+        hipLaunchKernelGGL(k_pq_expand_rows, grid, dim3(256), 0, c->stream, pq_tab(s), dst.as<float4>(), rows, c->bpad, c->b, stride);
+    else
+        hipLaunchKernelGGL(k_asym_expand_rows, grid, dim3(256), 0, c->stream, c->db.as<u32>(), dst.as<float4>(), rows, c->bpad, c->NW, c->b, stride);
+}
+// The database's float rows [N][bpad]: the loaded table; from the codes or the PQ tables, rows expanded into the source's work buffer on
+// first need per database (k_asym_expand_rows, k_pq_expand_rows; stats "asym_float_rows" / "pq_float_rows" say that a call came here)
 int float_rows(hg_ctx* c, const RealReq& r, const float** rows) {
     RowSource& s = *r.src;
-    if (s.kind == RowSource::CODES) {
+    if (s.kind != RowSource::FLOATS) {
+        const bool pq = s.kind == RowSource::PQ;
         s.rows_read = 1;
         if (!s.rows_valid) {
             HG_TRY(s.rows.reserve((size_t)c->N * c->bpad * 4 + 256));
-            c->t_begin(KI_ASYM_EXPAND);
-            hipLaunchKernelGGL(k_asym_expand_rows, dim3(grid_for(c->N * (c->bpad / 4))), dim3(256), 0, c->stream, c->db.as<u32>(), s.rows.as<float4>(),
-                               (i64)c->N, c->bpad, c->NW, c->b, (i64)1);
+            c->t_begin(pq ? KI_PQ_EXPAND : KI_ASYM_EXPAND);
+            expand_rows(c, s, s.rows, (i64)c->N, 1);
             c->t_end();
-            HG_TRY(c->check_launch("k_asym_expand_rows"));
+            HG_TRY(c->check_launch(pq ? "k_pq_expand_rows" : "k_asym_expand_rows"));
             s.rows_valid = true;
         }
     }
@@ -105,6 +116,8 @@ void expand_image16(hg_ctx* c, const RealReq& r, DevBuf& dst, i64 rows, i64 rows
     with_bool(s.img_half, [&](auto half) {
         if (s.kind == RowSource::CODES)
             hipLaunchKernelGGL(k_asym_image16<half>, grid, dim3(256), 0, c->stream, c->db.as<u32>(), dst.as<uint4>(), rows, rows16, KP, c->NW, c->b, stride);
+        else if (s.kind == RowSource::PQ)
+            hipLaunchKernelGGL(k_pq_image16<half>, grid, dim3(256), 0, c->stream, pq_tab(s), dst.as<uint4>(), rows, rows16, KP, c->b, stride);
         else
             hipLaunchKernelGGL(k_expand_dbf_bf16<half>, grid, dim3(256), 0, c->stream, s.rows.as<float>(), dst.as<uint4>(), rows, rows16, KP, stride);
         return HG_OK;
@@ -113,20 +126,23 @@ void expand_image16(hg_ctx* c, const RealReq& r, DevBuf& dst, i64 rows, i64 rows
 // The filter's 16-bit image of the database, built on first use, and with it the largest row norm^2 (xmax2: k_real_thr2's margin) and the
 // choice between IEEE half and bfloat16 -- once per database.  FLOATS: k_row_norm_max, one 4-byte download and a wait.  CODES: +-1 is exact
 // in either format and every row's norm^2 is exactly b -- the host writes that itself, a fill on the stream: no kernel, no download, no wait.
+// PQ: the loader's bound on every row's norm^2 (the largest codeword that occurs, subspace by subspace: k_real_thr2's margin holds for any
+// value >= the true maximum), written the same way.
 int ensure_filter_image(hg_ctx* c, const RealReq& r) {
     RowSource& s = *r.src;
     if (s.img_valid) return HG_OK;
-    const bool codes = s.kind == RowSource::CODES;
+    const bool pq = s.kind == RowSource::PQ;
+    const bool codes = s.kind != RowSource::FLOATS;         // (no float table: the host knows the norm word)
     const int KP = c->bpad;
     const i64 n16 = (c->N + 15) / 16 * 16;
     HG_TRY(s.img.reserve((size_t)n16 * KP * 2));
     HG_TRY(s.xmax2.reserve(4));
-    float xm = (float)c->b;
+    float xm = pq ? s.pq_xmax2 : (float)c->b;
     if (codes) {
         u32 xbits;
         memcpy(&xbits, &xm, 4);
         HG_HIP(hipMemsetD32Async((hipDeviceptr_t)s.xmax2.p, (int)xbits, 1, c->stream));
-        c->t_begin(KI_ASYM_IMAGE);
+        c->t_begin(pq ? KI_PQ_IMAGE : KI_ASYM_IMAGE);
     } else {
         HG_HIP(hipMemsetAsync(s.xmax2.p, 0, 4, c->stream));
         c->t_begin(KI_PACK);
@@ -140,19 +156,30 @@ int ensure_filter_image(hg_ctx* c, const RealReq& r) {
     s.img_half = c->opt.real_mfma == 2 && xm >= 1.0f && xm < 1073741824.0f;         // 1 <= largest row norm^2 < 2^30 (inf and the NaN marker fail the test)
     expand_image16(c, r, s.img, c->N, n16, KP, 1);
     c->t_end();
-    HG_TRY(c->check_launch(codes ? "k_asym_image16" : "k_expand_dbf_bf16"));
+    HG_TRY(c->check_launch(pq ? "k_pq_image16" : codes ? "k_asym_image16" : "k_expand_dbf_bf16"));
     s.img_valid = true;
     return HG_OK;
 }
 // The exact scores of the rows the filter kept: wavefront = (SG slices, query), `waves` of them.  FLOATS: k_real_rescore gathers the kept
 // rows' float rows through LDS.  CODES: k_asym_rescore reads their code words instead (no LDS), the word count a template argument up to two.
+// PQ: k_pq_rescore looks the operand up in the codebooks through the vector cache (no LDS), four features per read where dsub is a
+// multiple of four.
 template <int KP> int launch_rescore(hg_ctx* c, const RealReq& r, int SG, i64 waves) {
     const Geo& g = c->geo;
-    const bool codes = r.src->kind == RowSource::CODES;
+    const bool codes = r.src->kind == RowSource::CODES, pq = r.src->kind == RowSource::PQ;
     const float* rows = nullptr;
-    if (!codes) HG_TRY(float_rows(c, r, &rows));
-    c->t_begin(codes ? KI_ASYM_RESCORE : KI_REAL_RESCORE);
+    if (!codes && !pq) HG_TRY(float_rows(c, r, &rows));
+    c->t_begin(pq ? KI_PQ_RESCORE : codes ? KI_ASYM_RESCORE : KI_REAL_RESCORE);
     HG_TRY(with_slices(SG, [&](auto sg) {
+        if (pq) {
+            const RowSource& s = *r.src;
+            return with_bool(s.pq_dsub % 4 == 0, [&](auto wide) {
+                const PqRescoreArgs a{c->qf.as<float>(), pq_tab(s), c->sl_cnt.as<u32>(), c->krows.as<u32>(), c->cand.as<u64>(), c->cap, c->crow, c->thr.as<float>(),
+                                      c->sl_cnt.as<u32>(), c->cntq.as<u32>(), c->dblab.as<u64>(), c->qlab.as<u64>(), r.no_cut ? 0 : 1, KP, g};
+                hipLaunchKernelGGL((k_pq_rescore<(wide ? 4 : 1), sg>), dim3(grid_for(waves, WPB)), dim3(256), 0, c->stream, a);
+                return HG_OK;
+            });
+        }
         auto from_codes = [&](auto nwt) {
             hipLaunchKernelGGL((k_asym_rescore<nwt, sg>), dim3(grid_for(waves, WPB)), dim3(256), 0, c->stream, c->qf.as<float>(), c->db.as<u32>(),
                                c->sl_cnt.as<u32>(), c->krows.as<u32>(), c->cand.as<u64>(), c->cap, c->crow, c->thr.as<float>(), c->sl_cnt.as<u32>(),
@@ -167,17 +194,17 @@ template <int KP> int launch_rescore(hg_ctx* c, const RealReq& r, int SG, i64 wa
         return HG_OK;
     }));
     c->t_end();
-    return c->check_launch(codes ? "k_asym_rescore" : "k_real_rescore");
+    return c->check_launch(pq ? "k_pq_rescore" : codes ? "k_asym_rescore" : "k_real_rescore");
 }
 // Float rows for the staged sample beyond 128 features (k_real_sample_any), inside its timing slot, which this opens and the caller closes:
-// every *stride-th row of the table -- or, from the codes, the M sampled rows alone expanded into the sample's own per-call buffer (a few MB,
-// like the 16-bit sample images; *stride becomes 1), so that a bet on more than 128 features never asks for the whole database as floats
+// every *stride-th row of the table -- or, from the codes or the PQ tables, the M sampled rows alone expanded into the sample's own per-call
+// buffer (a few MB, like the 16-bit sample images; *stride becomes 1), so that a bet on more than 128 features never asks for the whole
+// database as floats
 int sampled_rows(hg_ctx* c, const RealReq& r, i64 M, i64* stride, const float** rows) {
-    if (r.src->kind == RowSource::CODES) {
+    if (r.src->kind != RowSource::FLOATS) {
         HG_TRY(c->sampx.reserve((size_t)M * c->bpad * 4 + 256));
         c->t_begin(KI_REAL_SAMPLE);
-        hipLaunchKernelGGL(k_asym_expand_rows, dim3(grid_for(M * (c->bpad / 4))), dim3(256), 0, c->stream, c->db.as<u32>(), c->sampx.as<float4>(),
-                           M, c->bpad, c->NW, c->b, *stride);
+        expand_rows(c, *r.src, c->sampx, M, *stride);
         *rows = c->sampx.as<float>();
         *stride = 1;
         return HG_OK;
@@ -751,9 +778,37 @@ int run_asym(hg_ctx* c, int64_t R, bool with_ap) {
     return HG_OK;
 }
 
+// The quantised call: the same ladder on the PQ tables hg_set_database_pq loaded and the queries' floats; what it leaves is what run_real
+// leaves.
+int run_pq(hg_ctx* c, int64_t R, bool with_ap) {
+    c->real_lists = false;                             // a refused call leaves no lists either
+    c->lists_valid = false;                            // ... and the call writes out_idx: a Hamming ranking's lists end here (hg_get_topr refuses)
+    if (!c->from_pq.pq_valid)
+        return fail(HG_ERR_STATE, "quantised ranking needs the database's PQ codes and codebooks: load them with hg_set_database_pq "
+                                  "(any other database loader forgets them)");
+    if (!c->bpad || !c->qf.p || !c->qf_resident)
+        return fail(HG_ERR_STATE, "quantised ranking needs the queries' float features on the GPU: set option keep_query_floats = 1, then load "
+                                  "them with hg_set_queries_f32 / hg_set_queries_dev");
+    c->from_pq.rows_read = 0;
+    HG_TRY(real_call(c, c->from_pq, R, with_ap));
+    c->pq_calls++;
+    return HG_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int hg_topr_pq(hg_ctx* c, int64_t R) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_topr_pq", "hg_set_database_pq + hg_set_queries_f32 (option keep_query_floats = 1)"));
+    return run_pq(c, R, false);
+}
+
+int hg_map_pq(hg_ctx* c, int64_t R, double* host_ap, int64_t* host_rel) {
+    HG_TRY(need(c, ST_DB | ST_Q, "hg_map_pq", "hg_set_database_pq + hg_set_queries_f32 (option keep_query_floats = 1)"));
+    HG_TRY(run_pq(c, R, true));
+    return hg_get_ap(c, host_ap, host_rel);
+}
 
 int hg_topr_real(hg_ctx* c, int64_t R) {
     HG_TRY(need(c, ST_DB | ST_Q, "hg_topr_real", "hg_set_database_f32 + hg_set_queries_f32"));
@@ -787,5 +842,8 @@ int preload_real() {
     HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_asym_image16<true>)));      // (the same code object: the asymmetric kernels' names for a reader)
     HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_asym_rescore<2, 6>)));
     HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_asym_expand_rows)));
+    HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_pq_image16<true>)));        // (... and the quantised kernels')
+    HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_pq_rescore<4, 6>)));
+    HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_pq_expand_rows)));
     return HG_OK;
 }

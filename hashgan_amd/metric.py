@@ -232,6 +232,24 @@ def _sides(codes, labels, what):
     return np.asarray(codes), np.asarray(labels)
 
 
+class PQTable:
+    """A product-quantised database as the loaders see it: the stand-in for database.output in 'quantised' mode.  It has the decoded
+    table's shape and nothing of its contents (codes uint8 [N, M], codebooks float32 [M, K, dsub]: hashgan_amd/pq.py)."""
+
+    def __init__(self, codes, codebooks):
+        from . import pq
+        if as_device_array(codes) is not None or as_device_array(codebooks) is not None:
+            raise ValueError("quantised=True takes codes and codebooks as host arrays")
+        self.codes, self.codebooks = pq.check_tables(codes, codebooks, values=False)
+        self.kept = (codes, codebooks)                 # the caller's own objects: what "the same arrays as last time" compares
+        self.ndim = 2
+        self.shape = (self.codes.shape[0], self.codebooks.shape[0] * self.codebooks.shape[2])
+
+    def same_readonly(self, other):
+        return (isinstance(other, PQTable) and self.kept[0] is other.kept[0] and self.kept[1] is other.kept[1]
+                and not any(getattr(getattr(a, "flags", None), "writeable", True) for a in self.kept))
+
+
 def _check_shapes(q_codes, db_codes, q_labels, db_labels, R):
     if db_codes.ndim != 2 or q_codes.ndim != 2 or db_codes.shape[1] != q_codes.shape[1]:
         raise ValueError("query and database codes must be [n, b] with the same b")
@@ -265,10 +283,12 @@ def _check_cutoffs(Rs, N, what="Rs"):
     return Rs
 
 
-def _ap_at(ctx, Rs, real, rerank=False, asym=False):
+def _ap_at(ctx, Rs, real, rerank=False, asym=False, quantised=False):
     """One ranking at the largest cut-off, then every cut-off from its match bitmap (hg_ap_at) -> (ap [Q, nR], rel [Q, nR])."""
     if rerank:
         ctx.topr_rerank(int(Rs[-1]), download=False)
+    elif quantised:
+        ctx.topr_pq(int(Rs[-1]), download=False)
     elif asym:
         ctx.topr_asym(int(Rs[-1]), download=False)
     elif real:
@@ -296,11 +316,16 @@ def _load_database(eng, db_codes, db_labels, mode="reference", floats=None):
     by inner product: never for the spellings that binarise or insist on binary codes, and in 'reference' mode only if
     the database is not a +-1 code (a +-1 database meeting real-valued queries is uploaded again with it, below); 'rerank' mode always
     keeps it (keep_floats = 1): the floats order the rows inside equal Hamming distances; 'asymmetric' mode never does (keep_floats = 0:
-    the loader signs the database, its floats never go to the GPU -- or, for device arrays, are never copied)."""
+    the loader signs the database, its floats never go to the GPU -- or, for device arrays, are never copied); 'quantised' mode hands a
+    PQTable's codes and codebooks to hg_set_database_pq: no float table exists, on either side of PCIe."""
     eng.b = eng.C = eng.N = eng.db_kind = eng.db_src = None      # nothing is resident until this load has succeeded
     eng.resident = None                               # whoever loads another database (extra_metrics, MAPs) ends _evaluate's shortcut
     on_device = isinstance(db_codes, DeviceArray)
-    if on_device:
+    if isinstance(db_codes, PQTable) != (mode == "quantised"):
+        raise ValueError("quantised=True ranks a database given as .codes / .codebooks, and only such a one")
+    if mode == "quantised":
+        bad_c, bad_l = eng.ctx.set_database_pq(db_codes.codes, db_codes.codebooks, db_labels)
+    elif on_device:
         # device arrays: in 'reference' mode the floats are kept at once (a copy inside the GPU's memory, no PCIe) -- the caller's
         # memory may have changed by the time real-valued queries would ask for a second load, so there is none
         eng.ctx.set_option("keep_floats", floats if floats is not None else (1 if mode in ("reference", "rerank") else 0))
@@ -335,13 +360,20 @@ def _rank(eng, q_codes, q_labels, R, mode, Rs=None, lists=False):
        'rerank'     MAPs(rerank=True): sign() first, Hamming distance, then the float32 inner product of the features inside
                     equal distances, then the index (hg_topr_rerank): both float tables are on the GPU (_load_database);
        'asymmetric' MAPs(asymmetric=True): the queries' float32 features against the database's sign() codes read as +-1
-                    (hg_topr_asym / hg_map_asym): the queries keep their floats on the GPU (keep_query_floats = 1), the database none."""
-    want_qf = 1 if mode == "asymmetric" else 0         # (set only when it changes: every hg_set_option ends hg_map_begin's licence to enqueue blind)
+                    (hg_topr_asym / hg_map_asym): the queries keep their floats on the GPU (keep_query_floats = 1), the database none;
+       'quantised'  MAPs(quantised=True): the queries' float32 features against the database's product-quantisation codes
+                    (hg_topr_pq / hg_map_pq), the queries' floats kept like the asymmetric mode's."""
+    want_qf = 1 if mode in ("asymmetric", "quantised") else 0         # (set only when it changes: every hg_set_option ends hg_map_begin's licence to enqueue blind)
     if eng.ctx.option_values.get("keep_query_floats", 0) != want_qf:
         eng.ctx.set_option("keep_query_floats", want_qf)
     qbad_c, qbad_l = _set_queries(eng, q_codes, q_labels)
     if qbad_l:
         raise ValueError("labels must be {0,1} indicator matrices")
+    if mode == "quantised":
+        if lists:
+            eng.ctx.topr_pq(R, download=False)
+            return "inner_product"
+        return eng.ctx.map_pq(R) if Rs is None else _ap_at(eng.ctx, Rs, True, quantised=True)
     if mode == "asymmetric":
         if q_codes.shape[1] > 255:
             raise ValueError("inner-product ranking supports up to 255 features (have %d)" % q_codes.shape[1])
@@ -466,13 +498,21 @@ class MAPs:
     calls (explicit), and a database whose arrays are the SAME read-only objects as last time is reused
     automatically (a writable array may have changed in place, so it is uploaded again)."""
 
-    def __init__(self, r, device=0, binarize=False, rerank=False, asymmetric=False):
+    def __init__(self, r, device=0, binarize=False, rerank=False, asymmetric=False, quantised=False):
         """rerank=True: sign() first (it implies binarize), rank by Hamming distance, and inside equal distances by the float32 inner
         product of the features (descending), then by database index -- the ties of the Hamming ranking resolved by the
         magnitudes sign() throws away; the threshold group's rows with the highest inner product make the cut at R.
         asymmetric=True: what a deployed hashing system ranks -- the database is its sign() codes (bit = feature > 0, read as +-1; its
         floats never go to the GPU), the query keeps its float32 features, rows are ranked by their inner product (descending), then by
-        database index (hg_map_asym).  Not together with binarize or rerank (ValueError)."""
+        database index (hg_map_asym).  Not together with binarize or rerank (ValueError).
+        quantised=True: the database is product-quantisation codes (hashgan_amd/pq.py) -- `database` exposes .codes uint8 [N, M],
+        .codebooks float32 [M, K, dsub] and .label, host arrays -- and rows are ranked by the float32 inner product of the query with
+        the decoded row (descending), then by database index (hg_map_pq): AQD.  `query` exposes .output [Q, M * dsub], or, without an
+        .output, .codes uint8 [Q, M], decoded on the host with the database's codebooks: SQD.  The decoded database exists nowhere.
+        Not together with binarize, rerank or asymmetric (ValueError)."""
+        if quantised and (binarize or rerank or asymmetric):
+            raise ValueError("quantised=True ranks real-valued queries against product-quantisation codes: not together with binarize, "
+                             "rerank or asymmetric")
         if asymmetric and (binarize or rerank):
             raise ValueError("asymmetric=True ranks real-valued queries against sign() codes: not together with binarize or rerank")
         self.R = r
@@ -480,6 +520,8 @@ class MAPs:
         self.binarize = binarize or rerank
         self.rerank = rerank
         self.asymmetric = asymmetric
+        self.quantised = quantised
+        self._books = None             # quantised: the resident database's codebooks (a query given as codes is decoded with them)
         self._eng = None
         self._lock = threading.RLock()
         self._resident = None          # (output array, label array) the engine holds, or ("explicit",)
@@ -495,7 +537,27 @@ class MAPs:
         return self._eng
 
     def _mode(self):
-        return "asymmetric" if self.asymmetric else "rerank" if self.rerank else "sign" if self.binarize else "reference"
+        return "quantised" if self.quantised else "asymmetric" if self.asymmetric else "rerank" if self.rerank else "sign" if self.binarize else "reference"
+
+    def _db_sides(self, database):
+        """database -> (features, labels) as the loaders take them; quantised: (PQTable of .codes / .codebooks, labels)."""
+        if not self.quantised:
+            return _sides(database.output, database.label, "database")
+        if getattr(database, "codes", None) is None or getattr(database, "codebooks", None) is None:
+            raise ValueError("quantised=True ranks a database given as .codes / .codebooks (hashgan_amd/pq.py), not as .output")
+        if as_device_array(database.label) is not None:
+            raise ValueError("quantised=True takes the database as host arrays")
+        return PQTable(database.codes, database.codebooks), np.asarray(database.label)
+
+    def _q_sides(self, database, query):
+        """query -> (features, labels); quantised and no .output: its .codes decoded with the database's codebooks (SQD)."""
+        if not self.quantised or getattr(query, "output", None) is not None:
+            return _sides(query.output, query.label, "query")
+        from . import pq
+        books = self._books if database is None else database.codebooks
+        if books is None:
+            raise ValueError("no resident database: call set_database first")
+        return pq.decode(query.codes, books), np.asarray(query.label)
 
     def close(self):
         with self._lock:
@@ -514,13 +576,14 @@ class MAPs:
         """Upload + pack `database` (.output [N, b], .label [N, C]) once; get_maps_by_feature(None, query) -- or with
         the same object -- then ranks against the resident copy.  Arrays in device memory are copied in: the caller may
         overwrite them afterwards."""
-        out, lab = _sides(database.output, database.label, "database")
+        out, lab = self._db_sides(database)
         if out.ndim != 2 or lab.ndim != 2 or out.shape[0] != lab.shape[0]:
             raise ValueError("database.output must be [N, b] and database.label [N, C]")
         with self._lock:
             self._resident = None                      # a failed load leaves NO database (never the previous one half replaced)
             self._guard(_load_database, self._engine(), out, lab, self._mode())
             self._resident = ("explicit", database)
+            self._books = out.codebooks if self.quantised else None
 
     def _guard(self, fn, *args):
         """A HIP-level failure (a fault, out of memory) may leave the context unusable: it is destroyed, not recycled."""
@@ -538,11 +601,15 @@ class MAPs:
             return
         if self._resident is not None and self._resident[0] == "explicit" and self._resident[1] is database:
             return
-        out, lab = _sides(database.output, database.label, "database")
+        out, lab = self._db_sides(database)
         # device arrays handed over here are loaded on every call (nothing says their memory is unchanged).  What the load leaves is
         # the library's own copy, so a later get_maps_by_feature(None, query) ranks against it like after set_database.
         on_device = isinstance(out, DeviceArray)
-        if (not on_device and self._resident is not None and self._resident[0] == "auto" and self._resident[1] is out
+        if self.quantised:
+            if (self._resident is not None and self._resident[0] == "auto" and out.same_readonly(self._resident[1])
+                    and self._resident[2] is lab and not lab.flags.writeable):
+                return
+        elif (not on_device and self._resident is not None and self._resident[0] == "auto" and self._resident[1] is out
                 and self._resident[2] is lab and not out.flags.writeable and not lab.flags.writeable):
             return                                     # the very same immutable arrays as last time
         if out.ndim != 2 or lab.ndim != 2 or out.shape[0] != lab.shape[0]:
@@ -550,10 +617,11 @@ class MAPs:
         self._resident = None                          # a failed load leaves NO database
         self._guard(_load_database, self._engine(), out, lab, self._mode())
         self._resident = ("device",) if on_device else ("auto", out, lab)
+        self._books = out.codebooks if self.quantised else None
 
     def get_maps_by_feature(self, database, query):
         """database/query: objects with .output [n, b] and .label [n, C] (main.py:157); database first."""
-        q_codes, q_labels = _sides(query.output, query.label, "query")
+        q_codes, q_labels = self._q_sides(database, query)
         with self._lock:
             self._ensure_database(database)
             eng = self._engine()
@@ -576,12 +644,12 @@ class MAPs:
         a prefix of the top Rs[-1], and each entry has the bits MAPs(R).get_maps_by_feature(database, query) returns.  Database
         residency, `binarize` and the routing (+-1 codes by Hamming distance, anything else by inner product) are
         get_maps_by_feature's; self.R is not used.  -> float64 [len(Rs)]"""
-        q_codes, q_labels = _sides(query.output, query.label, "query")
+        q_codes, q_labels = self._q_sides(database, query)
         Rs = _check_cutoffs(Rs, None)
         if q_codes.ndim != 2 or q_labels.ndim != 2 or q_labels.shape[0] != q_codes.shape[0]:
             raise ValueError("query.output must be [Q, b] and query.label [Q, C]")
         if database is not None:                       # (what can be refused before any GPU use is)
-            out, lab = _sides(database.output, database.label, "database")
+            out, lab = self._db_sides(database)
             if out.ndim != 2 or lab.ndim != 2 or out.shape[0] != lab.shape[0]:
                 raise ValueError("database.output must be [N, b] and database.label [N, C]")
             if q_codes.shape[1] != out.shape[1]:
@@ -614,14 +682,14 @@ class MAPs:
         lists; the list-free ranking get_maps_by_feature uses leaves nothing to vote on).  Database residency, `binarize`, `rerank` and
         the routing are get_maps_at's; self.R is not used.  -> extra_metrics.knn_from_tables' dict"""
         from . import extra_metrics as X               # (extra_metrics imports this module)
-        q_codes, q_labels = _sides(query.output, query.label, "query")
+        q_codes, q_labels = self._q_sides(database, query)
         ks = _check_cutoffs(ks, None, "ks")
         if q_codes.ndim != 2 or q_labels.ndim != 2 or q_labels.shape[0] != q_codes.shape[0]:
             raise ValueError("query.output must be [Q, b] and query.label [Q, C]")
         if q_labels.shape[1] > X.MAX_CLASSES:
             raise ValueError("class votes take up to %d classes (have %d)" % (X.MAX_CLASSES, q_labels.shape[1]))
         if database is not None:                       # (what can be refused before any GPU use is)
-            out, lab = _sides(database.output, database.label, "database")
+            out, lab = self._db_sides(database)
             if out.ndim != 2 or lab.ndim != 2 or out.shape[0] != lab.shape[0]:
                 raise ValueError("database.output must be [N, b] and database.label [N, C]")
             if q_codes.shape[1] != out.shape[1]:
@@ -657,13 +725,13 @@ class MAPs:
         handle, e.g. torch.cuda.current_stream().cuda_stream): what it holds so far is waited for, what is enqueued on it afterwards
         sees the data.  Database residency, `binarize`, `rerank` and the routing are get_maps_by_feature's.  dist on an inner-product
         ranking and score on a plain Hamming ranking raise ValueError.  -> {"by": "hamming" | "inner_product" | "rerank", "R": R}"""
-        q_codes, q_labels = _sides(query.output, query.label, "query")
+        q_codes, q_labels = self._q_sides(database, query)
         if q_codes.ndim != 2 or q_labels.ndim != 2 or q_labels.shape[0] != q_codes.shape[0]:
             raise ValueError("query.output must be [Q, b] and query.label [Q, C]")
         R = int(self.R)
         given = dict(idx=idx, dist=dist, score=score, match=match, ap=ap, hits=hits)
         if database is not None:                       # (what can be refused before any GPU use is)
-            out, lab = _sides(database.output, database.label, "database")
+            out, lab = self._db_sides(database)
             _check_shapes(q_codes, out, q_labels, lab, R)
             outs = _check_outs(given, q_codes.shape[0], out.shape[0], R, stream)
         with self._lock:

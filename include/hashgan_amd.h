@@ -302,6 +302,37 @@ int hg_get_topr_real(hg_ctx* ctx, uint32_t* host_idx, float* host_scores);   /* 
 int hg_map_asym(hg_ctx* ctx, int64_t R, double* host_ap, int64_t* host_rel);
 int hg_topr_asym(hg_ctx* ctx, int64_t R);
 
+/* ---- quantised databases: real-valued queries against product-quantisation codes (AQD, the asymmetric quantiser distance) ----
+ * The database is stored as PQ codes and small codebooks: M disjoint subspaces of dsub features each (b = M * dsub <= 255), K <= 256
+ * codewords per subspace; codebooks float32 [M][K][dsub], codes uint8 [N][M].  A row decodes by pure gather,
+ *     x[n][k] = codebooks[k / dsub][codes[n][k / dsub]][k % dsub],
+ * and is ranked by s(q, n) in the fixed arithmetic of the real-valued ranking: acc = fmaf(q_k, x_nk, acc) for k = 0 .. b - 1 from +0.0,
+ * then + 0.0.  Order: s descending, database index ascending; label match, AP and hit counts as hg_map_real's.  Bit for bit what
+ * hg_topr_real / hg_map_real return on the decoded table and what oracle/real_map.py::map_from_features returns on it -- without that
+ * table (256 MB at 1M x 64; the codes are 8 MB, the codebooks 64 KB): the filter's image and the exact rescoring look every feature up
+ * (k_pq_image16, k_pq_rescore).  SQD (the query quantised too) is the same call on the query's decoded codes: a gather on the host.
+ *   hg_set_database_pq   loads codes, codebooks and labels (int64 [N][C], as hg_set_database_f32).  Afterwards the context holds what
+ *             hg_set_database_f32 leaves for the decoded table under "keep_floats" = 0 -- the sign codes (bit = decoded feature > 0,
+ *             derived by host threads from per-codeword sign patterns: no N x b floats exist anywhere in a load), the labels, the census
+ *             -- plus the PQ tables, so every Hamming-side call works on it unchanged.  Any other database loader forgets the PQ tables.
+ *             Refused with HG_ERR_ARG, the message naming the offender: M, K or dsub < 1, K > 256, M * dsub > HG_MAX_BITS, a code byte
+ *             >= K (row and subspace), a non-finite codebook entry (a deliberate restriction: the filter's norm bound and the NaN
+ *             handling of a float table stay out of this form), idx_base != 0 or n_total != N (one shard only).
+ *   Queries   their float table: hg_set_queries_f32 / hg_set_queries_dev under option "keep_query_floats" = 1.
+ *   Refused   HG_ERR_STATE without PQ tables (the message names hg_set_database_pq) or without the queries' floats (names the option).
+ *   Limits    hg_map_real's: N < 2^31, 1 <= R <= N (else HG_ERR_ARG).  Additive codebooks over the full dimension are not supported.
+ *   State     a successful call leaves what hg_topr_real / hg_map_real leave (hg_get_topr_real, hg_get_ap, hg_get_match, hg_ap_at,
+ *             hg_graded, hg_votes, hg_export; hg_export refuses HG_OUT_DIST).  A failed or refused call leaves no lists.
+ *   Fallback  the paths that read plain float rows (no cut: R = N or an exhausted ladder; "real_mfma" < 2; the vector kernels; segments
+ *             that are no multiple of 16 rows) get them from a work buffer decoded on first need per database (k_pq_expand_rows;
+ *             N x bpad x 4 bytes, counted in "device_bytes", freed by hg_trim, forgotten by a database load).
+ *   Stats     "real_path" / "real_attempts" / "real_requeried" as for hg_map_real; "pq_calls" (successful quantised calls, cumulative);
+ *             "pq_float_rows" (1: the last quantised call read the decoded float rows; 0: codes and codebooks only). */
+int hg_set_database_pq(hg_ctx* ctx, const uint8_t* host_codes, const float* host_codebooks, const int64_t* host_labels, int64_t N,
+                       int M, int K, int dsub, int C, int64_t idx_base, int64_t n_total, int64_t* bad_codes, int64_t* bad_labels);
+int hg_map_pq(hg_ctx* ctx, int64_t R, double* host_ap, int64_t* host_rel);
+int hg_topr_pq(hg_ctx* ctx, int64_t R);
+
 /* ---- Hamming ranking with the tie groups re-ranked by the features ("sign, rank by Hamming distance, re-rank inside equal
  * distances by the real-valued inner product") ----
  * Row n against query q has d = popcount(code_q xor code_n) on the codes the loaders make (bit = feature > 0) and s = the float32
@@ -655,7 +686,7 @@ int hg_set_option(hg_ctx* ctx, const char* key, int64_t value);
  * "export_bytes" / "export_variant" (see hg_export);
  * "cut_beyond_planes" (1: the last hg_guess_finish met a query whose cut lies beyond the b/2 + 2 planes the owner-routed exchange carries -- its bet
  * cannot be won by wider slices; a download); real-valued path: "real_attempts", "real_requeried" (queries that lost the first cut and were ranked again on their own, cumulative), "real_cap_boost", "real_path" (bit 0 filter + rescoring, bit 1 ranked in LDS,
- * bit 2 lists ordered group by group), "asym_calls" / "asym_float_rows" (see hg_map_asym); re-rank: "rerank_records", "rerank_chunks", "rerank_groups_lds", "rerank_groups_global" (see hg_topr_rerank). */
+ * bit 2 lists ordered group by group), "asym_calls" / "asym_float_rows" (see hg_map_asym), "pq_calls" / "pq_float_rows" (see hg_map_pq); re-rank: "rerank_records", "rerank_chunks", "rerank_groups_lds", "rerank_groups_global" (see hg_topr_rerank). */
 int hg_get_stat(hg_ctx* ctx, const char* key, int64_t* value);
 /* What hg_set_database_f32 (queries = 0) / hg_set_queries_f32 (queries = 1) found in the float table: out[0] entries outside
  * {-1, 0, +1}, out[1] zeros, out[2] minus ones, out[3] = 1 if the float table is resident on the device -- from which the caller
