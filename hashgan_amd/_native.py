@@ -82,6 +82,10 @@ _SIGNATURES = {
     "hg_set_database_pq": [_p, _p, _p, _p, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64)],
     "hg_map_pq": [_p, _i64, _p, _p],
     "hg_topr_pq": [_p, _i64],
+    "hg_pq_encode": [_p, _p, _i64, _p, C.c_int, C.c_int, C.c_int, _p, _p, C.POINTER(_i64)],
+    "hg_pq_encode_dev": [_p, _p, _p, C.c_int, C.c_int, C.c_int, _p, _p, C.POINTER(_i64)],
+    "hg_set_database_pq_f32": [_p, _p, _p, _p, _i64, C.c_int, C.c_int, C.c_int, C.c_int, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64),
+                               C.POINTER(_i64)],
     "hg_topr_rerank": [_p, _i64],
     "hg_map_rerank": [_p, _i64, _p, _p],
     "hg_get_rerank_scores": [_p, _p],
@@ -607,6 +611,54 @@ class Context:
         bc, bl = _i64(), _i64()
         check(self._lib.hg_set_database_pq(self._h, _ptr(codes), _ptr(codebooks), _ptr(lab), N, M, K, dsub, lab.shape[1], 0, N,
                                            C.byref(bc), C.byref(bl)))
+        self.N, self.b, self.C, self.n_total = N, M * dsub, lab.shape[1], N
+        return bc.value, bl.value
+
+    def pq_encode(self, features, codebooks, want_err=False):
+        """The exact PQ encoder on the GPU (hg_pq_encode / hg_pq_encode_dev; the contract: include/hashgan_amd.h): features a host
+        array [N, M * dsub] (converted to float32) or a devarray.DeviceArray (float32 / float16 / bfloat16, any strides), codebooks
+        float32 [M, K, dsub].  Needs no database and leaves the context as it was.
+        -> (codes uint8 [N, M], err float64 [N] or None, rows with a non-finite feature -- their codes are 0 in that subspace)"""
+        from . import pq
+        cb = pq.check_codebooks(codebooks)
+        M, K, dsub = cb.shape
+        bad = _i64()
+        if hasattr(features, "ptr"):
+            f = _dev_struct(features)
+            N = max(int(f.rows), 0)
+            codes = np.empty((N, M), dtype=np.uint8)
+            err = np.empty(N, dtype=np.float64) if want_err else None
+            check(self._lib.hg_pq_encode_dev(self._h, C.byref(f), _ptr(cb), M, K, dsub, _ptr(codes), _ptr(err), C.byref(bad)))
+        else:
+            x = _carray(features, np.float32)
+            if x.ndim != 2 or x.shape[1] != M * dsub:
+                raise ValueError("features must be [N, M * dsub] = [N, %d] (have shape %r)" % (M * dsub, x.shape))
+            N = x.shape[0]
+            codes = np.empty((N, M), dtype=np.uint8)
+            err = np.empty(N, dtype=np.float64) if want_err else None
+            check(self._lib.hg_pq_encode(self._h, _ptr(x), N, _ptr(cb), M, K, dsub, _ptr(codes), _ptr(err), C.byref(bad)))
+        return codes, err, bad.value
+
+    def set_database_pq_f32(self, features, codebooks, labels):
+        """float32 [N, M * dsub] features + float32 [M, K, dsub] codebooks + int64 [N, C] labels (hg_set_database_pq_f32): encoded on
+        the GPU, then loaded as set_database_pq loads the codes.  ValueError, nothing loaded, when rows have a non-finite feature.
+        -> (decoded entries outside {-1,0,+1}, label entries outside {0,1})"""
+        from . import pq
+        cb = pq.check_codebooks(codebooks)
+        M, K, dsub = cb.shape
+        x = _carray(features, np.float32)
+        if x.ndim != 2 or x.shape[1] != M * dsub:
+            raise ValueError("features must be [N, M * dsub] = [N, %d] (have shape %r)" % (M * dsub, x.shape))
+        lab = _labels_i64(labels)
+        if lab.ndim != 2 or lab.shape[0] != x.shape[0]:
+            raise ValueError("labels must be [N, C] with the features' N")
+        N = x.shape[0]
+        bc, bl, br = _i64(), _i64(), _i64()
+        rc = self._lib.hg_set_database_pq_f32(self._h, _ptr(x), _ptr(cb), _ptr(lab), N, M, K, dsub, lab.shape[1], 0, N,
+                                              C.byref(bc), C.byref(bl), C.byref(br))
+        if rc == HG_ERR_ARG and br.value:
+            raise ValueError("%d feature rows are not finite: %s" % (br.value, self._lib.hg_last_error().decode("utf-8", "replace")))
+        check(rc)
         self.N, self.b, self.C, self.n_total = N, M * dsub, lab.shape[1], N
         return bc.value, bl.value
 

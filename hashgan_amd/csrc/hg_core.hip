@@ -30,7 +30,7 @@ const char* const kKernelNames[KI_COUNT] = {"k_hist", "k_hist_reduce", "k_plan",
                                             "k_label_max", "k_hist_joint", "k_hist_joint_reduce",
                                             "k_rr_scan", "k_rr_collect", "k_rr_score", "k_rr_order", "k_export", "k_votes", "k_vote_confusion", "k_side_pack", "k_side_merge",
                                             "k_list_grades", "k_list_merge_grades", "k_list_merge_votes", "k_vote_pick", "k_asym_image16", "k_asym_rescore", "k_asym_expand_rows",
-                                            "k_nbr_sort", "k_nbr_match", "k_nbr_hist", "k_pq_image16", "k_pq_rescore", "k_pq_expand_rows"};
+                                            "k_nbr_sort", "k_nbr_match", "k_nbr_hist", "k_pq_image16", "k_pq_rescore", "k_pq_expand_rows", "k_pq_encode"};
 // Flatten NumPy's pairwise-summation tree for a chunk of n elements (n <= 8192):
 // numpy/_core/src/umath/loops_utils.h.src, pairwise_sum: n <= 128 is a leaf,
 // otherwise split at n/2 rounded down to a multiple of 8.
@@ -769,7 +769,7 @@ int hg_set_queries_f32(hg_ctx* c, const float* host_x, const int64_t* host_label
 // ---- features and labels in DEVICE memory (hg_dev_in.hpp: the kernels; hg_dev_desc.hpp: the descriptor arithmetic) ----
 // Is a.ptr device memory of the context's GPU, and does the array's extent lie inside its allocation?  Asked of the runtime
 // before anything is launched: a pointer it does not know comes back as HG_ERR_ARG, never as a fault.
-static int check_dev_pointer(hg_ctx* c, const char* who, const char* what, const hg_dev_array& a, int64_t extent) {
+int check_dev_pointer(hg_ctx* c, const char* who, const char* what, const hg_dev_array& a, int64_t extent) {
     hipPointerAttribute_t at{};
     hipError_t e = hipPointerGetAttributes(&at, a.ptr);
     if (e != hipSuccess) {
@@ -803,7 +803,7 @@ static int check_dev_arrays(hg_ctx* c, const char* who, const hg_dev_array* f, c
 }
 
 // The context's stream behind whatever the producer has enqueued so far on `s` (NULL: the null stream)
-static int wait_for_producer(hg_ctx* c, void* s) {
+int wait_for_producer(hg_ctx* c, void* s) {
     if ((hipStream_t)s == c->stream) return HG_OK;
     hipEvent_t ev = c->get_event();
     if (!ev) return fail(HG_ERR_HIP, "hipEventCreate failed");
@@ -1319,6 +1319,7 @@ const OptionKey kOptionKeys[] = {
     ranged("timing_every", &Options::timing_every, 1, 1024, "timing_every must be 1..1024"),
     flag("host_pack", &Options::host_pack),
     ranged("keep_floats", &Options::keep_floats, 0, 2, "keep_floats must be 0, 1 or 2"),
+    ranged("pq_encode_chunk_rows", &Options::pq_encode_chunk_rows, 0, 0x7FFFFFFF, "pq_encode_chunk_rows must be 0 (the default) .. 2^31 - 1"),
     ranged("keep_query_floats", &Options::keep_query_floats, 0, 1, "keep_query_floats must be 0 or 1"),
     ranged("real_mfma", &Options::real_mfma, 0, 2, "real_mfma must be 0, 1 or 2"),
     flag("real_sample_half", &Options::real_sample_half),
@@ -1387,7 +1388,7 @@ int hg_preload(hg_ctx* c) {
     HG_TRY(ensure_pin(c, (size_t)1 << 20));
     hipFuncAttributes a;
     HG_HIP(hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_ap<AP_THREADS>)));
-    HG_TRY(preload_seq()); HG_TRY(preload_rank()); HG_TRY(preload_side()); HG_TRY(preload_valu()); HG_TRY(preload_mx()); HG_TRY(preload_mx1()); HG_TRY(preload_real()); HG_TRY(preload_rerank());
+    HG_TRY(preload_seq()); HG_TRY(preload_rank()); HG_TRY(preload_side()); HG_TRY(preload_valu()); HG_TRY(preload_mx()); HG_TRY(preload_mx1()); HG_TRY(preload_real()); HG_TRY(preload_rerank()); HG_TRY(preload_pq_encode());
     host_pack_warm();
     return HG_OK;
 }
@@ -1439,6 +1440,8 @@ int hg_get_stat(hg_ctx* c, const char* key, int64_t* value) {
     else if (!strcmp(key, "asym_float_rows")) *value = c->from_codes.rows_read;
     else if (!strcmp(key, "pq_calls")) *value = c->pq_calls;
     else if (!strcmp(key, "pq_float_rows")) *value = c->from_pq.rows_read;
+    else if (!strcmp(key, "pq_encode_calls")) *value = c->pq_encode_calls;
+    else if (!strcmp(key, "pq_encoded_rows")) *value = c->pq_encoded_rows;
     else if (!strcmp(key, "device_bytes")) *value = device_bytes(c);
 #ifdef HG_RANK_PROFILE
 #ifdef HG_RANK_PROFILE                        // (tools/rank_phase_profile.py: where k_rank_cnt left its phase timestamps)

@@ -15,6 +15,8 @@
 //   hg_real.hip        real-valued (float32 inner product) ranking: a ladder of attempts, each with one RealReq down and one RealState (hg_ctx::real) up;
 //                      its asymmetric form (hg_topr_asym, hg_map_asym): the same call on the other RowSource, the database's packed codes read as +-1 (hg_asym.hpp);
 //                      its quantised form (hg_topr_pq, hg_map_pq): the same call on a third, product-quantisation codes and codebooks (hg_pq.hpp; loaded by hg_set_database_pq, hg_core.hip)
+//   hg_pq_encode.hip   the exact product-quantisation encoder (hg_pq_encode, hg_pq_encode_dev: hg_pq_encode.hpp) and the loader from float features to a
+//                      quantised context (hg_set_database_pq_f32: encode, then hg_set_database_pq on the codes)
 //   hg_comm.hip        RCCL collectives (library dlopen'ed on first use)
 //
 // No torch, no CPU compute path: every entry point either runs HIP kernels or fails.
@@ -221,7 +223,7 @@ enum KernelId { KI_HIST = 0, KI_HIST_REDUCE, KI_PLAN, KI_SEG_COUNTS, KI_SEG_LAYO
                 KI_GRADED, KI_GRADE_HIST, KI_GRADE_HIST_REDUCE, KI_TIE_AP, KI_AP_AT, KI_LABEL_MAX, KI_HIST_JOINT, KI_HIST_JOINT_REDUCE,
                 KI_RR_SCAN, KI_RR_COLLECT, KI_RR_SCORE, KI_RR_ORDER, KI_EXPORT, KI_VOTES, KI_VOTE_CONFUSION, KI_SIDE_PACK, KI_SIDE_MERGE,
                 KI_LIST_GRADES, KI_LIST_MERGE_GRADES, KI_LIST_MERGE_VOTES, KI_VOTE_PICK, KI_ASYM_IMAGE, KI_ASYM_RESCORE, KI_ASYM_EXPAND,
-                KI_NBR_SORT, KI_NBR_MATCH, KI_NBR_HIST, KI_PQ_IMAGE, KI_PQ_RESCORE, KI_PQ_EXPAND, KI_COUNT };
+                KI_NBR_SORT, KI_NBR_MATCH, KI_NBR_HIST, KI_PQ_IMAGE, KI_PQ_RESCORE, KI_PQ_EXPAND, KI_PQ_ENCODE, KI_COUNT };
 enum Stage { ST_NONE = 0, ST_DB = 1, ST_Q = 2, ST_HIST = 4, ST_PLAN = 8, ST_SELECT = 16, ST_MATCH = 32, ST_AP = 64 };
 extern const char* const kKernelNames[KI_COUNT];
 // the kernel that took the last record pass / the last rank stage (stats "select_variant", "rank_variant"), and what the rank stage is asked for
@@ -280,6 +282,7 @@ struct Options {
     // hand-over of float32 / int64 arrays
     i64 host_pack = 1;             // packed on the host by a thread pool before the upload (hg_host_pack.hpp); 0 = upload the raw arrays, pack on the GPU
     i64 keep_floats = 2;           // database float table on the GPU -- 0 never, 1 always, 2 only if it is not a +-1 code
+    i64 pq_encode_chunk_rows = 0;  // rows per launch of the PQ encoder (host features: per upload through the work buffer); 0: 256 MB of work buffers
     i64 keep_query_floats = 0;     // 1: the query float table stays on the GPU whether or not the database's is there (the asymmetric ranking: hg_map_asym)
     // real-valued ranking
     i64 real_mfma = 2;             // 2 = bf16 filter on the matrix cores + exact rescoring of the survivors, 1 = exact float32 MFMA pass, 0 = vector ALU
@@ -530,6 +533,7 @@ struct hg_ctx : StepBufs, StepState {
     void forget_rows() { from_floats.forget_derived(); from_codes.forget_derived(); from_pq.forget_derived(); }
     i64 asym_calls = 0;        // stat "asym_calls": asymmetric calls that succeeded (cumulative)
     i64 pq_calls = 0;          // stat "pq_calls": quantised calls that succeeded (cumulative)
+    i64 pq_encode_calls = 0, pq_encoded_rows = 0;   // stats "pq_encode_calls" / "pq_encoded_rows": encoder calls that succeeded, the rows they encoded (cumulative)
     i64 real_requeried = 0;       // queries that lost the first real-valued bet and were ranked again on their own (cumulative)
     int bpad = 0;              // feature count padded to a multiple of 16 (0: no float tables loaded)
     i64 census_db[3] = {0, 0, 0}, census_q[3] = {0, 0, 0};
@@ -589,6 +593,7 @@ struct hg_ctx : StepBufs, StepState {
     DevBuf krows;              // real-valued path: the rows the filter kept, 4-byte row numbers [Q][S][cap] (k_real_select_bf writes, k_real_rescore reads)
     DevBuf thr2;               // filter + rescore path: lowered cuts
     DevBuf hist2;              // the second sample's counts [Q][RC_BINS] (k_real_sample_count)
+    DevBuf pqe_in, pqe_books, pqe_books64, pqe_codes, pqe_err;   // the PQ encoder (hg_pq_encode.hip): a chunk of host features f32 [chunk][b], the codebooks f32 and f64 [M][K][dsub], a chunk's codes u8 [chunk][M] and errors f64 [chunk]
     DevBuf gathered[4], scratch[4], comm_tmp, gath_idx, gath_dist;   // hg_allgather's landing zones, hg_scratch, the collectives' own
 
     // Every device buffer of the context, each once, with its class: hg_destroy, hg_trim and the stat "device_bytes" walk this.
@@ -602,7 +607,7 @@ struct hg_ctx : StepBufs, StepState {
                           &sortA, &sortB, &scores, &gtab, &sampx, &cntq, &krows, &thr2, &hist2, &comm_tmp, &gath_idx, &gath_dist, &rh_part, &rh_all, &rh_rel,
                           &gr_tab, &gr_out, &gr_grades, &gh_part, &gh_tab, &ta_tab, &ta_out, &aa_tab, &aa_out, &jh_max, &jh_part, &jh_tab, &vt_tab, &vt_votes, &vt_pred, &vt_conf,
                           &mg_pack, &mg_flag, &mg_rel, &mg_grade, &mg_joint, &lm_pack, &lm_flag, &lm_tab, &lm_grades, &lm_votes, &rr_recs, &rr_tmp, &rr_base, &rr_msz, &rr_cnt, &rr_scores,
-                          &nb_ids, &nb_cnt, &nb_flag, &nb_stage, &nh_tab})
+                          &nb_ids, &nb_cnt, &nb_flag, &nb_stage, &nh_tab, &pqe_in, &pqe_books, &pqe_books64, &pqe_codes, &pqe_err})
             f(*d, BUF_WORK);
         for (DevBuf& d : gathered) f(d, BUF_WORK);
         for (DevBuf& d : scratch) f(d, BUF_WORK);
@@ -775,6 +780,8 @@ inline int do_ap(hg_ctx* c) { return do_ap_range(c, 0, c->geo.Q); }
 int ensure_out_block(hg_ctx* c);                   // err / ap / rel as views of one block (before anything of the call is enqueued)
 int read_plan_flag(hg_ctx* c, int* flag);        // *err back to the host (synchronises)
 int launch_min_topr(hg_ctx* c, const u32* idx_all, const u8* dist_all, i64 n, int G);
+extern "C" int check_dev_pointer(hg_ctx* c, const char* who, const char* what, const hg_dev_array& a, int64_t extent);   // a.ptr is device memory of the context's GPU and the extent lies inside its allocation (else HG_ERR_ARG)
+extern "C" int wait_for_producer(hg_ctx* c, void* s);   // (both defined among the device-array entry points)  the context's stream behind whatever is enqueued so far on the producer's stream s
 hg_ctx* requery_child(hg_ctx* c, i64 nF);       // c->sub, set up to rerun nF lost queries of c
 // hg_seq.hip
 int stage_ap_download(hg_ctx* c, void* dst = nullptr);   // {verdict, AP, hit counts} into pinned host memory behind everything enqueued so far (no synchronisation)
@@ -804,7 +811,7 @@ bool hist_i8_applies(const hg_ctx* c);           // launch_hist_mx takes k_hist_
 int launch_select_mx(hg_ctx* c, int lw, const int* cut);    // k_select_mx<NW, LW, QT, COMPACT>
 int launch_select_mx3(hg_ctx* c, int lw, const int* cut);   // k_select_mx3 (codes of <= 64 bits, one-byte records)
 int launch_select_mx4(hg_ctx* c, int lw, const int* cut);   // k_select_mx4 (codes of 65..128 bits, one-byte records)
-int preload_valu(); int preload_mx(); int preload_mx1(); int preload_real(); int preload_seq(); int preload_rank(); int preload_side(); int preload_rerank();   // one per translation unit with kernels (hg_preload)
+int preload_valu(); int preload_mx(); int preload_mx1(); int preload_real(); int preload_seq(); int preload_rank(); int preload_side(); int preload_rerank(); int preload_pq_encode();   // one per translation unit with kernels (hg_preload)
 // hg_comm.hip
 void comm_release(hg_ctx* c);                    // destroys the context's communicator, if any
 

@@ -250,6 +250,33 @@ class PQTable:
                 and not any(getattr(getattr(a, "flags", None), "writeable", True) for a in self.kept))
 
 
+class PQFeatures:
+    """A database to be product-quantised on the way in: float features [N, M * dsub] -- a host array, or a DeviceArray -- and the
+    codebooks float32 [M, K, dsub] that the GPU assigns every row to (hg_set_database_pq_f32; device features: hg_pq_encode_dev, then
+    hg_set_database_pq).  The loaders' other stand-in for database.output in 'quantised' mode, next to PQTable."""
+
+    def __init__(self, features, codebooks):
+        from . import pq
+        if as_device_array(codebooks) is not None:
+            raise ValueError("quantised=True takes the codebooks as a host array")
+        self.codebooks = pq.check_codebooks(codebooks)
+        dev = as_device_array(features)
+        self.features = dev if dev is not None else np.asarray(features)
+        if dev is None and self.features.dtype.kind != "f":
+            raise ValueError("features must be floating point (have %s)" % self.features.dtype)
+        self.kept = (features, codebooks)              # the caller's own objects: what "the same arrays as last time" compares
+        self.ndim = self.features.ndim
+        b = self.codebooks.shape[0] * self.codebooks.shape[2]
+        if self.ndim != 2 or self.features.shape[1] != b:
+            raise ValueError("features must be [N, M * dsub] = [N, %d] (have shape %r)" % (b, tuple(self.features.shape)))
+        self.shape = (self.features.shape[0], b)
+
+    def same_readonly(self, other):
+        return (isinstance(other, PQFeatures) and self.kept[0] is other.kept[0] and self.kept[1] is other.kept[1]
+                and not isinstance(self.features, DeviceArray)           # (nothing says device memory is unchanged)
+                and not any(getattr(getattr(a, "flags", None), "writeable", True) for a in self.kept))
+
+
 def _check_shapes(q_codes, db_codes, q_labels, db_labels, R):
     if db_codes.ndim != 2 or q_codes.ndim != 2 or db_codes.shape[1] != q_codes.shape[1]:
         raise ValueError("query and database codes must be [n, b] with the same b")
@@ -321,9 +348,18 @@ def _load_database(eng, db_codes, db_labels, mode="reference", floats=None):
     eng.b = eng.C = eng.N = eng.db_kind = eng.db_src = None      # nothing is resident until this load has succeeded
     eng.resident = None                               # whoever loads another database (extra_metrics, MAPs) ends _evaluate's shortcut
     on_device = isinstance(db_codes, DeviceArray)
-    if isinstance(db_codes, PQTable) != (mode == "quantised"):
+    if isinstance(db_codes, (PQTable, PQFeatures)) != (mode == "quantised"):
         raise ValueError("quantised=True ranks a database given as .codes / .codebooks, and only such a one")
-    if mode == "quantised":
+    if mode == "quantised" and isinstance(db_codes, PQFeatures):
+        # features to be encoded on the GPU: host arrays in one call; device arrays are encoded where they lie and the codes loaded
+        if isinstance(db_codes.features, DeviceArray):
+            codes, _, bad_rows = eng.ctx.pq_encode(db_codes.features, db_codes.codebooks)
+            if bad_rows:
+                raise ValueError("%d feature rows are not finite" % bad_rows)
+            bad_c, bad_l = eng.ctx.set_database_pq(codes, db_codes.codebooks, db_labels)
+        else:
+            bad_c, bad_l = eng.ctx.set_database_pq_f32(db_codes.features, db_codes.codebooks, db_labels)
+    elif mode == "quantised":
         bad_c, bad_l = eng.ctx.set_database_pq(db_codes.codes, db_codes.codebooks, db_labels)
     elif on_device:
         # device arrays: in 'reference' mode the floats are kept at once (a copy inside the GPU's memory, no PCIe) -- the caller's
@@ -498,7 +534,7 @@ class MAPs:
     calls (explicit), and a database whose arrays are the SAME read-only objects as last time is reused
     automatically (a writable array may have changed in place, so it is uploaded again)."""
 
-    def __init__(self, r, device=0, binarize=False, rerank=False, asymmetric=False, quantised=False):
+    def __init__(self, r, device=0, binarize=False, rerank=False, asymmetric=False, quantised=False, quantise_queries=False):
         """rerank=True: sign() first (it implies binarize), rank by Hamming distance, and inside equal distances by the float32 inner
         product of the features (descending), then by database index -- the ties of the Hamming ranking resolved by the
         magnitudes sign() throws away; the threshold group's rows with the highest inner product make the cut at R.
@@ -509,7 +545,12 @@ class MAPs:
         .codebooks float32 [M, K, dsub] and .label, host arrays -- and rows are ranked by the float32 inner product of the query with
         the decoded row (descending), then by database index (hg_map_pq): AQD.  `query` exposes .output [Q, M * dsub], or, without an
         .output, .codes uint8 [Q, M], decoded on the host with the database's codebooks: SQD.  The decoded database exists nowhere.
-        Not together with binarize, rerank or asymmetric (ValueError)."""
+        Not together with binarize, rerank or asymmetric (ValueError).  A database that exposes .output (host or device memory) and
+        .codebooks and no .codes is encoded on the GPU on its way in (hg_set_database_pq_f32 / hg_pq_encode_dev: the exact encoder).
+        quantise_queries=True (with quantised=True only): the query's .output is encoded on the GPU with the resident codebooks and
+        decoded on the host -- SQD from features."""
+        if quantise_queries and not quantised:
+            raise ValueError("quantise_queries=True quantises the query with the database's codebooks: only together with quantised=True")
         if quantised and (binarize or rerank or asymmetric):
             raise ValueError("quantised=True ranks real-valued queries against product-quantisation codes: not together with binarize, "
                              "rerank or asymmetric")
@@ -521,6 +562,7 @@ class MAPs:
         self.rerank = rerank
         self.asymmetric = asymmetric
         self.quantised = quantised
+        self.quantise_queries = quantise_queries
         self._books = None             # quantised: the resident database's codebooks (a query given as codes is decoded with them)
         self._eng = None
         self._lock = threading.RLock()
@@ -543,21 +585,36 @@ class MAPs:
         """database -> (features, labels) as the loaders take them; quantised: (PQTable of .codes / .codebooks, labels)."""
         if not self.quantised:
             return _sides(database.output, database.label, "database")
-        if getattr(database, "codes", None) is None or getattr(database, "codebooks", None) is None:
+        books = getattr(database, "codebooks", None)
+        if books is None or (getattr(database, "codes", None) is None and getattr(database, "output", None) is None):
             raise ValueError("quantised=True ranks a database given as .codes / .codebooks (hashgan_amd/pq.py), not as .output")
         if as_device_array(database.label) is not None:
             raise ValueError("quantised=True takes the database as host arrays")
-        return PQTable(database.codes, database.codebooks), np.asarray(database.label)
+        if getattr(database, "codes", None) is None:   # .output + .codebooks: encoded on the GPU
+            return PQFeatures(database.output, books), np.asarray(database.label)
+        return PQTable(database.codes, books), np.asarray(database.label)
 
     def _q_sides(self, database, query):
         """query -> (features, labels); quantised and no .output: its .codes decoded with the database's codebooks (SQD)."""
-        if not self.quantised or getattr(query, "output", None) is not None:
+        if not self.quantised or (getattr(query, "output", None) is not None and not self.quantise_queries):
             return _sides(query.output, query.label, "query")
         from . import pq
         books = self._books if database is None else database.codebooks
         if books is None:
             raise ValueError("no resident database: call set_database first")
-        return pq.decode(query.codes, books), np.asarray(query.label)
+        if not self.quantise_queries:
+            return pq.decode(query.codes, books), np.asarray(query.label)
+        # SQD from features: the query's codes from the GPU's encoder (it leaves the context's tables alone), decoded on the host
+        if getattr(query, "output", None) is None:
+            raise ValueError("quantise_queries=True quantises query.output: the query has none")
+        if as_device_array(query.label) is not None:
+            raise ValueError("quantise_queries=True takes the query's labels as a host array")
+        feats = PQFeatures(query.output, books)       # (shape and dtype checked before any GPU use)
+        with self._lock:
+            codes, _, bad_rows = self._guard(self._engine().ctx.pq_encode, feats.features, feats.codebooks)
+        if bad_rows:
+            raise ValueError("%d query rows are not finite" % bad_rows)
+        return pq.decode(codes, feats.codebooks), np.asarray(query.label)
 
     def close(self):
         with self._lock:

@@ -4,8 +4,9 @@ M disjoint subspaces of dsub features each (b = M * dsub <= 255), K <= 256 codew
     codebooks  float32 [M, K, dsub]
     codes      uint8   [N, M]
 A row decodes by pure gather, x[n, k] = codebooks[k // dsub, codes[n, k // dsub], k % dsub] -- no arithmetic, so ranking against the
-codes is by definition ranking against decode(codes, codebooks), bit for bit.  encode() is a convenience for tests and for SQD (the
-query quantised too: MAPs(R, quantised=True) decodes a query's codes on the host); the GPU never encodes."""
+codes is by definition ranking against decode(codes, codebooks), bit for bit.  encode() is the host's encoder, in float64 on whatever
+float type it is given; encode_gpu() is the same contract on float32 features as a HIP kernel (hg_pq_encode / hg_pq_encode_dev), which is
+what MAPs(R, quantised=True) uses for a database given as .output + .codebooks and for quantise_queries=True (SQD from features)."""
 import numpy as np
 
 MAX_FEATURES = 255
@@ -86,6 +87,42 @@ def encode(features, codebooks):
                 best[close] = d.argmin(1)                # (argmin: the first, the lowest index, among equals)
             out[r0:r0 + step, m] = best
     return out
+
+
+def encode_gpu(features, codebooks, device=0, return_error=False):
+    """encode() on the GPU, exactly (include/hashgan_amd.h, hg_pq_encode: per subspace the float64 sum of squared differences feature by
+    feature, two roundings per step, the lowest index on ties): features a host array, a torch tensor, an object with
+    __cuda_array_interface__ or a devarray.DeviceArray -- float32, or float16 / bfloat16 widened exactly -- [N, M * dsub].  The context
+    comes from the pool MAPs objects draw theirs from.  ValueError for what encode() refuses, before any GPU use, and for rows with a
+    non-finite feature, after the call.  -> codes uint8 [N, M]; return_error=True: (codes, err float64 [N], the summed squared distance
+    to the chosen codewords)."""
+    from . import metric
+    from .devarray import as_device_array
+    cb = check_codebooks(codebooks)
+    M, K, dsub = cb.shape
+    if not np.isfinite(cb).all():
+        raise ValueError("codebooks must be finite")
+    x = as_device_array(features)
+    if x is None:
+        x = np.asarray(features)
+        if x.dtype.kind != "f":
+            raise ValueError("features must be floating point (have %s)" % x.dtype)
+        if x.dtype.itemsize > 4:
+            raise ValueError("the GPU encodes float32 (or float16) features: %s would be rounded first -- convert it, or use encode()" % x.dtype)
+    elif x.dtype not in ("float32", "float16", "bfloat16"):
+        raise ValueError("features must be floating point (have %s)" % x.dtype)
+    if x.ndim != 2 or x.shape[1] != M * dsub:
+        raise ValueError("features must be [N, M * dsub] = [N, %d] (have shape %r)" % (M * dsub, tuple(x.shape)))
+    if x.shape[0] < 1:
+        raise ValueError("features must have at least one row")
+    eng = metric._Pool.acquire(device)
+    try:
+        codes, err, bad = eng.ctx.pq_encode(x, cb, want_err=return_error)
+    finally:
+        metric._Pool.release(eng)
+    if bad:
+        raise ValueError("%d feature rows are not finite" % bad)
+    return (codes, err) if return_error else codes
 
 
 def sign_codes(codes, codebooks):

@@ -332,6 +332,34 @@ int hg_set_database_pq(hg_ctx* ctx, const uint8_t* host_codes, const float* host
                        int M, int K, int dsub, int C, int64_t idx_base, int64_t n_total, int64_t* bad_codes, int64_t* bad_labels);
 int hg_map_pq(hg_ctx* ctx, int64_t R, double* host_ap, int64_t* host_rel);
 int hg_topr_pq(hg_ctx* ctx, int64_t R);
+/* The codes themselves, from float features, on the GPU (k_pq_encode): the exact encoder.  For codebooks float32 [M][K][dsub] and a
+ * feature row x (b = M * dsub <= 255, K <= 256) the code of subspace m is
+ *     d_k = 0.0 (float64);  for j = 0 .. dsub-1:  t = (double)x[m*dsub+j] - (double)w[m][k][j];  d_k = d_k + t*t
+ *     code = the lowest k with d_k minimal:   best = 0; for k = 1 .. K-1: if (d_k < d_best) best = k
+ *     err(row) = 0.0; for m = 0 .. M-1: err += d_best(m)          (float64)
+ * Every operation is IEEE float64 and rounded once; t*t and the addition are two roundings (no fused multiply-add); features and
+ * codewords run in ascending order; the comparison is a strict `<`.  16-bit features (IEEE half, bfloat16) are widened exactly to
+ * float32 first.  A row with a non-finite feature makes every d_k of that subspace +inf or NaN, so the strict `<` leaves code 0 there,
+ * and its other subspaces are unaffected; such rows are counted in *bad_rows and not refused.
+ *   hg_pq_encode       host features float32 [N][b], uploaded in row chunks through a bounded work buffer (option
+ *             "pq_encode_chunk_rows"; 0 = the default, 256 MB of features); host_codes uint8 [N][M]; host_err float64 [N] or NULL.
+ *   hg_pq_encode_dev   features in device memory: float32 / float16 / bfloat16, any strides >= 1, no alignment assumed; refusals and
+ *             stream ordering as hg_set_database_dev's (copy-in, complete on return, waits on features->stream).
+ *             Both need no database and no queries, and leave whatever the context holds -- tables, ranked lists, PQ tables,
+ *             generations, hg_map_begin's licence -- exactly as it was; their work buffers are counted in "device_bytes" and freed by hg_trim.
+ *             Refused with HG_ERR_ARG before anything is launched, the message naming the offender: null pointers or N < 1; M, K or
+ *             dsub < 1; K > 256; M * dsub > HG_MAX_BITS; features->cols != M * dsub; a non-finite codebook entry; N >= 2^31.
+ *   hg_set_database_pq_f32   encodes host features on the GPU and loads the result: the context is left exactly as
+ *             hg_set_database_pq leaves it for those codes (which come back to the host on the way: N x M bytes).  It refuses what
+ *             hg_set_database_pq refuses; with *bad_rows > 0 it loads nothing and returns HG_ERR_ARG.
+ *   Stats     "pq_encode_calls" (encoder calls that succeeded) and "pq_encoded_rows" (the rows they encoded), both cumulative. */
+int hg_pq_encode(hg_ctx* ctx, const float* host_features, int64_t N, const float* host_codebooks, int M, int K, int dsub,
+                 uint8_t* host_codes, double* host_err, int64_t* bad_rows);
+int hg_pq_encode_dev(hg_ctx* ctx, const hg_dev_array* features, const float* host_codebooks, int M, int K, int dsub,
+                     uint8_t* host_codes, double* host_err, int64_t* bad_rows);
+int hg_set_database_pq_f32(hg_ctx* ctx, const float* host_features, const float* host_codebooks, const int64_t* host_labels,
+                           int64_t N, int M, int K, int dsub, int C, int64_t idx_base, int64_t n_total,
+                           int64_t* bad_codes, int64_t* bad_labels, int64_t* bad_rows);
 
 /* ---- Hamming ranking with the tie groups re-ranked by the features ("sign, rank by Hamming distance, re-rank inside equal
  * distances by the real-valued inner product") ----
