@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 from oracle import hamming_map as O
 from oracle import real_map
+from tests import brute_refs
 from hashgan_amd import DeviceArray, MAPs, _native, metric
 from hashgan_amd import extra_metrics as X
 
@@ -36,17 +37,7 @@ def one_hot(rng, n, C):
     return np.eye(C, dtype=np.int64)[rng.integers(0, C, n)]
 
 
-def oracle_at(imatch, Rs):
-    """imatch bool [Q, >= max(Rs)] in canonical order -> (ap float64 [Q, nR] with nan for skipped queries, rel int64 [Q, nR])."""
-    Q = imatch.shape[0]
-    ap, rel = np.full((Q, len(Rs)), np.nan), np.zeros((Q, len(Rs)), np.int64)
-    for q in range(Q):
-        for j, R in enumerate(Rs):
-            a, r = O.average_precision(imatch[q, :R], int(R))
-            rel[q, j] = r
-            if a is not None:
-                ap[q, j] = a
-    return ap, rel
+oracle_at = brute_refs.ap_at_oracle                       # (shared with tests/test_second_hand_gpu.py)
 
 
 @functools.lru_cache(maxsize=None)

@@ -10,7 +10,7 @@ import functools
 
 import numpy as np
 import pytest
-from tests import cases
+from tests import brute_refs, cases
 from hashgan_amd import _native, metric
 from hashgan_amd import extra_metrics as X
 
@@ -19,57 +19,9 @@ pytestmark = pytest.mark.gpu
 STATE, ARG = _native.HG_ERR_STATE, _native.HG_ERR_ARG
 
 
-def REL(k):
-    return (np.asarray(k, dtype=np.float64) + 2.0) * 2.0 ** -52
-
-
-def hamming(qb, db):
-    """Q x N Hamming distances: +-1 products in float32 are exact for any code length here."""
-    b = qb.shape[1]
-    ip = (2.0 * qb.astype(np.float32) - 1.0) @ (2.0 * db.astype(np.float32) - 1.0).T
-    return ((b - ip) / 2).astype(np.int64)
-
-
-def ranked_by(key):
-    """np.lexsort((index, key)) per query: key ascending, then index ascending."""
-    return np.argsort(key, axis=1, kind="stable")
-
-
-def pair_grades(ql, dl):
-    return ql.astype(np.int64) @ dl.astype(np.int64).T
-
-
-def brute_tables(G, ks, gain, disc):
-    """G: int64 [Q, R] grades in rank order -> gsum, hits, dcg, wsum [Q, len(ks)] by the definitions."""
-    ks = np.asarray(ks, dtype=np.int64)
-    R = G.shape[1]
-    S = np.cumsum(G, axis=1)
-    gsum = S[:, ks - 1]
-    hits = np.cumsum(G > 0, axis=1)[:, ks - 1]
-    t1 = gain[G] * disc[None, :R]
-    t2 = np.where(G > 0, S / np.arange(1, R + 1, dtype=np.float64)[None, :], 0.0)
-    dcg = np.stack([t1[:, :k].sum(1) for k in ks], axis=1)
-    wsum = np.stack([t2[:, :k].sum(1) for k in ks], axis=1)
-    return gsum, hits, dcg, wsum
-
-
-def assert_tables(got, ref, ks):
-    gsum, hits, dcg, wsum = got
-    assert gsum.dtype == np.int64 and hits.dtype == np.int64 and dcg.dtype == np.float64 and wsum.dtype == np.float64
-    assert np.array_equal(gsum, ref[0]), "gsum"
-    assert np.array_equal(hits, ref[1]), "hits"
-    tol = REL(ks)[None, :]
-    for name, a, r in (("dcg", dcg, ref[2]), ("wsum", wsum, ref[3])):
-        err = np.abs(a - r)
-        worst = (err / np.maximum(tol * np.abs(r), 1e-300)).max()
-        print("%s: largest error %.3g of its bound" % (name, worst))
-        assert (err <= tol * np.abs(r)).all(), (name, worst)
-
-
-def brute_hist(ql, dl):
-    Gm = pair_grades(ql, dl)
-    C = ql.shape[1]
-    return np.stack([np.bincount(Gm[q], minlength=C + 1) for q in range(len(ql))]).T    # [C + 1, Q]
+# the brute-force tables and the bound REL(k) of the docstring: tests/brute_refs.py (shared with tests/test_second_hand_gpu.py)
+REL, hamming, ranked_by, pair_grades = brute_refs.REL, brute_refs.hamming, brute_refs.ranked_by, brute_refs.pair_grades
+brute_tables, assert_tables, brute_hist = brute_refs.graded_tables, brute_refs.assert_graded_tables, brute_refs.grade_hist
 
 
 def code_ctx(qb, db, ql, dl, opts=(), idx_base=0, n_total=None):

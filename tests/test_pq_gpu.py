@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import real_map as RM
+from tests import brute_refs
 from hashgan_amd import _native, metric, pq, MAPs, pool_stats, release_engines
 from hashgan_amd.devarray import DeviceOut
 
@@ -30,12 +31,7 @@ SHAPES = [BET,
           (5, 1000, 5, 51, 256, 1000, 3)]         # b = 255
 
 
-def oracle(qf, x, ql, dl, R):
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        _, ap, idx, score = RM.map_from_features(qf, x, ql.astype(np.int8), dl.astype(np.int8), R)
-    match = (dl[idx].astype(bool) & ql[:, None, :].astype(bool)).any(-1)
-    return ap, idx, score, match.astype(np.uint8), match.sum(1).astype(np.int64)
+oracle = brute_refs.real_lists                            # (shared with tests/test_second_hand_gpu.py)
 
 
 @functools.lru_cache(maxsize=None)

@@ -5,7 +5,7 @@ import functools
 
 import numpy as np
 import pytest
-from tests import cases
+from tests import brute_refs, cases
 from hashgan_amd import _native, metric
 
 pytestmark = pytest.mark.gpu
@@ -16,16 +16,7 @@ def expected_variant(b, C, hist_mfma):
     return 1
 
 
-def brute(qb, db, ql, dl):
-    """-> (all, rel) int64 [b+1, Q] from the Q x N distance matrix and the label match."""
-    b = qb.shape[1]
-    D = np.zeros((qb.shape[0], db.shape[0]), np.int64)
-    for j in range(b):                                 # (bit by bit: no Q x N x b temporary)
-        D += qb[:, j, None] != db[None, :, j]
-    rel = (ql.astype(np.int64) @ dl.astype(np.int64).T) > 0
-    all_h = np.stack([np.bincount(D[q], minlength=b + 1) for q in range(len(qb))])
-    rel_h = np.stack([np.bincount(D[q][rel[q]], minlength=b + 1) for q in range(len(qb))])
-    return all_h.T, rel_h.T
+brute = brute_refs.rel_hist                            # (shared with tests/test_second_hand_gpu.py)
 
 
 def gpu_pass(qb, db, ql, dl, hist_mfma, opts=(), idx_base=0, n_total=None):

@@ -10,7 +10,7 @@ import functools
 
 import numpy as np
 import pytest
-from tests import cases
+from tests import brute_refs, cases
 from hashgan_amd import DeviceArray, _native, metric
 from hashgan_amd import extra_metrics as X
 
@@ -34,17 +34,7 @@ def raw(x):
     return tuple(a.tobytes() for a in x) if isinstance(x, tuple) else x.tobytes()
 
 
-def defined_G(ql, dl):
-    return 1 + int(min(ql.sum(1).max(), dl.sum(1).max()))
-
-
-def brute_joint(qb, db, ql, dl, G):
-    """uint32 [b + 1, G, Q] by the definition; a grade beyond G - 1 would raise."""
-    d = (qb[:, None, :] != db[None, :, :]).sum(2)
-    g = ql.astype(np.int64) @ dl.astype(np.int64).T
-    J = np.zeros((qb.shape[1] + 1, G, len(qb)), dtype=np.uint32)
-    np.add.at(J, (d, g, np.arange(len(qb))[:, None]), 1)
-    return J
+defined_G, brute_joint = brute_refs.defined_G, brute_refs.joint_hist      # (shared with tests/test_second_hand_gpu.py)
 
 
 def load(ctx, qb, db, ql, dl, idx_base=0, n_total=None):

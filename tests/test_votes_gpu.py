@@ -9,7 +9,7 @@ import types
 
 import numpy as np
 import pytest
-from tests import cases
+from tests import brute_refs, cases
 from hashgan_amd import MAPs, _native, metric
 from hashgan_amd import extra_metrics as X
 
@@ -18,21 +18,7 @@ pytestmark = pytest.mark.gpu
 STATE, ARG = _native.HG_ERR_STATE, _native.HG_ERR_ARG
 
 
-def hamming(qb, db):
-    """Q x N Hamming distances: +-1 products in float32 are exact for any code length here."""
-    b = qb.shape[1]
-    ip = (2.0 * qb.astype(np.float32) - 1.0) @ (2.0 * db.astype(np.float32) - 1.0).T
-    return ((b - ip) / 2).astype(np.int64)
-
-
-def tables_of(L, ql, ks):
-    """L: {0,1} [Q, R, C] labels in rank order -> votes uint32 [Q, nk, C], pred int32, top int64 [Q, nk], conf int64 [nk, C, C]."""
-    ks = np.asarray(ks, dtype=np.int64)
-    votes = np.cumsum(L.astype(np.int64), axis=1)[:, ks - 1, :]
-    top = votes.max(2)
-    pred = np.where(top > 0, votes.argmax(2), -1).astype(np.int32)       # (argmax: the first, so the smallest, class at the maximum)
-    conf = np.einsum("qa,qjb->jab", ql.astype(np.int64), votes)
-    return votes.astype(np.uint32), pred, top, conf
+hamming, tables_of = brute_refs.hamming, brute_refs.vote_tables      # (shared with tests/test_second_hand_gpu.py)
 
 
 def brute(qb, db, ql, dl, R, ks):
