@@ -123,8 +123,29 @@ void expand_image16(hg_ctx* c, const RealReq& r, DevBuf& dst, i64 rows, i64 rows
         return HG_OK;
     });
 }
+// The smallest float32 that is >= x (x >= 0, or +inf): in integer arithmetic, whatever rounding and subnormal modes the host runs in.  A value
+// below the smallest subnormal becomes that subnormal, one beyond the largest finite float +inf -- which makes the filter keep every row.
+float float_at_least(double x) {
+    if (!(x > 0.0)) return 0.0f;
+    u64 d;
+    memcpy(&d, &x, 8);
+    const int e = (int)(d >> 52) - 1023;                 // x = (1 + frac / 2^52) 2^e (a subnormal double: e = -1023, far below every float)
+    const u64 frac = d & ((1ull << 52) - 1);
+    u32 f;
+    if (e > 127) f = 0x7F800000u;
+    else if (e >= -126) f = (((u32)(e + 127) << 23) | (u32)(frac >> 29)) + ((frac & ((1ull << 29) - 1)) ? 1u : 0u);   // (a carry runs into the exponent, up to +inf)
+    else {
+        const int sh = -97 - e;                          // x / 2^-149 = (2^52 + frac) >> sh, rounded up: the subnormal's significand (2^23: the smallest normal)
+        const u64 full = frac | (1ull << 52);
+        f = sh >= 64 ? 1u : (u32)(full >> sh) + ((full & ((1ull << sh) - 1)) ? 1u : 0u);
+    }
+    float r;
+    memcpy(&r, &f, 4);
+    return r;
+}
 // The filter's 16-bit image of the database, built on first use, and with it the largest row norm^2 (xmax2: k_real_thr2's margin) and the
-// choice between IEEE half and bfloat16 -- once per database.  FLOATS: k_row_norm_max, one 4-byte download and a wait.  CODES: +-1 is exact
+// choice between IEEE half and bfloat16 -- once per database.  FLOATS: k_row_norm_max in double, one 8-byte download and a wait, rounded up
+// to the float the margin reads.  CODES: +-1 is exact
 // in either format and every row's norm^2 is exactly b -- the host writes that itself, a fill on the stream: no kernel, no download, no wait.
 // PQ: the loader's bound on every row's norm^2 (the largest codeword that occurs, subspace by subspace: k_real_thr2's margin holds for any
 // value >= the true maximum), written the same way.
@@ -136,20 +157,21 @@ int ensure_filter_image(hg_ctx* c, const RealReq& r) {
     const int KP = c->bpad;
     const i64 n16 = (c->N + 15) / 16 * 16;
     HG_TRY(s.img.reserve((size_t)n16 * KP * 2));
-    HG_TRY(s.xmax2.reserve(4));
+    HG_TRY(s.xmax2.reserve(8));                             // (the float the margin reads; FLOATS: first the double k_row_norm_max leaves)
     float xm = pq ? s.pq_xmax2 : (float)c->b;
-    if (codes) {
-        u32 xbits;
-        memcpy(&xbits, &xm, 4);
-        HG_HIP(hipMemsetD32Async((hipDeviceptr_t)s.xmax2.p, (int)xbits, 1, c->stream));
-        c->t_begin(pq ? KI_PQ_IMAGE : KI_ASYM_IMAGE);
-    } else {
-        HG_HIP(hipMemsetAsync(s.xmax2.p, 0, 4, c->stream));
+    if (!codes) {
+        double x2 = 0.0;
+        HG_HIP(hipMemsetAsync(s.xmax2.p, 0, 8, c->stream));
         c->t_begin(KI_PACK);
-        hipLaunchKernelGGL(k_row_norm_max, dim3(grid_for(c->N)), dim3(256), 0, c->stream, s.rows.as<float>(), (i64)c->N, KP, s.xmax2.as<u32>());
-        HG_HIP(hipMemcpyAsync(&xm, s.xmax2.p, 4, hipMemcpyDeviceToHost, c->stream));
+        hipLaunchKernelGGL(k_row_norm_max, dim3(grid_for(c->N)), dim3(256), 0, c->stream, s.rows.as<float>(), (i64)c->N, KP, s.xmax2.as<u64>());
+        HG_HIP(hipMemcpyAsync(&x2, s.xmax2.p, 8, hipMemcpyDeviceToHost, c->stream));
         HG_TRY(c->sync());
+        xm = float_at_least(x2);
     }
+    u32 xbits;
+    memcpy(&xbits, &xm, 4);
+    HG_HIP(hipMemsetD32Async((hipDeviceptr_t)s.xmax2.p, (int)xbits, 1, c->stream));
+    if (codes) c->t_begin(pq ? KI_PQ_IMAGE : KI_ASYM_IMAGE);
     // IEEE half (three more significant bits: a margin an eighth of bfloat16's) when no feature can overflow it (every |x_k| <= the row's
     // norm < 2^15) and the rows are not tiny either: half's error has an absolute floor -- subnormals, flushed or not -- that outgrows the
     // relative term once norms fall below ~0.1; bfloat16 has float32's exponents and no such floor

@@ -70,19 +70,27 @@ static __global__ __launch_bounds__(256) void k_expand_dbf_bf16(const float* __r
     img[(((row >> 4) * (KP / 16) + m) * 2 + hh) * 16 + (row & 15)] = v;
 }
 
-// max over the rows of |x|_2^2 (float32 sum of squares; the caller inflates it), as float bits (non-negative floats
-// order like unsigned integers).  out must be zeroed.
-static __global__ __launch_bounds__(256) void k_row_norm_max(const float* __restrict__ dbf, i64 N, int KP, u32* __restrict__ out) {
+// max over the rows of |x|_2^2, as double bits (non-negative doubles order like unsigned integers).  out must be zeroed.
+// The sum of squares runs in DOUBLE: a float32 square underflows below |x_k| ~ 2^-75 and is subnormal -- a few bits -- up to ~2^-63, so a
+// table of tiny features came out with a norm of 0, or one short of the truth, and k_real_thr2's margin with it; in double the square of any
+// finite float32 is exact and normal, and up to 256 of them add up to 2^-44 relative, far inside the margin's 1.0001 (float_at_least rounds up).
+static __global__ __launch_bounds__(256) void k_row_norm_max(const float* __restrict__ dbf, i64 N, int KP, u64* __restrict__ out) {
     const i64 row = (i64)blockIdx.x * 256 + threadIdx.x;
-    float s = 0.0f;
+    double s = 0.0;
     if (row < N) {
         const float4* f = (const float4*)(dbf + row * KP);
-        for (int k = 0; k < KP / 4; ++k) { const float4 v = f[k]; s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w; }
+        for (int k = 0; k < KP / 4; ++k) {
+            const float4 v = f[k];
+            s += ((double)v.x * (double)v.x + (double)v.y * (double)v.y) + ((double)v.z * (double)v.z + (double)v.w * (double)v.w);
+        }
     }
-    u32 b = __float_as_uint(s);
-    if (s != s) b = 0x7F800000u;                                  // NaN features: no bound holds; +inf keeps every pair
-    for (int o = 32; o > 0; o >>= 1) { const u32 t = (u32)__shfl_xor((int)b, o); b = t > b ? t : b; }
-    if ((threadIdx.x & 63) == 0 && b) atomicMax(out, b);
+    u64 b = (u64)__double_as_longlong(s);
+    if (s != s) b = 0x7FF0000000000000ull;                        // NaN features: no bound holds; +inf keeps every pair
+    for (int o = 32; o > 0; o >>= 1) {
+        const u64 t = (u64)(u32)__shfl_xor((int)(u32)b, o) | ((u64)(u32)__shfl_xor((int)(u32)(b >> 32), o) << 32);
+        b = t > b ? t : b;
+    }
+    if ((threadIdx.x & 63) == 0 && b) atomicMax((unsigned long long*)out, (unsigned long long)b);
 }
 
 // thr2[q] = thr[q] - eps[q], rounded down (see the header).  One thread per query, double arithmetic.
@@ -98,7 +106,7 @@ static __global__ __launch_bounds__(256) void k_real_thr2(const float* __restric
     if (!(t > -INFINITY && t < INFINITY)) { thr2[q] = t; return; }   // -inf: everything qualifies; +inf: nothing
     double qq = 0.0;
     for (int k = 0; k < KP; ++k) { const double v = (double)qf[(i64)q * KP + k]; qq += v * v; }
-    const double xx = (double)__uint_as_float(*xmax2) * 1.0001;       // the float32 sum of squares, inflated
+    const double xx = (double)__uint_as_float(*xmax2) * 1.0001;       // >= the largest row norm^2 (ensure_filter_image), inflated
     const double c = 2.0 * u + u * u + (double)(KP + 2) * 4.76837158203125e-07;   // 2^-21
     const double eps = 1.0001 * c * sqrt(qq * xx) + (double)(KP + 2) * 4.76837158203125e-07 * fabs((double)t)
                      + 1.01 * eta * sqrt((double)KP) * (sqrt(qq) + sqrt(xx)) + (double)KP * eta * eta + 1e-30;
