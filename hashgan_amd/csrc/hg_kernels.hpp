@@ -1604,8 +1604,8 @@ __device__ __forceinline__ void ap_eval(const WordFn& word_at, const i64 RW, con
 
 // ap_eval with a third of the instructions (round 4; k_rank_lean's epilogue).  Same arithmetic, same order of additions:
 //   * a lane (leaf, j) walks its stride-8 elements incrementally: 32 window bits per step come from two LDS reads and a
-//     funnel shift, the running match count from v_bcnt of the window's bytes (no per-element prefix lookup, no 64-bit
-//     masks), the rank as a double from b += 8.0, the reciprocal through an immediate offset from one per-lane pointer;
+//     funnel shift, the running match count from v_bcnt of the window shifted by a per-lane amount (no per-element prefix lookup,
+//     no 64-bit masks, no bytes), the rank as a double from b += 8.0, the reciprocal through an immediate offset from one per-lane pointer;
 //     a slot without a match contributes a = 0 -> q = 0 -> +0.0, and r + 0.0 == r exactly, so no branch per element;
 //   * the < 8 tail elements of a leaf are evaluated by lanes 0..6 of its group at once and added by lane 0 in order (DPP);
 //   * the eight accumulators combine through DPP (xor 1, xor 2, half mirror) instead of ds_bpermute;
@@ -1677,25 +1677,41 @@ __device__ __forceinline__ void ap_eval2(const WordFn& word_at, const i64 RW, co
             const double* __restrict__ rp = recip + (cb + ls + j + 1);
             double b = (double)(cb + ls + j + 1);
             double r = 0.0;
-            for (int i4 = 0; __any(32 * i4 < body); ++i4) {    // 32 elements of the leaf = 4 of the lane's per step
+            // A 32-slot window W of the leaf = four slots of the lane: step k is slot 8 k + j.  T = W << (7 - j) has the lane's last
+            // slot in the sign bit and T << 8 (3 - k) that of step k, with nothing above it: its population count is the matches of
+            // the window up to the slot (added to P, the matches before the window, by the v_bcnt itself -- no byte extracted), and
+            // its sign spread over the word masks the INTEGER count -- one v_and, where masking the converted double took a
+            // compare and two selects.  One per-lane constant (7 - j) serves all four steps.
+            const u32 sj = 7u - (u32)j;
+            auto slot = [&](const u32 T, const int k, const double y) {
+                const u32 t = T << (8 * (3 - k));
+                const u32 cnt = P + (u32)__builtin_popcount(t);
+                const double a = (double)(cnt & (u32)((int)t >> 31));               // 0 without a match
+                const double q = a * y;
+                r += __builtin_fma(__builtin_fma(-q, b, a), y, q);
+                b += 8.0;
+            };
+            // whole windows pay nothing for raggedness: only the leaf's last window (body mod 32 = 8, 16 or 24 slots) masks W, and the
+            // same masked W feeds P.  A lane whose leaf has fewer whole windows than its neighbours' sits the others out (exec), which
+            // is what adding their +0.0 came to.
+            const int nfull = body >> 5;
+            for (int i4 = 0; i4 < nfull; ++i4) {               // 32 elements of the leaf = 4 of the lane's per step
                 const u32 lo = cw32[wd + i4], hi = cw32[wd + i4 + 1];
-                u32 W = __builtin_amdgcn_alignbit(hi, lo, (u32)bs);      // elements 32 i4 .. 32 i4 + 31 of the leaf
-                const int nb = body - 32 * i4;
-                W = nb >= 32 ? W : nb <= 0 ? 0u : W & ((1u << nb) - 1u);
+                const u32 W = __builtin_amdgcn_alignbit(hi, lo, (u32)bs);      // elements 32 i4 .. 32 i4 + 31 of the leaf
                 const double y0 = rp[0], y1 = rp[8], y2 = rp[16], y3 = rp[24];
-                const double ys[4] = {y0, y1, y2, y3};
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const u32 byte = (W >> (8 * k)) & 0xFFu;
-                    const u32 cnt = P + (u32)__builtin_popcount(byte & lmask);
-                    P += (u32)__builtin_popcount(byte);
-                    const u32 bit = (byte >> j) & 1u;
-                    const double a = (double)(cnt * bit);
-                    const double q = a * ys[k];
-                    r += __builtin_fma(__builtin_fma(-q, b, a), ys[k], q);
-                    b += 8.0;
-                }
+                const u32 T = W << sj;
+                slot(T, 0, y0); slot(T, 1, y1); slot(T, 2, y2); slot(T, 3, y3);
+                P += (u32)__builtin_popcount(W);
                 rp += 32;
+            }
+            const int nb = body & 31;
+            if (__any(nb > 0)) {
+                const u32 lo = cw32[wd + nfull], hi = cw32[wd + nfull + 1];
+                const u32 W = __builtin_amdgcn_alignbit(hi, lo, (u32)bs) & ((1u << nb) - 1u);        // (nb = 0: nothing)
+                const double y0 = rp[0], y1 = rp[8], y2 = rp[16], y3 = rp[24];      // (slots past the leaf load a finite entry: AP_RECIP_SLACK)
+                const u32 T = W << sj;
+                slot(T, 0, y0); slot(T, 1, y1); slot(T, 2, y2); slot(T, 3, y3);
+                P += (u32)__builtin_popcount(W);
             }
             r += ap_dpp_mov<0xB1>(r);                          // quad_perm [1, 0, 3, 2]: lane ^ 1
             r += ap_dpp_mov<0x4E>(r);                          // quad_perm [2, 3, 0, 1]: lane ^ 2
