@@ -1338,6 +1338,11 @@ int hg_set_option(hg_ctx* c, const char* key, int64_t value) {
         c->handicap_next = value;
         return HG_OK;
     }
+    if (!strcmp(key, "real_far_cursors")) {            // test hook: the filter's 64-bit-cursor drain at sizes a test can afford (valid at every size; same results)
+        if (value < 0 || value > 1) return fail(HG_ERR_ARG, "real_far_cursors must be 0 or 1");
+        c->real_far_cursors = value;
+        return HG_OK;
+    }
     if (!strcmp(key, "optimistic")) {                  // (a fresh start: the latches of lost bets are cleared)
         c->opt.optimistic = value != 0;
         c->bet_consecutive_fail = c->shard_bet_fail = 0;

@@ -521,6 +521,7 @@ struct hg_ctx : StepBufs, StepState {
     i64 map_async_steps = 0, map_async_redone = 0;
     unsigned long long q_gen = 0, db_gen = 0;      // bumped by every (re)load of the query / database tables
     i64 handicap_next = 0;     // test hook "handicap_next_bet": the NEXT bet's guess sits this many deviations BELOW the expected count (it loses), once
+    i64 real_far_cursors = 0;  // test hook "real_far_cursors": 1 = k_real_select_bf keeps its 64-bit cursors (FAR) at any size, not only when a wavefront's record rows span 4 GB
     // hg_set_queries stages the packed tables through two alternating pinned blocks and does not wait for the stream: a new batch
     // can be handed over while a step on the previous one is still in flight (hg_map_begin / hg_map_end, batch after batch)
     struct QStage { void* pin = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; } qstage[2];

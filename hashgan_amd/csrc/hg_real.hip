@@ -332,7 +332,8 @@ template <int KP> int real_launch_select_bf(hg_ctx* c, const RealReq& r) {
     // (a wavefront's 64 record rows within 4 GB: 32-bit cursors -- every bet; beyond, e.g. every row a record of a 10M-row database, 64-bit ones)
     // (a 32-bit cursor keeps counting past a full slice -- by up to a segment's rows -- so that the hits it dropped are known: the
     // furthest it can get is the wavefront's 64 record rows plus one segment)
-    const bool far_rows = (64ull * (unsigned long long)c->crow + (unsigned long long)g.L) * 4ull >= (1ull << 32);
+    // (test hook "real_far_cursors": the 64-bit cursors at any size)
+    const bool far_rows = c->real_far_cursors != 0 || (64ull * (unsigned long long)c->crow + (unsigned long long)g.L) * 4ull >= (1ull << 32);
     c->t_begin(KI_REAL_SELECT);
     HG_TRY(with_bool(s.img_half, [&](auto half) { return with_bool(far_rows, [&](auto far_) {
         if (real_bf_lds_bytes(KP) > 64 * 1024)

@@ -678,7 +678,8 @@ int hg_synchronize(hg_ctx* ctx);
 int hg_set_stream(hg_ctx* ctx, void* hip_stream);
 
 /* ---- tuning and measurement -------------------------------------------------- */
-/* Engine options (39 keys, plus the test hook "handicap_next_bet" described at hg_map_begin; DESIGN.md section 9 lists every key with its
+/* Engine options (39 keys, plus the test hooks "handicap_next_bet", described at hg_map_begin, and "real_far_cursors" -- 0; 1: the real-valued
+ * filter keeps its 64-bit slice cursors at any size, same results --; DESIGN.md section 9 lists every key with its
  * default and the test that sets it):
  *   geometry      "target_units" (16384: wavefront-sized units the pair passes are split into), "min_segment" (256 rows), "max_segments" (2048)
  *   the bet       "optimistic" (1: one-shot calls bet on a sampled threshold -- verified on the device, exact fallback), "sample_stride" (0 = auto: every
