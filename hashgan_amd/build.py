@@ -21,7 +21,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB_DIR = os.path.join(PKG, "_lib")
 LIB_PATH = os.path.join(LIB_DIR, "libhashgan_amd.so")
 PROBE_LIB_PATH = os.path.join(LIB_DIR, "libhashgan_amd_probe.so")   # measurement probes compiled in (-DHG_PROBES=1)
-UNITS = ["hg_core", "hg_seq", "hg_rank", "hg_side", "hg_rerank", "hg_pairs_valu", "hg_pairs_mx", "hg_pairs_mx1", "hg_real", "hg_pq_encode", "hg_comm"]
+UNITS = ["hg_core", "hg_tables", "hg_seq", "hg_rank", "hg_side", "hg_rerank", "hg_pairs_valu", "hg_pairs_mx", "hg_pairs_mx1", "hg_real", "hg_pq_encode", "hg_comm"]
 SOURCES = [os.path.join(CSRC, u + ".hip") for u in UNITS]
 DEPS = SOURCES + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".hpp")] + [
     os.path.join(ROOT, "include", "hashgan_amd.h")]

@@ -1,7 +1,8 @@
 // Host side of libhashgan_amd.so, shared by its translation units: error plumbing, device buffers, the context
 // (struct hg_ctx, opaque in include/hashgan_amd.h) and the handful of host functions one unit calls in another.
 //
-//   hg_core.hip        context, tables (hg_set_*), options / statistics / timing, label match, AP, downloads, results into device arrays (hg_export)
+//   hg_core.hip        context, options / statistics / timing, label match, AP, downloads, results into device arrays (hg_export)
+//   hg_tables.hip      the table loaders (hg_set_database*, hg_set_queries*, hg_get_packed): one shape check, three packers with one destination and one result record, one commit per table
 //   hg_seq.hip         the Hamming sequences: geometry, histogram -> plan -> select -> rank, staged (sharded) and one-shot forms
 //   hg_rank.hip        their rank stage: the choice of the kernel (RankChoice), one launcher per kernel, the leftovers of a fused step, k_order
 //   hg_side.hip        the side metrics (hg_rel_hist, hg_graded, hg_grade_hist, hg_tie_ap, hg_ap_at, hg_joint_hist, hg_votes, hg_nbr_hist) and their getters: one SideResult each;
@@ -14,7 +15,7 @@
 //   hg_pairs_mx1.hip   launcher of k_select_mx (every code length: the longest compile)
 //   hg_real.hip        real-valued (float32 inner product) ranking: a ladder of attempts, each with one RealReq down and one RealState (hg_ctx::real) up;
 //                      its asymmetric form (hg_topr_asym, hg_map_asym): the same call on the other RowSource, the database's packed codes read as +-1 (hg_asym.hpp);
-//                      its quantised form (hg_topr_pq, hg_map_pq): the same call on a third, product-quantisation codes and codebooks (hg_pq.hpp; loaded by hg_set_database_pq, hg_core.hip)
+//                      its quantised form (hg_topr_pq, hg_map_pq): the same call on a third, product-quantisation codes and codebooks (hg_pq.hpp; loaded by hg_set_database_pq, hg_tables.hip)
 //   hg_pq_encode.hip   the exact product-quantisation encoder (hg_pq_encode, hg_pq_encode_dev: hg_pq_encode.hpp) and the loader from float features to a
 //                      quantised context (hg_set_database_pq_f32: encode, then hg_set_database_pq on the codes)
 //   hg_comm.hip        RCCL collectives (library dlopen'ed on first use)
@@ -159,6 +160,12 @@ inline hipError_t pin_alloc(void** p, size_t want, size_t* cap) {
     return e;
 }
 inline void pin_free(void* p, size_t cap) { if (p) cache_give_pin(p, cap); }
+inline hipError_t pin_grow(void** p, size_t* cap, size_t want) {     // a block of at least `want` bytes (a smaller one is given back, its contents with it)
+    if (*cap >= want) return hipSuccess;
+    pin_free(*p, *cap);
+    *p = nullptr; *cap = 0;
+    return pin_alloc(p, want, cap);
+}
 
 // A device buffer that only ever grows.
 struct DevBuf {
@@ -768,11 +775,11 @@ inline void widen_u32(int64_t* dst, const void* src, size_t n) {
 
 inline int grid_for(i64 n, int per_block = 256) { return (int)((n + per_block - 1) / per_block); }
 inline int padded_grid(int nBlk) { return (nBlk + 7) / 8 * 8; }
+inline int pad16(int b) { return (b + 15) / 16 * 16; }   // a float table's row pitch: the feature count padded to a multiple of 16 (hg_ctx::bpad)
 
 // ---- across translation units --------------------------------------------------------------------------------------
 // hg_core.hip
 int need(hg_ctx* c, unsigned st, const char* who, const char* what);     // stage check + hipSetDevice
-int upload_codes(hg_ctx* c, DevBuf& dst, const uint64_t* host, i64 n, int W, int NW);
 int ensure_pin(hg_ctx* c, size_t need_b);
 int do_match(hg_ctx* c);                         // k_match through the ranked idx list (> 128 classes, real-valued lists)
 int ensure_ap_tables(hg_ctx* c, bool* use_recip);   // summation trees + reciprocals for the current R, c->ap / c->rel sized
@@ -781,9 +788,11 @@ inline int do_ap(hg_ctx* c) { return do_ap_range(c, 0, c->geo.Q); }
 int ensure_out_block(hg_ctx* c);                   // err / ap / rel as views of one block (before anything of the call is enqueued)
 int read_plan_flag(hg_ctx* c, int* flag);        // *err back to the host (synchronises)
 int launch_min_topr(hg_ctx* c, const u32* idx_all, const u8* dist_all, i64 n, int G);
+hg_ctx* requery_child(hg_ctx* c, i64 nF);       // c->sub, set up to rerun nF lost queries of c
+// hg_tables.hip
 extern "C" int check_dev_pointer(hg_ctx* c, const char* who, const char* what, const hg_dev_array& a, int64_t extent);   // a.ptr is device memory of the context's GPU and the extent lies inside its allocation (else HG_ERR_ARG)
 extern "C" int wait_for_producer(hg_ctx* c, void* s);   // (both defined among the device-array entry points)  the context's stream behind whatever is enqueued so far on the producer's stream s
-hg_ctx* requery_child(hg_ctx* c, i64 nF);       // c->sub, set up to rerun nF lost queries of c
+int preload_tables(hg_ctx* c);                   // hg_preload: the loaders' staging blocks, second stream and packing threads; the unit's code object
 // hg_seq.hip
 int stage_ap_download(hg_ctx* c, void* dst = nullptr);   // {verdict, AP, hit counts} into pinned host memory behind everything enqueued so far (no synchronisation)
 int wait_verdict(hg_ctx* c, bool staged, int* flag);     // waits for the stream; the verdict word from the context's pinned block (staged) or by a download of its own

@@ -1263,11 +1263,7 @@ int hg_map_begin(hg_ctx* c, int64_t R) {
     }
     if (blind) {
         const size_t need_b = (size_t)c->Q * 12 + 16;
-        if (m.cap < need_b) {
-            pin_free(m.pin, m.cap);
-            m.pin = nullptr; m.cap = 0;
-            HG_HIP(pin_alloc(&m.pin, need_b, &m.cap));
-        }
+        HG_HIP(pin_grow(&m.pin, &m.cap, need_b));
         if (!m.ev) HG_HIP(hipEventCreateWithFlags(&m.ev, hipEventDisableTiming));
         c->bet_runs++;
         // two streams unless the caller owns the stream (hg_set_stream) or per-kernel timing is on (its events assume one stream)

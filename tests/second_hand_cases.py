@@ -49,7 +49,7 @@ def shape(name):
 
 
 def padding(s):
-    """The padded sizes of a shape, by the rules of hg_core.hip's loaders."""
+    """The padded sizes of a shape, by the rules of the loaders (hg_tables.hip)."""
     return dict(Qpad=(s.Q + 63) // 64 * 64, words32=(s.b + 31) // 32, words64=(s.b + 63) // 64, LW=(s.C + 63) // 64,
                 bpad=(s.bf + 15) // 16 * 16, bpad_pq=(s.M * s.dsub + 15) // 16 * 16, bitmap_words=(s.R + 63) // 64, cutoffs=len(s.ks),
                 pq_tables=(s.M, s.K), G=s.G)
